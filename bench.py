@@ -18,10 +18,15 @@ N*shots; the Threefry counter is the global row index, so the sharded result equ
 ``f`` batches are resident in HBM before the timed region starts - ``NF`` distinct ones, used in rotation - and
 for N > 1 the bit-packed detector/observable rows are collected by RCCL every ``GATHER_EVERY`` steps.
 
-The ``--steps`` loop is repeated ``--repeats`` times, each repetition bracketed by barrier + synchronize on
-both sides; ``value`` / ``ms_per_step`` are the MEDIAN repetition (max over ranks), ``repeat_ms_per_step`` lists
-all of them.  Untimed extra legs (N = 1) put the headline in context: the full kernel alone, dense error
-patterns, end-to-end ``CompiledDetectorSampler.sample()`` (host buffers in and out) and time-to-first-batch.
+The ``--steps`` loop is timed ``--repeats`` times (default once: exactly ``--steps`` timed steps), each repetition
+bracketed by barrier + synchronize on both sides and started from the same key and f batch; ``value`` /
+``ms_per_step`` are the MEDIAN repetition (max over ranks), ``repeat_ms_per_step`` lists all of them.
+``--dump-outputs DIR`` writes the rows the last timed step produced to ``DIR/samples.npy``.
+
+A plain run does only what the headline needs.  ``--full`` adds what puts it in context (N = 1): the check of the
+last timed region against the C oracle, the per-kernel split, the rate after a clock spin-up, the other BASELINE
+configs, the full kernel alone, dense error patterns, end-to-end ``CompiledDetectorSampler.sample()`` (host buffers
+in and out), time-to-first-batch and the CPU baseline.
 """
 
 from __future__ import annotations
@@ -274,13 +279,17 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=8, help="repetitions of the timed --steps loop (median reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the timed --steps loop, median reported (default 1; 8 with --full)")
+    ap.add_argument("--full", action="store_true", help="also run the untimed context legs, the oracle check of the last timed region "
+                    "and the CPU baseline (off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the detector/observable bits the last "
+                    "timed step produced (rank 0's rows; a fixed, seeded sample of them beyond 48 MiB) as float32 to DIR/samples.npy")
     ap.add_argument("--spinup-ms", type=float, default=0.0,
                     help="untimed steps worth this many ms before every timed repetition (clock spin-up; default 0 = none: `value` is what "
-                         "--warmup steps and then --steps timed steps give; the rate after 30 ms of spin-up is reported beside it)")
+                         "--warmup steps and then --steps timed steps give; with --full the rate after 30 ms of spin-up is reported beside it)")
     ap.add_argument("--nf", type=int, default=NF_DEFAULT, help="distinct resident f batches the timed loop rotates through (the first "
                     f"{NF_HOST} from the seeded host generator, the others drawn on the device with the same per-bit probability)")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the driver-timed legs of the other BASELINE configs (C3, C4, C5)")
+    ap.add_argument("--no-config-legs", action="store_true", help="with --full: skip the driver-timed legs of the other BASELINE configs (C3, C4, C5)")
     ap.add_argument("--shots", type=int, default=1_000_000, help="shots per step per GPU (--scaling weak) / per step of the whole job (--scaling strong)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="weak: every GPU samples --shots rows per step (rank r owns rows "
                     "[r * shots, (r + 1) * shots) of a global batch of N * shots); strong: ONE global batch of --shots rows per step, rank r samples rows "
@@ -297,13 +306,15 @@ def main() -> None:
                     "itself drew, scripts/export_from_tsim.py --golden) and compare bit for bit: `golden_check` in the JSON line")
     ap.add_argument("--num-f", type=int, default=None, help="with --program: width of the synthetic f batches (default: from the file, "
                     "else the largest f index + 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the untimed context legs (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the untimed context legs (profiling runs)")
     ap.add_argument("--no-full-leg", action="store_true", help=argparse.SUPPRESS)  # older name
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     args = ap.parse_args()
     if args.no_full_leg:
         args.no_extra_legs = True
+    if args.repeats is None:
+        args.repeats = 8 if args.full else 1
 
     # the host driver supports dmabuf IPC only: RCCL's peer mappings fail without this (exported on the GPU boxes;
     # set here too in case a launcher scrubs the environment) - before any HIP runtime is loaded
@@ -538,6 +549,7 @@ def main() -> None:
 
     steps_fn = lib.tsim_sample_steps_device
     ptr_cache = {}
+    last_out = [None]  # device address of the bit_packed rows (B x RB bytes) the latest launched step writes
 
     last_collective = [None]
 
@@ -563,6 +575,7 @@ def main() -> None:
                               (0 if launched[0] < NSLOT else PIPE_READY) | PIPE_PACKED)
             if rc < 0:
                 raise RuntimeError(f"pipelined launch failed ({rc}): {_lib.last_error()}")
+            last_out[0] = grp[g].ptr + (pos + n - 1) * B * RB
             launched[0] += n
             step_no[0] = j + n
             if pos + n == GATHER_EVERY:  # group complete: join every slot on the join lane, then collect
@@ -590,6 +603,7 @@ def main() -> None:
         rc = steps_fn(h_prog, k, arrs[0], B, num_f, key_state, shot_offset, arrs[1], None, PIPE_READY | PIPE_PACKED)
         if rc < 0:
             raise RuntimeError(f"tsim_sample_steps_device failed ({rc}): {_lib.last_error()}")
+        last_out[0] = out_ptrs[(j0 + k - 1) % NSLOT]
 
     def step(f_list=f_bufs) -> None:
         # one host split per batch, key, subkey = split(key) (sampler.py:399), inside the launch call
@@ -603,6 +617,7 @@ def main() -> None:
             rc = begin_split(h_prog, b, d_f, B, num_f, key_state, shot_offset, out_ptrs[b], None, None, PIPE_READY | PIPE_PACKED)
             if rc < 0:
                 raise RuntimeError(f"tsim_sample_batch_device_begin failed ({rc}): {_lib.last_error()}")
+            last_out[0] = out_ptrs[b]
             return
         g, pos = (j // GATHER_EVERY) & 1, j % GATHER_EVERY
         rc = 0
@@ -621,6 +636,7 @@ def main() -> None:
         launched[0] += 1
         if rc < 0:
             raise RuntimeError(f"pipelined launch failed ({rc}): {_lib.last_error()}")
+        last_out[0] = grp[g].ptr + pos * B * RB
         if pos == GATHER_EVERY - 1:  # group complete: join every slot on the join lane, then collect
             join_fn(h_prog, join_ptr)
             gather_next(GATHER_EVERY)
@@ -692,6 +708,8 @@ def main() -> None:
         # --steps 200).  About 8 bracketed launches over all repetitions together.
         launches_per_rep = max(1, -(-args.steps // 8))
         PROF_EVERY = max(1, launches_per_rep * max(1, args.repeats) // 8)  # (about one bracketed launch per repetition at --steps 20)
+        if not args.full:
+            PROF_EVERY = launches_per_rep  # a plain run: one bracketed launch per repetition, whatever --repeats says
     PROF_LEVEL = 0 if os.environ.get("TSIM_BENCH_NO_PROFILE") == "1" else 2
     hp.profile_set_sampling(PROF_EVERY)
     hp.profile_enable(PROF_LEVEL)
@@ -743,6 +761,11 @@ def main() -> None:
                     hp.synchronize()
             hp.profile_enable(PROF_LEVEL)
         fence()
+        # every timed region starts from the run's first key and f batch, whatever the untimed steps before it were (their
+        # number depends on how soon the tables settle): the same arguments give the same outputs from run to run
+        key_state[0], key_state[1] = key[0] & 0xFFFFFFFF, key[1] & 0xFFFFFFFF
+        if not use_dist:  # (drain() has already restarted the count in the N > 1 path)
+            step_no[0] = 0
         region_start = (int(key_state[0]), int(key_state[1]), step_no[0])  # what the in-run check below replays
         t0 = time.perf_counter()
         if os.environ.get("TSIM_BENCH_TRACE") == "2":
@@ -777,7 +800,11 @@ def main() -> None:
     kern_ms, launches = hp.profile_read(reset=True)
     prof_steps = hp.profile_read_steps()  # batches covered by the bracketed (fused) first passes
     hp.profile_enable(False)
-    if not use_dist and rank == 0 and verify is None:
+    dump = None
+    if args.dump_outputs and rank == 0:
+        # (untimed) before anything overwrites the buffers: what a caller of the timed path receives from its last step
+        dump = dump_outputs(hp, last_out[0], args.dump_outputs, B, n_out, RB)
+    if args.full and not use_dist and rank == 0 and verify is None:
         # (untimed) what the LAST timed region left in the output buffers, against the CPU oracle - before anything overwrites them
         try:
             verify = verify_last_region(hp, program, prng, f_bufs, d_outs, region_start, args.steps, NSLOT, B, num_f, WF, RB, shot_offset)
@@ -790,7 +817,7 @@ def main() -> None:
     detail = serial_ms = None
     d_out0 = d_outs[0]
     hp.profile_set_sampling(1)
-    if info.get("pattern_tables") and os.environ.get("TSIM_BENCH_NO_CONTEXT") != "1":  # (counter runs: timed launches only)
+    if args.full and info.get("pattern_tables") and os.environ.get("TSIM_BENCH_NO_CONTEXT") != "1":  # (counter runs: timed launches only)
         # every kernel of 8 launches bracketed: per-kernel split and first-kernel-start -> last-kernel-end latency
         hp.profile_enable(1)
         for _ in range(8):
@@ -823,7 +850,7 @@ def main() -> None:
     # the same timed region once the chip has been busy for 30 ms (its power management raises the clocks over the first ~25 ms of
     # sustained work, profiles/r03/steps_dependence.txt): context, NOT `value`
     sustained = None
-    if N == 1 and not use_dist and args.spinup_ms == 0 and os.environ.get("TSIM_BENCH_NO_CONTEXT") != "1":
+    if args.full and N == 1 and not use_dist and args.spinup_ms == 0 and os.environ.get("TSIM_BENCH_NO_CONTEXT") != "1":
         fence()
         t0 = time.perf_counter()
         steps(32)
@@ -847,7 +874,7 @@ def main() -> None:
         sustained = {"untimed_ms_before_each_region": 30.0, "untimed_steps": n_spin, "ms_per_step": [w / args.steps * 1e3 for w in warm],
                      "value_median": B * N * args.steps / statistics.median(warm)}
     extra = {}
-    if N == 1 and not use_dist and not args.no_extra_legs and not args.no_config_legs and not args.program and args.config == "C2":
+    if args.full and N == 1 and not use_dist and not args.no_extra_legs and not args.no_config_legs and not args.program and args.config == "C2":
         # the other BASELINE configs, timed by this process with their own rooflines (22 / 11 / 56 B per shot)
         legs = {}
         for cname, cshots, csteps in (("C3", 1_000_000, 64), ("C4", 100_000, 64), ("C5", 1_000_000, 64)):
@@ -856,7 +883,7 @@ def main() -> None:
             except Exception as exc:  # a leg must never cost the headline line
                 legs[cname] = {"error": repr(exc)}
         extra["configs"] = legs
-    if N == 1 and not use_dist and not args.no_extra_legs:
+    if args.full and N == 1 and not use_dist and not args.no_extra_legs:
         extra.update(extra_legs(backend, synth, program, cfg, hp, info, B, num_f, n_out, key, f_bufs, d_out0, local_rank, t_build,
                                 resident_f, steps, drain, INIT_STEPS, args))
 
@@ -1002,11 +1029,13 @@ def main() -> None:
             res["golden_check"] = golden_check
         if gather_calibration is not None:
             res["gather_calibration"] = gather_calibration
+        if dump is not None:
+            res["dump_outputs"] = dump
         if args.approx or args.live_padding or args.program:
             res["config"]["variant"] = ("approximate floatfactors (compile/evaluate.py:56-59) " if args.approx else "") + \
                 ("live padding " if args.live_padding else "") + (f"exported program {args.program}" if args.program else "")
         res.update(extra)
-        if N == 1 and not args.no_cpu_baseline:
+        if args.full and N == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(program, cfg, args.cpu_seconds)
     if comm is not None:
         comm.barrier()
@@ -1015,6 +1044,25 @@ def main() -> None:
     C.CDLL(None).fflush(None)
     if rank == 0:
         print(json.dumps(res), flush=True)
+
+
+def dump_outputs(hp, ptr, out_dir: str, B: int, n_out: int, RB: int, limit_bytes: int = 48 << 20) -> dict:
+    """The bit_packed rows at device address `ptr` (B rows of RB bytes, the reference's bit_packed layout) as the
+    (rows, n_out) detector/observable bits sample_program returns, float32, in out_dir/samples.npy.  Beyond
+    `limit_bytes` a fixed, seeded choice of rows (ascending) is written instead of all of them."""
+    packed = np.zeros((B, RB), np.uint8)
+    hp.d2h(packed, ptr)
+    max_rows = max(1, limit_bytes // (4 * max(1, n_out)))
+    if B <= max_rows:
+        rows = np.arange(B)
+    else:
+        rows = np.sort(np.random.default_rng(20261016).choice(B, size=max_rows, replace=False))
+    bits = np.unpackbits(packed[rows], axis=1, bitorder="little")[:, :n_out].astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "samples.npy"), bits)
+    return {"dir": out_dir, "files": ["samples.npy"], "shape": list(bits.shape), "dtype": "float32",
+            "rows": "all" if B <= max_rows else f"{len(rows)} of {B}, np.random.default_rng(20261016).choice without replacement, ascending",
+            "note": "detector/observable bits of the last timed step (rank 0's rows)"}
 
 
 def device_f_batches(backend, hp, num_f: int, p_bit: float, B: int, WF: int, count: int, seed: int, noise_model=None) -> list:

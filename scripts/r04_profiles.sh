@@ -6,8 +6,8 @@ WHAT=" ${*:-all} "   # any of: bench shapes rocprof c5 transition long tests (de
 want() { [[ "$WHAT" == *" all "* || "$WHAT" == *" $1 "* ]]; }
 q() { scripts/bq.sh --no-config-legs "$@" | sed -e 's/enqueue_ms.*//'; }
 if want bench; then
-  python bench.py > $O/bench.json 2> $O/bench.err
-  python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2>> $O/bench.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2>> $O/bench.err
   { echo "== bench.py --steps K (no spin-up, 64 resident f batches = 488 MB + 92 MB of outputs)"; for k in 5 10 20 50 200 1000; do q --steps $k; done;
     echo "== --spinup-ms 30"; for k in 20 200; do q --steps $k --spinup-ms 30; done;
     echo "== --nf 4 (round 3's working set: 32 MB of f, inside the Infinity Cache)"; for k in 20 200; do q --steps $k --nf 4; done; } > $O/steps_dependence.txt 2>&1

@@ -7,8 +7,8 @@ WHAT=" ${*:-all} "
 want() { [[ "$WHAT" == *" all "* || "$WHAT" == *" $1 "* ]]; }
 q() { scripts/bq.sh --no-config-legs "$@" | sed -e 's/enqueue_ms.*//'; }
 if want bench; then
-  python bench.py > $O/bench.json 2> $O/bench.err
-  python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2>> $O/bench.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2>> $O/bench.err
   { echo "== bench.py --steps K (no spin-up, 64 resident f batches)"; for k in 5 10 20 50 200 1000; do q --steps $k; done; } > $O/steps_dependence.txt 2>&1
 fi
 if want rocprof; then

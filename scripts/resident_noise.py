@@ -3,7 +3,7 @@
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 cfg = sys.argv[1] if len(sys.argv) > 1 else "C2"
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-config-legs"],
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-config-legs"],
                      capture_output=True, text=True)
 d = json.loads(out.stdout.strip().splitlines()[-1])
 r = d.get("resident_device_noise", {})

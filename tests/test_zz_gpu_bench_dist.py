@@ -32,7 +32,7 @@ def test_bench_distributed_path_on_one_gpu(hip, mode):
     else:
         env.update(TSIM_BENCH_GATHER=mode, TSIM_BENCH_GATHER_EVERY="8")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "21", "--warmup", "2", "--shots", "200000",
-           "--no-cpu-baseline", "--no-full-leg"]
+           "--no-cpu-baseline", "--no-full-leg", "--full"]
     try:
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     except subprocess.TimeoutExpired:
@@ -83,3 +83,31 @@ def test_bench_on_an_exported_program_with_its_own_noise_model(hip, tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["value"] > 0 and "exported program" in d["config"]["variant"] and "its own noise model" in d["config"]["workload"]
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(hip, tmp_path):
+    """A plain `bench.py --dump-outputs DIR`: one timed region of exactly --steps steps, no context legs, and
+    DIR/samples.npy holds the bits its last step computed - the C oracle on that step's f batch and subkey (the
+    region starts from the run's first key and f batch) gives the same rows."""
+    import numpy as np
+
+    from oracle import oracle_c
+    from tsim_amd import prng, synth
+
+    steps, shots, nf = 6, 100_000, 4
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "2", "--shots", str(shots),
+                        "--nf", str(nf), "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == steps and d["repeats"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert "cpu_baseline" not in d and "configs" not in d and "verify" not in d
+    assert d["dump_outputs"]["files"] == ["samples.npy"] and d["dump_outputs"]["rows"] == "all"
+    prog, cfg = synth.config_program("C2")
+    got = np.load(tmp_path / "samples.npy")
+    assert got.dtype == np.float32 and got.shape == (shots, prog.num_outputs)
+    key = prng.key(cfg["seed"])
+    for _ in range(steps):
+        key, sub = prng.split(key)
+    f = synth.synth_f(shots, cfg["num_f"], cfg["p_bit"], seed=cfg["seed"] + 7919 * ((steps - 1) % nf))
+    want = oracle_c.OracleProgram(prog).sample_program(f, sub)
+    assert np.array_equal(got, np.asarray(want, np.float32))
