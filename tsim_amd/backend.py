@@ -719,6 +719,15 @@ class DeviceNoiseSampler:
             "tsim_noise_sample_device",
         )
 
+    FORMS = {-1: None, 0: "k_noise_wave", 1: "k_noise_tile", 2: "k_noise"}
+
+    def info(self) -> dict:
+        """What ``tsim_noise_create`` fixed (``tsim_noise_info``): the kernel ``sample_into`` launches and its geometry."""
+        out = (C.c_int64 * 8)()
+        _lib.check(self._lib.tsim_noise_info(self._n, out), "tsim_noise_info")
+        return dict(form=self.FORMS[int(out[0])], wave_tile=int(out[1]), wave_g=int(out[2]), tile=int(out[3]), tseg=int(out[4]),
+                    seg=int(out[5]), fusable=bool(out[6]), words=int(out[7]))
+
     def sample(self, B: int, key) -> np.ndarray:
         """Convenience: ``uint8[B, num_f]`` on the host (for tests)."""
         wf = max(1, (self.num_f + 63) // 64)

@@ -210,6 +210,12 @@ extern "C" int tsim_noise_sample_device(tsim_noise *n, int64_t B, uint32_t key_h
   return TSIM_OK;
 }
 
+// the fused noise + first pass kernel can take the sampler's tiles: a whole number of 1024-row blocks, the channel records beside the
+// first pass's tables (k_noise_wave's form only)
+static bool noise_fusable(const tsim_noise *n) {
+  return (n->wave_tile % 1024) == 0 && (size_t)n->wave_tile * n->WF * 8 + (size_t)n->n_ch * 24 <= 56 * 1024;
+}
+
 // the request's batch launcher (tsim_sample.hip calls it for the paths that do not fuse the noise into their first pass)
 static int noise_launch_one(void *noise, int64_t B, uint32_t k0, uint32_t k1, uint64_t *d_f, hipStream_t s) {
   return tsim_noise_sample_device((tsim_noise *)noise, B, k0, k1, d_f, (void *)s);
@@ -225,12 +231,14 @@ extern "C" int tsim_sample_steps_noise_device(tsim_program *p, tsim_noise *n, in
   if (!noise_key) return tsim_fail(TSIM_EINVAL, "NULL argument");
   if (num_f != n->num_f) return tsim_fail(TSIM_EINVAL, "the noise sampler draws %d f bits, the call says %d", n->num_f, num_f);
   if (n_steps <= 0) return tsim_sample_steps_device(p, n_steps, (const uint64_t *const *)d_f, B, num_f, key, shot_offset, d_out, d_max_norm_dev, flags);
+  // (the splits run on a copy: the caller's noise key moves only when the call succeeds, like `key`)
+  uint32_t nk[2] = {noise_key[0], noise_key[1]};
   std::vector<uint32_t> keys(2 * (size_t)n_steps);
   for (int j = 0; j < n_steps; ++j) {
     uint32_t o[4];
-    tsim_key_split(noise_key[0], noise_key[1], o);
-    noise_key[0] = o[0];
-    noise_key[1] = o[1];
+    tsim_key_split(nk[0], nk[1], o);
+    nk[0] = o[0];
+    nk[1] = o[1];
     keys[2 * (size_t)j] = o[2];
     keys[2 * (size_t)j + 1] = o[3];
   }
@@ -254,13 +262,32 @@ extern "C" int tsim_sample_steps_noise_device(tsim_program *p, tsim_noise *n, in
     rq.N.g = n->wave_g;
     // (the fused kernel's blocks are 1024 threads: groups of g lanes for up to 1024 / g channels at a time; LDS: the tile, the
     // channel records and the first pass's ~5 KB of tables - two blocks per CU)
-    rq.fusable = (n->wave_tile % 1024) == 0 && (size_t)n->wave_tile * n->WF * 8 + (size_t)n->n_ch * 24 <= 56 * 1024;
+    rq.fusable = noise_fusable(n);
   }
   g_noise_req = &rq;
   // (the f rows do not exist before this call: whatever the caller says about its inputs, every path orders its reads behind the noise)
   const int r = tsim_sample_steps_device(p, n_steps, (const uint64_t *const *)d_f, B, num_f, key, shot_offset, d_out, d_max_norm_dev, flags);
   g_noise_req = nullptr;
+  if (r >= 0) {
+    noise_key[0] = nk[0];
+    noise_key[1] = nk[1];
+  }
   return r;
+}
+
+extern "C" int tsim_noise_info(tsim_noise *n, int64_t out[8]) {
+  if (!n || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
+  // the kernel tsim_noise_sample_device launches for any B > 0 (the same tests in the same order; no channels: a memset only)
+  out[0] = n->n_ch == 0 ? -1 : n->wave_g > 0 ? 0 : n->tile > 0 ? 1 : 2;
+  out[1] = n->wave_g > 0 ? n->wave_tile : 0;
+  out[2] = n->wave_g;
+  out[3] = n->tile;
+  out[4] = n->tseg;
+  out[5] = n->seg;
+  // tsim_sample_steps_noise_device may fuse the noise into the first pass (the program's own launch plan decides the rest)
+  out[6] = n->wave_g > 0 && n->n_ch > 0 && noise_fusable(n);
+  out[7] = n->WF;
+  return TSIM_OK;
 }
 
 extern "C" void tsim_noise_destroy(tsim_noise *n) {

@@ -1521,13 +1521,15 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
         return r;
       done += n;
     } else {
+      // (the noise first: noise_first orders it behind the previous launches of slot steps_slot - the slot this batch takes.
+      // Behind the increment it waited for the next slot's instead, and the noise could rewrite rows this slot's hard rows read)
+      if (int r = noise_first(1)) return r;
       const int slot = (int)(p->steps_slot++ % (unsigned long long)TSIM_PIPELINE_SLOTS);
       uint32_t o[4];
       tsim_key_split(key[0], key[1], o);
       key[0] = o[0];
       key[1] = o[1];
       g_carry_plan = have_plan ? &plan : nullptr;
-      if (int r = noise_first(1)) return r;
       if (int r = tsim_sample_batch_device_begin(p, slot, d_f[done], B, num_f, o[2], o[3], shot_offset, (uint64_t *)d_out[done],
                                                  d_max_norm_dev ? d_max_norm_dev[done] : nullptr, nullptr, flags))
         return r;
