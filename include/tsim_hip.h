@@ -387,6 +387,35 @@ int tsim_sample_steps_noise_device(tsim_program *p, tsim_noise *n, int32_t n_ste
                                    void *const *d_out, float *const *d_max_norm_dev, uint32_t flags);
 void tsim_noise_destroy(tsim_noise *n);
 
+/* ---- measurements -> detection events (replaces Circuit.compile_m2d_converter, src/tsim/circuit.py:423-456, which
+ *      hands the work to stim's CompiledMeasurementsToDetectionEventsConverter) --------------------------------------
+ * Per shot, out_j = ref_j XOR (XOR of m_k over k in cols[row_ptr[j] .. row_ptr[j+1]-1]): a GF(2) affine map over the
+ * measurement record.  A handle of its own, bound to HIP device `device` (no tsim_program involved):
+ *   row_ptr   int32 [n_out + 1], row_ptr[0] = 0, non-decreasing;  cols  int32 [row_ptr[n_out]], each in [0, M);
+ *   ref       uint8 [n_out], 0/1 (the noiseless value of each output; zeros for skip_reference_sample).
+ * Any M: the records' 64-bit shot masks live in LDS, in windows of 2048 records when M exceeds 7616 (each window
+ * with its own CSR, built here); TSIM_ENOTSUP only when the windows' CSRs would exceed 2^28 row pointers.
+ * Rows: input row r starts at byte r * in_row_bytes and holds M bytes (in_packed = 0: nonzero = 1) or ceil(M/8) bytes
+ * little-endian (in_packed = 1; pad bits ignored) - the padded uint64 rows of tsim_sample_steps_device qualify with
+ * in_row_bytes = 8 ceil(M/64).  The input buffer must span B * in_row_bytes bytes: whole rows, the last one included,
+ * may be read.  Output row r starts at byte r * out_row_bytes and receives outputs col0 .. col0+n_cols-1 as
+ * n_cols bytes 0/1 (out_packed = 0) or ceil(n_cols/8) bytes with zero pad bits (out_packed = 1); the bytes of a row past
+ * those are not written. */
+typedef struct tsim_m2d tsim_m2d;
+int tsim_m2d_create(int32_t device, int32_t num_measurements, int32_t n_out, const int32_t *row_ptr, const int32_t *cols,
+                    const uint8_t *ref, tsim_m2d **out);
+void tsim_m2d_destroy(tsim_m2d *h);
+/* host arrays: chunked H2D -> kernel -> D2H through pinned staging owned by the handle (device memory bounded for any B);
+ * synchronous.  out_row_bytes bytes of every output row are copied back. */
+int tsim_m2d_convert(tsim_m2d *h, const uint8_t *meas, int64_t B, int64_t in_row_bytes, int32_t in_packed, uint8_t *out,
+                     int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols);
+/* device buffers owned by the caller, asynchronous on `stream` (NULL: the handle's own stream) */
+int tsim_m2d_convert_device(tsim_m2d *h, const uint8_t *d_meas, int64_t B, int64_t in_row_bytes, int32_t in_packed,
+                            uint8_t *d_out, int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols,
+                            void *stream);
+/* out[0] num_measurements, [1] n_out, [2] nnz, [3] device */
+int tsim_m2d_info(const tsim_m2d *h, int64_t out[4]);
+
 /* ---- multi-GPU: RCCL over xGMI, issued by the library (no PyTorch) --------------------------------------
  *
  * The path shards over shots: rank r of R evaluates in-batch rows [r B/R, (r+1) B/R)

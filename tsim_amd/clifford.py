@@ -325,6 +325,16 @@ class _Analysis:
     rec_syms: list = field(default_factory=list)    # random symbols of every record (0: deterministic)
     detectors: list = field(default_factory=list)   # (error bitmask, flip)
     observables: dict = field(default_factory=dict)  # index -> [error bitmask, flip]
+    detector_records: list = field(default_factory=list)     # record indices each detector XORs (duplicates cancelled)
+    observable_records: dict = field(default_factory=dict)   # index -> record indices (duplicates cancelled)
+
+
+def _odd_records(indices) -> set:
+    """The records that occur an odd number of times (``DETECTOR rec[-1] rec[-1]`` is the constant 0)."""
+    odd: set = set()
+    for i in indices:
+        odd ^= {i}
+    return odd
 
 
 class _Sim:
@@ -722,9 +732,12 @@ class CliffordCircuit:
                     raise ValueError(f"DETECTOR {' '.join(tg)} (detector {len(out.detectors)}) is not deterministic: "
                                      "its measurements depend on random outcomes that do not cancel")
                 out.detectors.append((s, v))
+                out.detector_records.append(sorted(_odd_records(rec(t) for t in tg)))
             elif name == "OBSERVABLE_INCLUDE":
                 idx = int(args[0]) if args else 0
                 cur = out.observables.setdefault(idx, [0, 0, 0])
+                recs = out.observable_records.setdefault(idx, set())
+                recs ^= _odd_records(rec(t) for t in tg)
                 for t in tg:
                     cur[0] ^= out.rec_sets[rec(t)]
                     cur[1] ^= out.rec_vals[rec(t)]
@@ -875,6 +888,25 @@ class CliffordCircuit:
         program, channel_probs, error_transform = self.compile()
         return CompiledDetectorSampler(program, channel_probs=channel_probs, error_transform=error_transform,
                                        seed=seed, device=device, noise=noise, mode=mode)
+
+    def compile_m2d_converter(self, *, skip_reference_sample: bool = False, device: int = 0):
+        """Mirror of ``Circuit.compile_m2d_converter`` (src/tsim/circuit.py:423-456): measurement records (the columns
+        of ``compile_sampler()``) -> detection events and observable flips, in the output columns of ``compile()``.  The
+        reference bits are the noiseless values of the outputs (zero with ``skip_reference_sample=True``)."""
+        from .m2d import CompiledMeasurementsToDetectionEventsConverter
+
+        an = self.analyze()
+        for k, (_, _, y) in an.observables.items():
+            if y:
+                raise ValueError(f"OBSERVABLE {k} is not deterministic: its random outcomes do not cancel")
+        keys = sorted(an.observables)
+        records = list(an.detector_records) + [sorted(an.observable_records.get(k, ())) for k in keys]
+        ref = [v for _, v in an.detectors] + [an.observables[k][1] for k in keys]
+        if skip_reference_sample:
+            ref = [0] * len(ref)
+        return CompiledMeasurementsToDetectionEventsConverter(
+            records, np.asarray(ref, np.uint8), num_measurements=len(an.rec_sets), num_detectors=len(an.detectors),
+            device=device)
 
     @property
     def num_detectors(self) -> int:
