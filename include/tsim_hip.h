@@ -416,6 +416,20 @@ int tsim_m2d_convert_device(tsim_m2d *h, const uint8_t *d_meas, int64_t B, int64
 /* out[0] num_measurements, [1] n_out, [2] nnz, [3] device */
 int tsim_m2d_info(const tsim_m2d *h, int64_t out[4]);
 
+/* ---- counts over bit-packed device rows (the samplers' count(): rates without moving the rows to the host) ---------------
+ * Row r starts at byte r * row_bytes of d_rows and holds n_cols columns little-endian (row_bytes >= ceil(n_cols/8); the
+ * buffer spans n * row_bytes bytes).  Optional rows of ceil(n_cols/8) bytes: d_xor is XORed into every row first, and a
+ * row is KEPT iff (row ^ xor) & test == 0 (d_test NULL: every row is kept).  ACCUMULATED into d_counts (uint64, 8-byte
+ * aligned, never zeroed here; 2 + n_cols + 2^n_hist entries):
+ *   [0] kept rows;  [1] kept rows with a set bit in columns obs_lo .. obs_hi - 1;  [2 + c] kept rows with column c set;
+ *   [2 + n_cols + b] kept rows whose bits at hist_cols[0 .. n_hist-1] (host array, distinct columns, n_hist <= 16) spell
+ *   b, bit i = column hist_cols[i].
+ * Asynchronous on `stream` (NULL: the null stream) of HIP device `device`.  Arguments are checked before any launch;
+ * n == 0 returns 0 without a launch. */
+int tsim_tally_rows_device(int32_t device, const uint8_t *d_rows, int64_t n, int64_t row_bytes, int32_t n_cols,
+                           const uint8_t *d_xor, const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, const int32_t *hist_cols,
+                           int32_t n_hist, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU: RCCL over xGMI, issued by the library (no PyTorch) --------------------------------------
  *
  * The path shards over shots: rank r of R evaluates in-batch rows [r B/R, (r+1) B/R)

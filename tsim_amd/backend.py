@@ -370,6 +370,17 @@ class HipProgram:
                                                          C.c_void_p(d_gone) if d_gone else None, stream or None),
                    "tsim_postselect_rows_device")
 
+    def tally_rows_device(self, d_rows: int, n: int, row_bytes: int, n_cols: int, d_counts: int, *, d_xor: int = 0, d_test: int = 0,
+                          observables: tuple = (0, 0), histogram_columns=(), stream: int = 0) -> None:
+        """Counts over bit-packed device rows, accumulated into ``d_counts`` (``tsim_tally_rows_device``, include/tsim_hip.h);
+        asynchronous on ``stream`` (0: the handle's stream)."""
+        hc = np.ascontiguousarray(histogram_columns, dtype=np.int32)
+        _lib.check(self._lib.tsim_tally_rows_device(self.device, C.c_void_p(int(d_rows)), int(n), int(row_bytes), int(n_cols),
+                                                    C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
+                                                    int(observables[0]), int(observables[1]), _lib.ptr(hc) if hc.size else None, int(hc.size),
+                                                    C.c_void_p(int(d_counts)), C.c_void_p(stream or self.stream_ptr())),
+                   "tsim_tally_rows_device")
+
     def sample_batch_device(self, d_f: int, B: int, num_f: int, key, d_out: int, *,
                             shot_offset: int = 0, d_norm_dev: int = 0, stream: int = 0) -> None:
         """Asynchronous launch on the handle's stream (``stream``: a HIP stream of the caller instead); buffers are raw

@@ -1,0 +1,218 @@
+"""Counts instead of rows: kept shots, observable flips, per-column counts and a histogram, reduced on the GPU.
+
+``CompiledDetectorSampler.count()`` / ``CompiledMeasurementSampler.count()`` run the batches ``sample()`` would run and
+hand the finished rows, still in HBM, to the tally kernel (``tsim_tally_rows_device``, ``csrc/tsim_tally.hip.h``)
+instead of downloading them: only the counters cross PCIe.  The results are exact integers; for a fresh sampler with
+the same seed and arguments they are the numpy tally (:func:`tally_rows`) of what ``sample()`` returns, and the key
+chains stand where ``sample()`` would leave them.
+
+:func:`tally_rows_device` runs the kernel on device rows the caller owns (``m2d`` output, ``sample_steps_device`` rows).
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["ShotCounts", "tally_rows", "tally_rows_device", "counters_length", "MAX_HISTOGRAM_COLUMNS"]
+
+MAX_HISTOGRAM_COLUMNS = 16
+
+
+@dataclass(frozen=True, eq=False)
+class ShotCounts:
+    """Counts over the kept shots of a request.  ``column_counts[c]``: kept shots with column ``c`` set (detectors, then
+    observables); ``histogram[b]``: kept shots whose bits at ``histogram_columns`` spell ``b`` (bit ``i`` = column
+    ``histogram_columns[i]``; no columns: one bin, ``kept``)."""
+
+    shots: int
+    kept: int
+    kept_with_observable_flip: int
+    column_counts: np.ndarray
+    num_detectors: int
+    histogram_columns: tuple
+    histogram: np.ndarray
+
+    @property
+    def detector_counts(self) -> np.ndarray:
+        return self.column_counts[: self.num_detectors]
+
+    @property
+    def observable_counts(self) -> np.ndarray:
+        return self.column_counts[self.num_detectors:]
+
+    @property
+    def kept_fraction(self) -> float:
+        return self.kept / self.shots if self.shots else math.nan
+
+    def __eq__(self, other) -> bool:
+        if not isinstance(other, ShotCounts):
+            return NotImplemented
+        return (self.shots == other.shots and self.kept == other.kept
+                and self.kept_with_observable_flip == other.kept_with_observable_flip
+                and self.num_detectors == other.num_detectors and tuple(self.histogram_columns) == tuple(other.histogram_columns)
+                and np.array_equal(self.column_counts, other.column_counts) and np.array_equal(self.histogram, other.histogram))
+
+    __hash__ = None
+
+    @classmethod
+    def from_counters(cls, counters: np.ndarray, *, shots: int, n_cols: int, num_detectors: int, histogram_columns=()) -> "ShotCounts":
+        """The counters of :func:`tally_rows_device` (``counters_length(n_cols, k)`` uint64) as counts."""
+        c = np.asarray(counters).astype(np.int64)
+        hc = tuple(int(x) for x in histogram_columns)
+        if c.shape != (counters_length(n_cols, len(hc)),):
+            raise ValueError(f"counters must have {counters_length(n_cols, len(hc))} entries, got shape {c.shape}")
+        return cls(int(shots), int(c[0]), int(c[1]), c[2:2 + n_cols].copy(), int(num_detectors), hc, c[2 + n_cols:].copy())
+
+
+def counters_length(n_cols: int, n_hist: int) -> int:
+    """uint64 entries of the counter buffer of :func:`tally_rows_device`: kept, kept with an observable, the columns, the bins."""
+    return 2 + int(n_cols) + (1 << int(n_hist))
+
+
+def check_histogram_columns(columns, n_cols: int) -> tuple:
+    """Distinct column indices ``0 <= c < n_cols``, at most 16 of them, as a tuple of ints (raises ``ValueError``)."""
+    cols = np.asarray(list(columns) if not isinstance(columns, np.ndarray) else columns)
+    if cols.ndim != 1 or (cols.size and not np.issubdtype(cols.dtype, np.integer)):
+        raise ValueError("histogram_columns must be a sequence of column indices")
+    if cols.size > MAX_HISTOGRAM_COLUMNS:
+        raise ValueError(f"at most {MAX_HISTOGRAM_COLUMNS} histogram columns, got {cols.size}")
+    if cols.size and (cols.min() < 0 or cols.max() >= n_cols):
+        raise ValueError(f"histogram columns must lie in 0 .. {n_cols - 1}, got {cols.tolist()}")
+    if len(set(cols.tolist())) != cols.size:
+        raise ValueError(f"histogram columns must be distinct, got {cols.tolist()}")
+    return tuple(int(c) for c in cols)
+
+
+def default_histogram_columns(num_detectors: int, n_cols: int) -> tuple:
+    """The observables when there are 1 .. 16 of them, else none."""
+    n_obs = n_cols - num_detectors
+    return tuple(range(num_detectors, n_cols)) if 1 <= n_obs <= MAX_HISTOGRAM_COLUMNS else ()
+
+
+class _HostTally:
+    """The numpy statement of the tally, accumulated batch by batch (memory O(columns + bins))."""
+
+    def __init__(self, n_cols: int, num_detectors: int, postselection_mask, histogram_columns):
+        self.n_cols, self.nd = int(n_cols), int(num_detectors)
+        self.mask = None if postselection_mask is None else np.asarray(postselection_mask, dtype=np.bool_)
+        self.hc = tuple(histogram_columns)
+        self.shots = self.kept = self.kept_obs = 0
+        self.cols = np.zeros(self.n_cols, dtype=np.int64)
+        self.hist = np.zeros(1 << len(self.hc), dtype=np.int64)
+
+    def add(self, rows: np.ndarray) -> None:
+        rows = np.asarray(rows, dtype=np.bool_).reshape(-1, self.n_cols)
+        self.shots += len(rows)
+        if self.mask is not None:
+            rows = rows[~(rows[:, : self.nd] & self.mask).any(axis=1)]
+        self.kept += len(rows)
+        self.kept_obs += int(rows[:, self.nd:].any(axis=1).sum())
+        self.cols += rows.sum(axis=0, dtype=np.int64)
+        idx = np.zeros(len(rows), dtype=np.int64)
+        for i, c in enumerate(self.hc):
+            idx |= rows[:, c].astype(np.int64) << i
+        self.hist += np.bincount(idx, minlength=len(self.hist))
+
+    def result(self) -> ShotCounts:
+        return ShotCounts(self.shots, self.kept, self.kept_obs, self.cols.copy(), self.nd, self.hc, self.hist.copy())
+
+
+def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_columns=()) -> ShotCounts:
+    """The tally of boolean rows (detectors, then observables) in numpy: a row is kept iff no masked detector is set; the
+    column counts, ``kept_with_observable_flip`` (a set observable) and the histogram are taken over the kept rows."""
+    rows = np.asarray(rows, dtype=np.bool_)
+    if rows.ndim != 2:
+        raise ValueError(f"rows must be 2-D, got shape {rows.shape}")
+    n_cols = rows.shape[1]
+    if not 0 <= num_detectors <= n_cols:
+        raise ValueError(f"num_detectors={num_detectors} of {n_cols} columns")
+    if postselection_mask is not None and np.asarray(postselection_mask).shape != (num_detectors,):
+        raise ValueError(f"postselection_mask must have shape ({num_detectors},), got {np.asarray(postselection_mask).shape}")
+    t = _HostTally(n_cols, num_detectors, postselection_mask, check_histogram_columns(histogram_columns, n_cols))
+    t.add(rows)
+    return t.result()
+
+
+def tally_rows_device(d_rows: int, n: int, *, row_bytes: int, n_cols: int, d_counts: int, d_xor: int = 0, d_test: int = 0,
+                      observables: tuple = (0, 0), histogram_columns=(), device: int = 0, stream: int = 0) -> None:
+    """Counts over ``n`` bit-packed device rows (``row_bytes`` apart, ``n_cols`` columns, little-endian), ACCUMULATED into
+    the caller's ``uint64[counters_length(n_cols, len(histogram_columns))]`` at ``d_counts`` - read them back with
+    :meth:`ShotCounts.from_counters`.  ``d_xor`` / ``d_test``: optional device rows of ``ceil(n_cols/8)`` bytes (XORed into
+    every row; a row is kept iff ``(row ^ xor) & test == 0``); ``observables``: the column range ``[lo, hi)`` of
+    ``kept_with_observable_flip``.  Asynchronous on ``stream`` (0: the null stream) of ``device``."""
+    n, n_cols = int(n), int(n_cols)
+    if n < 0:
+        raise ValueError(f"n must be non-negative, got {n}")
+    if n_cols < 1:
+        raise ValueError(f"n_cols must be at least 1, got {n_cols}")
+    if int(row_bytes) < (n_cols + 7) // 8:
+        raise ValueError(f"rows of {row_bytes} bytes cannot hold {n_cols} columns")
+    lo, hi = (int(x) for x in observables)
+    if not 0 <= lo <= hi <= n_cols:
+        raise ValueError(f"observables {lo} .. {hi} of {n_cols} columns")
+    hc = np.asarray(check_histogram_columns(histogram_columns, n_cols), dtype=np.int32)
+    if n == 0:
+        return
+    _lib.check(_lib.load().tsim_tally_rows_device(int(device), C.c_void_p(int(d_rows)), n, int(row_bytes), n_cols,
+                                                  C.c_void_p(int(d_xor)) if d_xor else None,
+                                                  C.c_void_p(int(d_test)) if d_test else None, lo, hi,
+                                                  _lib.ptr(hc) if hc.size else None, int(hc.size), C.c_void_p(int(d_counts)),
+                                                  C.c_void_p(int(stream)) if stream else None),
+               "tsim_tally_rows_device")
+
+
+class _DeviceTally:
+    """The counters of one ``count()`` on a program's device, the masks in the layout of its rows, and the shot range
+    ``[lo, hi)`` of the rows handed to it that belong to the request (a reference row riding in front, padding behind)."""
+
+    def __init__(self, hp, n_cols: int, num_detectors: int, *, xor_bits=None, test_bits=None, histogram_columns=(), lo: int = 0,
+                 hi: int = 0):
+        self.hp, self.n_cols, self.nd, self.hc = hp, int(n_cols), int(num_detectors), tuple(histogram_columns)
+        self.lo, self.hi = int(lo), int(hi)
+        self._bufs = []
+        try:
+            self.d_counts = self._upload(np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64))
+            self.d_xor = self._upload(self._row(xor_bits)) if xor_bits is not None and np.any(xor_bits) else None
+            self.d_test = self._upload(self._row(test_bits)) if test_bits is not None else None
+        except BaseException:
+            self.release()
+            raise
+
+    def _row(self, bits) -> np.ndarray:
+        full = np.zeros(self.n_cols, dtype=np.uint8)
+        b = np.asarray(bits, dtype=np.uint8)
+        full[: len(b)] = b
+        return np.packbits(full, bitorder="little")
+
+    def _upload(self, a: np.ndarray):
+        buf = self.hp.malloc(a.nbytes + 16)
+        self._bufs.append(buf)
+        self.hp.h2d(buf, a)
+        return buf
+
+    def __call__(self, d_first: int, row_bytes: int, r0: int, r1: int, stream: int = 0) -> None:
+        """Rows ``r0 .. r1 - 1`` of the request's row space, row ``r0`` at device address ``d_first``."""
+        a, b = max(r0, self.lo), min(r1, self.hi)
+        if b <= a:
+            return
+        self.hp.tally_rows_device(d_first + (a - r0) * row_bytes, b - a, row_bytes, self.n_cols, self.d_counts.ptr,
+                                  d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
+                                  d_test=self.d_test.ptr if self.d_test is not None else 0,
+                                  observables=(self.nd, self.n_cols), histogram_columns=self.hc, stream=stream)
+
+    def result(self, shots: int) -> ShotCounts:
+        """The counters, once every tally launch has completed (the caller has synchronised their streams)."""
+        c = np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64)
+        self.hp.d2h(c, self.d_counts)
+        return ShotCounts.from_counters(c, shots=shots, n_cols=self.n_cols, num_detectors=self.nd, histogram_columns=self.hc)
+
+    def release(self) -> None:
+        for buf in self._bufs:
+            buf.free()
+        self._bufs = []

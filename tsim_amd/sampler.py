@@ -45,7 +45,9 @@ from .backend import (  # noqa: F401
     get_hip_program,
     sample_program,
 )
+from . import counts as counts_mod
 from .channels import ChannelSampler
+from .counts import ShotCounts
 from .program import CompiledProgram, from_tsim, load_npz
 
 _backend_sample_program = sample_program
@@ -348,6 +350,17 @@ class _DevicePostselect:
             owner._check_devs(dev)
         return rows, gone.view(np.bool_)
 
+    def tally_device(self, tally) -> None:
+        """``count()``: the finished rows go to the tally where they are (its masks drop the discarded rows: their masked
+        direct detector fires), then the batches' normalisation deviations are checked as :meth:`collect_device` does."""
+        tally(self.d_rows.ptr, self.wo * 8, 0, self.shots)  # (the handle's stream, behind the scatters)
+        if self.n_dispatch:
+            devs = np.zeros(self.n_dispatch * self.n_comp, dtype=np.float32)
+            self.hp.d2h(devs, self.d_devs.ptr)
+            self.devs += [devs[k * self.n_comp:(k + 1) * self.n_comp] for k in range(self.n_dispatch)]
+        for dev in self.devs:
+            self.owner._check_devs(dev)
+
     def collect(self):
         rows, gone = self.owner._download_bools(self.hp, self.d_rows, self.shots), np.empty(self.shots, dtype=np.uint8)
         self.hp.d2h(gone, self.d_flags)
@@ -492,12 +505,13 @@ class _CompiledSamplerBase:
         except Exception:  # noqa: BLE001 - no library / no device: the host path is complete on its own
             return False
 
-    def _direct_device(self, shots: int, batch_size: int | None, packed_columns: int | None = None) -> np.ndarray:
+    def _direct_device(self, shots: int, batch_size: int | None, packed_columns: int | None = None, sink=None) -> np.ndarray:
         """Direct outputs by the streaming kernel (``tsim_direct.hip.h`` through ``tsim_sample_steps_device``).  Device noise:
         the three-stage pipeline of :meth:`_device_noise_plain`.  Host noise: ONE ``sample_packed(shots)`` call - the
-        reference's stream for this request (sampler.py:549) - uploaded and processed in chunks."""
+        reference's stream for this request (sampler.py:549) - uploaded and processed in chunks.  ``sink``: ``count()``'s
+        tally takes each chunk's rows where they are, nothing is downloaded."""
         if self._noise == "device":
-            return self._device_noise_plain(shots, batch_size, False, packed_columns)[0]
+            return self._device_noise_plain(shots, batch_size, False, packed_columns, sink=sink)[0]
         hp = self._hip()
         cs = self._channel_sampler
         num_f, n_out = cs.num_f, int(self._program.num_outputs)
@@ -507,7 +521,10 @@ class _CompiledSamplerBase:
         direct_packed = packed_columns is not None and packed_columns == n_out
         row_bytes = (n_out + 7) // 8 if direct_packed else wo * 8
         d_f, d_rows = self._scratch(hp, "direct_f", chunk * wf * 8), self._scratch(hp, "rows", chunk * row_bytes + 16)
-        if packed_columns is not None:
+        out = None
+        if sink is not None:
+            s_tally = hp.aux_stream(1)
+        elif packed_columns is not None:
             rb = (packed_columns + 7) // 8
             out = np.empty((shots, rb), dtype=np.uint8)
             d_c = d_rows if direct_packed else self._scratch(hp, "compact", chunk * rb + 16)
@@ -520,13 +537,18 @@ class _CompiledSamplerBase:
             hp.h2d(d_f, f_all[lo:lo + n])
             hp.sample_steps_device([d_f.ptr], n, num_f, key_state, [d_rows.ptr], out_bit_packed=direct_packed)
             hp.synchronize()
-            if packed_columns is not None:
+            if sink is not None:  # (the next chunk overwrites the rows: the tally finishes first)
+                sink(d_rows.ptr, row_bytes, lo, lo + n, s_tally)
+                hp.stream_synchronize(s_tally)
+            elif packed_columns is not None:
                 if not direct_packed:
                     hp.compact_rows_device(d_rows.ptr, n, packed_columns, d_c.ptr, in_words=wo)
                 hp.d2h(out[lo:lo + n], d_c.ptr)
             else:
                 hp.unpack_bits_device(d_rows.ptr, n, n_out, d_u8.ptr)
                 hp.d2h(out[lo:lo + n], d_u8.ptr)
+        if out is None:
+            return None
         return out if packed_columns is not None else out.view(np.bool_)
 
     def _seam_plain(self, shots: int, plan: BatchPlan, want_ref: bool):
@@ -622,13 +644,14 @@ class _CompiledSamplerBase:
         return [(b["out"][lo:hi] if b["packed"] else b["out"][lo:hi].view(np.bool_)) for b in blocks]
 
     def _device_noise_plain(self, shots: int, batch_size: int | None, want_ref: bool, packed_columns: int | None = None,
-                            post: dict | None = None, layout: list | None = None):
+                            post: dict | None = None, layout: list | None = None, sink=None):
         """``noise="device"``: three things at once - ``k_noise`` fills the f rows of group g + 1 on its own stream, the
         sampling kernels of group g run on the pipeline lanes (``tsim_sample_steps_device``: fused first passes, one
         hard-row batch per group), the rows of group g - 1 travel to the host on a copy stream.  A group is a few
         batches; every batch owns the f buffer of its pipeline slot, so the noise stream only waits for the batch that
         used the slot before (``tsim_sample_batch_device_end`` on it).  The reference's loop does the same things one
-        after the other (``sampler.py:393-415``: sample f, upload, sample_program, concatenate, download once)."""
+        after the other (``sampler.py:393-415``: sample f, upload, sample_program, concatenate, download once).
+        ``sink`` (``count()``): called with each group's finished rows on the copy stream instead of the download."""
         hp = self._hip()
         # device-side noise has no stream contract with the reference: batch_size only bounds memory here, so batches of
         # fewer than 2^20 shots are merged (batch_size = 10^4: 2.5e8 -> 5e9 shots/s; a fixed seed still gives fixed
@@ -661,7 +684,9 @@ class _CompiledSamplerBase:
         # results land in recycled pinned memory (backend.PinnedPool): truly asynchronous copies, no first-touch page faults
         pool = result_pool()
         blocks = None
-        if layout is not None:  # column selection / order / flips / packing per output block, on the device
+        if sink is not None:
+            out = None
+        elif layout is not None:  # column selection / order / flips / packing per output block, on the device
             blocks = self._layout_blocks(hp, layout, total)
             out = None
         elif direct_packed:
@@ -701,7 +726,9 @@ class _CompiledSamplerBase:
             r0, r1 = lo * size, (lo + n) * size
             if post is not None:  # blank the discarded rows where they are, before any layout conversion
                 hp.postselect_rows_device(d_rows.ptr + r0 * row_bytes, r1 - r0, row_bytes, d_masks.ptr, d_gone.ptr + r0, stream=s_copy)
-            if blocks is not None:
+            if sink is not None:
+                sink(d_rows.ptr + r0 * row_bytes, row_bytes, r0, r1, s_copy)
+            elif blocks is not None:
                 self._layout_download(hp, blocks, d_rows.ptr + r0 * row_bytes, wo, r0, r1, s_copy)
             elif direct_packed:
                 hp.d2h_async(out[r0:r1], d_rows.ptr + r0 * row_bytes, s_copy)
@@ -740,6 +767,8 @@ class _CompiledSamplerBase:
         hp.d2h(devs, d_devs.ptr)
         for b in range(plan.count):
             self._check_devs(devs[b * n_comp:(b + 1) * n_comp])
+        if sink is not None:
+            return None, ref
         if blocks is not None:
             res = self._layout_result(blocks, 0, shots)
         else:
@@ -752,7 +781,7 @@ class _CompiledSamplerBase:
         return res, ref
 
     def _device_plain(self, shots: int, batch_size: int | None, want_ref: bool, packed_columns: int | None = None,
-                      layout: list | None = None):
+                      layout: list | None = None, sink=None):
         """noise -> f -> ``sample_program`` -> layout conversion, the GPU busy beside the channel sampler.
 
         ``noise="device"``: :meth:`_device_noise_plain`.  ``noise="host"`` (the reference's numpy/PCG64 stream, bit for
@@ -761,9 +790,10 @@ class _CompiledSamplerBase:
         buffers, batch after batch in stream order, while this thread uploads batch i (asynchronous copy from the
         pinned buffer), launches its kernels on the pipeline lanes and sends the rows of batch i - 1 to the host
         (asynchronous copy into recycled pinned result memory).  Wall time = the sampler's, plus the last batch's trip.
-        The reference row, when wanted, is row 0 of the first batch (``sampler.py:395-404``)."""
+        The reference row, when wanted, is row 0 of the first batch (``sampler.py:395-404``).  ``sink`` (``count()``):
+        called with each batch's finished rows on the copy stream instead of the download."""
         if self._noise != "host":
-            return self._device_noise_plain(shots, batch_size, want_ref, packed_columns, layout=layout)
+            return self._device_noise_plain(shots, batch_size, want_ref, packed_columns, layout=layout, sink=sink)
         import queue
         import threading
 
@@ -784,7 +814,9 @@ class _CompiledSamplerBase:
         s_up, s_copy = hp.aux_stream(0), hp.aux_stream(1)
         pool = result_pool()
         blocks = None
-        if layout is not None:
+        if sink is not None:
+            out = None
+        elif layout is not None:
             blocks = self._layout_blocks(hp, layout, total)
             out = None
         elif direct_packed:
@@ -822,7 +854,9 @@ class _CompiledSamplerBase:
         def download(b: int) -> None:
             hp.sample_batch_device_end(b % _LANES, s_copy)  # the copy stream waits for exactly this batch
             r0, r1 = b * size, (b + 1) * size
-            if blocks is not None:
+            if sink is not None:
+                sink(d_rows.ptr + r0 * row_bytes, row_bytes, r0, r1, s_copy)
+            elif blocks is not None:
                 self._layout_download(hp, blocks, d_rows.ptr + r0 * row_bytes, wo, r0, r1, s_copy)
             elif direct_packed:
                 hp.d2h_async(out[r0:r1], d_rows.ptr + r0 * row_bytes, s_copy)
@@ -869,6 +903,10 @@ class _CompiledSamplerBase:
         hp.stream_synchronize(s_copy)  # behind every batch: the devs below are final
         devs = np.zeros(plan.count * n_comp, dtype=np.float32)
         hp.d2h(devs, d_devs.ptr)
+        if sink is not None:
+            for b in range(plan.count):
+                self._check_devs(devs[b * n_comp:(b + 1) * n_comp])
+            return None, None
         skip = 1 if rides else 0
         if rides:
             if blocks is not None:  # (arranged output: the caller computed the reference row beforehand, see sample())
@@ -988,6 +1026,67 @@ class _CompiledSamplerBase:
         rows, _, gone = self._device_noise_plain(shots, batch_size, False, packed_columns, post=post)
         return rows, ref, gone
 
+    # -- counts instead of rows (counts.py) ----------------------------------------------------------------------------
+    def _count(self, shots: int, batch_size: int | None, *, mask: np.ndarray | None = None, xor_det: bool = False,
+               xor_obs: bool = False, histogram_columns=None, sample_kw: dict | None = None) -> ShotCounts:
+        """The tally of what ``sample()`` with the same arguments returns (rows: detectors, then observables), computed
+        where the rows are.  Every batch, key and noise key ``sample()`` would use is used in the same order; only the
+        download is replaced.  ``mask``: the caller's post-selection mask (validated)."""
+        nd, n_out = self._num_detectors, int(self._program.num_outputs)
+        hist = (counts_mod.default_histogram_columns(nd, n_out) if histogram_columns is None
+                else counts_mod.check_histogram_columns(histogram_columns, n_out))
+        _check_request(shots, batch_size)
+        if shots == 0:
+            return counts_mod._HostTally(n_out, nd, mask, hist).result()
+        want_ref = xor_det or xor_obs
+        if self._seam_replaced() or n_out == 0:
+            # rows never live on the device here: the same rows, tallied on the host
+            host = counts_mod._HostTally(n_out, nd, mask, hist)
+            host.add(self._sample_rows_for_count(shots, batch_size, sample_kw or {}))
+            return host.result()
+        hp = self._hip()
+        comps = bool(self._program.components)
+        direct_mask = mask is not None and comps and bool((mask & self._direct_detector_mask).any())
+        ref = None
+        if want_ref:
+            if not comps or self._noise == "device" or direct_mask:
+                ref = self._compute_reference_sample()  # (draws a key iff something is compiled, as sample() does first)
+            else:  # host noise: the reference row rides as row 0 of the first batch - its bits, computed first (as sample())
+                quiet = np.zeros((1, self._channel_sampler.num_f), dtype=np.uint8)
+                ref = np.asarray(self._seam(quiet, prng.split(self._key)[1])[0], dtype=np.bool_)
+        xor = np.zeros(n_out, dtype=np.bool_)
+        if ref is not None:
+            if xor_det:
+                xor[:nd] = ref[:nd]
+            if xor_obs:
+                xor[nd:] = ref[nd:]
+        rides = want_ref and comps and self._noise == "host" and not direct_mask
+        skip = 1 if rides else 0
+        tally = counts_mod._DeviceTally(hp, n_out, nd, xor_bits=xor, test_bits=mask, histogram_columns=hist, lo=skip, hi=skip + shots)
+        try:
+            if not comps:
+                self._direct_device(shots, batch_size, sink=tally)
+            elif direct_mask and self._noise == "host":
+                test_mask = mask & self._direct_detector_mask
+                size = plan_batches(shots, batch_size, self._estimate_batch_size()).size
+                ref_det = ref[:nd] if (ref is not None and xor_det) else None
+                work = _DevicePostselect(self, shots, size, test_mask, ref_det)
+                try:
+                    _run_postselected_device(shots, size, work, self._next_key, self._channel_sampler.sample_packed)
+                    work.tally_device(tally)
+                    out = tally.result(shots)
+                finally:
+                    work.release()
+                return out
+            else:
+                self._device_plain(shots, batch_size, rides, sink=tally)
+            return tally.result(shots)
+        finally:
+            tally.release()
+
+    def _sample_rows_for_count(self, shots: int, batch_size: int | None, sample_kw: dict) -> np.ndarray:
+        return self._sample_batches(shots, batch_size)
+
     def __repr__(self) -> str:
         """Compilation statistics in the reference's format (sampler.py:557-609)."""
         levels = [(len(c.output_indices), lv) for c in self._program.components for lv in c.compiled_scalar_graphs]
@@ -1022,6 +1121,13 @@ class CompiledMeasurementSampler(_CompiledSamplerBase):
     def sample(self, shots: int, *, batch_size: int | None = None) -> np.ndarray:
         return self._sample_batches(shots, batch_size)
 
+    def count(self, shots: int, *, batch_size: int | None = None, histogram_columns=None) -> ShotCounts:
+        """Counts over what ``sample(shots, batch_size=batch_size)`` returns, reduced on the GPU (:mod:`tsim_amd.counts`):
+        every shot is kept, ``column_counts`` are the measurements' counts, ``kept_with_observable_flip`` counts the shots
+        with a measurement of 1 (the records play the observables' part).  ``histogram_columns``: up to 16 distinct
+        measurement indices (default: every measurement when there are 1 .. 16)."""
+        return self._count(shots, batch_size, histogram_columns=histogram_columns)
+
 
 def _deliver(bit_packed: bool, *blocks: np.ndarray):
     """The column blocks as the caller gets them: bools, or - ``bit_packed=True`` - little-endian bytes per row
@@ -1033,6 +1139,30 @@ def _deliver(bit_packed: bool, *blocks: np.ndarray):
 
 class CompiledDetectorSampler(_CompiledSamplerBase):
     """Samples detector and observable outcomes."""
+
+    def count(self, shots: int, *, batch_size: int | None = None, postselection_mask: np.ndarray | None = None,
+              use_detector_reference_sample: bool = False, use_observable_reference_sample: bool = False,
+              histogram_columns=None) -> ShotCounts:
+        """Counts over the rows ``sample()`` returns for the same arguments, reduced on the GPU - only the counters cross
+        PCIe (:mod:`tsim_amd.counts`).  A shot is kept iff none of its detectors in ``postselection_mask`` is set (the
+        reference's advice: sample, then drop the rows with a masked detector); ``column_counts`` (detectors, then
+        observables), ``kept_with_observable_flip`` and the histogram over ``histogram_columns`` (default: the observables
+        when there are 1 .. 16) are taken over the kept shots.  For a fresh sampler with the same seed and arguments this
+        equals ``counts.tally_rows(sample(..., append_observables=True), ...)``, and the sampler's keys stand where that
+        ``sample()`` would leave them."""
+        nd = self._num_detectors
+        mask = None
+        if postselection_mask is not None:
+            mask = np.asarray(postselection_mask, dtype=np.bool_)
+            if mask.shape != (nd,):
+                raise ValueError(f"postselection_mask must have shape ({nd},), got {mask.shape}")
+        kw = dict(postselection_mask=postselection_mask, use_detector_reference_sample=use_detector_reference_sample,
+                  use_observable_reference_sample=use_observable_reference_sample)
+        return self._count(shots, batch_size, mask=mask, xor_det=use_detector_reference_sample,
+                           xor_obs=use_observable_reference_sample, histogram_columns=histogram_columns, sample_kw=kw)
+
+    def _sample_rows_for_count(self, shots: int, batch_size: int | None, sample_kw: dict) -> np.ndarray:
+        return self.sample(shots, batch_size=batch_size, append_observables=True, **sample_kw)
 
     def sample(self, shots: int, *, batch_size: int | None = None, prepend_observables: bool = False,
                append_observables: bool = False, separate_observables: bool = False, bit_packed: bool = False,
