@@ -430,6 +430,40 @@ int tsim_tally_rows_device(int32_t device, const uint8_t *d_rows, int64_t n, int
                            const uint8_t *d_xor, const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, const int32_t *hist_cols,
                            int32_t n_hist, uint64_t *d_counts, void *stream);
 
+/* ---- stim's shot-data formats on the device (stim.read_shot_data_file / write_shot_data_file, the samplers'
+ *      sample_write, CompiledMeasurementsToDetectionEventsConverter.convert_file) ------------------------------------
+ * format: 0 "01", 1 "b8", 2 "r8", 3 "ptb64", 4 "hits", 5 "dets" (layouts: tsim_amd/shotdata.py).  A handle of its own,
+ * bound to HIP device `device` (no tsim_program involved): scan scratch, a result block, a stream (used when a call
+ * passes stream NULL) and grow-only staging buffers for callers.
+ * Rows: row r starts at byte r * row_bytes and holds n_bits columns little-endian (row_bytes >= ceil(n_bits/8)); the
+ * padded uint64 rows of the samplers qualify.  dets needs num_m + num_d + num_o == n_bits (its M, D, L sections). */
+typedef struct tsim_shotdata tsim_shotdata;
+int tsim_shotdata_create(int32_t device, tsim_shotdata **out);
+void tsim_shotdata_destroy(tsim_shotdata *h);
+/* encode n rows into d_out (caller-owned device memory of out_cap bytes; 8-byte aligned for ptb64, whose n must be a
+ * multiple of 64).  *out_bytes receives the encoded size (r8, hits, dets: a length pass and a scan, then ONE 8-byte
+ * read, synchronous on `stream`).  Returns 0 when the bytes were written (asynchronously on `stream`), 1 when out_cap
+ * is too small (nothing written: grow the buffer and call again), or a negative error. */
+int tsim_shotdata_encode(tsim_shotdata *h, int32_t format, const uint8_t *d_rows, int64_t n, int64_t row_bytes, int32_t n_bits,
+                         int32_t num_m, int32_t num_d, int32_t num_o, uint8_t *d_out, int64_t out_cap, int64_t *out_bytes,
+                         void *stream);
+/* decode a chunk of a file (n_in bytes at d_in, starting at a row boundary; is_final: the file ends with it) into at most
+ * max_rows rows at d_rows (a multiple of 64 for ptb64).  result: [0] rows decoded, [1] bytes consumed (the next chunk
+ * starts there: a partial last row is read again), [2] byte offset within the chunk of the first fault (-1: none), [3]
+ * its kind (1 bad character, 2 01 line of the wrong length, 3 index outside its section, 4 unknown or missing dets
+ * prefix, 5 r8 run past the row's end, 6 the file ends inside a row or group, 7 malformed token).  Synchronous; r8,
+ * hits and dets zero rows 0 .. max_rows - 1 first and set bits with dword atomics (the row buffer must extend to the
+ * next multiple of 4 bytes).  b8 and ptb64 need n_bits >= 1. */
+int tsim_shotdata_decode(tsim_shotdata *h, int32_t format, const uint8_t *d_in, int64_t n_in, int32_t is_final, int32_t n_bits,
+                         int32_t num_m, int32_t num_d, int32_t num_o, uint8_t *d_rows, int64_t row_bytes, int64_t max_rows,
+                         int64_t result[4], void *stream);
+/* staging owned by the handle: slot 0 .. 15 of device (pinned = 0) or pinned host (pinned = 1) memory of at least nbytes
+ * (+16), grown on demand (contents are not kept when it grows) */
+int tsim_shotdata_staging(tsim_shotdata *h, int32_t slot, int32_t pinned, int64_t nbytes, void **ptr);
+/* hipMemcpyAsync of any direction on `stream`, and a synchronisation of `stream` (NULL: the handle's own) */
+int tsim_shotdata_copy(tsim_shotdata *h, void *dst, const void *src, int64_t nbytes, void *stream);
+int tsim_shotdata_synchronize(tsim_shotdata *h, void *stream);
+
 /* ---- multi-GPU: RCCL over xGMI, issued by the library (no PyTorch) --------------------------------------
  *
  * The path shards over shots: rank r of R evaluates in-batch rows [r B/R, (r+1) B/R)

@@ -150,6 +150,57 @@ class CompiledMeasurementsToDetectionEventsConverter:
                                                        int(bool(out_packed)), start, n, stream or None),
                    "tsim_m2d_convert_device")
 
+    def convert_file(self, *, measurements_filepath, measurements_format: str = "01", sweep_bits_filepath=None,
+                     sweep_bits_format: str = "01", detection_events_filepath, detection_events_format: str = "01",
+                     append_observables: bool = False, obs_out_filepath=None, obs_out_format: str = "01") -> None:
+        """stim's ``convert_file``: the measurement file is decoded on the device (:mod:`tsim_amd.shotdata`), converted by
+        :meth:`convert_device` and encoded on the device - the rows never exist on the host.  The detection event file
+        (and ``obs_out_filepath``'s observables) equal the encoding of ``convert(measurements=<the file's rows>,
+        append_observables=append_observables)`` (``dets``: measurements ``M``, detectors ``D``, observables ``L``)."""
+        from . import shotdata
+
+        if sweep_bits_filepath is not None:
+            raise NotImplementedError("sweep bits are not supported: the Clifford front-end has no sweep[] targets")
+        for f in (measurements_format, sweep_bits_format, detection_events_format) + ((obs_out_format,) if obs_out_filepath is not None else ()):
+            shotdata.check_format(f)
+        if obs_out_filepath is not None and append_observables:
+            raise ValueError("Can't specify obs_out_filepath with append_observables=True")
+        if measurements_format in ("b8", "ptb64") and self._M < 1:
+            raise ValueError(f"{measurements_format} needs at least one measurement to be read")
+        n_obs = self._n_out - self._nd
+        main = slice(0, self._n_out if append_observables else self._nd)
+        outs = [(detection_events_filepath, detection_events_format, main, (0, self._nd, n_obs if append_observables else 0))]
+        if obs_out_filepath is not None:
+            outs.append((obs_out_filepath, obs_out_format, slice(self._nd, self._n_out), (0, 0, n_obs)))
+        c = shotdata.codec(self._device)
+        lib = _lib.load()
+        writers, slots = [], []
+        try:
+            for path, fmt, cols, sec in outs:
+                writers.append(shotdata.ShotWriter(path, fmt, cols.stop - cols.start, sec, device=self._device))
+                slots.append(c.take_slot())
+            for d_meas, B, rb in shotdata.iter_device_rows(measurements_filepath, measurements_format, self._M, (self._M, 0, 0),
+                                                                  device=self._device):
+                for w, (_p, _f, cols, _s), slot in zip(writers, outs, slots):
+                    n = cols.stop - cols.start
+                    ob = (n + 7) // 8
+                    d_out = c.staging(slot, B * ob, pinned=False)
+                    self.convert_device(d_meas, B, d_out, in_row_bytes=rb, in_packed=True, out_row_bytes=ob, out_packed=True, cols=cols)
+                    _lib.check(lib.tsim_device_synchronize(self._device), "tsim_device_synchronize")
+                    w.write_device(d_out, B, ob)
+                for w in writers:  # the decoded rows and the outputs are reused by the next chunk
+                    w._flush(0)
+                c.sync()
+        except BaseException:
+            for w in writers:
+                w.abort()
+            for s in slots:
+                c.give_slot(s)
+            raise
+        for s in slots:
+            c.give_slot(s)
+        shotdata.close_all(writers)
+
     def __repr__(self) -> str:
         return (f"CompiledMeasurementsToDetectionEventsConverter(num_measurements={self._M}, "
                 f"num_detectors={self._nd}, num_observables={self.num_observables})")

@@ -1087,6 +1087,65 @@ class _CompiledSamplerBase:
     def _sample_rows_for_count(self, shots: int, batch_size: int | None, sample_kw: dict) -> np.ndarray:
         return self._sample_batches(shots, batch_size)
 
+    # -- rows into files (shotdata.py) ---------------------------------------------------------------------------------
+    def _sample_write(self, shots: int, batch_size: int | None, files: list, *, xor_det: bool = False, xor_obs: bool = False,
+                      host_rows=None) -> None:
+        """The rows ``sample()`` with the same arguments returns, encoded into files on the device.  ``files``: per file
+        ``(path, format, column blocks, sections)``, a block being ``("det" | "obs")``; every batch, key and noise key
+        ``sample()`` would use is used in the same order, only the download is replaced (as in :meth:`_count`).
+        ``host_rows``: ``sample()`` itself, for the paths on which the rows never live on the device."""
+        from . import shotdata
+
+        nd, n_out = self._num_detectors, int(self._program.num_outputs)
+        _check_request(shots, batch_size)
+        want_ref = xor_det or xor_obs
+        comps = bool(self._program.components)
+        on_host = shots == 0 or self._seam_replaced() or n_out == 0
+        ref = None
+        if not on_host and want_ref:
+            if not comps or self._noise == "device":
+                ref = self._compute_reference_sample()
+            else:  # host noise: the reference row rides as row 0 of the first batch - its bits, computed first (as sample())
+                quiet = np.zeros((1, self._channel_sampler.num_f), dtype=np.uint8)
+                ref = np.asarray(self._seam(quiet, prng.split(self._key)[1])[0], dtype=np.bool_)
+        det = np.arange(nd, dtype=np.uint32)
+        obs = np.arange(nd, n_out, dtype=np.uint32)
+        if ref is not None and xor_det:
+            det = det | (ref[:nd].astype(np.uint32) << np.uint32(31))
+        if ref is not None and xor_obs:
+            obs = obs | (ref[nd:].astype(np.uint32) << np.uint32(31))
+        writers = []
+        try:
+            for path, fmt, blocks, sec in files:
+                n_cols = sum(nd if b == "det" else n_out - nd for b in blocks)
+                writers.append(shotdata.ShotWriter(path, fmt, n_cols, sec, device=self._device))
+            if on_host:
+                rows = host_rows() if shots else None
+                rows = rows if isinstance(rows, tuple) else (rows,)
+                for i, w in enumerate(writers):  # (one block per file: sample(separate_observables=True) gives two)
+                    w.write_packed(np.packbits(np.asarray(rows[i], dtype=np.uint8), axis=1, bitorder="little") if shots
+                                   else np.zeros((0, (w.n_bits + 7) // 8), np.uint8))
+            else:
+                hp = self._hip()
+                rides = want_ref and comps and self._noise == "host"
+                skip = 1 if rides else 0
+                cols = [np.concatenate([det if b == "det" else obs for b in blocks]) if blocks else np.zeros(0, np.uint32)
+                        for _p, _f, blocks, _s in files]
+                sink = shotdata.FileSink(hp, (n_out + 63) // 64, list(zip(writers, cols)), lo=skip, hi=skip + shots)
+                try:
+                    if not comps:
+                        self._direct_device(shots, batch_size, sink=sink)
+                    else:
+                        self._device_plain(shots, batch_size, rides, sink=sink)
+                finally:
+                    hp.synchronize()
+                    sink.release()
+        except BaseException:
+            for w in writers:
+                w.abort()
+            raise
+        shotdata.close_all(writers)
+
     def __repr__(self) -> str:
         """Compilation statistics in the reference's format (sampler.py:557-609)."""
         levels = [(len(c.output_indices), lv) for c in self._program.components for lv in c.compiled_scalar_graphs]
@@ -1128,6 +1187,19 @@ class CompiledMeasurementSampler(_CompiledSamplerBase):
         measurement indices (default: every measurement when there are 1 .. 16)."""
         return self._count(shots, batch_size, histogram_columns=histogram_columns)
 
+    def sample_write(self, shots: int, *, filepath, format: str = "01", batch_size: int | None = None) -> None:
+        """stim's ``sample_write``: what ``sample(shots, batch_size=batch_size)`` returns, written to ``filepath`` in
+        ``format`` (:mod:`tsim_amd.shotdata`; measurements are ``M`` in ``dets``), encoded on the GPU where the rows are."""
+        from . import shotdata
+
+        shotdata.check_format(format)
+        _check_request(shots, batch_size)
+        if format == "ptb64" and shots % 64:
+            raise ValueError(f"ptb64 needs a multiple of 64 shots, got {shots}")
+        n_out = int(self._program.num_outputs)
+        self._sample_write(shots, batch_size, [(filepath, format, ("det", "obs"), (n_out, 0, 0))],
+                           host_rows=lambda: self.sample(shots, batch_size=batch_size))
+
 
 def _deliver(bit_packed: bool, *blocks: np.ndarray):
     """The column blocks as the caller gets them: bools, or - ``bit_packed=True`` - little-endian bytes per row
@@ -1163,6 +1235,48 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
 
     def _sample_rows_for_count(self, shots: int, batch_size: int | None, sample_kw: dict) -> np.ndarray:
         return self.sample(shots, batch_size=batch_size, append_observables=True, **sample_kw)
+
+    def sample_write(self, shots: int, *, filepath, format: str = "01", obs_out_filepath=None, obs_out_format: str = "01",
+                     batch_size: int | None = None, prepend_observables: bool = False, append_observables: bool = False,
+                     use_detector_reference_sample: bool = False, use_observable_reference_sample: bool = False) -> None:
+        """stim's ``sample_write``: the columns ``sample()`` returns for the same flags, written to ``filepath`` in
+        ``format`` (:mod:`tsim_amd.shotdata`; ``dets``: detectors ``D``, observables ``L``); ``obs_out_filepath`` takes the
+        observables in ``obs_out_format`` (``sample(separate_observables=True)``).  Encoded on the GPU where the rows are;
+        for a fresh sampler with the same seed the file holds exactly the encoding of that ``sample()``, and the keys stand
+        where it leaves them.  Arguments are checked before anything is sampled."""
+        from . import shotdata
+
+        shotdata.check_format(format)
+        separate = obs_out_filepath is not None
+        if separate:
+            shotdata.check_format(obs_out_format)
+        if separate and (prepend_observables or append_observables):
+            raise ValueError("Can't specify obs_out_filepath with append_observables=True or prepend_observables=True")
+        if format == "dets" and prepend_observables:
+            raise ValueError("the dets format cannot put observables before detectors (prepend_observables=True)")
+        _check_request(shots, batch_size)
+        if shots % 64 and (format == "ptb64" or (separate and obs_out_format == "ptb64")):
+            raise ValueError(f"ptb64 needs a multiple of 64 shots, got {shots}")
+        nd, n_obs = self._num_detectors, int(self._program.num_outputs) - self._num_detectors
+        if prepend_observables:
+            blocks = ("obs", "det") + (("obs",) if append_observables else ())
+        else:
+            blocks = ("det", "obs") if append_observables else ("det",)
+        files = [(filepath, format, blocks, (0, nd, n_obs if "obs" in blocks else 0))]
+        if separate:
+            files.append((obs_out_filepath, obs_out_format, ("obs",), (0, 0, n_obs)))
+        kw = dict(batch_size=batch_size, prepend_observables=prepend_observables, append_observables=append_observables,
+                  separate_observables=separate, use_detector_reference_sample=use_detector_reference_sample,
+                  use_observable_reference_sample=use_observable_reference_sample)
+        if format == "b8" and (not separate or obs_out_format == "b8"):
+            # b8 is the layout sample(bit_packed=True) already produces on the device (the kernels write it, or the
+            # arrangement kernel does): its rows go to the file as they arrive, nothing to encode
+            res = self.sample(shots, bit_packed=True, **kw)
+            for arr, path in zip(res if separate else (res,), files):
+                np.ascontiguousarray(arr).tofile(path[0])
+            return
+        self._sample_write(shots, batch_size, files, xor_det=use_detector_reference_sample, xor_obs=use_observable_reference_sample,
+                           host_rows=lambda: self.sample(shots, **kw))
 
     def sample(self, shots: int, *, batch_size: int | None = None, prepend_observables: bool = False,
                append_observables: bool = False, separate_observables: bool = False, bit_packed: bool = False,
