@@ -430,6 +430,31 @@ int tsim_tally_rows_device(int32_t device, const uint8_t *d_rows, int64_t n, int
                            const uint8_t *d_xor, const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, const int32_t *hist_cols,
                            int32_t n_hist, uint64_t *d_counts, void *stream);
 
+/* ---- pair counts over bit-packed device rows (count(pair_columns=...): the matrix the p_ij correlation analysis of
+ *      detection events is computed from) ---------------------------------------------------------------------------
+ * N[a][b] = kept rows with columns pair_cols[a] and pair_cols[b] both set, for all ordered pairs of n_pair selected
+ * columns (1 .. 4096 of them, distinct, any order, each in 0 .. n_cols-1): a binary X^T X, exact uint64.  Rows, d_xor and
+ * d_test are those of tsim_tally_rows_device and mean the same: a row is KEPT iff (row ^ xor) & test == 0, the counts are
+ * taken over row ^ xor, so N[a][a] is the tally's count of column pair_cols[a]; pad bits and padding bytes of the rows
+ * are never counted.  A handle of its own, bound to HIP device `device` (no tsim_program involved): it owns the column
+ * list, the n_pair x n_pair counters (zero after create) and the bit-plane workspace of one slab of rows (at most
+ * 32 MiB; a slab is 2^16 .. 2^20 rows).  Arguments are checked before any device call. */
+typedef struct tsim_pairs tsim_pairs;
+int tsim_pairs_create(int32_t device, int32_t n_cols, const int32_t *pair_cols, int32_t n_pair, tsim_pairs **out);
+void tsim_pairs_destroy(tsim_pairs *h);
+/* ACCUMULATES the counts of n rows, slab by slab (two launches each); asynchronous on `stream` (NULL: the null stream).
+ * The launches share the handle's workspace: calls on one handle go to one stream, or are ordered by the caller.
+ * n == 0 returns 0 without a launch. */
+int tsim_pairs_add_device(tsim_pairs *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                          const uint8_t *d_test, void *stream);
+/* the counters as the full symmetric matrix, out[a * n_pair + b] (host array); enqueued behind the work of `stream`, which
+ * is synchronised */
+int tsim_pairs_read(tsim_pairs *h, uint64_t *out, void *stream);
+/* zeroes the counters, asynchronous on `stream` */
+int tsim_pairs_reset(tsim_pairs *h, void *stream);
+/* out[0] n_pair, [1] workspace bytes, [2] rows per slab, [3] kernel launches so far */
+int tsim_pairs_info(const tsim_pairs *h, int64_t out[4]);
+
 /* ---- stim's shot-data formats on the device (stim.read_shot_data_file / write_shot_data_file, the samplers'
  *      sample_write, CompiledMeasurementsToDetectionEventsConverter.convert_file) ------------------------------------
  * format: 0 "01", 1 "b8", 2 "r8", 3 "ptb64", 4 "hits", 5 "dets" (layouts: tsim_amd/shotdata.py).  A handle of its own,

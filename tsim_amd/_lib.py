@@ -104,6 +104,12 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_m2d_convert_device": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P]),
     "tsim_m2d_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_tally_rows_device": (C.c_int, [_I32, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P]),
+    "tsim_pairs_create": (C.c_int, [_I32, _I32, _P, _I32, C.POINTER(_P)]),
+    "tsim_pairs_destroy": (None, [_P]),
+    "tsim_pairs_add_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "tsim_pairs_read": (C.c_int, [_P, _P, _P]),
+    "tsim_pairs_reset": (C.c_int, [_P, _P]),
+    "tsim_pairs_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_shotdata_create": (C.c_int, [_I32, C.POINTER(_P)]),
     "tsim_shotdata_destroy": (None, [_P]),
     "tsim_shotdata_encode": (C.c_int, [_P, _I32, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(_I64), _P]),

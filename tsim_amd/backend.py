@@ -381,6 +381,31 @@ class HipProgram:
                                                     C.c_void_p(int(d_counts)), C.c_void_p(stream or self.stream_ptr())),
                    "tsim_tally_rows_device")
 
+    def pairs_create(self, n_cols: int, pair_columns) -> int:
+        """A pair counter on this program's device (``tsim_pairs_create``, include/tsim_hip.h): the handle, to be given
+        back to :meth:`pairs_destroy`."""
+        pc = np.ascontiguousarray(pair_columns, dtype=np.int32)
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_pairs_create(self.device, int(n_cols), _lib.ptr(pc) if pc.size else None, int(pc.size), C.byref(h)),
+                   "tsim_pairs_create")
+        return h.value
+
+    def pairs_add_device(self, handle: int, d_rows: int, n: int, row_bytes: int, *, d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
+        """Pair counts over bit-packed device rows, accumulated in the handle (``tsim_pairs_add_device``); asynchronous on
+        ``stream`` (0: the handle's stream)."""
+        _lib.check(self._lib.tsim_pairs_add_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
+                                                   C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
+                                                   C.c_void_p(stream or self.stream_ptr())), "tsim_pairs_add_device")
+
+    def pairs_read(self, handle: int, k: int, *, stream: int = 0) -> np.ndarray:
+        """The handle's counters as the symmetric int64 ``[k, k]`` matrix, behind the work of ``stream`` (``tsim_pairs_read``)."""
+        out = np.zeros((int(k), int(k)), dtype=np.uint64)
+        _lib.check(self._lib.tsim_pairs_read(C.c_void_p(handle), _lib.ptr(out), C.c_void_p(stream or self.stream_ptr())), "tsim_pairs_read")
+        return out.astype(np.int64)
+
+    def pairs_destroy(self, handle: int) -> None:
+        self._lib.tsim_pairs_destroy(C.c_void_p(handle))
+
     def sample_batch_device(self, d_f: int, B: int, num_f: int, key, d_out: int, *,
                             shot_offset: int = 0, d_norm_dev: int = 0, stream: int = 0) -> None:
         """Asynchronous launch on the handle's stream (``stream``: a HIP stream of the caller instead); buffers are raw

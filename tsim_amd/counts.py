@@ -6,7 +6,12 @@ instead of downloading them: only the counters cross PCIe.  The results are exac
 the same seed and arguments they are the numpy tally (:func:`tally_rows`) of what ``sample()`` returns, and the key
 chains stand where ``sample()`` would leave them.
 
-:func:`tally_rows_device` runs the kernel on device rows the caller owns (``m2d`` output, ``sample_steps_device`` rows).
+``pair_columns`` adds the second-order statistic: ``pair_counts[a, b]``, the kept shots with columns ``pair_columns[a]``
+and ``pair_columns[b]`` both set (a binary ``X^T X`` by the pair kernels, ``tsim_pairs_*``, ``csrc/tsim_pairs.hip.h``), and
+:meth:`ShotCounts.pair_correlations`, the p_ij estimator computed from it.
+
+:func:`tally_rows_device` / :func:`tally_pairs_device` run the kernels on device rows the caller owns (``m2d`` output,
+``sample_steps_device`` rows).
 """
 
 from __future__ import annotations
@@ -19,16 +24,20 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["ShotCounts", "tally_rows", "tally_rows_device", "counters_length", "MAX_HISTOGRAM_COLUMNS"]
+__all__ = ["ShotCounts", "tally_rows", "tally_rows_device", "tally_pairs_device", "counters_length", "check_pair_columns",
+           "pair_correlations_from_moments", "MAX_HISTOGRAM_COLUMNS", "MAX_PAIR_COLUMNS"]
 
 MAX_HISTOGRAM_COLUMNS = 16
+MAX_PAIR_COLUMNS = 4096
 
 
 @dataclass(frozen=True, eq=False)
 class ShotCounts:
     """Counts over the kept shots of a request.  ``column_counts[c]``: kept shots with column ``c`` set (detectors, then
     observables); ``histogram[b]``: kept shots whose bits at ``histogram_columns`` spell ``b`` (bit ``i`` = column
-    ``histogram_columns[i]``; no columns: one bin, ``kept``)."""
+    ``histogram_columns[i]``; no columns: one bin, ``kept``).  ``pair_counts[a, b]`` (int64, symmetric; ``None`` when no
+    ``pair_columns`` were asked for): kept shots with columns ``pair_columns[a]`` and ``pair_columns[b]`` both set - its
+    diagonal is ``column_counts[list(pair_columns)]``."""
 
     shots: int
     kept: int
@@ -37,6 +46,8 @@ class ShotCounts:
     num_detectors: int
     histogram_columns: tuple
     histogram: np.ndarray
+    pair_columns: tuple = ()
+    pair_counts: np.ndarray | None = None
 
     @property
     def detector_counts(self) -> np.ndarray:
@@ -56,7 +67,20 @@ class ShotCounts:
         return (self.shots == other.shots and self.kept == other.kept
                 and self.kept_with_observable_flip == other.kept_with_observable_flip
                 and self.num_detectors == other.num_detectors and tuple(self.histogram_columns) == tuple(other.histogram_columns)
-                and np.array_equal(self.column_counts, other.column_counts) and np.array_equal(self.histogram, other.histogram))
+                and np.array_equal(self.column_counts, other.column_counts) and np.array_equal(self.histogram, other.histogram)
+                and tuple(self.pair_columns) == tuple(other.pair_columns)
+                and (self.pair_counts is None) == (other.pair_counts is None)
+                and (self.pair_counts is None or np.array_equal(self.pair_counts, other.pair_counts)))
+
+    def pair_correlations(self) -> np.ndarray:
+        """The float64 ``[k, k]`` matrix of the p_ij estimator over ``pair_columns`` (diagonal NaN):
+        :func:`pair_correlations_from_moments` of ``pair_counts / kept``."""
+        if self.pair_counts is None:
+            raise ValueError("no pair counts: ask count() for pair_columns")
+        n = np.asarray(self.pair_counts, dtype=np.float64)
+        if self.kept == 0:
+            return np.full(n.shape, np.nan)
+        return pair_correlations_from_moments(np.diagonal(n) / self.kept, n / self.kept)
 
     __hash__ = None
 
@@ -89,6 +113,49 @@ def check_histogram_columns(columns, n_cols: int) -> tuple:
     return tuple(int(c) for c in cols)
 
 
+def check_pair_columns(columns, n_cols: int, num_detectors: int) -> tuple:
+    """The selection of ``count(pair_columns=...)`` as a tuple of ints: ``None`` / ``()`` (none), ``"all"`` (every column),
+    ``"detectors"`` (columns ``0 .. num_detectors - 1``) or a sequence of distinct indices ``0 <= c < n_cols`` in any
+    order; at most 4096 (raises ``ValueError``)."""
+    if columns is None:
+        return ()
+    if isinstance(columns, str):
+        if columns not in ("all", "detectors"):
+            raise ValueError(f'pair_columns must be "all", "detectors" or a sequence of column indices, got {columns!r}')
+        count = int(n_cols) if columns == "all" else int(num_detectors)
+        if count > MAX_PAIR_COLUMNS:
+            raise ValueError(f"at most {MAX_PAIR_COLUMNS} pair columns, got {count}")
+        return tuple(range(count))
+    cols = np.asarray(list(columns) if not isinstance(columns, np.ndarray) else columns)
+    if cols.ndim != 1 or (cols.size and not np.issubdtype(cols.dtype, np.integer)):
+        raise ValueError("pair_columns must be a sequence of column indices")
+    if cols.size > MAX_PAIR_COLUMNS:
+        raise ValueError(f"at most {MAX_PAIR_COLUMNS} pair columns, got {cols.size}")
+    if cols.size and (cols.min() < 0 or cols.max() >= n_cols):
+        raise ValueError(f"pair columns must lie in 0 .. {n_cols - 1}, got {cols.tolist()}")
+    if len(set(cols.tolist())) != cols.size:
+        raise ValueError(f"pair columns must be distinct, got {cols.tolist()}")
+    return tuple(int(c) for c in cols)
+
+
+def pair_correlations_from_moments(x, xx) -> np.ndarray:
+    """The standard p_ij estimator from first moments ``x[i] = <x_i>`` and second moments ``xx[i, j] = <x_i x_j>``:
+    ``p_ij = 1/2 - sqrt(1/4 - (xx_ij - x_i x_j) / (1 - 2 (x_i + x_j - 2 xx_ij)))``.  For two detectors that share one
+    error mechanism of probability ``p`` and otherwise see independent errors it is ``p`` on the exact moments.  NaN on
+    the diagonal and where the denominator or the radicand is not positive."""
+    x = np.asarray(x, dtype=np.float64)
+    xx = np.asarray(xx, dtype=np.float64)
+    if x.ndim != 1 or xx.shape != (x.size, x.size):
+        raise ValueError(f"moments of shapes {x.shape} and {xx.shape}: expected [k] and [k, k]")
+    xi, xj = x[:, None], x[None, :]
+    den = 1.0 - 2.0 * (xi + xj - 2.0 * xx)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rad = 0.25 - (xx - xi * xj) / np.where(den > 0, den, np.nan)
+        p = 0.5 - np.sqrt(np.where(rad > 0, rad, np.nan))
+    p[np.arange(x.size), np.arange(x.size)] = np.nan
+    return p
+
+
 def default_histogram_columns(num_detectors: int, n_cols: int) -> tuple:
     """The observables when there are 1 .. 16 of them, else none."""
     n_obs = n_cols - num_detectors
@@ -98,8 +165,10 @@ def default_histogram_columns(num_detectors: int, n_cols: int) -> tuple:
 class _HostTally:
     """The numpy statement of the tally, accumulated batch by batch (memory O(columns + bins))."""
 
-    def __init__(self, n_cols: int, num_detectors: int, postselection_mask, histogram_columns):
+    def __init__(self, n_cols: int, num_detectors: int, postselection_mask, histogram_columns, pair_columns=()):
         self.n_cols, self.nd = int(n_cols), int(num_detectors)
+        self.pc = tuple(pair_columns)
+        self.pairs = np.zeros((len(self.pc), len(self.pc)), dtype=np.int64) if self.pc else None
         self.mask = None if postselection_mask is None else np.asarray(postselection_mask, dtype=np.bool_)
         self.hc = tuple(histogram_columns)
         self.shots = self.kept = self.kept_obs = 0
@@ -118,14 +187,19 @@ class _HostTally:
         for i, c in enumerate(self.hc):
             idx |= rows[:, c].astype(np.int64) << i
         self.hist += np.bincount(idx, minlength=len(self.hist))
+        if self.pc:  # (float64 products of 0/1 are exact below 2^53 rows; BLAS does not multiply integers)
+            sel = rows[:, list(self.pc)].astype(np.float64)
+            self.pairs += np.rint(sel.T @ sel).astype(np.int64)
 
     def result(self) -> ShotCounts:
-        return ShotCounts(self.shots, self.kept, self.kept_obs, self.cols.copy(), self.nd, self.hc, self.hist.copy())
+        return ShotCounts(self.shots, self.kept, self.kept_obs, self.cols.copy(), self.nd, self.hc, self.hist.copy(), self.pc,
+                          None if self.pairs is None else self.pairs.copy())
 
 
-def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_columns=()) -> ShotCounts:
+def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_columns=(), pair_columns=()) -> ShotCounts:
     """The tally of boolean rows (detectors, then observables) in numpy: a row is kept iff no masked detector is set; the
-    column counts, ``kept_with_observable_flip`` (a set observable) and the histogram are taken over the kept rows."""
+    column counts, ``kept_with_observable_flip`` (a set observable), the histogram and the pair counts over
+    ``pair_columns`` (:func:`check_pair_columns`) are taken over the kept rows."""
     rows = np.asarray(rows, dtype=np.bool_)
     if rows.ndim != 2:
         raise ValueError(f"rows must be 2-D, got shape {rows.shape}")
@@ -134,7 +208,8 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
         raise ValueError(f"num_detectors={num_detectors} of {n_cols} columns")
     if postselection_mask is not None and np.asarray(postselection_mask).shape != (num_detectors,):
         raise ValueError(f"postselection_mask must have shape ({num_detectors},), got {np.asarray(postselection_mask).shape}")
-    t = _HostTally(n_cols, num_detectors, postselection_mask, check_histogram_columns(histogram_columns, n_cols))
+    t = _HostTally(n_cols, num_detectors, postselection_mask, check_histogram_columns(histogram_columns, n_cols),
+                   check_pair_columns(pair_columns, n_cols, num_detectors))
     t.add(rows)
     return t.result()
 
@@ -167,16 +242,50 @@ def tally_rows_device(d_rows: int, n: int, *, row_bytes: int, n_cols: int, d_cou
                "tsim_tally_rows_device")
 
 
+def tally_pairs_device(d_rows: int, n: int, *, row_bytes: int, n_cols: int, pair_columns, d_xor: int = 0, d_test: int = 0,
+                       device: int = 0, stream: int = 0) -> np.ndarray:
+    """Pair counts over ``n`` bit-packed device rows the caller owns (laid out as for :func:`tally_rows_device`, ``d_xor`` /
+    ``d_test`` meaning the same): the symmetric int64 ``[k, k]`` matrix over ``pair_columns`` (distinct indices, at most
+    4096).  Runs on ``stream`` (0: the null stream) of ``device`` and returns when the counts are on the host."""
+    n, n_cols = int(n), int(n_cols)
+    if n < 0:
+        raise ValueError(f"n must be non-negative, got {n}")
+    if n_cols < 1:
+        raise ValueError(f"n_cols must be at least 1, got {n_cols}")
+    if int(row_bytes) < (n_cols + 7) // 8:
+        raise ValueError(f"rows of {row_bytes} bytes cannot hold {n_cols} columns")
+    pc = np.asarray(check_pair_columns(pair_columns, n_cols, n_cols), dtype=np.int32)
+    if pc.size == 0:
+        raise ValueError("pair_columns is empty")
+    lib = _lib.load()
+    h = C.c_void_p()
+    _lib.check(lib.tsim_pairs_create(int(device), n_cols, _lib.ptr(pc), int(pc.size), C.byref(h)), "tsim_pairs_create")
+    try:
+        st = C.c_void_p(int(stream)) if stream else None
+        _lib.check(lib.tsim_pairs_add_device(h, C.c_void_p(int(d_rows)), n, int(row_bytes), C.c_void_p(int(d_xor)) if d_xor else None,
+                                             C.c_void_p(int(d_test)) if d_test else None, st), "tsim_pairs_add_device")
+        out = np.zeros((pc.size, pc.size), dtype=np.uint64)
+        _lib.check(lib.tsim_pairs_read(h, _lib.ptr(out), st), "tsim_pairs_read")
+    finally:
+        lib.tsim_pairs_destroy(h)
+    return out.astype(np.int64)
+
+
 class _DeviceTally:
     """The counters of one ``count()`` on a program's device, the masks in the layout of its rows, and the shot range
     ``[lo, hi)`` of the rows handed to it that belong to the request (a reference row riding in front, padding behind)."""
 
     def __init__(self, hp, n_cols: int, num_detectors: int, *, xor_bits=None, test_bits=None, histogram_columns=(), lo: int = 0,
-                 hi: int = 0):
+                 hi: int = 0, pair_columns=()):
         self.hp, self.n_cols, self.nd, self.hc = hp, int(n_cols), int(num_detectors), tuple(histogram_columns)
         self.lo, self.hi = int(lo), int(hi)
+        self.pc = tuple(pair_columns)
         self._bufs = []
+        self._pairs = None       # the pair counter's handle (tsim_pairs), when pair columns are asked for
+        self._pairs_stream = 0   # the stream its launches went to
         try:
+            if self.pc:
+                self._pairs = hp.pairs_create(self.n_cols, self.pc)
             self.d_counts = self._upload(np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64))
             self.d_xor = self._upload(self._row(xor_bits)) if xor_bits is not None and np.any(xor_bits) else None
             self.d_test = self._upload(self._row(test_bits)) if test_bits is not None else None
@@ -205,14 +314,27 @@ class _DeviceTally:
                                   d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
                                   d_test=self.d_test.ptr if self.d_test is not None else 0,
                                   observables=(self.nd, self.n_cols), histogram_columns=self.hc, stream=stream)
+        if self._pairs is not None:
+            self._pairs_stream = stream
+            self.hp.pairs_add_device(self._pairs, d_first + (a - r0) * row_bytes, b - a, row_bytes,
+                                     d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
+                                     d_test=self.d_test.ptr if self.d_test is not None else 0, stream=stream)
 
     def result(self, shots: int) -> ShotCounts:
         """The counters, once every tally launch has completed (the caller has synchronised their streams)."""
         c = np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64)
         self.hp.d2h(c, self.d_counts)
-        return ShotCounts.from_counters(c, shots=shots, n_cols=self.n_cols, num_detectors=self.nd, histogram_columns=self.hc)
+        out = ShotCounts.from_counters(c, shots=shots, n_cols=self.n_cols, num_detectors=self.nd, histogram_columns=self.hc)
+        if self._pairs is None:
+            return out
+        pairs = self.hp.pairs_read(self._pairs, len(self.pc), stream=self._pairs_stream)
+        return ShotCounts(out.shots, out.kept, out.kept_with_observable_flip, out.column_counts, out.num_detectors,
+                          out.histogram_columns, out.histogram, self.pc, pairs)
 
     def release(self) -> None:
+        if self._pairs is not None:
+            self.hp.pairs_destroy(self._pairs)
+            self._pairs = None
         for buf in self._bufs:
             buf.free()
         self._bufs = []
