@@ -455,6 +455,49 @@ int tsim_pairs_reset(tsim_pairs *h, void *stream);
 /* out[0] n_pair, [1] workspace bytes, [2] rows per slab, [3] kernel launches so far */
 int tsim_pairs_info(const tsim_pairs *h, int64_t out[4]);
 
+/* ---- pattern counts over bit-packed device rows (count(pattern_columns=...): which whole patterns occurred, how often)
+ *      and the lookup decoder built from them (count(decoder=...)) ---------------------------------------------------
+ * The distinct patterns of the kept rows, each with its exact uint64 count.  Rows, d_xor and d_test are those of
+ * tsim_tally_rows_device and mean the same: a row is KEPT iff (row ^ xor) & test == 0, and its pattern is row ^ xor at
+ * the n_key key columns (distinct, any order, each in 0 .. n_cols-1; no limit but memory), bit i of the pattern = column
+ * key_cols[i]; pad bits and padding bytes of the rows never belong to a pattern.  A handle of its own, bound to HIP
+ * device `device`: an open-addressing table of `capacity` slots (1 .. 2^30, rounded up to a power of two; 16 bytes per
+ * slot for n_key <= 63, 16 + 8 * ceil(n_key / 64) otherwise, 8 more once tsim_rowtab_load gave it values), zero after
+ * create.  Keys of at most 63 bits are the compared-and-swapped word themselves; wider keys are found by a 63-bit
+ * fingerprint, and EVERY kept row's full key is then compared with the key its slot stores (a second launch): a
+ * mismatch is counted (info [5]) and makes tsim_rowtab_read fail - a count is exact or the call says so.  A row whose
+ * pattern is absent and finds no empty slot within min(capacity, 1024) probes is counted as OVERFLOW (info [4]) and
+ * dropped; slots are never freed, so every pattern in the table carries its full count and
+ * sum(counts) + overflow == kept at all times.  Arguments are checked before any device call. */
+typedef struct tsim_rowtab tsim_rowtab;
+int tsim_rowtab_create(int32_t device, int32_t n_cols, const int32_t *key_cols, int32_t n_key, int64_t capacity, tsim_rowtab **out);
+void tsim_rowtab_destroy(tsim_rowtab *h);
+/* ACCUMULATES n rows into the table (one launch; two for keys wider than 63 bits); asynchronous on `stream` (NULL: the
+ * null stream).  Calls on one handle go to one stream, or are ordered by the caller.  n == 0 returns 0 without a launch. */
+int tsim_rowtab_add_device(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                           const uint8_t *d_test, void *stream);
+/* the entries, in slot order: keys_out[e * ceil(n_key/8) ..] the pattern bit-packed little-endian over the key columns in
+ * the order given at create, counts_out[e] its rows (host arrays with room for max_entries); *n_entries: how many there
+ * are (TSIM_EINVAL when more than max_entries - *n_entries is set all the same).  Enqueued behind the work of `stream`,
+ * which is synchronised.  TSIM_ESTATE when a fingerprint collision was met: nothing is returned. */
+int tsim_rowtab_read(tsim_rowtab *h, uint8_t *keys_out, uint64_t *counts_out, int64_t max_entries, int64_t *n_entries, void *stream);
+/* empties the table and zeroes its counters, asynchronous on `stream` */
+int tsim_rowtab_reset(tsim_rowtab *h, void *stream);
+/* out[0] capacity, [1] distinct entries, [2] rows added, [3] rows kept, [4] overflow rows, [5] unresolved collisions
+ * (rows whose key differs from the key of the slot their fingerprint leads to), [6] kernel launches so far, [7] bytes
+ * of device memory.  Synchronises the device. */
+int tsim_rowtab_info(tsim_rowtab *h, int64_t out[8]);
+/* The lookup decoder.  tsim_rowtab_load replaces the table's contents by n distinct keys (host array, laid out as
+ * keys_out of tsim_rowtab_read) with one 8-byte value each (synchronous; TSIM_ENOTSUP when a key finds no slot).
+ * tsim_rowtab_decode_device then looks every kept row's key up, read-only (full keys compared), XORs the slot's value
+ * (0 for a key that is not in the table) with the row's columns obs_lo .. obs_hi - 1 (at most 64; bit i = column
+ * obs_lo + i) and ACCUMULATES into d_counters (uint64[3], 8-byte aligned, never zeroed here): [0] kept rows, [1] kept
+ * rows whose value differs from their observables, [2] kept rows whose key is not in the table.  Asynchronous on
+ * `stream`; TSIM_ESTATE before a load. */
+int tsim_rowtab_load(tsim_rowtab *h, const uint8_t *keys, const uint64_t *values, int64_t n);
+int tsim_rowtab_decode_device(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                              const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, void *stream);
+
 /* ---- stim's shot-data formats on the device (stim.read_shot_data_file / write_shot_data_file, the samplers'
  *      sample_write, CompiledMeasurementsToDetectionEventsConverter.convert_file) ------------------------------------
  * format: 0 "01", 1 "b8", 2 "r8", 3 "ptb64", 4 "hits", 5 "dets" (layouts: tsim_amd/shotdata.py).  A handle of its own,

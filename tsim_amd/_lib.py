@@ -110,6 +110,14 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_pairs_read": (C.c_int, [_P, _P, _P]),
     "tsim_pairs_reset": (C.c_int, [_P, _P]),
     "tsim_pairs_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "tsim_rowtab_create": (C.c_int, [_I32, _I32, _P, _I32, _I64, C.POINTER(_P)]),
+    "tsim_rowtab_destroy": (None, [_P]),
+    "tsim_rowtab_add_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "tsim_rowtab_read": (C.c_int, [_P, _P, _P, _I64, C.POINTER(_I64), _P]),
+    "tsim_rowtab_reset": (C.c_int, [_P, _P]),
+    "tsim_rowtab_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "tsim_rowtab_load": (C.c_int, [_P, _P, _P, _I64]),
+    "tsim_rowtab_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P]),
     "tsim_shotdata_create": (C.c_int, [_I32, C.POINTER(_P)]),
     "tsim_shotdata_destroy": (None, [_P]),
     "tsim_shotdata_encode": (C.c_int, [_P, _I32, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(_I64), _P]),

@@ -406,6 +406,56 @@ class HipProgram:
     def pairs_destroy(self, handle: int) -> None:
         self._lib.tsim_pairs_destroy(C.c_void_p(handle))
 
+    def rowtab_create(self, n_cols: int, key_columns, capacity: int) -> int:
+        """A row table on this program's device (``tsim_rowtab_create``, include/tsim_hip.h): the handle, to be given back
+        to :meth:`rowtab_destroy`."""
+        kc = np.ascontiguousarray(key_columns, dtype=np.int32)
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_rowtab_create(self.device, int(n_cols), _lib.ptr(kc) if kc.size else None, int(kc.size), int(capacity),
+                                                C.byref(h)), "tsim_rowtab_create")
+        return h.value
+
+    def rowtab_add_device(self, handle: int, d_rows: int, n: int, row_bytes: int, *, d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
+        """The patterns of bit-packed device rows, accumulated in the handle (``tsim_rowtab_add_device``); asynchronous on
+        ``stream`` (0: the handle's stream)."""
+        _lib.check(self._lib.tsim_rowtab_add_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
+                                                    C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
+                                                    C.c_void_p(stream or self.stream_ptr())), "tsim_rowtab_add_device")
+
+    def rowtab_read(self, handle: int, n_key: int, *, stream: int = 0):
+        """The handle's entries behind the work of ``stream``: ``(keys uint8[D, ceil(n_key/8)], counts uint64[D], info int64[8])``
+        in slot order (``tsim_rowtab_read``, ``tsim_rowtab_info``)."""
+        from .counts import rowtab_read
+
+        return rowtab_read(self._lib, C.c_void_p(handle), n_key, C.c_void_p(stream or self.stream_ptr()))
+
+    def rowtab_info(self, handle: int) -> list:
+        out = (C.c_int64 * 8)()
+        _lib.check(self._lib.tsim_rowtab_info(C.c_void_p(handle), out), "tsim_rowtab_info")
+        return list(out)
+
+    def rowtab_reset(self, handle: int, *, stream: int = 0) -> None:
+        _lib.check(self._lib.tsim_rowtab_reset(C.c_void_p(handle), C.c_void_p(stream or self.stream_ptr())), "tsim_rowtab_reset")
+
+    def rowtab_load(self, handle: int, keys: np.ndarray, values: np.ndarray) -> None:
+        """Replace the table's contents by distinct bit-packed keys with one uint64 value each (``tsim_rowtab_load``)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        _lib.check(self._lib.tsim_rowtab_load(C.c_void_p(handle), _lib.ptr(keys) if keys.size else None,
+                                              _lib.ptr(values) if values.size else None, int(values.size)), "tsim_rowtab_load")
+
+    def rowtab_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_xor: int = 0,
+                             d_test: int = 0, stream: int = 0) -> None:
+        """Look the rows' keys up in a loaded table and count kept / wrong / unknown into ``d_counters``
+        (``tsim_rowtab_decode_device``); asynchronous on ``stream`` (0: the handle's stream)."""
+        _lib.check(self._lib.tsim_rowtab_decode_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
+                                                       C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
+                                                       int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
+                                                       C.c_void_p(stream or self.stream_ptr())), "tsim_rowtab_decode_device")
+
+    def rowtab_destroy(self, handle: int) -> None:
+        self._lib.tsim_rowtab_destroy(C.c_void_p(handle))
+
     def sample_batch_device(self, d_f: int, B: int, num_f: int, key, d_out: int, *,
                             shot_offset: int = 0, d_norm_dev: int = 0, stream: int = 0) -> None:
         """Asynchronous launch on the handle's stream (``stream``: a HIP stream of the caller instead); buffers are raw

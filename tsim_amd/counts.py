@@ -10,8 +10,13 @@ chains stand where ``sample()`` would leave them.
 and ``pair_columns[b]`` both set (a binary ``X^T X`` by the pair kernels, ``tsim_pairs_*``, ``csrc/tsim_pairs.hip.h``), and
 :meth:`ShotCounts.pair_correlations`, the p_ij estimator computed from it.
 
-:func:`tally_rows_device` / :func:`tally_pairs_device` run the kernels on device rows the caller owns (``m2d`` output,
-``sample_steps_device`` rows).
+:func:`tally_rows_device` / :func:`tally_pairs_device` / :func:`tally_patterns_device` run the kernels on device rows the
+caller owns (``m2d`` output, ``sample_steps_device`` rows).
+
+``pattern_columns`` adds the joint statistic: the distinct patterns of the kept shots over those columns, each with its
+exact count (the row table, ``tsim_rowtab_*``, ``csrc/tsim_rowtab.hip.h``) - what ``np.unique(sample(), axis=0)`` gives
+without the rows crossing PCIe.  ``decoder`` (:class:`tsim_amd.decode.LookupDecoder`) applies a lookup decoder to every
+kept shot where it lies and counts the wrong predictions.
 """
 
 from __future__ import annotations
@@ -24,11 +29,13 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["ShotCounts", "tally_rows", "tally_rows_device", "tally_pairs_device", "counters_length", "check_pair_columns",
-           "pair_correlations_from_moments", "MAX_HISTOGRAM_COLUMNS", "MAX_PAIR_COLUMNS"]
+__all__ = ["ShotCounts", "tally_rows", "tally_rows_device", "tally_pairs_device", "tally_patterns_device", "counters_length",
+           "check_pair_columns", "check_pattern_columns", "pair_correlations_from_moments", "MAX_HISTOGRAM_COLUMNS",
+           "MAX_PAIR_COLUMNS", "DEFAULT_PATTERN_CAPACITY"]
 
 MAX_HISTOGRAM_COLUMNS = 16
 MAX_PAIR_COLUMNS = 4096
+DEFAULT_PATTERN_CAPACITY = 1 << 20
 
 
 @dataclass(frozen=True, eq=False)
@@ -37,7 +44,13 @@ class ShotCounts:
     observables); ``histogram[b]``: kept shots whose bits at ``histogram_columns`` spell ``b`` (bit ``i`` = column
     ``histogram_columns[i]``; no columns: one bin, ``kept``).  ``pair_counts[a, b]`` (int64, symmetric; ``None`` when no
     ``pair_columns`` were asked for): kept shots with columns ``pair_columns[a]`` and ``pair_columns[b]`` both set - its
-    diagonal is ``column_counts[list(pair_columns)]``."""
+    diagonal is ``column_counts[list(pair_columns)]``.  ``patterns`` (bool ``[D, k]``, columns in the order of
+    ``pattern_columns``) and ``pattern_counts`` (int64 ``[D]``; both ``None`` when no ``pattern_columns`` were asked for):
+    the distinct patterns of the kept shots over ``pattern_columns`` and how often each occurred, ordered by count
+    descending, ties by the bit-packed (little-endian) pattern bytes ascending; ``pattern_overflow``: kept shots whose
+    pattern found no room (``sum(pattern_counts) + pattern_overflow == kept``; the patterns present are exact).
+    ``decoded_errors`` / ``decoder_misses`` (``None`` without a decoder): kept shots whose observables differ from the
+    decoder's prediction, and kept shots whose syndrome the decoder does not know (it predicts no flip for them)."""
 
     shots: int
     kept: int
@@ -48,6 +61,12 @@ class ShotCounts:
     histogram: np.ndarray
     pair_columns: tuple = ()
     pair_counts: np.ndarray | None = None
+    pattern_columns: tuple = ()
+    patterns: np.ndarray | None = None
+    pattern_counts: np.ndarray | None = None
+    pattern_overflow: int = 0
+    decoded_errors: int | None = None
+    decoder_misses: int | None = None
 
     @property
     def detector_counts(self) -> np.ndarray:
@@ -70,7 +89,13 @@ class ShotCounts:
                 and np.array_equal(self.column_counts, other.column_counts) and np.array_equal(self.histogram, other.histogram)
                 and tuple(self.pair_columns) == tuple(other.pair_columns)
                 and (self.pair_counts is None) == (other.pair_counts is None)
-                and (self.pair_counts is None or np.array_equal(self.pair_counts, other.pair_counts)))
+                and (self.pair_counts is None or np.array_equal(self.pair_counts, other.pair_counts))
+                and tuple(self.pattern_columns) == tuple(other.pattern_columns)
+                and (self.patterns is None) == (other.patterns is None)
+                and (self.patterns is None or (np.array_equal(self.patterns, other.patterns)
+                                               and np.array_equal(self.pattern_counts, other.pattern_counts)))
+                and self.pattern_overflow == other.pattern_overflow
+                and self.decoded_errors == other.decoded_errors and self.decoder_misses == other.decoder_misses)
 
     def pair_correlations(self) -> np.ndarray:
         """The float64 ``[k, k]`` matrix of the p_ij estimator over ``pair_columns`` (diagonal NaN):
@@ -138,6 +163,54 @@ def check_pair_columns(columns, n_cols: int, num_detectors: int) -> tuple:
     return tuple(int(c) for c in cols)
 
 
+def check_pattern_columns(columns, n_cols: int, num_detectors: int) -> tuple:
+    """The selection of ``count(pattern_columns=...)`` as a tuple of ints: ``None`` / ``()`` (none), ``"all"`` (every
+    column), ``"detectors"`` (columns ``0 .. num_detectors - 1``) or a sequence of distinct indices ``0 <= c < n_cols`` in
+    any order, as many as there are columns (raises ``ValueError``)."""
+    if columns is None:
+        return ()
+    if isinstance(columns, str):
+        if columns not in ("all", "detectors"):
+            raise ValueError(f'pattern_columns must be "all", "detectors" or a sequence of column indices, got {columns!r}')
+        return tuple(range(int(n_cols) if columns == "all" else int(num_detectors)))
+    cols = np.asarray(list(columns) if not isinstance(columns, np.ndarray) else columns)
+    if cols.ndim != 1 or (cols.size and not np.issubdtype(cols.dtype, np.integer)):
+        raise ValueError("pattern_columns must be a sequence of column indices")
+    if cols.size and (cols.min() < 0 or cols.max() >= n_cols):
+        raise ValueError(f"pattern columns must lie in 0 .. {n_cols - 1}, got {cols.tolist()}")
+    if len(set(cols.tolist())) != cols.size:
+        raise ValueError(f"pattern columns must be distinct, got {cols.tolist()}")
+    return tuple(int(c) for c in cols)
+
+
+def check_pattern_capacity(capacity) -> int | None:
+    if capacity is None:
+        return None
+    if int(capacity) != capacity or not 1 <= int(capacity) <= 1 << 30:
+        raise ValueError(f"pattern_capacity must be an integer in 1 .. 2^30, got {capacity!r}")
+    return int(capacity)
+
+
+def ordered_patterns(keys: np.ndarray, counts: np.ndarray, k: int):
+    """Bit-packed patterns ``uint8[D, ceil(k/8)]`` with their counts -> ``(bool[D, k], int64[D])`` in the order of
+    :class:`ShotCounts`: count descending, ties by the packed bytes ascending."""
+    keys = np.asarray(keys, dtype=np.uint8).reshape(len(counts), (k + 7) // 8)
+    counts = np.asarray(counts).astype(np.int64)
+    order = np.lexsort(tuple(keys[:, j] for j in range(keys.shape[1] - 1, -1, -1)) + (-counts,))
+    bits = np.unpackbits(keys[order], axis=1, bitorder="little", count=k).astype(np.bool_)
+    return bits.reshape(len(counts), k), counts[order]
+
+
+def warn_pattern_overflow(counts: "ShotCounts", capacity) -> "ShotCounts":
+    if counts.pattern_overflow > 0:
+        import warnings
+
+        warnings.warn(f"count(): {counts.pattern_overflow} kept shots carry a pattern that found no room in a table of "
+                      f"pattern_capacity={capacity} (the {len(counts.pattern_counts)} patterns returned are exact); raise "
+                      "pattern_capacity", RuntimeWarning, stacklevel=3)
+    return counts
+
+
 def pair_correlations_from_moments(x, xx) -> np.ndarray:
     """The standard p_ij estimator from first moments ``x[i] = <x_i>`` and second moments ``xx[i, j] = <x_i x_j>``:
     ``p_ij = 1/2 - sqrt(1/4 - (xx_ij - x_i x_j) / (1 - 2 (x_i + x_j - 2 xx_ij)))``.  For two detectors that share one
@@ -165,8 +238,14 @@ def default_histogram_columns(num_detectors: int, n_cols: int) -> tuple:
 class _HostTally:
     """The numpy statement of the tally, accumulated batch by batch (memory O(columns + bins))."""
 
-    def __init__(self, n_cols: int, num_detectors: int, postselection_mask, histogram_columns, pair_columns=()):
+    def __init__(self, n_cols: int, num_detectors: int, postselection_mask, histogram_columns, pair_columns=(), pattern_columns=(),
+                 pattern_capacity=None, decoder=None):
         self.n_cols, self.nd = int(n_cols), int(num_detectors)
+        self.tc, self.tcap = tuple(pattern_columns), pattern_capacity
+        self.table = {}          # packed pattern bytes -> rows, in the order of first appearance
+        self.overflow = 0
+        self.decoder = decoder
+        self.errors = self.misses = 0
         self.pc = tuple(pair_columns)
         self.pairs = np.zeros((len(self.pc), len(self.pc)), dtype=np.int64) if self.pc else None
         self.mask = None if postselection_mask is None else np.asarray(postselection_mask, dtype=np.bool_)
@@ -190,16 +269,42 @@ class _HostTally:
         if self.pc:  # (float64 products of 0/1 are exact below 2^53 rows; BLAS does not multiply integers)
             sel = rows[:, list(self.pc)].astype(np.float64)
             self.pairs += np.rint(sel.T @ sel).astype(np.int64)
+        if self.tc and len(rows):
+            packed = np.packbits(rows[:, list(self.tc)], axis=1, bitorder="little")
+            uniq, first, cnt = np.unique(packed, axis=0, return_index=True, return_counts=True)
+            for i in np.argsort(first, kind="stable"):  # (a capacity admits patterns in the order of first appearance)
+                key = uniq[i].tobytes()
+                if key in self.table:
+                    self.table[key] += int(cnt[i])
+                elif self.tcap is None or len(self.table) < self.tcap:
+                    self.table[key] = int(cnt[i])
+                else:
+                    self.overflow += int(cnt[i])
+        if self.decoder is not None and len(rows):
+            dets, obs = rows[:, : self.nd], rows[:, self.nd:]
+            self.errors += int((self.decoder.decode(dets) != obs).any(axis=1).sum())
+            self.misses += int(self.decoder.missed(dets).sum())
 
     def result(self) -> ShotCounts:
+        patterns = pattern_counts = None
+        if self.tc:
+            kb = (len(self.tc) + 7) // 8
+            keys = np.frombuffer(b"".join(self.table), dtype=np.uint8).reshape(len(self.table), kb)
+            patterns, pattern_counts = ordered_patterns(keys, np.fromiter(self.table.values(), np.int64, len(self.table)), len(self.tc))
         return ShotCounts(self.shots, self.kept, self.kept_obs, self.cols.copy(), self.nd, self.hc, self.hist.copy(), self.pc,
-                          None if self.pairs is None else self.pairs.copy())
+                          None if self.pairs is None else self.pairs.copy(), self.tc, patterns, pattern_counts, self.overflow,
+                          None if self.decoder is None else self.errors, None if self.decoder is None else self.misses)
 
 
-def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_columns=(), pair_columns=()) -> ShotCounts:
+def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_columns=(), pair_columns=(), pattern_columns=(),
+               pattern_capacity=None, decoder=None) -> ShotCounts:
     """The tally of boolean rows (detectors, then observables) in numpy: a row is kept iff no masked detector is set; the
     column counts, ``kept_with_observable_flip`` (a set observable), the histogram and the pair counts over
-    ``pair_columns`` (:func:`check_pair_columns`) are taken over the kept rows."""
+    ``pair_columns`` (:func:`check_pair_columns`) are taken over the kept rows.  ``pattern_columns``
+    (:func:`check_pattern_columns`): the distinct patterns of the kept rows (``np.unique``) with their counts, in the order
+    of :class:`ShotCounts`; ``pattern_capacity`` (default: no limit) admits that many patterns in the order of first
+    appearance and counts the rows of the others in ``pattern_overflow``.  ``decoder``: a
+    :class:`tsim_amd.decode.LookupDecoder` applied to the kept rows."""
     rows = np.asarray(rows, dtype=np.bool_)
     if rows.ndim != 2:
         raise ValueError(f"rows must be 2-D, got shape {rows.shape}")
@@ -209,9 +314,23 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
     if postselection_mask is not None and np.asarray(postselection_mask).shape != (num_detectors,):
         raise ValueError(f"postselection_mask must have shape ({num_detectors},), got {np.asarray(postselection_mask).shape}")
     t = _HostTally(n_cols, num_detectors, postselection_mask, check_histogram_columns(histogram_columns, n_cols),
-                   check_pair_columns(pair_columns, n_cols, num_detectors))
+                   check_pair_columns(pair_columns, n_cols, num_detectors),
+                   check_pattern_columns(pattern_columns, n_cols, num_detectors), check_pattern_capacity(pattern_capacity),
+                   check_decoder(decoder, n_cols, num_detectors))
     t.add(rows)
     return t.result()
+
+
+def check_decoder(decoder, n_cols: int, num_detectors: int):
+    """``decoder`` (or ``None``) when it fits rows of ``num_detectors`` detectors and ``n_cols - num_detectors`` observables."""
+    if decoder is None:
+        return None
+    if (decoder.num_detectors, decoder.num_observables) != (int(num_detectors), int(n_cols) - int(num_detectors)):
+        raise ValueError(f"the decoder is for {decoder.num_detectors} detectors and {decoder.num_observables} observables, the rows "
+                         f"have {num_detectors} and {int(n_cols) - int(num_detectors)}")
+    if decoder.num_detectors < 1:
+        raise ValueError("a decoder needs at least one detector")
+    return decoder
 
 
 def tally_rows_device(d_rows: int, n: int, *, row_bytes: int, n_cols: int, d_counts: int, d_xor: int = 0, d_test: int = 0,
@@ -271,21 +390,75 @@ def tally_pairs_device(d_rows: int, n: int, *, row_bytes: int, n_cols: int, pair
     return out.astype(np.int64)
 
 
+def tally_patterns_device(d_rows: int, n: int, *, row_bytes: int, n_cols: int, pattern_columns, capacity: int = DEFAULT_PATTERN_CAPACITY,
+                          d_xor: int = 0, d_test: int = 0, device: int = 0, stream: int = 0):
+    """Pattern counts over ``n`` bit-packed device rows the caller owns (laid out as for :func:`tally_rows_device`, ``d_xor`` /
+    ``d_test`` meaning the same): ``(patterns bool[D, k], counts int64[D], overflow)`` over ``pattern_columns`` (distinct
+    indices, any number), ordered as in :class:`ShotCounts`, from a table of ``capacity`` slots.  Runs on ``stream`` (0: the
+    null stream) of ``device`` and returns when the entries are on the host."""
+    n, n_cols = int(n), int(n_cols)
+    if n < 0:
+        raise ValueError(f"n must be non-negative, got {n}")
+    if n_cols < 1:
+        raise ValueError(f"n_cols must be at least 1, got {n_cols}")
+    if int(row_bytes) < (n_cols + 7) // 8:
+        raise ValueError(f"rows of {row_bytes} bytes cannot hold {n_cols} columns")
+    tc = np.asarray(check_pattern_columns(pattern_columns, n_cols, n_cols), dtype=np.int32)
+    if tc.size == 0:
+        raise ValueError("pattern_columns is empty")
+    lib = _lib.load()
+    h = C.c_void_p()
+    _lib.check(lib.tsim_rowtab_create(int(device), n_cols, _lib.ptr(tc), int(tc.size), check_pattern_capacity(capacity), C.byref(h)),
+               "tsim_rowtab_create")
+    try:
+        st = C.c_void_p(int(stream)) if stream else None
+        _lib.check(lib.tsim_rowtab_add_device(h, C.c_void_p(int(d_rows)), n, int(row_bytes), C.c_void_p(int(d_xor)) if d_xor else None,
+                                              C.c_void_p(int(d_test)) if d_test else None, st), "tsim_rowtab_add_device")
+        keys, counts, info = rowtab_read(lib, h, int(tc.size), st)
+    finally:
+        lib.tsim_rowtab_destroy(h)
+    return ordered_patterns(keys, counts, int(tc.size)) + (int(info[4]),)
+
+
+def rowtab_read(lib, handle, n_key: int, stream):
+    """``(keys uint8[D, ceil(n_key/8)], counts uint64[D], info int64[8])`` of a row table (``tsim_rowtab_info``, ``tsim_rowtab_read``)."""
+    info = (C.c_int64 * 8)()
+    _lib.check(lib.tsim_rowtab_info(handle, info), "tsim_rowtab_info")
+    entries = int(info[1])
+    keys = np.zeros((entries, (int(n_key) + 7) // 8), dtype=np.uint8)
+    counts = np.zeros(entries, dtype=np.uint64)
+    got = C.c_int64()
+    _lib.check(lib.tsim_rowtab_read(handle, _lib.ptr(keys), _lib.ptr(counts), entries, C.byref(got), stream), "tsim_rowtab_read")
+    return keys, counts, np.array(list(info), dtype=np.int64)
+
+
 class _DeviceTally:
     """The counters of one ``count()`` on a program's device, the masks in the layout of its rows, and the shot range
     ``[lo, hi)`` of the rows handed to it that belong to the request (a reference row riding in front, padding behind)."""
 
     def __init__(self, hp, n_cols: int, num_detectors: int, *, xor_bits=None, test_bits=None, histogram_columns=(), lo: int = 0,
-                 hi: int = 0, pair_columns=()):
+                 hi: int = 0, pair_columns=(), pattern_columns=(), pattern_capacity=None, decoder=None):
         self.hp, self.n_cols, self.nd, self.hc = hp, int(n_cols), int(num_detectors), tuple(histogram_columns)
         self.lo, self.hi = int(lo), int(hi)
         self.pc = tuple(pair_columns)
+        self.tc = tuple(pattern_columns)
+        self.decoder = decoder
         self._bufs = []
         self._pairs = None       # the pair counter's handle (tsim_pairs), when pair columns are asked for
         self._pairs_stream = 0   # the stream its launches went to
+        self._table = None       # the row table's handle (tsim_rowtab), when pattern columns are asked for
+        self._lookup = None      # the decoder's row table, loaded from the host
+        self.d_decoded = None    # its three counters
         try:
             if self.pc:
                 self._pairs = hp.pairs_create(self.n_cols, self.pc)
+            if self.tc:
+                self._table = hp.rowtab_create(self.n_cols, self.tc, pattern_capacity or DEFAULT_PATTERN_CAPACITY)
+            if decoder is not None:
+                keys, values = decoder.table()
+                self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))
+                hp.rowtab_load(self._lookup, keys, values)
+                self.d_decoded = self._upload(np.zeros(3, dtype=np.uint64))
             self.d_counts = self._upload(np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64))
             self.d_xor = self._upload(self._row(xor_bits)) if xor_bits is not None and np.any(xor_bits) else None
             self.d_test = self._upload(self._row(test_bits)) if test_bits is not None else None
@@ -319,19 +492,44 @@ class _DeviceTally:
             self.hp.pairs_add_device(self._pairs, d_first + (a - r0) * row_bytes, b - a, row_bytes,
                                      d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
                                      d_test=self.d_test.ptr if self.d_test is not None else 0, stream=stream)
+        if self._table is not None or self._lookup is not None:
+            self._pairs_stream = stream
+            masks = dict(d_xor=self.d_xor.ptr if self.d_xor is not None else 0, d_test=self.d_test.ptr if self.d_test is not None else 0,
+                         stream=stream)
+            if self._table is not None:
+                self.hp.rowtab_add_device(self._table, d_first + (a - r0) * row_bytes, b - a, row_bytes, **masks)
+            if self._lookup is not None:
+                self.hp.rowtab_decode_device(self._lookup, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
+                                             self.d_decoded.ptr, **masks)
 
     def result(self, shots: int) -> ShotCounts:
         """The counters, once every tally launch has completed (the caller has synchronised their streams)."""
         c = np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64)
         self.hp.d2h(c, self.d_counts)
         out = ShotCounts.from_counters(c, shots=shots, n_cols=self.n_cols, num_detectors=self.nd, histogram_columns=self.hc)
-        if self._pairs is None:
+        if self._pairs is None and self._table is None and self._lookup is None:
             return out
-        pairs = self.hp.pairs_read(self._pairs, len(self.pc), stream=self._pairs_stream)
+        pairs = self.hp.pairs_read(self._pairs, len(self.pc), stream=self._pairs_stream) if self._pairs is not None else None
+        patterns = pattern_counts = errors = misses = None
+        overflow = 0
+        if self._table is not None:
+            keys, cnt, info = self.hp.rowtab_read(self._table, len(self.tc), stream=self._pairs_stream)
+            patterns, pattern_counts = ordered_patterns(keys, cnt, len(self.tc))
+            overflow = int(info[4])
+        if self._lookup is not None:
+            self.hp.stream_synchronize(self._pairs_stream)
+            d = np.zeros(3, dtype=np.uint64)
+            self.hp.d2h(d, self.d_decoded)
+            errors, misses = int(d[1]), int(d[2])
         return ShotCounts(out.shots, out.kept, out.kept_with_observable_flip, out.column_counts, out.num_detectors,
-                          out.histogram_columns, out.histogram, self.pc, pairs)
+                          out.histogram_columns, out.histogram, self.pc, pairs, self.tc, patterns, pattern_counts, overflow,
+                          errors, misses)
 
     def release(self) -> None:
+        for name in ("_table", "_lookup"):
+            if getattr(self, name) is not None:
+                self.hp.rowtab_destroy(getattr(self, name))
+                setattr(self, name, None)
         if self._pairs is not None:
             self.hp.pairs_destroy(self._pairs)
             self._pairs = None

@@ -1028,21 +1028,31 @@ class _CompiledSamplerBase:
 
     # -- counts instead of rows (counts.py) ----------------------------------------------------------------------------
     def _count(self, shots: int, batch_size: int | None, *, mask: np.ndarray | None = None, xor_det: bool = False,
-               xor_obs: bool = False, histogram_columns=None, pair_columns=None, sample_kw: dict | None = None) -> ShotCounts:
+               xor_obs: bool = False, histogram_columns=None, pair_columns=None, pattern_columns=None,
+               pattern_capacity=counts_mod.DEFAULT_PATTERN_CAPACITY, decoder=None, sample_kw: dict | None = None) -> ShotCounts:
         """The tally of what ``sample()`` with the same arguments returns (rows: detectors, then observables), computed
         where the rows are.  Every batch, key and noise key ``sample()`` would use is used in the same order; only the
-        download is replaced.  ``mask``: the caller's post-selection mask (validated)."""
+        download is replaced.  ``mask``: the caller's post-selection mask (validated).  Warns (``RuntimeWarning``) when
+        patterns overflowed ``pattern_capacity``."""
+        nd, n_out = self._num_detectors, int(self._program.num_outputs)
+        patterns = counts_mod.check_pattern_columns(pattern_columns, n_out, nd)
+        capacity = counts_mod.check_pattern_capacity(pattern_capacity) or counts_mod.DEFAULT_PATTERN_CAPACITY
+        extra = dict(pattern_columns=patterns, pattern_capacity=capacity, decoder=counts_mod.check_decoder(decoder, n_out, nd))
+        out = self._count_rows(shots, batch_size, mask, xor_det, xor_obs, histogram_columns, pair_columns, extra, sample_kw)
+        return counts_mod.warn_pattern_overflow(out, capacity)
+
+    def _count_rows(self, shots, batch_size, mask, xor_det, xor_obs, histogram_columns, pair_columns, extra, sample_kw) -> ShotCounts:
         nd, n_out = self._num_detectors, int(self._program.num_outputs)
         hist = (counts_mod.default_histogram_columns(nd, n_out) if histogram_columns is None
                 else counts_mod.check_histogram_columns(histogram_columns, n_out))
         pairs = counts_mod.check_pair_columns(pair_columns, n_out, nd)
         _check_request(shots, batch_size)
         if shots == 0:
-            return counts_mod._HostTally(n_out, nd, mask, hist, pairs).result()
+            return counts_mod._HostTally(n_out, nd, mask, hist, pairs, **extra).result()
         want_ref = xor_det or xor_obs
         if self._seam_replaced() or n_out == 0:
             # rows never live on the device here: the same rows, tallied on the host
-            host = counts_mod._HostTally(n_out, nd, mask, hist, pairs)
+            host = counts_mod._HostTally(n_out, nd, mask, hist, pairs, **extra)
             host.add(self._sample_rows_for_count(shots, batch_size, sample_kw or {}))
             return host.result()
         hp = self._hip()
@@ -1064,7 +1074,7 @@ class _CompiledSamplerBase:
         rides = want_ref and comps and self._noise == "host" and not direct_mask
         skip = 1 if rides else 0
         tally = counts_mod._DeviceTally(hp, n_out, nd, xor_bits=xor, test_bits=mask, histogram_columns=hist, lo=skip, hi=skip + shots,
-                                        pair_columns=pairs)
+                                        pair_columns=pairs, **extra)
         try:
             if not comps:
                 self._direct_device(shots, batch_size, sink=tally)
@@ -1182,13 +1192,18 @@ class CompiledMeasurementSampler(_CompiledSamplerBase):
     def sample(self, shots: int, *, batch_size: int | None = None) -> np.ndarray:
         return self._sample_batches(shots, batch_size)
 
-    def count(self, shots: int, *, batch_size: int | None = None, histogram_columns=None, pair_columns=None) -> ShotCounts:
+    def count(self, shots: int, *, batch_size: int | None = None, histogram_columns=None, pair_columns=None, pattern_columns=None,
+              pattern_capacity: int = counts_mod.DEFAULT_PATTERN_CAPACITY) -> ShotCounts:
         """Counts over what ``sample(shots, batch_size=batch_size)`` returns, reduced on the GPU (:mod:`tsim_amd.counts`):
         every shot is kept, ``column_counts`` are the measurements' counts, ``kept_with_observable_flip`` counts the shots
         with a measurement of 1 (the records play the observables' part).  ``histogram_columns``: up to 16 distinct
         measurement indices (default: every measurement when there are 1 .. 16).  ``pair_columns``: ``"all"`` or up to 4096
-        distinct measurement indices whose pair counts are wanted (``ShotCounts.pair_counts``; default: none)."""
-        return self._count(shots, batch_size, histogram_columns=histogram_columns, pair_columns=pair_columns)
+        distinct measurement indices whose pair counts are wanted (``ShotCounts.pair_counts``; default: none).
+        ``pattern_columns``: ``"all"`` or any distinct measurement indices: the distinct outcomes over them with their
+        exact counts (``ShotCounts.patterns`` / ``pattern_counts``; the support of the output distribution), from a table of
+        ``pattern_capacity`` slots - see :meth:`CompiledDetectorSampler.count`."""
+        return self._count(shots, batch_size, histogram_columns=histogram_columns, pair_columns=pair_columns,
+                           pattern_columns=pattern_columns, pattern_capacity=pattern_capacity)
 
     def sample_write(self, shots: int, *, filepath, format: str = "01", batch_size: int | None = None) -> None:
         """stim's ``sample_write``: what ``sample(shots, batch_size=batch_size)`` returns, written to ``filepath`` in
@@ -1217,14 +1232,25 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
 
     def count(self, shots: int, *, batch_size: int | None = None, postselection_mask: np.ndarray | None = None,
               use_detector_reference_sample: bool = False, use_observable_reference_sample: bool = False,
-              histogram_columns=None, pair_columns=None) -> ShotCounts:
+              histogram_columns=None, pair_columns=None, pattern_columns=None,
+              pattern_capacity: int = counts_mod.DEFAULT_PATTERN_CAPACITY, decoder=None) -> ShotCounts:
         """Counts over the rows ``sample()`` returns for the same arguments, reduced on the GPU - only the counters cross
         PCIe (:mod:`tsim_amd.counts`).  A shot is kept iff none of its detectors in ``postselection_mask`` is set (the
         reference's advice: sample, then drop the rows with a masked detector); ``column_counts`` (detectors, then
         observables), ``kept_with_observable_flip`` and the histogram over ``histogram_columns`` (default: the observables
         when there are 1 .. 16) are taken over the kept shots.  ``pair_columns`` (``"all"``, ``"detectors"`` or up to 4096
         distinct columns; default: none) adds ``pair_counts``, the kept shots with both columns of a pair set, and with it
-        ``ShotCounts.pair_correlations()``.  For a fresh sampler with the same seed and arguments this
+        ``ShotCounts.pair_correlations()``.  ``pattern_columns`` (``"all"``, ``"detectors"`` or any distinct columns;
+        default: none) adds ``patterns`` and ``pattern_counts``: the distinct patterns of the kept shots over those columns,
+        each with its exact count, ordered by count descending - ``np.unique(sample(), axis=0)`` without the rows leaving
+        the GPU.  They are collected in a hash table of ``pattern_capacity`` slots (rounded up to a power of two) in device
+        memory: 16 bytes per slot for up to 63 columns, ``16 + 8 * ceil(k / 64)`` bytes for ``k`` columns beyond that (the
+        default 2^20 slots over the 121 columns of a d = 5 memory experiment: 32 MiB).  Keep it at a few times the number
+        of distinct patterns expected: shots whose pattern finds no room are counted in ``pattern_overflow`` and a
+        ``RuntimeWarning`` names the capacity - the patterns that are returned carry their exact counts all the same.
+        ``decoder`` (a :class:`tsim_amd.decode.LookupDecoder`) is applied to every kept shot on the GPU:
+        ``decoded_errors`` kept shots whose observables differ from its prediction, ``decoder_misses`` kept shots whose
+        syndrome it does not know.  For a fresh sampler with the same seed and arguments this
         equals ``counts.tally_rows(sample(..., append_observables=True), ...)``, and the sampler's keys stand where that
         ``sample()`` would leave them."""
         nd = self._num_detectors
@@ -1237,7 +1263,7 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
                   use_observable_reference_sample=use_observable_reference_sample)
         return self._count(shots, batch_size, mask=mask, xor_det=use_detector_reference_sample,
                            xor_obs=use_observable_reference_sample, histogram_columns=histogram_columns, pair_columns=pair_columns,
-                           sample_kw=kw)
+                           pattern_columns=pattern_columns, pattern_capacity=pattern_capacity, decoder=decoder, sample_kw=kw)
 
     def _sample_rows_for_count(self, shots: int, batch_size: int | None, sample_kw: dict) -> np.ndarray:
         return self.sample(shots, batch_size=batch_size, append_observables=True, **sample_kw)
