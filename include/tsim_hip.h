@@ -416,6 +416,28 @@ int tsim_m2d_convert_device(tsim_m2d *h, const uint8_t *d_meas, int64_t B, int64
 /* out[0] num_measurements, [1] n_out, [2] nnz, [3] device */
 int tsim_m2d_info(const tsim_m2d *h, int64_t out[4]);
 
+/* ---- affine measurement sampler (CliffordCircuit.compile_sampler(method="affine")) ---------------------------------------
+ * Every measurement record of a Clifford circuit with Pauli noise is an affine GF(2) function of the error bits and of
+ * independent uniform bits.  Per shot n, output j = flip[j] XOR (XOR of x[cols[k]] over k in row_ptr[j] .. row_ptr[j+1]-1);
+ * a column listed twice cancels.  Columns 0 <= c < num_f are bit c of the shot's packed f row (little-endian bits, rows
+ * f_row_bytes apart, as tsim_noise_sample_device writes them; num_f = 0 allows d_f = NULL).  Columns num_f <= c <
+ * num_f + n_random are random symbol s = c - num_f: with g = first_shot + n, (x0, x1) = threefry2x32((key_hi, key_lo),
+ * counter (s, g / 64)) and w = x0 | x1 << 32, the symbol's value is bit g % 64 of w.  first_shot must be a multiple of 64
+ * and first_shot + B at most 2^38; results depend on the key and on g only, not on how a request is cut into launches.
+ * A handle of its own, bound to HIP device `device`; every argument is checked before any device call (TSIM_EINVAL).
+ * Output rows follow tsim_m2d_convert_device: row r at byte r * out_row_bytes receives outputs col0 .. col0+n_cols-1 as
+ * n_cols bytes 0/1 (out_packed = 0) or ceil(n_cols/8) bytes with zero pad bits (out_packed = 1); the bytes of a row past
+ * those are not written.  Asynchronous on `stream` (NULL: the handle's own stream). */
+typedef struct tsim_affine tsim_affine;
+int tsim_affine_create(int32_t device, int32_t num_f, int32_t n_random, int32_t n_out, const int32_t *row_ptr,
+                       const int32_t *cols, const uint8_t *flip, tsim_affine **out);
+void tsim_affine_destroy(tsim_affine *h);
+int tsim_affine_sample_device(tsim_affine *h, const uint64_t *d_f, int64_t f_row_bytes, int64_t B, int64_t first_shot,
+                              uint32_t key_hi, uint32_t key_lo, uint8_t *d_out, int64_t out_row_bytes, int32_t out_packed,
+                              int32_t col0, int32_t n_cols, void *stream);
+/* out[0] num_f, [1] n_random, [2] n_out, [3] nnz, [4] device, [5] columns per window, [6] windows, [7] LDS bytes per wave */
+int tsim_affine_info(const tsim_affine *h, int64_t out[8]);
+
 /* ---- counts over bit-packed device rows (the samplers' count(): rates without moving the rows to the host) ---------------
  * Row r starts at byte r * row_bytes of d_rows and holds n_cols columns little-endian (row_bytes >= ceil(n_cols/8); the
  * buffer spans n * row_bytes bytes).  Optional rows of ceil(n_cols/8) bytes: d_xor is XORed into every row first, and a

@@ -103,6 +103,10 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_m2d_convert": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32]),
     "tsim_m2d_convert_device": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32, _P]),
     "tsim_m2d_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "tsim_affine_create": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, C.POINTER(_P)]),
+    "tsim_affine_destroy": (None, [_P]),
+    "tsim_affine_sample_device": (C.c_int, [_P, _P, _I64, _I64, _I64, _U32, _U32, _P, _I64, _I32, _I32, _I32, _P]),
+    "tsim_affine_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_tally_rows_device": (C.c_int, [_I32, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P]),
     "tsim_pairs_create": (C.c_int, [_I32, _I32, _P, _I32, C.POINTER(_P)]),
     "tsim_pairs_destroy": (None, [_P]),

@@ -337,6 +337,31 @@ def _odd_records(indices) -> set:
     return odd
 
 
+def _bits(mask: int) -> list[int]:
+    """Positions of the set bits of a Python-int bitmask, ascending."""
+    out = []
+    while mask:
+        low = mask & -mask
+        out.append(low.bit_length() - 1)
+        mask ^= low
+    return out
+
+
+def _record_basis(an: _Analysis) -> tuple[int, np.ndarray, list[int]]:
+    """``(num_f, error_transform, fcombo)`` of the measurement records: the :func:`find_basis` basis of the records' error
+    sets (rows of ``error_transform``, ``uint8[num_f, num_e]``) and every record's error set as a bitmask over it."""
+    rows = [(i, s) for i, s in enumerate(an.rec_sets) if s]
+    basis_idx, combos = find_basis([s for _, s in rows])
+    num_f = len(basis_idx)
+    error_transform = np.zeros((num_f, an.num_e), dtype=np.uint8)
+    for pos, bi in enumerate(basis_idx):
+        error_transform[pos, _bits(rows[bi][1])] = 1
+    fcombo = [0] * len(an.rec_sets)
+    for j, (i, _) in enumerate(rows):
+        fcombo[i] = combos[j]
+    return num_f, error_transform, fcombo
+
+
 class _Sim:
     def __init__(self, n_qubits: int):
         self.n = n_qubits + 1  # one auxiliary qubit for Pauli-product measurements
@@ -795,17 +820,7 @@ class CliffordCircuit:
             return self._compiled_m
         an = self.analyze()
         n_out = len(an.rec_sets)
-        rows = [(i, s) for i, s in enumerate(an.rec_sets) if s]
-        basis_idx, combos = find_basis([s for _, s in rows])
-        num_f = len(basis_idx)
-        error_transform = np.zeros((num_f, an.num_e), dtype=np.uint8)
-        for pos, bi in enumerate(basis_idx):
-            for e in range(an.num_e):
-                if (rows[bi][1] >> e) & 1:
-                    error_transform[pos, e] = 1
-        fcombo = [0] * n_out
-        for j, (i, _) in enumerate(rows):
-            fcombo[i] = combos[j]
+        num_f, error_transform, fcombo = _record_basis(an)
         # direct entries: no random bit and exactly one f bit
         direct, rest = [], []
         for i in range(n_out):
@@ -872,8 +887,38 @@ class CliffordCircuit:
         self._compiled_m = (program, list(an.channel_probs), error_transform)
         return self._compiled_m
 
-    def compile_sampler(self, *, seed: int | None = None, device: int = 0, noise: str = "host", mode: str = "auto"):
-        """Mirror of ``Circuit.compile_sampler`` (src/tsim/circuit.py:812-834)."""
+    def compile_affine_measurements(self) -> dict:
+        """The measurement records as an affine GF(2) map: record ``i`` is ``flip[i]`` XOR the columns
+        ``cols[row_ptr[i]:row_ptr[i + 1]]`` of ``[f | r]`` - ``num_f`` error bits in the basis, ``num_f`` and
+        ``error_transform`` of :meth:`compile_measurements` (both forms consume the same channel stream), then ``n_random``
+        independent uniform bits, the random outcomes of the noiseless run.  Nothing is built per level: the cost is
+        :meth:`analyze` plus the basis."""
+        if getattr(self, "_compiled_a", None) is not None:
+            return self._compiled_a
+        an = self.analyze()
+        num_f, error_transform, fcombo = _record_basis(an)
+        n_random = max((int(y).bit_length() for y in an.rec_syms), default=0)
+        lists = [_bits(c) + [num_f + s for s in _bits(int(y))] for c, y in zip(fcombo, an.rec_syms)]
+        row_ptr = np.zeros(len(lists) + 1, np.int32)
+        row_ptr[1:] = np.cumsum([len(l) for l in lists], dtype=np.int64)
+        cols = np.asarray([c for l in lists for c in l], dtype=np.int32)
+        self._compiled_a = dict(flip=np.asarray([int(v) & 1 for v in an.rec_vals], dtype=np.uint8), row_ptr=row_ptr, cols=cols,
+                                num_f=num_f, n_random=n_random, channel_probs=list(an.channel_probs),
+                                error_transform=error_transform)
+        return self._compiled_a
+
+    def compile_sampler(self, *, seed: int | None = None, device: int = 0, noise: str = "host", mode: str = "auto",
+                        method: str = "autoregressive"):
+        """Mirror of ``Circuit.compile_sampler`` (src/tsim/circuit.py:812-834).  ``method="autoregressive"``: the
+        reference's formulation (one level per record of a component, its seeded stream).  ``method="affine"``: the
+        records as an affine map of the error bits and of uniform bits (:mod:`tsim_amd.affine`) - the same law from a
+        different stream, for circuits of any size."""
+        if method not in ("autoregressive", "affine"):
+            raise ValueError(f"method must be 'autoregressive' or 'affine', got {method!r}")
+        if method == "affine":
+            from .affine import CompiledAffineMeasurementSampler
+
+            return CompiledAffineMeasurementSampler(self.compile_affine_measurements(), seed=seed, device=device, noise=noise)
         from .sampler import CompiledMeasurementSampler
 
         program, channel_probs, error_transform = self.compile_measurements()

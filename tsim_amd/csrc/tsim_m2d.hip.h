@@ -12,7 +12,8 @@
 // Records beyond what one wave's LDS holds go through in windows of `win` columns: phase 1 builds the window's masks,
 // phase 2 XORs the window's part of every output (a CSR per window, window-local column indices) into the rows the
 // earlier windows wrote - chunks and 64-output groups without a record in the window are skipped.
-// Every address is formed in 64 bits (B x row bytes may exceed 2^31).
+// Every address is formed in 64 bits (B x row bytes may exceed 2^31).  Phase 2 is a function of its own (outputs): the affine
+// measurement sampler (tsim_affine.hip.h) builds its masks differently and shares it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -124,6 +125,85 @@ __device__ __forceinline__ void slice(uint64_t *mask, const uint8_t *row, int cb
   }
 }
 
+// Phase 2 on one tile: outputs a.col0 .. a.col0 + a.n_cols - 1 from the column masks in `mask` and the CSR of one window
+// (`rp`: its row_ptr, window-local indices in a.cols); xr: XOR into the rows already at dst (a later window).
+template <bool OUT_PACKED>
+__device__ __forceinline__ void outputs(const Args &a, const int32_t *rp, bool xr, const uint64_t *mask, uint8_t *stage, uint8_t *dst,
+                                        int rows, int lane) {
+  constexpr int kPerChunk = OUT_PACKED ? 512 : 64;
+  for (int o0 = 0; o0 < a.n_cols; o0 += kPerChunk) {
+    const int o1 = min(o0 + kPerChunk, a.n_cols);
+    if (xr && rp[a.col0 + o0] == rp[a.col0 + o1]) continue;  // no record of this window in the chunk
+    const int ss = a.out_contig ? (int)a.out_rb : kStageRow;
+    const int b0 = OUT_PACKED ? o0 / 8 : o0;
+    const int nb = min(64, a.out_used - b0);
+    if (xr) {  // the rows as the earlier windows left them
+      if (a.out_contig) load_span(stage, dst, rows * (int)a.out_rb, a.out_w4, lane);
+      else load_rows(stage, dst + b0, rows, nb, a.out_rb, a.out_w4 && !(nb & 3), lane);
+      wsync();
+    }
+    uint8_t *mine = stage + lane * ss;
+    for (int g = 0; g < kPerChunk / 64; ++g) {
+      const int ob = o0 + g * 64;
+      if (ob >= a.n_cols) break;
+      if (xr && rp[a.col0 + ob] == rp[a.col0 + min(ob + 64, a.n_cols)]) continue;
+      // lane l forms the shot mask of output ob + l (its own CSR list), then 64 ballots transpose the 64 x 64 bit block:
+      // ballot j collects bit j (shot j) of every lane's output mask, i.e. shot j's 64 output bits
+      uint64_t acc = 0;
+      const int o = ob + lane;
+      if (o < a.n_cols) {
+        const int q = a.col0 + o;
+        acc = (!xr && a.ref[q]) ? ~0ull : 0ull;
+        const int k1 = rp[q + 1];
+        for (int k = rp[q]; k < k1; ++k) acc ^= mask[a.cols[k]];
+      }
+      uint64_t word = 0;
+#pragma unroll 1
+      for (int i = 0; i < 8; ++i) {
+        const uint32_t byte = (uint32_t)(acc >> (8 * i)) & 0xFFu;
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) put_lane(word, __builtin_amdgcn_ballot_w64(((byte >> jj) & 1u) != 0u), lane, 8 * i + jj);
+      }
+      const uint32_t wlo = (uint32_t)word, whi = (uint32_t)(word >> 32);
+      if (OUT_PACKED) {
+        if (a.out_contig) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q)  // the row is out_rb bytes: the next lane's row starts there
+            if (g * 8 + q < ss) {
+              const uint8_t v = (uint8_t)((q < 4 ? wlo : whi) >> (8 * (q & 3)));
+              mine[g * 8 + q] = xr ? (uint8_t)(mine[g * 8 + q] ^ v) : v;
+            }
+        } else {
+          uint32_t *p = reinterpret_cast<uint32_t *>(mine + g * 8);
+          p[0] = xr ? p[0] ^ wlo : wlo;
+          p[1] = xr ? p[1] ^ whi : whi;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const uint32_t wq = q < 8 ? wlo >> (4 * q) : whi >> (4 * (q - 8));
+          const uint32_t v = (wq & 1u) | ((wq & 2u) << 7) | ((wq & 4u) << 14) | ((wq & 8u) << 21);
+          if (a.out_contig) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (4 * q + k < ss) {
+                const uint8_t vb = (uint8_t)(v >> (8 * k));
+                mine[4 * q + k] = xr ? (uint8_t)(mine[4 * q + k] ^ vb) : vb;
+              }
+          } else {
+            uint32_t *p = reinterpret_cast<uint32_t *>(mine + 4 * q);
+            *p = xr ? *p ^ v : v;
+          }
+        }
+      }
+    }
+    wsync();
+    if (a.out_contig) store_span(dst, stage, rows * (int)a.out_rb, a.out_w4, lane);
+    else store_rows(dst + b0, stage, rows, nb, a.out_rb, a.out_w4 && !(nb & 3), lane);
+    wsync();
+  }
+}
+
 template <bool IN_PACKED, bool OUT_PACKED>
 __global__ void __launch_bounds__(256) k_m2d(Args a) {
   extern __shared__ uint64_t lds[];
@@ -131,7 +211,6 @@ __global__ void __launch_bounds__(256) k_m2d(Args a) {
   uint64_t *mask = lds + (size_t)wave * (a.win + kStageBytes / 8);
   uint8_t *stage = reinterpret_cast<uint8_t *>(mask + a.win);
   const long long tiles = (a.B + 63) >> 6;
-  constexpr int kPerChunk = OUT_PACKED ? 512 : 64;
   for (long long t = (long long)blockIdx.x * nw + wave; t < tiles; t += (long long)gridDim.x * nw) {
     const long long r0 = t << 6;
     const int rows = (int)min(64LL, a.B - r0);
@@ -164,77 +243,7 @@ __global__ void __launch_bounds__(256) k_m2d(Args a) {
       }
       wsync();
       // ---- phase 2: outputs, one chunk of 64 bytes per row at a time
-      for (int o0 = 0; o0 < a.n_cols; o0 += kPerChunk) {
-        const int o1 = min(o0 + kPerChunk, a.n_cols);
-        if (xr && rp[a.col0 + o0] == rp[a.col0 + o1]) continue;  // no record of this window in the chunk
-        const int ss = a.out_contig ? (int)a.out_rb : kStageRow;
-        const int b0 = OUT_PACKED ? o0 / 8 : o0;
-        const int nb = min(64, a.out_used - b0);
-        if (xr) {  // the rows as the earlier windows left them
-          if (a.out_contig) load_span(stage, dst, rows * (int)a.out_rb, a.out_w4, lane);
-          else load_rows(stage, dst + b0, rows, nb, a.out_rb, a.out_w4 && !(nb & 3), lane);
-          wsync();
-        }
-        uint8_t *mine = stage + lane * ss;
-        for (int g = 0; g < kPerChunk / 64; ++g) {
-          const int ob = o0 + g * 64;
-          if (ob >= a.n_cols) break;
-          if (xr && rp[a.col0 + ob] == rp[a.col0 + min(ob + 64, a.n_cols)]) continue;
-          // lane l forms the shot mask of output ob + l (its own CSR list), then 64 ballots transpose the 64 x 64 bit block:
-          // ballot j collects bit j (shot j) of every lane's output mask, i.e. shot j's 64 output bits
-          uint64_t acc = 0;
-          const int o = ob + lane;
-          if (o < a.n_cols) {
-            const int q = a.col0 + o;
-            acc = (!xr && a.ref[q]) ? ~0ull : 0ull;
-            const int k1 = rp[q + 1];
-            for (int k = rp[q]; k < k1; ++k) acc ^= mask[a.cols[k]];
-          }
-          uint64_t word = 0;
-#pragma unroll 1
-          for (int i = 0; i < 8; ++i) {
-            const uint32_t byte = (uint32_t)(acc >> (8 * i)) & 0xFFu;
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) put_lane(word, __builtin_amdgcn_ballot_w64(((byte >> jj) & 1u) != 0u), lane, 8 * i + jj);
-          }
-          const uint32_t wlo = (uint32_t)word, whi = (uint32_t)(word >> 32);
-          if (OUT_PACKED) {
-            if (a.out_contig) {
-#pragma unroll
-              for (int q = 0; q < 8; ++q)  // the row is out_rb bytes: the next lane's row starts there
-                if (g * 8 + q < ss) {
-                  const uint8_t v = (uint8_t)((q < 4 ? wlo : whi) >> (8 * (q & 3)));
-                  mine[g * 8 + q] = xr ? (uint8_t)(mine[g * 8 + q] ^ v) : v;
-                }
-            } else {
-              uint32_t *p = reinterpret_cast<uint32_t *>(mine + g * 8);
-              p[0] = xr ? p[0] ^ wlo : wlo;
-              p[1] = xr ? p[1] ^ whi : whi;
-            }
-          } else {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-              const uint32_t wq = q < 8 ? wlo >> (4 * q) : whi >> (4 * (q - 8));
-              const uint32_t v = (wq & 1u) | ((wq & 2u) << 7) | ((wq & 4u) << 14) | ((wq & 8u) << 21);
-              if (a.out_contig) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                  if (4 * q + k < ss) {
-                    const uint8_t vb = (uint8_t)(v >> (8 * k));
-                    mine[4 * q + k] = xr ? (uint8_t)(mine[4 * q + k] ^ vb) : vb;
-                  }
-              } else {
-                uint32_t *p = reinterpret_cast<uint32_t *>(mine + 4 * q);
-                *p = xr ? *p ^ v : v;
-              }
-            }
-          }
-        }
-        wsync();
-        if (a.out_contig) store_span(dst, stage, rows * (int)a.out_rb, a.out_w4, lane);
-        else store_rows(dst + b0, stage, rows, nb, a.out_rb, a.out_w4 && !(nb & 3), lane);
-        wsync();
-      }
+      outputs<OUT_PACKED>(a, rp, xr, mask, stage, dst, rows, lane);
     }
   }
 }
