@@ -438,6 +438,48 @@ int tsim_affine_sample_device(tsim_affine *h, const uint64_t *d_f, int64_t f_row
 /* out[0] num_f, [1] n_random, [2] n_out, [3] nnz, [4] device, [5] columns per window, [6] windows, [7] LDS bytes per wave */
 int tsim_affine_info(const tsim_affine *h, int64_t out[8]);
 
+/* ---- Pauli-frame sampler (CliffordCircuit.compile_sampler / compile_detector_sampler(method="frame")) ----------------------
+ * A Pauli frame (x_q, z_q) per shot is carried through the circuit, 64 shots to a word; noise is drawn where it acts.  The
+ * compiled form (tsim_amd/frame.py documents it and states the same function in numpy):
+ *   operations  op_kind uint8 [n_ops] (0 H, 1 S, 2 CX, 3 RESET, 4 MEASURE, 5 FEEDBACK, 6 NOISE), op_a / op_b / op_c int32:
+ *               H/S/RESET a = qubit; CX a = control, b = target; MEASURE a = qubit or -1 (the flip word is zero), b = record;
+ *               FEEDBACK a = record, b = qubit, c = 1 (into x) | 2 (into z); NOISE a = site;
+ *   batches     batch_ptr int32 [n_batches + 1]: operations of one kind whose qubits and records are pairwise disjoint;
+ *   sites       site_chan (the index folded into the site's key), site_table int32 [n_sites], site_bit int32 [n_sites + 1]
+ *               (the site's error bits, 1 .. 32 of them), bit_ptr int32 [n_bits + 1] (targets of an error bit), targets
+ *               int32 [n_targets] = 4 * index + kind (0 x of qubit, 1 z of qubit, 2 record);
+ *   tables      table_ptr int32 [n_tables + 1], table_gap int32 [n_tables], out_vals / out_thr uint32 [n_outcomes] (the
+ *               outcome's error bits; ceil(cdf 2^32), non-decreasing), gap_thr uint32 [n_gaps][64] (floor((1-p)^k 2^32),
+ *               k = 1 .. 64);
+ *   outputs     out_const uint8 [n_out], out_ptr int32 [n_out + 1], out_cols int32 [n_cols] over the columns
+ *               [n_records records | n_random random symbols]; records n_records .. n_records + n_hidden - 1 are scratch.
+ * Per shot g = first_shot + n, output j = out_const[j] XOR its records' flips XOR its symbols; symbol s is bit g % 64 of
+ * x0 | x1 << 32 of threefry2x32((key_hi, key_lo), (s, g / 64)) as in tsim_affine_sample_device; site n draws under
+ * (n0 ^ site_chan[n] * 0x9E3779B9, n1) with (n0, n1) = threefry2x32(key, (0x6E6F6973, 0x6672616D)), counter (g / 64, draw).
+ * Results depend on the key and on g only.  n_qubits (16 bytes of LDS per qubit and word) above 10240 is TSIM_ENOTSUP at create
+ * time; every index of the form is checked there, before any device call.  The handle owns the record-flip scratch (at most
+ * 256 MiB) and cuts a request into launches that fit it; launches of one handle must be ordered (one stream at a time).
+ * Output rows, col0 / n_cols, first_shot and stream: as tsim_affine_sample_device. */
+typedef struct tsim_frame_desc {
+  int32_t n_qubits, n_records, n_hidden, n_random, n_out, n_ops, n_batches, n_sites, n_bits, n_targets, n_tables, n_outcomes,
+      n_gaps, n_cols;
+  const uint8_t *op_kind;
+  const int32_t *op_a, *op_b, *op_c, *batch_ptr;
+  const int32_t *site_chan, *site_table, *site_bit, *bit_ptr, *targets, *table_ptr, *table_gap;
+  const uint32_t *out_vals, *out_thr, *gap_thr;
+  const uint8_t *out_const;
+  const int32_t *out_ptr, *out_cols;
+} tsim_frame_desc;
+typedef struct tsim_frame tsim_frame;
+int tsim_frame_create(int32_t device, const tsim_frame_desc *desc, tsim_frame **out);
+void tsim_frame_destroy(tsim_frame *h);
+int tsim_frame_sample_device(tsim_frame *h, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo, uint8_t *d_out,
+                             int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols, void *stream);
+/* out[0] n_qubits, [1] n_records, [2] n_hidden, [3] n_random, [4] n_out, [5] n_ops, [6] n_batches, [7] n_sites, [8] device,
+ * [9] T (64-shot words per block of k_frame), [10] LDS bytes of its frames, [11] the most qubits a handle takes, [12] columns
+ * per window of the output stage, [13] its windows, [14] words per launch, [15] items of the largest batch */
+int tsim_frame_info(const tsim_frame *h, int64_t out[16]);
+
 /* ---- counts over bit-packed device rows (the samplers' count(): rates without moving the rows to the host) ---------------
  * Row r starts at byte r * row_bytes of d_rows and holds n_cols columns little-endian (row_bytes >= ceil(n_cols/8); the
  * buffer spans n * row_bytes bytes).  Optional rows of ceil(n_cols/8) bytes: d_xor is XORed into every row first, and a

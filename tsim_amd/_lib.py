@@ -55,6 +55,16 @@ class LevelDesc(C.Structure):
     ]
 
 
+class FrameDesc(C.Structure):
+    """``tsim_frame_desc`` (include/tsim_hip.h)."""
+
+    SIZES = ("n_qubits", "n_records", "n_hidden", "n_random", "n_out", "n_ops", "n_batches", "n_sites", "n_bits", "n_targets",
+             "n_tables", "n_outcomes", "n_gaps", "n_cols")
+    ARRAYS = ("op_kind", "op_a", "op_b", "op_c", "batch_ptr", "site_chan", "site_table", "site_bit", "bit_ptr", "targets",
+              "table_ptr", "table_gap", "out_vals", "out_thr", "gap_thr", "out_const", "out_ptr", "out_cols")
+    _fields_ = [(n, C.c_int32) for n in SIZES] + [(n, C.c_void_p) for n in ARRAYS]
+
+
 # every symbol include/tsim_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I32, _I64, _U32 = C.c_int32, C.c_int64, C.c_uint32
@@ -107,6 +117,10 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_affine_destroy": (None, [_P]),
     "tsim_affine_sample_device": (C.c_int, [_P, _P, _I64, _I64, _I64, _U32, _U32, _P, _I64, _I32, _I32, _I32, _P]),
     "tsim_affine_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "tsim_frame_create": (C.c_int, [_I32, C.POINTER(FrameDesc), C.POINTER(_P)]),
+    "tsim_frame_destroy": (None, [_P]),
+    "tsim_frame_sample_device": (C.c_int, [_P, _I64, _I64, _U32, _U32, _P, _I64, _I32, _I32, _I32, _P]),
+    "tsim_frame_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_tally_rows_device": (C.c_int, [_I32, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P]),
     "tsim_pairs_create": (C.c_int, [_I32, _I32, _P, _I32, C.POINTER(_P)]),
     "tsim_pairs_destroy": (None, [_P]),

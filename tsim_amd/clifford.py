@@ -324,6 +324,7 @@ class _Analysis:
     rec_vals: list = field(default_factory=list)    # noiseless outcome of every record
     rec_syms: list = field(default_factory=list)    # random symbols of every record (0: deterministic)
     detectors: list = field(default_factory=list)   # (error bitmask, flip)
+    detector_syms: list = field(default_factory=list)  # random symbols of every detector (0 unless gauge detectors are allowed)
     observables: dict = field(default_factory=dict)  # index -> [error bitmask, flip]
     detector_records: list = field(default_factory=list)     # record indices each detector XORs (duplicates cancelled)
     observable_records: dict = field(default_factory=dict)   # index -> record indices (duplicates cancelled)
@@ -363,6 +364,8 @@ def _record_basis(an: _Analysis) -> tuple[int, np.ndarray, list[int]]:
 
 
 class _Sim:
+    allow_gauge = False  # a DETECTOR whose random symbols do not cancel is an error (the frame recorder keeps it)
+
     def __init__(self, n_qubits: int):
         self.n = n_qubits + 1  # one auxiliary qubit for Pauli-product measurements
         self.aux = n_qubits
@@ -439,10 +442,13 @@ class _Sim:
         if out.rec_vals[rec_index]:
             self.tab.pauli(q, px, pz)
         self.tab.pauli_if(q, out.rec_syms[rec_index], px, pz)
+        self._feedback_frame(rec_index, q, px, pz)
+
+    def _feedback_frame(self, rec_index, q, px, pz):
         if px:
-            self.fx[q] ^= out.rec_sets[rec_index]
+            self.fx[q] ^= self.out.rec_sets[rec_index]
         if pz:
-            self.fz[q] ^= out.rec_sets[rec_index]
+            self.fz[q] ^= self.out.rec_sets[rec_index]
 
     def spp(self, paulis, dag=False):
         """Phase the -1 eigenspace of a Pauli product by i (-i for dag): parity of the rotated qubits
@@ -568,12 +574,25 @@ class _Sim:
         if val:
             self.tab.pauli(q, 1, 0)
         self.tab.pauli_if(q, sym)
+        self._reset_frame(q)
+
+    def _reset_frame(self, q):
         self.fx[q] = 0
         self.fz[q] = 0
 
     def reset(self, q, basis="Z"):
         self._reset_z(q)
         self._basis_in(q, basis)
+
+    def mpad(self, value, p=0.0):
+        """A fixed bit in the measurement record (instructions.py:1040-1053)."""
+        flips = 0
+        if p > 0:
+            self.out.channel_probs.append(error_probs(p))
+            (flips,) = self._new_bits(1)
+        self.out.rec_sets.append(flips)
+        self.out.rec_vals.append(value & 1)
+        self.out.rec_syms.append(0)
 
     def mpp(self, paulis, p=0.0, invert=False):
         """One Pauli product through the auxiliary qubit (instructions.py:874-909)."""
@@ -651,7 +670,11 @@ class CliffordCircuit:
         return hi + 1
 
     def analyze(self) -> _Analysis:
-        sim = _Sim(max(1, self._qubit_count()))
+        return self._walk(_Sim(max(1, self._qubit_count())))
+
+    def _walk(self, sim) -> _Analysis:
+        """The instructions, once, through ``sim``: a :class:`_Sim` (:meth:`analyze`) or the frame recorder that shares its
+        gate decompositions (:meth:`compile_frame`)."""
         out = sim.out
 
         def rec(tok: str) -> int:
@@ -721,15 +744,9 @@ class CliffordCircuit:
                     inv = tg[i].startswith("!") ^ tg[i + 1].startswith("!")
                     sim.mpp([(name[1], int(tg[i].lstrip("!"))), (name[2], int(tg[i + 1].lstrip("!")))],
                             p=args[0] if args else 0.0, invert=inv)
-            elif name == "MPAD":  # a fixed bit in the measurement record (instructions.py:1040-1053)
+            elif name == "MPAD":
                 for t in tg:
-                    flips = 0
-                    if args and args[0] > 0:
-                        out.channel_probs.append(error_probs(args[0]))
-                        (flips,) = sim._new_bits(1)
-                    out.rec_sets.append(flips)
-                    out.rec_vals.append(int(t) & 1)
-                    out.rec_syms.append(0)
+                    sim.mpad(int(t), args[0] if args else 0.0)
             elif name == "MPP":
                 for t in tg:
                     inv = t.startswith("!")
@@ -753,10 +770,11 @@ class CliffordCircuit:
                     s ^= out.rec_sets[rec(t)]
                     v ^= out.rec_vals[rec(t)]
                     y ^= out.rec_syms[rec(t)]
-                if y:
+                if y and not sim.allow_gauge:
                     raise ValueError(f"DETECTOR {' '.join(tg)} (detector {len(out.detectors)}) is not deterministic: "
                                      "its measurements depend on random outcomes that do not cancel")
                 out.detectors.append((s, v))
+                out.detector_syms.append(y)
                 out.detector_records.append(sorted(_odd_records(rec(t) for t in tg)))
             elif name == "OBSERVABLE_INCLUDE":
                 idx = int(args[0]) if args else 0
@@ -790,10 +808,7 @@ class CliffordCircuit:
         need_zero_col = any(not s for s, _ in outputs)
         error_transform = np.zeros((num_f + (1 if need_zero_col else 0), an.num_e), dtype=np.uint8)
         for pos, bi in enumerate(basis_idx):
-            s = rows[bi][1]
-            for e in range(an.num_e):
-                if (s >> e) & 1:
-                    error_transform[pos, e] = 1
+            error_transform[pos, _bits(rows[bi][1])] = 1
         combo_of = {i: combos[j] for j, (i, _) in enumerate(rows)}
         direct, components = [], []
         for i, (s, flip) in enumerate(outputs):
@@ -907,14 +922,37 @@ class CliffordCircuit:
                                 error_transform=error_transform)
         return self._compiled_a
 
+    def compile_frame(self, kind: str = "measurements"):
+        """The Pauli-frame form (:class:`tsim_amd.frame.FrameForm`) with the records (``kind="measurements"``) or the
+        detectors, then the observables by index (``kind="detectors"``), as outputs: one walk over the instructions with a
+        recorder that keeps the tableau of :meth:`analyze` and logs the frame operations instead of propagating error masks.
+        Nothing dense is built: the form is linear in the circuit."""
+        from . import frame
+
+        forms = self.__dict__.setdefault("_compiled_frame", {})
+        if kind not in forms:
+            if "walk" not in forms:
+                rec = frame._FrameRecorder(max(1, self._qubit_count()))
+                self._walk(rec)
+                rec.tab = None  # (quadratic in the qubits; the forms are built from the log alone)
+                forms["walk"] = rec
+            forms[kind] = frame.build_form(forms["walk"], kind)
+        return forms[kind]
+
     def compile_sampler(self, *, seed: int | None = None, device: int = 0, noise: str = "host", mode: str = "auto",
                         method: str = "autoregressive"):
         """Mirror of ``Circuit.compile_sampler`` (src/tsim/circuit.py:812-834).  ``method="autoregressive"``: the
         reference's formulation (one level per record of a component, its seeded stream).  ``method="affine"``: the
         records as an affine map of the error bits and of uniform bits (:mod:`tsim_amd.affine`) - the same law from a
-        different stream, for circuits of any size."""
-        if method not in ("autoregressive", "affine"):
-            raise ValueError(f"method must be 'autoregressive' or 'affine', got {method!r}")
+        different stream, without levels; its limit is the dense ``error_transform`` (quadratic in the circuit).
+        ``method="frame"``: a Pauli frame per shot carried through the circuit (:mod:`tsim_amd.frame`) - the same law from
+        a third stream, linear in the circuit."""
+        if method not in ("autoregressive", "affine", "frame"):
+            raise ValueError(f"method must be 'autoregressive', 'affine' or 'frame', got {method!r}")
+        if method == "frame":
+            from .frame import CompiledFrameMeasurementSampler
+
+            return CompiledFrameMeasurementSampler(self.compile_frame("measurements"), seed=seed, device=device, noise=noise)
         if method == "affine":
             from .affine import CompiledAffineMeasurementSampler
 
@@ -926,8 +964,16 @@ class CliffordCircuit:
                                           seed=seed, device=device, noise=noise, mode=mode)
 
     def compile_detector_sampler(self, *, seed: int | None = None, device: int = 0, noise: str = "host",
-                                 mode: str = "auto"):
-        """Mirror of ``Circuit.compile_detector_sampler`` (src/tsim/circuit.py:836-867)."""
+                                 mode: str = "auto", method: str = "autoregressive"):
+        """Mirror of ``Circuit.compile_detector_sampler`` (src/tsim/circuit.py:836-867).  ``method="frame"``: the Pauli-frame
+        sampler (:mod:`tsim_amd.frame`): the same law from another stream, linear in the circuit, and detectors whose random
+        outcomes do not cancel are sampled instead of refused."""
+        if method not in ("autoregressive", "frame"):
+            raise ValueError(f"method must be 'autoregressive' or 'frame', got {method!r}")
+        if method == "frame":
+            from .frame import CompiledFrameDetectorSampler
+
+            return CompiledFrameDetectorSampler(self.compile_frame("detectors"), seed=seed, device=device, noise=noise)
         from .sampler import CompiledDetectorSampler
 
         program, channel_probs, error_transform = self.compile()
