@@ -480,6 +480,41 @@ int tsim_frame_sample_device(tsim_frame *h, int64_t B, int64_t first_shot, uint3
  * per window of the output stage, [13] its windows, [14] words per launch, [15] items of the largest batch */
 int tsim_frame_info(const tsim_frame *h, int64_t out[16]);
 
+/* ---- fault-driven detector sampler (CliffordCircuit.compile_detector_sampler(method="faults")) ----------------------------
+ * Every deterministic detector and observable is a constant XOR some error bits: a shot draws which noise sites fire, by
+ * geometric skipping over the sites that share one outcome table, and XORs each fired error bit's list of outputs into its
+ * row.  The compiled form (tsim_amd/faults.py documents it and states the same function in numpy):
+ *   classes     class_ptr int32 [n_classes + 1]: the sites of class c (they share table c), site_e0 int32 [n_sites] (class-
+ *               major: the site's first error bit), table_bits int32 [n_classes] (error bits per site, 1 .. 32);
+ *   tables      table_ptr int32 [n_classes + 1], table_gap int32 [n_classes], out_vals / out_thr uint32 [n_outcomes] (the
+ *               outcome's error bits; ceil(cdf 2^32), non-decreasing), gap_thr uint32 [n_gaps][gap_k] (floor((1-p)^k 2^32),
+ *               k = 1 .. gap_k, non-increasing; gap_k must be 1024, a constant of the stream);
+ *   columns     col_ptr int32 [num_e + 1], cols int32 [n_cols]: the outputs error bit e flips; out_const uint8 [n_out].
+ * Per shot g = first_shot + n and class c of n_c sites: key (n0 ^ c * 0x9E3779B9, n1) with (n0, n1) = threefry2x32(key,
+ * (0x6E6F6973, 0x66616C74)); pos = -1; draw j: (x0, x1) = threefry2x32(class key, (g mod 2^32, (g >> 32) | (j << 6)));
+ * skip = #{k : x0 < gap_thr[k]}; skip == gap_k: pos += gap_k and draw again; else pos += skip + 1, the class is done when
+ * pos >= n_c, else site pos fires with the first outcome whose threshold exceeds x1 (the last one when none does).  Results
+ * depend on the key and on g only.  A class of more than 2^25 sites (the draw index has 26 bits) is TSIM_ENOTSUP at create
+ * time; every index, CSR pointer, threshold order and size of the form is checked there, before any device call.  The handle
+ * owns no scratch: a request is one launch, rows live in LDS (outputs beyond one wave's LDS, about 20 000, go through in
+ * column windows that redraw the stream).  Output rows, col0 / n_cols, first_shot and stream: as tsim_frame_sample_device. */
+typedef struct tsim_faults_desc {
+  int32_t n_out, num_e, n_sites, n_classes, n_outcomes, n_gaps, gap_k, n_cols;
+  const int32_t *class_ptr, *site_e0, *table_bits, *table_ptr, *table_gap;
+  const uint32_t *out_vals, *out_thr, *gap_thr;
+  const int32_t *col_ptr, *cols;
+  const uint8_t *out_const;
+} tsim_faults_desc;
+typedef struct tsim_faults tsim_faults;
+int tsim_faults_create(int32_t device, const tsim_faults_desc *desc, tsim_faults **out);
+void tsim_faults_destroy(tsim_faults *h);
+int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo, uint8_t *d_out,
+                              int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols, void *stream);
+/* out[0] n_out, [1] num_e, [2] n_sites, [3] n_classes, [4] device, [5] gap_k, [6] columns per window, [7] windows of all
+ * outputs, [8] 32-bit words per LDS row, [9] waves per block, [10] LDS bytes per block, [11] 1 when the tables live in LDS,
+ * [12] n_gaps, [13] n_cols, [14] sites of the largest class, [15] the most columns a window can have */
+int tsim_faults_info(const tsim_faults *h, int64_t out[16]);
+
 /* ---- counts over bit-packed device rows (the samplers' count(): rates without moving the rows to the host) ---------------
  * Row r starts at byte r * row_bytes of d_rows and holds n_cols columns little-endian (row_bytes >= ceil(n_cols/8); the
  * buffer spans n * row_bytes bytes).  Optional rows of ceil(n_cols/8) bytes: d_xor is XORed into every row first, and a

@@ -65,6 +65,15 @@ class FrameDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in SIZES] + [(n, C.c_void_p) for n in ARRAYS]
 
 
+class FaultsDesc(C.Structure):
+    """``tsim_faults_desc`` (include/tsim_hip.h)."""
+
+    SIZES = ("n_out", "num_e", "n_sites", "n_classes", "n_outcomes", "n_gaps", "gap_k", "n_cols")
+    ARRAYS = ("class_ptr", "site_e0", "table_bits", "table_ptr", "table_gap", "out_vals", "out_thr", "gap_thr", "col_ptr", "cols",
+              "out_const")
+    _fields_ = [(n, C.c_int32) for n in SIZES] + [(n, C.c_void_p) for n in ARRAYS]
+
+
 # every symbol include/tsim_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I32, _I64, _U32 = C.c_int32, C.c_int64, C.c_uint32
@@ -121,6 +130,10 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_frame_destroy": (None, [_P]),
     "tsim_frame_sample_device": (C.c_int, [_P, _I64, _I64, _U32, _U32, _P, _I64, _I32, _I32, _I32, _P]),
     "tsim_frame_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "tsim_faults_create": (C.c_int, [_I32, C.POINTER(FaultsDesc), C.POINTER(_P)]),
+    "tsim_faults_destroy": (None, [_P]),
+    "tsim_faults_sample_device": (C.c_int, [_P, _I64, _I64, _U32, _U32, _P, _I64, _I32, _I32, _I32, _P]),
+    "tsim_faults_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_tally_rows_device": (C.c_int, [_I32, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P]),
     "tsim_pairs_create": (C.c_int, [_I32, _I32, _P, _I32, C.POINTER(_P)]),
     "tsim_pairs_destroy": (None, [_P]),

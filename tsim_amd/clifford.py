@@ -939,6 +939,23 @@ class CliffordCircuit:
             forms[kind] = frame.build_form(forms["walk"], kind)
         return forms[kind]
 
+    def compile_faults(self):
+        """The fault form (:class:`tsim_amd.faults.FaultForm`) of the detectors, then the observables by index - the columns of
+        :meth:`compile`: :meth:`analyze`'s channels as noise sites grouped by outcome table, and the transpose of its detector
+        and observable masks (error bit -> the outputs it flips).  No basis and nothing dense is built; detectors and
+        observables whose random outcomes do not cancel are refused as :meth:`compile` refuses them."""
+        if "_compiled_faults" not in self.__dict__:
+            from . import faults
+
+            an = self.analyze()
+            for k, (_, _, y) in an.observables.items():
+                if y:
+                    raise ValueError(f"OBSERVABLE {k} is not deterministic: its random outcomes do not cancel")
+            outputs = list(an.detectors) + [tuple(an.observables[k][:2]) for k in sorted(an.observables)]
+            self.__dict__["_compiled_faults"] = faults.build_form(an.channel_probs, an.num_e, [s for s, _ in outputs],
+                                                                  [v for _, v in outputs], len(an.detectors))
+        return self.__dict__["_compiled_faults"]
+
     def compile_sampler(self, *, seed: int | None = None, device: int = 0, noise: str = "host", mode: str = "auto",
                         method: str = "autoregressive"):
         """Mirror of ``Circuit.compile_sampler`` (src/tsim/circuit.py:812-834).  ``method="autoregressive"``: the
@@ -967,9 +984,15 @@ class CliffordCircuit:
                                  mode: str = "auto", method: str = "autoregressive"):
         """Mirror of ``Circuit.compile_detector_sampler`` (src/tsim/circuit.py:836-867).  ``method="frame"``: the Pauli-frame
         sampler (:mod:`tsim_amd.frame`): the same law from another stream, linear in the circuit, and detectors whose random
-        outcomes do not cancel are sampled instead of refused."""
-        if method not in ("autoregressive", "frame"):
-            raise ValueError(f"method must be 'autoregressive' or 'frame', got {method!r}")
+        outcomes do not cancel are sampled instead of refused.  ``method="faults"``: the fault-driven sampler
+        (:mod:`tsim_amd.faults`): the same law from a third stream, a shot draws which noise sites fire and XORs their
+        detectors; built from :meth:`analyze` alone, work per shot proportional to the faults that happened."""
+        if method not in ("autoregressive", "frame", "faults"):
+            raise ValueError(f"method must be 'autoregressive', 'frame' or 'faults', got {method!r}")
+        if method == "faults":
+            from .faults import CompiledFaultDetectorSampler
+
+            return CompiledFaultDetectorSampler(self.compile_faults(), seed=seed, device=device, noise=noise)
         if method == "frame":
             from .frame import CompiledFrameDetectorSampler
 
