@@ -597,6 +597,37 @@ int tsim_rowtab_load(tsim_rowtab *h, const uint8_t *keys, const uint64_t *values
 int tsim_rowtab_decode_device(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
                               const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, void *stream);
 
+/* ---- the union-find (cluster-growth) decoder over bit-packed device rows (count(decoder=UnionFindDecoder)) ----------
+ * The decoding graph: node 0 is the boundary, node i + 1 is detector (column) i; edge e joins edge_u[e] < edge_v[e], the
+ * pairs strictly ascending, and flips the observables edge_obs[e] (bit k = observable k).  The rule - synchronous
+ * growth rounds, the forest of smallest-index roots and parent edges, peeling - is the module docstring of
+ * tsim_amd/decode.py; it fixes the prediction whatever the order of the lanes.  n_cols: the columns of the rows this
+ * handle will be given (>= n_nodes - 1).  A handle of its own, bound to HIP device `device`.  tsim_uf_create checks every
+ * index and the ordering before any device call (TSIM_EINVAL); TSIM_ENOTSUP for more than 65535 nodes or edges and when
+ * one shot's state (8 bytes per node, 10 bytes per 32 edges) does not fit a block's 64 KiB of LDS. */
+typedef struct tsim_uf tsim_uf;
+typedef struct tsim_uf_desc {
+  int32_t n_nodes, n_edges, n_cols;
+  const int32_t *edge_u, *edge_v;
+  const uint64_t *edge_obs;
+} tsim_uf_desc;
+int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf **out);
+void tsim_uf_destroy(tsim_uf *h);
+/* out[0] nodes, [1] edges, [2] LDS bytes per shot, [3] shots (waves) per block, [4] kernel launches so far, [5] the most
+ * growth rounds a row took, [6] bytes of device memory, [7] rows decoded in LDS (kept rows with a defect), [8] n_cols,
+ * [9] blocks of a full grid; the rest 0.  Synchronises the device. */
+int tsim_uf_info(tsim_uf *h, int64_t out[16]);
+/* Rows, d_xor, d_test, obs_lo, obs_hi and d_counters are those of tsim_rowtab_decode_device and mean the same (masks of
+ * ceil(n_cols / 8) bytes): a row is KEPT iff (row ^ xor) & test == 0, its syndrome is row ^ xor at columns
+ * 0 .. n_nodes - 2, the prediction is compared with its columns obs_lo .. obs_hi - 1, and the call ACCUMULATES into
+ * d_counters: [0] kept rows, [1] kept rows whose prediction differs from their observables, [2] kept rows that are a
+ * miss (growth stopped with an active cluster left: no flip is predicted).  d_pred (NULL: not wanted; 8-byte aligned)
+ * receives every row's prediction as uint64[n]: 0 for a row that is not kept, and for a miss.  Asynchronous on `stream`;
+ * calls on one handle go to one stream, or are ordered by the caller.  n == 0 returns 0 without a launch. */
+int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                          const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                          void *stream);
+
 /* ---- stim's shot-data formats on the device (stim.read_shot_data_file / write_shot_data_file, the samplers'
  *      sample_write, CompiledMeasurementsToDetectionEventsConverter.convert_file) ------------------------------------
  * format: 0 "01", 1 "b8", 2 "r8", 3 "ptb64", 4 "hits", 5 "dets" (layouts: tsim_amd/shotdata.py).  A handle of its own,

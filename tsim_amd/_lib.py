@@ -74,6 +74,13 @@ class FaultsDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in SIZES] + [(n, C.c_void_p) for n in ARRAYS]
 
 
+class UfDesc(C.Structure):
+    """``tsim_uf_desc`` (include/tsim_hip.h)."""
+
+    _fields_ = [("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("n_cols", C.c_int32), ("edge_u", C.c_void_p), ("edge_v", C.c_void_p),
+                ("edge_obs", C.c_void_p)]
+
+
 # every symbol include/tsim_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I32, _I64, _U32 = C.c_int32, C.c_int64, C.c_uint32
@@ -149,6 +156,10 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_rowtab_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_rowtab_load": (C.c_int, [_P, _P, _P, _I64]),
     "tsim_rowtab_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P]),
+    "tsim_uf_create": (C.c_int, [_I32, C.POINTER(UfDesc), C.POINTER(_P)]),
+    "tsim_uf_destroy": (None, [_P]),
+    "tsim_uf_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "tsim_uf_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _P]),
     "tsim_shotdata_create": (C.c_int, [_I32, C.POINTER(_P)]),
     "tsim_shotdata_destroy": (None, [_P]),
     "tsim_shotdata_encode": (C.c_int, [_P, _I32, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(_I64), _P]),

@@ -456,6 +456,38 @@ class HipProgram:
     def rowtab_destroy(self, handle: int) -> None:
         self._lib.tsim_rowtab_destroy(C.c_void_p(handle))
 
+    UF_INFO = ("n_nodes", "n_edges", "lds_bytes_per_shot", "shots_per_block", "launches", "max_rounds", "device_bytes", "rows_decoded",
+               "n_cols", "grid_blocks")
+
+    def uf_create(self, graph, n_cols: int) -> int:
+        """A union-find decoder over ``graph`` (:class:`tsim_amd.decode.DecodingGraph`) for rows of ``n_cols`` columns on this
+        program's device (``tsim_uf_create``, include/tsim_hip.h): the handle, to be given back to :meth:`uf_destroy`."""
+        eu = np.ascontiguousarray(graph.edge_u, dtype=np.int32)
+        ev = np.ascontiguousarray(graph.edge_v, dtype=np.int32)
+        eo = np.ascontiguousarray(graph.edge_obs, dtype=np.uint64)
+        desc = _lib.UfDesc(int(graph.n_nodes), int(eu.size), int(n_cols), eu.ctypes.data, ev.ctypes.data, eo.ctypes.data)
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_uf_create(self.device, C.byref(desc), C.byref(h)), "tsim_uf_create")
+        return h.value
+
+    def uf_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,
+                         d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
+        """Decode the rows' syndromes and count kept / wrong / missed into ``d_counters``; ``d_pred``: ``uint64[n]`` for the
+        predictions (``tsim_uf_decode_device``); asynchronous on ``stream`` (0: the handle's stream)."""
+        _lib.check(self._lib.tsim_uf_decode_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
+                                                   C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
+                                                   int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
+                                                   C.c_void_p(int(d_pred)) if d_pred else None,
+                                                   C.c_void_p(stream or self.stream_ptr())), "tsim_uf_decode_device")
+
+    def uf_info(self, handle: int) -> dict:
+        out = (C.c_int64 * 16)()
+        _lib.check(self._lib.tsim_uf_info(C.c_void_p(handle), out), "tsim_uf_info")
+        return {k: int(v) for k, v in zip(self.UF_INFO, out)}
+
+    def uf_destroy(self, handle: int) -> None:
+        self._lib.tsim_uf_destroy(C.c_void_p(handle))
+
     def sample_batch_device(self, d_f: int, B: int, num_f: int, key, d_out: int, *,
                             shot_offset: int = 0, d_norm_dev: int = 0, stream: int = 0) -> None:
         """Asynchronous launch on the handle's stream (``stream``: a HIP stream of the caller instead); buffers are raw

@@ -15,8 +15,9 @@ caller owns (``m2d`` output, ``sample_steps_device`` rows).
 
 ``pattern_columns`` adds the joint statistic: the distinct patterns of the kept shots over those columns, each with its
 exact count (the row table, ``tsim_rowtab_*``, ``csrc/tsim_rowtab.hip.h``) - what ``np.unique(sample(), axis=0)`` gives
-without the rows crossing PCIe.  ``decoder`` (:class:`tsim_amd.decode.LookupDecoder`) applies a lookup decoder to every
-kept shot where it lies and counts the wrong predictions.
+without the rows crossing PCIe.  ``decoder`` (:class:`tsim_amd.decode.LookupDecoder`, a table of syndromes, or
+:class:`tsim_amd.decode.UnionFindDecoder`, cluster growth on the circuit's decoding graph, ``tsim_uf_*``) is applied to
+every kept shot where it lies, and the wrong predictions are counted.
 """
 
 from __future__ import annotations
@@ -304,7 +305,7 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
     (:func:`check_pattern_columns`): the distinct patterns of the kept rows (``np.unique``) with their counts, in the order
     of :class:`ShotCounts`; ``pattern_capacity`` (default: no limit) admits that many patterns in the order of first
     appearance and counts the rows of the others in ``pattern_overflow``.  ``decoder``: a
-    :class:`tsim_amd.decode.LookupDecoder` applied to the kept rows."""
+    :class:`tsim_amd.decode.LookupDecoder` or :class:`tsim_amd.decode.UnionFindDecoder` applied to the kept rows."""
     rows = np.asarray(rows, dtype=np.bool_)
     if rows.ndim != 2:
         raise ValueError(f"rows must be 2-D, got shape {rows.shape}")
@@ -447,7 +448,8 @@ class _DeviceTally:
         self._pairs = None       # the pair counter's handle (tsim_pairs), when pair columns are asked for
         self._pairs_stream = 0   # the stream its launches went to
         self._table = None       # the row table's handle (tsim_rowtab), when pattern columns are asked for
-        self._lookup = None      # the decoder's row table, loaded from the host
+        self._lookup = None      # the decoder's row table, loaded from the host (a LookupDecoder)
+        self._uf = None          # the decoder's graph handle (tsim_uf; a UnionFindDecoder)
         self.d_decoded = None    # its three counters
         try:
             if self.pc:
@@ -455,9 +457,14 @@ class _DeviceTally:
             if self.tc:
                 self._table = hp.rowtab_create(self.n_cols, self.tc, pattern_capacity or DEFAULT_PATTERN_CAPACITY)
             if decoder is not None:
-                keys, values = decoder.table()
-                self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))
-                hp.rowtab_load(self._lookup, keys, values)
+                from .decode import UnionFindDecoder
+
+                if isinstance(decoder, UnionFindDecoder):
+                    self._uf = hp.uf_create(decoder.graph, self.n_cols)
+                else:
+                    keys, values = decoder.table()
+                    self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))
+                    hp.rowtab_load(self._lookup, keys, values)
                 self.d_decoded = self._upload(np.zeros(3, dtype=np.uint64))
             self.d_counts = self._upload(np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64))
             self.d_xor = self._upload(self._row(xor_bits)) if xor_bits is not None and np.any(xor_bits) else None
@@ -492,7 +499,7 @@ class _DeviceTally:
             self.hp.pairs_add_device(self._pairs, d_first + (a - r0) * row_bytes, b - a, row_bytes,
                                      d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
                                      d_test=self.d_test.ptr if self.d_test is not None else 0, stream=stream)
-        if self._table is not None or self._lookup is not None:
+        if self._table is not None or self._lookup is not None or self._uf is not None:
             self._pairs_stream = stream
             masks = dict(d_xor=self.d_xor.ptr if self.d_xor is not None else 0, d_test=self.d_test.ptr if self.d_test is not None else 0,
                          stream=stream)
@@ -501,13 +508,16 @@ class _DeviceTally:
             if self._lookup is not None:
                 self.hp.rowtab_decode_device(self._lookup, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
                                              self.d_decoded.ptr, **masks)
+            if self._uf is not None:
+                self.hp.uf_decode_device(self._uf, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
+                                         self.d_decoded.ptr, **masks)
 
     def result(self, shots: int) -> ShotCounts:
         """The counters, once every tally launch has completed (the caller has synchronised their streams)."""
         c = np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64)
         self.hp.d2h(c, self.d_counts)
         out = ShotCounts.from_counters(c, shots=shots, n_cols=self.n_cols, num_detectors=self.nd, histogram_columns=self.hc)
-        if self._pairs is None and self._table is None and self._lookup is None:
+        if self._pairs is None and self._table is None and self._lookup is None and self._uf is None:
             return out
         pairs = self.hp.pairs_read(self._pairs, len(self.pc), stream=self._pairs_stream) if self._pairs is not None else None
         patterns = pattern_counts = errors = misses = None
@@ -516,7 +526,7 @@ class _DeviceTally:
             keys, cnt, info = self.hp.rowtab_read(self._table, len(self.tc), stream=self._pairs_stream)
             patterns, pattern_counts = ordered_patterns(keys, cnt, len(self.tc))
             overflow = int(info[4])
-        if self._lookup is not None:
+        if self._lookup is not None or self._uf is not None:
             self.hp.stream_synchronize(self._pairs_stream)
             d = np.zeros(3, dtype=np.uint64)
             self.hp.d2h(d, self.d_decoded)
@@ -530,6 +540,9 @@ class _DeviceTally:
             if getattr(self, name) is not None:
                 self.hp.rowtab_destroy(getattr(self, name))
                 setattr(self, name, None)
+        if self._uf is not None:
+            self.hp.uf_destroy(self._uf)
+            self._uf = None
         if self._pairs is not None:
             self.hp.pairs_destroy(self._pairs)
             self._pairs = None

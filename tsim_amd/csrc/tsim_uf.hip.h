@@ -1,0 +1,302 @@
+// tsim_uf.hip.h - the union-find (cluster-growth) decoder over bit-packed device rows (tsim_uf_*); the rule is the module
+// docstring of tsim_amd/decode.py, which is also its numpy statement.  Rows, xor and test are those of k_decode
+// (tsim_rowtab.hip.h): a row is kept iff (row ^ xor) & test == 0, its syndrome is row ^ xor at columns 0 .. n_nodes - 2.
+//
+// One wave owns a tile of 64 rows (a persistent grid).  Pass 1, row r = lane r: the keep mask, "has a defect" and the
+// observables, read straight from the row; a row without defects is finished here and touches no per-shot state.  Pass 2:
+// the kept rows with defects, one after the other, each decoded by the whole wave on the wave's own state in LDS:
+//   label[v]  uint16  the cluster of v: min-label propagation over the full edges, by plain stores repeated to the fixpoint
+//                     (a store only ever lowers a label to another label of the same cluster, so the fixpoint is the
+//                     smallest index of the cluster whichever store wins a race: the root the forest rule wants)
+//   lp[v]     uint32  level << 16 | parent edge: atomicMin of (level(u) + 1) << 16 | e over the full edges, to the fixpoint,
+//                     is the breadth-first level and the smallest-index edge to the level above
+//   s[v]      uint8   the defect, then the peeling state (32-bit LDS XOR on the word that holds the byte)
+//   par[v]    uint8   the parity of the defects of the cluster whose root is v (same XOR)
+//   half, full        bitmaps over the edges: grown >= 1, grown == 2.  A round visits the nodes of the active clusters and
+//                     ORs the half bit of every edge at such a node; the visit that finds it set (from an earlier round, or
+//                     from the other end in this round) ORs the full bit - grown + active(u) + active(v), capped at 2, in
+//                     any order of the visits
+//   wlist     uint16  the 32-bit words of `full` that are not zero (appended by the lane that set a word's first bit; the
+//                     order is arbitrary and nothing depends on it): labels, levels and peeling sweep these words only, a
+//                     lane per word, so no step of a shot sweeps all edges
+// The edge table (u | v << 16), the observable masks and the node adjacency (CSR) are read-only in global memory.
+// Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ufk {
+
+constexpr int kMaxWaves = 4;             // shots (waves) per block at most
+constexpr uint32_t kNone = 0xFFFFFFFFu;  // lp of a node no level has reached
+constexpr int kLdsBlock = 64 * 1024;     // LDS a block may ask for
+constexpr int kLdsCU = 160 * 1024;
+
+struct Args {
+  const uint8_t *rows;
+  long long n, rb;            // rows, row stride in bytes
+  int n_cols, used;           // columns; bytes of a row that hold them
+  const uint8_t *xr, *test;   // optional rows of `used` bytes (NULL: none)
+  int w8;                     // the row pointer and rb are multiples of 8
+  int n_nodes, n_edges, w32;  // w32: 32-bit words of an edge bitmap
+  const uint32_t *edge_uv;    // [n_edges] u | v << 16
+  const unsigned long long *edge_obs;
+  const uint32_t *adj_ptr;    // [n_nodes + 1]
+  const uint16_t *adj_edge;   // the edges at a node
+  int obs_lo, obs_hi;
+  int waves, shot_bytes;      // waves of a block; LDS bytes of one wave's state
+  int off_lp, off_s, off_par, off_half, off_full, off_wlist, off_misc;
+  unsigned long long *dec;    // [0] kept [1] wrong [2] missed
+  unsigned long long *pred;   // [n] or NULL
+  unsigned long long *stats;  // [0] most growth rounds [1] rows decoded in LDS
+};
+
+// the layout of one wave's state, shared by the host (sizes, limits) and the kernel
+__host__ __device__ inline int a16(long long x) { return (int)((x + 15) / 16 * 16); }
+__host__ inline long long layout(Args *a) {
+  const long long N = a->n_nodes, W = a->w32;
+  long long at = a16(2 * N);
+  a->off_lp = (int)at, at += a16(4 * N);
+  a->off_s = (int)at, at += a16(N);
+  a->off_par = (int)at, at += a16(N);
+  a->off_half = (int)at, at += a16(4 * W);
+  a->off_full = (int)at, at += a16(4 * W);
+  a->off_wlist = (int)at, at += a16(2 * W);
+  a->off_misc = (int)at, at += 16;
+  return at;
+}
+
+// keeps the compiler from moving LDS accesses of this wave across the point (the wave's LDS operations execute in order)
+__device__ __forceinline__ void wsync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// bytes b .. b + 7 of a mask row of `used` bytes (0 past its end, 0 for no mask)
+__device__ __forceinline__ uint64_t mask_word(const uint8_t *m, int b, int used) {
+  if (!m) return 0;
+  uint64_t w = 0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+    if (b + q < used) w |= (uint64_t)m[b + q] << (8 * q);
+  return w;
+}
+
+// the bits of columns 8 b .. 8 b + 63 that are below column `end`
+__device__ __forceinline__ uint64_t below(int b, int end) {
+  const long long left = (long long)end - 8ll * b;
+  return left <= 0 ? 0ull : left >= 64 ? ~0ull : ~0ull >> (64 - left);
+}
+
+struct State {
+  uint16_t *label;
+  uint32_t *lp, *s32, *par32, *half, *full, *misc;  // misc: [0] listed words [1] deepest level [2] [3] the prediction
+  uint8_t *s, *par;
+  uint16_t *wlist;
+};
+
+// f(e, u, v) for every full edge, a lane per listed word
+template <class F>
+__device__ __forceinline__ void full_edges(const Args &a, const State &st, int n_words, int lane, F f) {
+  for (int i = lane; i < n_words; i += 64) {
+    const int w = st.wlist[i];
+    uint32_t bits = st.full[w];
+    while (bits) {
+      const int e = 32 * w + __builtin_ctz(bits);
+      bits &= bits - 1;
+      const uint32_t uv = a.edge_uv[e];
+      f(e, (int)(uv & 0xFFFFu), (int)(uv >> 16));
+    }
+  }
+}
+
+// one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform
+__device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds) {
+  const int N = a.n_nodes;
+  for (int v = lane; v < N; v += 64) {
+    uint32_t bit = 0;
+    if (v) {
+      const int c = v - 1;
+      uint32_t byte = row[c >> 3];
+      if (a.xr) byte ^= a.xr[c >> 3];
+      bit = (byte >> (c & 7)) & 1u;
+    }
+    st.s[v] = (uint8_t)bit;
+    st.label[v] = (uint16_t)v;
+  }
+  for (int i = lane; i < a.w32; i += 64) st.half[i] = 0, st.full[i] = 0;
+  if (lane < 4) st.misc[lane] = 0;
+  wsync();
+  *missed = false;
+  *rounds = 0;
+  // ---- growth
+  for (;;) {
+    const int n_words = (int)st.misc[0];
+    for (;;) {  // the clusters: labels to their fixpoint (they stay upper bounds from round to round: clusters only merge)
+      bool moved = false;
+      full_edges(a, st, n_words, lane, [&](int, int u, int v) {
+        const uint16_t lu = st.label[u], lv = st.label[v];
+        if (lu < lv) st.label[v] = lu, moved = true;
+        else if (lv < lu) st.label[u] = lv, moved = true;
+      });
+      wsync();
+      if (!__builtin_amdgcn_ballot_w64(moved)) break;
+    }
+    for (int i = lane; i < (N + 3) / 4; i += 64) st.par32[i] = 0;
+    wsync();
+    for (int v = lane; v < N; v += 64)
+      if (st.s[v]) {
+        const int l = st.label[v];
+        atomicXor(&st.par32[l >> 2], 1u << (8 * (l & 3)));
+      }
+    wsync();
+    bool active = false, changed = false;
+    for (int v = lane; v < N; v += 64) {
+      const int l = st.label[v];
+      if (l == 0 || !st.par[l]) continue;
+      active = true;
+      for (uint32_t k = a.adj_ptr[v]; k < a.adj_ptr[v + 1]; ++k) {
+        const int e = a.adj_edge[k], w = e >> 5;
+        const uint32_t bit = 1u << (e & 31);
+        if (st.full[w] & bit) continue;  // (bits are only ever set: a set bit read here is final)
+        if (!(atomicOr(&st.half[w], bit) & bit)) {
+          changed = true;
+          continue;
+        }
+        const uint32_t was = atomicOr(&st.full[w], bit);
+        if (was & bit) continue;
+        changed = true;
+        if (was == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)w;  // (each word once: at most w32 entries)
+      }
+    }
+    wsync();
+    if (!__builtin_amdgcn_ballot_w64(active)) break;
+    if (!__builtin_amdgcn_ballot_w64(changed)) {
+      *missed = true;
+      return 0;
+    }
+    ++*rounds;
+  }
+  // ---- the forest
+  const int n_words = (int)st.misc[0];
+  for (int v = lane; v < N; v += 64) st.lp[v] = st.label[v] == v ? 0u : kNone;
+  wsync();
+  for (;;) {
+    bool moved = false;
+    full_edges(a, st, n_words, lane, [&](int e, int u, int v) {
+      const uint32_t pu = st.lp[u], pv = st.lp[v];
+      if (pu != kNone) {
+        const uint32_t cand = ((pu >> 16) + 1) << 16 | (uint32_t)e;
+        if (cand < pv && cand < atomicMin(&st.lp[v], cand)) moved = true;
+      }
+      if (pv != kNone) {
+        const uint32_t cand = ((pv >> 16) + 1) << 16 | (uint32_t)e;
+        if (cand < pu && cand < atomicMin(&st.lp[u], cand)) moved = true;
+      }
+    });
+    wsync();
+    if (!__builtin_amdgcn_ballot_w64(moved)) break;
+  }
+  full_edges(a, st, n_words, lane, [&](int, int u, int v) { atomicMax(&st.misc[1], max(st.lp[u], st.lp[v]) >> 16); });
+  wsync();
+  // ---- peeling: an edge is looked at by the level of the end whose parent edge it is
+  uint64_t flips = 0;
+  for (int level = (int)st.misc[1]; level >= 1; --level) {
+    full_edges(a, st, n_words, lane, [&](int e, int u, int v) {
+      const uint32_t want = (uint32_t)level << 16 | (uint32_t)e;
+      int child = -1, parent = 0;
+      if (st.lp[v] == want) child = v, parent = u;
+      else if (st.lp[u] == want) child = u, parent = v;
+      if (child < 0 || !st.s[child]) return;
+      atomicXor(&st.s32[parent >> 2], 1u << (8 * (parent & 3)));  // (the parent is of the level above: nobody reads it in this pass)
+      flips ^= a.edge_obs[e];
+    });
+    wsync();
+  }
+  if (flips) {
+    atomicXor(&st.misc[2], (uint32_t)flips);
+    atomicXor(&st.misc[3], (uint32_t)(flips >> 32));
+  }
+  wsync();
+  return (uint64_t)st.misc[2] | (uint64_t)st.misc[3] << 32;
+}
+
+__global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
+  State st;
+  st.label = reinterpret_cast<uint16_t *>(base);
+  st.lp = reinterpret_cast<uint32_t *>(base + a.off_lp);
+  st.s = base + a.off_s;
+  st.s32 = reinterpret_cast<uint32_t *>(st.s);
+  st.par = base + a.off_par;
+  st.par32 = reinterpret_cast<uint32_t *>(st.par);
+  st.half = reinterpret_cast<uint32_t *>(base + a.off_half);
+  st.full = reinterpret_cast<uint32_t *>(base + a.off_full);
+  st.wlist = reinterpret_cast<uint16_t *>(base + a.off_wlist);
+  st.misc = reinterpret_cast<uint32_t *>(base + a.off_misc);
+  if (threadIdx.x < 4) stat[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
+  int most_rounds = 0;
+  const int nd = a.n_nodes - 1;
+  const long long tiles = (a.n + 63) >> 6;
+  for (long long t = (long long)blockIdx.x * a.waves + wave; t < tiles; t += (long long)gridDim.x * a.waves) {
+    const long long r = (t << 6) + lane;
+    const bool valid = r < a.n;
+    const uint8_t *row = a.rows + (valid ? r : 0) * a.rb;
+    uint64_t fail = 0, defects = 0;
+    for (int b = 0; b < a.used; b += 8) {
+      const uint64_t tw = mask_word(a.test, b, a.used) & below(b, a.n_cols), dw = below(b, nd);  // (pad bits are not columns)
+      if ((tw | dw) == 0) continue;
+      uint64_t w = 0;
+      if (valid) {
+        if (a.w8) w = *reinterpret_cast<const uint64_t *>(row + b);  // (rb is a multiple of 8: inside the row)
+        else
+          for (int q = 0; q < 8 && b + q < a.used; ++q) w |= (uint64_t)row[b + q] << (8 * q);
+      }
+      w ^= mask_word(a.xr, b, a.used);
+      fail |= w & tw;
+      defects |= w & dw;
+    }
+    const bool kept = valid && fail == 0;
+    uint64_t obs = 0;
+    if (kept)
+      for (int c = a.obs_lo; c < a.obs_hi; ++c) {
+        uint32_t byte = row[c >> 3];
+        if (a.xr) byte ^= a.xr[c >> 3];
+        obs |= (uint64_t)((byte >> (c & 7)) & 1u) << (c - a.obs_lo);
+      }
+    uint64_t pred = 0;
+    bool missed = false;
+    uint64_t work = __builtin_amdgcn_ballot_w64(kept && defects != 0);
+    while (work) {
+      const int src = __builtin_ctzll(work);
+      work &= work - 1;
+      bool m;
+      int rounds;
+      const uint64_t p = decode_shot(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds);
+      if (lane == src) pred = p, missed = m;
+      most_rounds = max(most_rounds, rounds);
+      ++decoded_acc;
+    }
+    kept_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept));
+    wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
+    miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && missed));
+    if (a.pred && valid) a.pred[r] = pred;  // (0 for a row that is not kept, and for a miss)
+  }
+  if (lane == 0) {
+    if (kept_acc) atomicAdd(&stat[0], kept_acc);
+    if (wrong_acc) atomicAdd(&stat[1], wrong_acc);
+    if (miss_acc) atomicAdd(&stat[2], miss_acc);
+    if (most_rounds) atomicMax(&a.stats[0], (unsigned long long)most_rounds);
+    if (decoded_acc) atomicAdd(&a.stats[1], (unsigned long long)decoded_acc);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && stat[threadIdx.x]) atomicAdd(&a.dec[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
+}
+
+}  // namespace ufk

@@ -6,13 +6,47 @@ often; :meth:`LookupDecoder.from_counts` keeps, per detector pattern (syndrome),
 ``tsim_rowtab_load`` / ``tsim_rowtab_decode_device``, ``csrc/tsim_rowtab.hip.h``) and counts the shots whose observables
 differ from the prediction (``ShotCounts.decoded_errors``) and those whose syndrome is unknown
 (``ShotCounts.decoder_misses``); :meth:`LookupDecoder.decode` / :meth:`LookupDecoder.missed` are the same in numpy.
+
+A union-find (cluster-growth) decoder over the decoding graph of a Clifford circuit
+------------------------------------------------------------------------------------
+A table of syndromes stops at d = 3 .. 5: beyond that almost every syndrome is new.  :class:`UnionFindDecoder` needs no
+training run: it decodes on the graph of the circuit's error bits and always returns a correction that reproduces the
+syndrome (or reports a miss).  ``sampler.count(M, decoder=uf)`` runs it on the GPU (``tsim_uf_*``, ``csrc/tsim_uf.hip.h``);
+:meth:`UnionFindDecoder.decode` / :meth:`UnionFindDecoder.missed` are the numpy statement and the oracle of the GPU tests.
+
+The graph (:class:`DecodingGraph`, from the ``FaultForm`` of ``CliffordCircuit.compile_faults()``).  Node 0 is the boundary,
+node ``i + 1`` is detector ``i``.  The marginal of an error bit is the sum of its site's outcome probabilities over the
+outcomes that have the bit set; bits of marginal 0 are skipped.  A bit that flips the detector nodes ``{a}`` gives the pair
+``(0, a)``, one that flips ``{a, b}``, ``a < b``, gives ``(a, b)``; its observable mask is a uint64, bit ``k`` = observable
+``k``.  Bits of one pair merge: within one mask the probabilities combine as ``p (1 - q) + q (1 - p)`` (in the order of the
+bits); of several masks the one with the largest combined probability is kept, a tie going to the smaller mask.  Edges are
+numbered in ascending ``(u, v)`` order.  A bit without a detector and with an observable counts in ``undetectable_bits``, a
+bit with more than two detectors in ``dropped_bits`` (:meth:`DecodingGraph.info`); neither is refused.  At most 65535
+nodes and 65535 edges (uint16 indices on the device).  ``edge_p`` is kept for later use: this version decodes UNWEIGHTED.
+
+The decoding rule, stated so that no parallel order can change the answer.  For one shot ``defect[v]`` is the bit of
+detector ``v - 1``, ``defect[0] = 0``; every edge has ``grown[e]`` in ``{0, 1, 2}``, 0 at first.
+
+1. Growth, in synchronous rounds.  Clusters are the connected components of the nodes under the edges with ``grown == 2``
+   (every node is at least its own cluster).  A cluster is ACTIVE when it holds an odd number of defects and does not
+   contain node 0.  No active cluster: growth ends.  Otherwise, from the state at the start of the round, every edge gets
+   ``grown[e] = min(2, grown[e] + active(cluster(u)) + active(cluster(v)))``.  A round that changes nothing while a cluster
+   is active makes the shot a MISS (no flip is predicted): it happens only in a component without a boundary edge.
+2. Forest.  The root of a cluster is its node of smallest index (node 0 whenever the cluster contains it); ``level(v)`` is
+   the distance from the root over ``grown == 2`` edges; the parent edge of ``v`` is the smallest-index such edge to a node
+   of ``level(v) - 1``.
+3. Peeling, from the deepest level up.  ``s = defect``; a node ``v`` that is not a root and has ``s[v] = 1`` flips its
+   parent edge ``e``: both ends of ``e`` toggle in ``s`` and ``prediction ^= edge_obs[e]``.  Afterwards ``s`` is zero off
+   node 0 (asserted in the numpy statement).
 """
 
 from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["LookupDecoder"]
+__all__ = ["LookupDecoder", "DecodingGraph", "UnionFindDecoder"]
+
+MAX_GRAPH = 65535  # nodes, and edges: uint16 indices on the device
 
 
 def _pack(bits: np.ndarray) -> np.ndarray:
@@ -102,3 +136,268 @@ class LookupDecoder:
     def missed(self, dets) -> np.ndarray:
         """bool ``[n]``: the rows whose syndrome is not in the table."""
         return self._lookup(dets) < 0
+
+
+class DecodingGraph:
+    """The decoding graph (module docstring): ``n_nodes`` (node 0 the boundary), ``edge_u < edge_v`` (int32, strictly
+    ascending pairs), ``edge_obs`` (uint64 observable masks) and ``edge_p`` (float64, kept and not used by the decoder)."""
+
+    def __init__(self, n_nodes: int, edge_u, edge_v, edge_obs, edge_p=None, *, dropped_bits: int = 0, undetectable_bits: int = 0):
+        u, v = np.asarray(edge_u), np.asarray(edge_v)
+        if u.ndim != 1 or v.shape != u.shape or np.asarray(edge_obs).shape != u.shape:
+            raise ValueError(f"edge_u, edge_v and edge_obs must be 1-D and equally long, got shapes {u.shape}, {v.shape} and "
+                             f"{np.asarray(edge_obs).shape}")
+        if int(n_nodes) != n_nodes or n_nodes < 2:
+            raise ValueError(f"n_nodes = {n_nodes!r}: the boundary and at least one detector")
+        if n_nodes > MAX_GRAPH or len(u) > MAX_GRAPH:
+            raise NotImplementedError(f"{n_nodes} nodes and {len(u)} edges (at most {MAX_GRAPH} each: indices are uint16 on the device)")
+        if len(u) and not (np.issubdtype(u.dtype, np.integer) and np.issubdtype(v.dtype, np.integer)):
+            raise ValueError("edge_u and edge_v must be integers")
+        u, v = u.astype(np.int64), v.astype(np.int64)
+        if len(u) and (u.min() < 0 or v.max() >= n_nodes or v.min() < 0 or u.max() >= n_nodes):
+            raise ValueError(f"edge ends must lie in 0 .. {int(n_nodes) - 1}")
+        if (u >= v).any():
+            raise ValueError(f"edge {int(np.flatnonzero(u >= v)[0])}: u < v expected")
+        key = u * int(n_nodes) + v
+        if (np.diff(key) <= 0).any():
+            raise ValueError(f"edge {int(np.flatnonzero(np.diff(key) <= 0)[0]) + 1}: the pairs (u, v) must be strictly ascending")
+        p = np.zeros(len(u)) if edge_p is None else np.asarray(edge_p, dtype=np.float64)
+        if p.shape != u.shape:
+            raise ValueError(f"edge_p must have shape {u.shape}, got {p.shape}")
+        self.n_nodes = int(n_nodes)
+        self.edge_u, self.edge_v = u.astype(np.int32), v.astype(np.int32)
+        self.edge_obs = np.asarray(edge_obs).astype(np.uint64)
+        self.edge_p = p.copy()
+        self.dropped_bits, self.undetectable_bits = int(dropped_bits), int(undetectable_bits)
+
+    @property
+    def n_edges(self) -> int:
+        return len(self.edge_u)
+
+    def info(self) -> dict:
+        deg = np.bincount(np.concatenate([self.edge_u, self.edge_v]), minlength=self.n_nodes)
+        return dict(n_nodes=self.n_nodes, n_edges=self.n_edges, dropped_bits=self.dropped_bits,
+                    undetectable_bits=self.undetectable_bits, boundary_degree=int(deg[0]),
+                    max_node_degree=int(deg[1:].max()) if self.n_nodes > 1 else 0)
+
+    @classmethod
+    def from_form(cls, form) -> "DecodingGraph":
+        """From the ``FaultForm`` of ``CliffordCircuit.compile_faults()`` (module docstring)."""
+        if getattr(form, "kind", None) != "detectors":
+            raise ValueError("the decoding graph needs the form of compile_faults()")
+        nd, n_obs = int(form.num_detectors), int(form.n_out) - int(form.num_detectors)
+        if n_obs > 64:
+            raise ValueError(f"at most 64 observables, got {n_obs}")
+        if nd < 1:
+            raise ValueError("a decoder needs at least one detector")
+        if nd + 1 > MAX_GRAPH:
+            raise NotImplementedError(f"{nd + 1} nodes (at most {MAX_GRAPH}: indices are uint16 on the device)")
+        pairs: dict = {}   # (u, v) -> {mask: probability}
+        dropped = undetectable = 0
+        e0 = 0
+        for probs in form.channel_probs:
+            probs = np.asarray(probs, dtype=np.float64)
+            k = int(len(probs)).bit_length() - 1
+            outcomes = np.arange(len(probs))
+            for i in range(k):
+                e = e0 + i
+                p = float(probs[((outcomes >> i) & 1).astype(np.bool_)].sum())
+                if p <= 0.0:
+                    continue
+                cols = form.cols[form.col_ptr[e]:form.col_ptr[e + 1]]
+                dets = sorted(int(c) + 1 for c in cols if c < nd)
+                mask = 0
+                for c in cols:
+                    if c >= nd:
+                        mask |= 1 << (int(c) - nd)
+                if not dets:
+                    undetectable += bool(mask)
+                    continue
+                if len(dets) > 2:
+                    dropped += 1
+                    continue
+                pair = (0, dets[0]) if len(dets) == 1 else (dets[0], dets[1])
+                by_mask = pairs.setdefault(pair, {})
+                q = by_mask.get(mask, 0.0)
+                by_mask[mask] = p * (1.0 - q) + q * (1.0 - p)
+            e0 += k
+        if len(pairs) > MAX_GRAPH:
+            raise NotImplementedError(f"{len(pairs)} edges (at most {MAX_GRAPH}: indices are uint16 on the device)")
+        order = sorted(pairs)
+        best = [min(pairs[pr].items(), key=lambda mp: (-mp[1], mp[0])) for pr in order]   # the likelier mask, a tie to the smaller
+        return cls(nd + 1, np.array([pr[0] for pr in order], np.int32), np.array([pr[1] for pr in order], np.int32),
+                   np.array([m for m, _ in best], np.uint64), np.array([p for _, p in best], np.float64),
+                   dropped_bits=dropped, undetectable_bits=undetectable)
+
+
+def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray:
+    """Min-label propagation over the edges ``(fu, fv)``, from labels that are upper bounds, to its fixpoint."""
+    while len(fu):
+        m = np.minimum(label[fu], label[fv])
+        if (m == label[fu]).all() and (m == label[fv]).all():
+            break
+        np.minimum.at(label, fu, m)
+        np.minimum.at(label, fv, m)
+    return label
+
+
+class UnionFindDecoder:
+    """The union-find decoder of a :class:`DecodingGraph` (module docstring) for rows of ``graph.n_nodes - 1`` detectors and
+    ``num_observables`` observables (default: as many as the masks of the graph use, at least one; at most 64).
+    ``decode`` / ``missed`` have the signatures of :class:`LookupDecoder`; they decode each distinct syndrome once."""
+
+    def __init__(self, graph: DecodingGraph, num_observables: int | None = None):
+        used = int(np.bitwise_or.reduce(graph.edge_obs)) if graph.n_edges else 0
+        n_obs = max(1, used.bit_length()) if num_observables is None else int(num_observables)
+        if n_obs > 64:
+            raise ValueError(f"at most 64 observables, got {n_obs}")
+        if used >> n_obs:
+            raise ValueError(f"an edge flips observable {used.bit_length() - 1}, the rows have {n_obs}")
+        self.graph, self._n_obs = graph, n_obs
+        self._cache: dict = {}   # packed syndrome -> (prediction, missed, flipped edges, rounds)
+
+    @classmethod
+    def from_circuit(cls, circuit) -> "UnionFindDecoder":
+        """Of a :class:`tsim_amd.clifford.CliffordCircuit` with deterministic detectors (or its program text)."""
+        if isinstance(circuit, str):
+            from .clifford import CliffordCircuit
+
+            circuit = CliffordCircuit(circuit)
+        form = circuit.compile_faults()
+        return cls(DecodingGraph.from_form(form), int(form.n_out) - int(form.num_detectors))
+
+    @property
+    def num_detectors(self) -> int:
+        return self.graph.n_nodes - 1
+
+    @property
+    def num_observables(self) -> int:
+        return self._n_obs
+
+    def info(self) -> dict:
+        return self.graph.info()
+
+    # -- the numpy statement ---------------------------------------------------------------------------------------------
+    def _decode_one(self, defects: np.ndarray):
+        """One syndrome (the defect NODES, ascending): ``(prediction, missed, flipped edges ascending, growth rounds)``."""
+        g = self.graph
+        n, eu, ev = g.n_nodes, g.edge_u, g.edge_v
+        defect = np.zeros(n, np.bool_)
+        defect[defects] = True
+        grown = np.zeros(g.n_edges, np.int8)
+        label = np.arange(n)
+        rounds = 0
+        while True:
+            f = grown == 2
+            label = _components(label, eu[f], ev[f])
+            odd = (np.bincount(label[defect], minlength=n) & 1).astype(np.bool_)
+            odd[0] = False
+            active = odd[label]
+            if not active.any():
+                break
+            new = np.minimum(2, grown + active[eu] + active[ev]).astype(np.int8)
+            if np.array_equal(new, grown):
+                return 0, True, np.zeros(0, np.int64), rounds
+            grown, rounds = new, rounds + 1
+        # the forest: levels from the roots, the parent edge the smallest-index edge to the level above
+        fe = np.flatnonzero(grown == 2)
+        fu, fv = eu[fe], ev[fe]
+        level = np.where(label == np.arange(n), 0, -1)
+        parent = np.full(n, -1, np.int64)
+        depth = 0
+        while True:
+            down = (level[fu] == depth) & (level[fv] < 0)
+            up = (level[fv] == depth) & (level[fu] < 0)
+            child = np.concatenate([fv[down], fu[up]])
+            if not len(child):
+                break
+            via = np.concatenate([fe[down], fe[up]])
+            parent[child] = g.n_edges
+            np.minimum.at(parent, child, via)
+            level[child] = depth + 1
+            depth += 1
+        # peeling, from the deepest level up
+        s = defect.copy()
+        prediction, flipped = 0, []
+        for lv in range(depth, 0, -1):
+            for v in np.flatnonzero((level == lv) & s):
+                e = int(parent[v])
+                s[eu[e]] ^= True
+                s[ev[e]] ^= True
+                prediction ^= int(g.edge_obs[e])
+                flipped.append(e)
+        assert not s[1:].any(), "the correction does not reproduce the syndrome"
+        return prediction, False, np.array(sorted(flipped), np.int64), rounds
+
+    def _decoded(self, dets):
+        """Per row the cache entry of its syndrome (``None`` for a row without defects)."""
+        d = np.asarray(dets, dtype=np.bool_)
+        if d.ndim != 2 or d.shape[1] != self.num_detectors:
+            raise ValueError(f"dets must be [n, {self.num_detectors}], got shape {d.shape}")
+        out = [None] * len(d)
+        rows = np.flatnonzero(d.any(axis=1))
+        if not len(rows):
+            return out
+        uniq, inv = np.unique(_pack(d[rows]), axis=0, return_inverse=True)
+        inv = np.asarray(inv).reshape(-1)
+        entries = []
+        for k in uniq:
+            key = k.tobytes()
+            if key not in self._cache:
+                bits = np.unpackbits(k, bitorder="little", count=self.num_detectors)
+                self._cache[key] = self._decode_one(np.flatnonzero(bits) + 1)
+            entries.append(self._cache[key])
+        for r, i in zip(rows, inv):
+            out[r] = entries[i]
+        return out
+
+    def predictions(self, dets) -> np.ndarray:
+        """uint64 ``[n]``: the predicted observable mask of every row (bit ``k`` = observable ``k``; 0 for a miss) - what the
+        device kernel writes to ``d_pred``."""
+        return np.array([0 if e is None else e[0] for e in self._decoded(dets)], dtype=np.uint64)
+
+    def decode(self, dets) -> np.ndarray:
+        """bool ``[n, num_observables]``: the predicted observable flips of detector rows bool ``[n, num_detectors]``."""
+        p = self.predictions(dets)
+        return ((p[:, None] >> np.arange(self._n_obs, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.bool_)
+
+    def missed(self, dets) -> np.ndarray:
+        """bool ``[n]``: the rows whose growth stopped with an active cluster left (no flip is predicted for them)."""
+        return np.array([e is not None and e[1] for e in self._decoded(dets)], dtype=np.bool_)
+
+    def flipped_edges(self, dets) -> list:
+        """Per row the edges of its correction (int64, ascending; empty for a row without defects and for a miss)."""
+        return [np.zeros(0, np.int64) if e is None else e[2] for e in self._decoded(dets)]
+
+    def growth_rounds(self, dets) -> np.ndarray:
+        """int64 ``[n]``: the growth rounds every row took."""
+        return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
+
+    # -- the device side -------------------------------------------------------------------------------------------------
+    def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
+                      stream: int = 0):
+        """``(predictions uint64[n], (kept, wrong, missed))`` for ``n`` bit-packed rows already in HBM (detectors, then
+        observables; ``n_cols`` columns, default ``num_detectors + num_observables``; ``d_xor`` / ``d_test``: device masks of
+        ``ceil(n_cols / 8)`` bytes) by one ``tsim_uf`` handle on ``hp``'s device, created and destroyed here.  A row that is
+        not kept and a miss predict 0.  Returns when the results are on the host."""
+        nd = self.num_detectors
+        n_cols = nd + self._n_obs if n_cols is None else int(n_cols)
+        h = hp.uf_create(self.graph, n_cols)
+        bufs = []
+        try:
+            pred = np.zeros(int(n), np.uint64)
+            cnt = np.zeros(3, np.uint64)
+            d_pred, d_cnt = hp.malloc(pred.nbytes + 16), hp.malloc(cnt.nbytes + 16)
+            bufs += [d_pred, d_cnt]
+            hp.h2d(d_cnt, cnt)
+            hp.uf_decode_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, d_pred=d_pred.ptr, d_xor=d_xor,
+                                d_test=d_test, stream=stream)
+            hp.stream_synchronize(stream)
+            if n:
+                hp.d2h(pred, d_pred)
+            hp.d2h(cnt, d_cnt)
+            return pred, tuple(int(x) for x in cnt)
+        finally:
+            hp.uf_destroy(h)
+            for b in bufs:
+                b.free()

@@ -1248,9 +1248,12 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
         default 2^20 slots over the 121 columns of a d = 5 memory experiment: 32 MiB).  Keep it at a few times the number
         of distinct patterns expected: shots whose pattern finds no room are counted in ``pattern_overflow`` and a
         ``RuntimeWarning`` names the capacity - the patterns that are returned carry their exact counts all the same.
-        ``decoder`` (a :class:`tsim_amd.decode.LookupDecoder`) is applied to every kept shot on the GPU:
-        ``decoded_errors`` kept shots whose observables differ from its prediction, ``decoder_misses`` kept shots whose
-        syndrome it does not know.  For a fresh sampler with the same seed and arguments this
+        ``decoder`` is applied to every kept shot on the GPU: a :class:`tsim_amd.decode.LookupDecoder` (a table of
+        syndromes from a training run: exact at d = 3, blind beyond d = 5) or a :class:`tsim_amd.decode.UnionFindDecoder`
+        (cluster growth on the circuit's decoding graph, ``UnionFindDecoder.from_circuit(circuit)``: no training, any
+        distance whose graph fits).  ``decoded_errors``: kept shots whose observables differ from its prediction;
+        ``decoder_misses``: kept shots for which it has no prediction (an unknown syndrome; a cluster that cannot reach the
+        boundary) and predicts no flip.  For a fresh sampler with the same seed and arguments this
         equals ``counts.tally_rows(sample(..., append_observables=True), ...)``, and the sampler's keys stand where that
         ``sample()`` would leave them."""
         nd = self._num_detectors
