@@ -612,10 +612,15 @@ typedef struct tsim_uf_desc {
   const uint64_t *edge_obs;
 } tsim_uf_desc;
 int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf **out);
+/* Weighted growth: edge_cap[e] in 1 .. 14 is the growth an edge takes to be full (grown[e] = min(cap[e], grown[e] +
+ * active ends) per round); edge_cap == NULL is tsim_uf_create, which is cap 2 everywhere.  A cap outside 1 .. 14 is
+ * TSIM_EINVAL, checked with the other arguments before any device call.  A shot's state then holds 4 bits per edge in
+ * the place of one of the two edge bitmaps (8 bytes per node, 6 + 16 bytes per 32 edges) for the 64 KiB limit. */
+int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, tsim_uf **out);
 void tsim_uf_destroy(tsim_uf *h);
 /* out[0] nodes, [1] edges, [2] LDS bytes per shot, [3] shots (waves) per block, [4] kernel launches so far, [5] the most
  * growth rounds a row took, [6] bytes of device memory, [7] rows decoded in LDS (kept rows with a defect), [8] n_cols,
- * [9] blocks of a full grid; the rest 0.  Synchronises the device. */
+ * [9] blocks of a full grid, [10] the largest cap (0: an unweighted handle); the rest 0.  Synchronises the device. */
 int tsim_uf_info(tsim_uf *h, int64_t out[16]);
 /* Rows, d_xor, d_test, obs_lo, obs_hi and d_counters are those of tsim_rowtab_decode_device and mean the same (masks of
  * ceil(n_cols / 8) bytes): a row is KEPT iff (row ^ xor) & test == 0, its syndrome is row ^ xor at columns

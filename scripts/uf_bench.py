@@ -2,6 +2,7 @@
 
     python scripts/uf_bench.py                       # the table: per distance, JSON lines
     python scripts/uf_bench.py --circuits d15 --shots 1000000
+    python scripts/uf_bench.py --resolution 4        # weighted against unweighted growth: d = 5, 9, 15
 
 Per distance the ``method="faults"`` sampler counts ``--shots`` shots per call in batches of 10^6, once without a decoder and
 once with ``decoder=UnionFindDecoder.from_circuit(circuit)``, alternating, each warmed up first; the time is a host clock
@@ -9,6 +10,12 @@ around a call that returns the counters (it ends in a device synchronise); the m
 reported, with the decoded logical error rate, the misses and what ``tsim_uf_info`` says about the kernel (LDS per shot, shots
 per block, the most growth rounds a row took).  At d = 3 a ``LookupDecoder`` trained on ``--train`` shots of another seed
 runs beside it: the maximum-likelihood bound at that size.  All three noise options are set to ``--p``.
+
+``--resolution R`` is a leg of its own (``--circuits`` then defaults to d5,d9,d15): the same circuit, the same seeded rows and
+the same ``count()`` call with ``UnionFindDecoder.from_circuit(circuit)`` and with ``from_circuit(circuit,
+weights="probability", resolution=R)``, alternating; both rates with the spread of the calls, both decoded error counts and
+misses, and per decoder the most growth rounds ``tsim_uf_info`` reports after decoding ``--info-rows`` sampled rows on a
+handle of its own.
 """
 
 from __future__ import annotations
@@ -27,22 +34,86 @@ from tsim_amd.clifford import CliffordCircuit  # noqa: E402
 from tsim_amd.decode import LookupDecoder, UnionFindDecoder  # noqa: E402
 
 
+def memory(d: int, p: float) -> CliffordCircuit:
+    return CliffordCircuit(circuits.rotated_surface_code_memory(d, d, after_clifford_depolarization=p, before_measure_flip_probability=p,
+                                                                after_reset_flip_probability=p))
+
+
+def device_info(hp, sampler, uf, n: int) -> dict:
+    """``tsim_uf_info`` of a handle that has decoded ``n`` rows of ``sampler`` (bit-packed on the host, then uploaded)."""
+    import numpy as np
+
+    rows = np.ascontiguousarray(np.packbits(sampler.sample(n, append_observables=True), axis=1, bitorder="little"))
+    nd, n_cols = uf.num_detectors, uf.num_detectors + uf.num_observables
+    h = hp.uf_create(uf.graph, n_cols, uf.edge_caps)
+    d_rows, d_cnt = hp.malloc(rows.nbytes + 16), hp.malloc(64)
+    try:
+        hp.h2d(d_rows, rows)
+        hp.h2d(d_cnt, np.zeros(3, np.uint64))
+        hp.uf_decode_device(h, d_rows.ptr, len(rows), rows.shape[1], (nd, n_cols), d_cnt.ptr)
+        return hp.uf_info(h)
+    finally:
+        hp.uf_destroy(h)
+        d_rows.free()
+        d_cnt.free()
+
+
+def weighted_leg(args) -> None:
+    for name in (args.circuits or "d5,d9,d15").split(","):
+        d = int(name[1:])
+        c = memory(d, args.p)
+        decoders = {"unweighted": UnionFindDecoder.from_circuit(c),
+                    "weighted": UnionFindDecoder.from_circuit(c, weights="probability", resolution=args.resolution)}
+        def sampler():  # a fresh one per call: every call counts the same seeded rows
+            return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+        times, last = {m: [] for m in decoders}, {}
+        for m, uf in decoders.items():
+            sampler().count(args.shots, batch_size=10**6, decoder=uf)  # warm-up at the timed size
+        for _ in range(args.reps):
+            for m, uf in decoders.items():
+                s = sampler()
+                t0 = time.perf_counter()
+                last[m] = s.count(args.shots, batch_size=10**6, decoder=uf)
+                times[m].append(time.perf_counter() - t0)
+        if last["weighted"].kept_with_observable_flip != last["unweighted"].kept_with_observable_flip:
+            sys.exit("uf_bench: the two decoders did not see the same rows")
+        hp = s._hip()
+        info = {m: device_info(hp, c.compile_detector_sampler(seed=3, noise="device", method="faults"), uf, args.info_rows)
+                for m, uf in decoders.items()}
+        rate = {m: args.shots / statistics.median(t) for m, t in times.items()}
+        caps = decoders["weighted"].edge_caps
+        print(json.dumps(dict(
+            case=name, leg="resolution", resolution=args.resolution, p=args.p, shots=args.shots, reps=args.reps,
+            graph=decoders["unweighted"].info(), caps={int(k): int((caps == k).sum()) for k in sorted(set(caps.tolist()))},
+            median_s={m: statistics.median(t) for m, t in times.items()}, min_s={m: min(t) for m, t in times.items()},
+            max_s={m: max(t) for m, t in times.items()}, shots_per_s=rate, weighted_over_unweighted=rate["weighted"] / rate["unweighted"],
+            kept={m: last[m].kept for m in decoders}, raw_flips={m: last[m].kept_with_observable_flip for m in decoders},
+            decoded_errors={m: last[m].decoded_errors for m in decoders}, misses={m: last[m].decoder_misses for m in decoders},
+            info_rows=args.info_rows, max_rounds={m: info[m]["max_rounds"] for m in decoders},
+            lds_bytes_per_shot={m: info[m]["lds_bytes_per_shot"] for m in decoders},
+            shots_per_block={m: info[m]["shots_per_block"] for m in decoders}, grid_blocks={m: info[m]["grid_blocks"] for m in decoders})),
+            flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shots", type=int, default=10**7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--p", type=float, default=1e-3)
-    ap.add_argument("--circuits", default="d3,d5,d7,d11,d15")
+    ap.add_argument("--circuits", default=None, help="default d3,d5,d7,d11,d15; d5,d9,d15 with --resolution")
     ap.add_argument("--train", type=int, default=10**8)
+    ap.add_argument("--resolution", type=int, default=None, help="the leg that runs weighted against unweighted growth")
+    ap.add_argument("--info-rows", type=int, default=20000)
     args = ap.parse_args()
     _lib.load()
     if _lib.device_count() < 1:
         sys.exit("uf_bench: no HIP device - nothing is measured without one")
-    for name in args.circuits.split(","):
+    if args.resolution is not None:
+        return weighted_leg(args)
+    for name in (args.circuits or "d3,d5,d7,d11,d15").split(","):
         d = int(name[1:])
-        c = CliffordCircuit(circuits.rotated_surface_code_memory(d, d, after_clifford_depolarization=args.p,
-                                                                 before_measure_flip_probability=args.p,
-                                                                 after_reset_flip_probability=args.p))
+        c = memory(d, args.p)
         t0 = time.perf_counter()
         uf = UnionFindDecoder.from_circuit(c)
         graph_s = time.perf_counter() - t0

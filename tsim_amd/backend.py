@@ -457,17 +457,26 @@ class HipProgram:
         self._lib.tsim_rowtab_destroy(C.c_void_p(handle))
 
     UF_INFO = ("n_nodes", "n_edges", "lds_bytes_per_shot", "shots_per_block", "launches", "max_rounds", "device_bytes", "rows_decoded",
-               "n_cols", "grid_blocks")
+               "n_cols", "grid_blocks", "max_cap")
 
-    def uf_create(self, graph, n_cols: int) -> int:
+    def uf_create(self, graph, n_cols: int, caps=None) -> int:
         """A union-find decoder over ``graph`` (:class:`tsim_amd.decode.DecodingGraph`) for rows of ``n_cols`` columns on this
-        program's device (``tsim_uf_create``, include/tsim_hip.h): the handle, to be given back to :meth:`uf_destroy`."""
+        program's device (``tsim_uf_create``, include/tsim_hip.h): the handle, to be given back to :meth:`uf_destroy`.
+        ``caps``: ``None``, or an integer per edge in 1 .. 14 for weighted growth (``tsim_uf_create_weighted``)."""
         eu = np.ascontiguousarray(graph.edge_u, dtype=np.int32)
         ev = np.ascontiguousarray(graph.edge_v, dtype=np.int32)
         eo = np.ascontiguousarray(graph.edge_obs, dtype=np.uint64)
         desc = _lib.UfDesc(int(graph.n_nodes), int(eu.size), int(n_cols), eu.ctypes.data, ev.ctypes.data, eo.ctypes.data)
         h = C.c_void_p()
-        _lib.check(self._lib.tsim_uf_create(self.device, C.byref(desc), C.byref(h)), "tsim_uf_create")
+        if caps is None:
+            _lib.check(self._lib.tsim_uf_create(self.device, C.byref(desc), C.byref(h)), "tsim_uf_create")
+            return h.value
+        ec = np.ascontiguousarray(caps)
+        if ec.shape != (eu.size,) or not np.issubdtype(ec.dtype, np.integer) or (ec.size and (ec.min() < 0 or ec.max() > 255)):
+            raise ValueError(f"caps: {eu.size} integers in 1 .. 14 expected")
+        ec = np.concatenate([ec.astype(np.uint8), np.zeros(1, np.uint8)])  # (never an empty buffer: NULL means unweighted)
+        _lib.check(self._lib.tsim_uf_create_weighted(self.device, C.byref(desc), C.c_void_p(ec.ctypes.data), C.byref(h)),
+                   "tsim_uf_create_weighted")
         return h.value
 
     def uf_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,

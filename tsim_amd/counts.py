@@ -460,7 +460,7 @@ class _DeviceTally:
                 from .decode import UnionFindDecoder
 
                 if isinstance(decoder, UnionFindDecoder):
-                    self._uf = hp.uf_create(decoder.graph, self.n_cols)
+                    self._uf = hp.uf_create(decoder.graph, self.n_cols, decoder.edge_caps)
                 else:
                     keys, values = decoder.table()
                     self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))

@@ -30,15 +30,21 @@ struct tsim_uf {
   uint32_t *d_edge_uv = nullptr, *d_adj_ptr = nullptr;
   unsigned long long *d_edge_obs = nullptr, *d_stats = nullptr;
   uint16_t *d_adj_edge = nullptr;
+  uint8_t *d_cap = nullptr;
+  int max_cap = 0;  // 0: unweighted
 };
 
 static void uf_release(tsim_uf *h) {
   if (h->device >= 0) (void)hipSetDevice(h->device);
-  for (void *p : {(void *)h->d_edge_uv, (void *)h->d_adj_ptr, (void *)h->d_edge_obs, (void *)h->d_stats, (void *)h->d_adj_edge})
+  for (void *p : {(void *)h->d_edge_uv, (void *)h->d_adj_ptr, (void *)h->d_edge_obs, (void *)h->d_stats, (void *)h->d_adj_edge, (void *)h->d_cap})
     if (p) (void)hipFree(p);
 }
 
 extern "C" int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf **out) {
+  return tsim_uf_create_weighted(device, desc, nullptr, out);
+}
+
+extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, tsim_uf **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
   *out = nullptr;
   if (!desc) return tsim_fail(TSIM_EINVAL, "desc is NULL");
@@ -57,11 +63,19 @@ extern "C" int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf 
     if (e > 0 && (desc->edge_u[e - 1] > u || (desc->edge_u[e - 1] == u && desc->edge_v[e - 1] >= v)))
       return tsim_fail(TSIM_EINVAL, "edge %d = (%d, %d) does not come after edge %d: the pairs must be strictly ascending", e, u, v, e - 1);
   }
+  int max_cap = 0;
+  if (edge_cap)
+    for (int e = 0; e < E; ++e) {
+      if (edge_cap[e] < 1 || edge_cap[e] > ufk::kMaxCap)
+        return tsim_fail(TSIM_EINVAL, "edge %d has cap %d (1 .. %d: a 4-bit counter that may overshoot by one)", e, edge_cap[e], ufk::kMaxCap);
+      max_cap = std::max<int>(max_cap, edge_cap[e]);
+    }
   ufk::Args a{};
   a.n_nodes = N;
   a.n_edges = E;
   a.n_cols = desc->n_cols;
   a.w32 = std::max(1, (E + 31) / 32);
+  a.w_cnt = edge_cap ? std::max(1, (E + 7) / 8) : 0;
   const long long shot = ufk::layout(&a);
   if (16 + shot > ufk::kLdsBlock)
     return tsim_fail(TSIM_ENOTSUP, "one shot's state takes %lld bytes of LDS (%d nodes, %d edges), a block has %d", shot, N, E, ufk::kLdsBlock - 16);
@@ -98,12 +112,16 @@ extern "C" int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf 
   h->device = device;
   h->grid = std::max(1, cus) * per_cu;
   const size_t ne = uv.size(), na = adj.size();
-  h->bytes = (int64_t)(ne * 12 + ptr.size() * 4 + na * 2 + 16);
+  h->max_cap = max_cap;
+  h->bytes = (int64_t)(ne * 12 + ptr.size() * 4 + na * 2 + 16 + (edge_cap ? ne : 0));
   hipError_t e = hipMalloc(&h->d_edge_uv, ne * 4);
   if (e == hipSuccess) e = hipMalloc(&h->d_edge_obs, ne * 8);
   if (e == hipSuccess) e = hipMalloc(&h->d_adj_ptr, ptr.size() * 4);
   if (e == hipSuccess) e = hipMalloc(&h->d_adj_edge, na * 2);
   if (e == hipSuccess) e = hipMalloc(&h->d_stats, 16);
+  if (e == hipSuccess && edge_cap) e = hipMalloc(&h->d_cap, ne);
+  if (e == hipSuccess && edge_cap) e = hipMemset(h->d_cap, 1, ne);
+  if (e == hipSuccess && edge_cap && E) e = hipMemcpy(h->d_cap, edge_cap, (size_t)E, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->d_edge_uv, uv.data(), ne * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(h->d_edge_obs, 0, ne * 8);
   if (e == hipSuccess && E) e = hipMemcpy(h->d_edge_obs, desc->edge_obs, (size_t)E * 8, hipMemcpyHostToDevice);
@@ -120,6 +138,7 @@ extern "C" int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf 
   a.edge_obs = h->d_edge_obs;
   a.adj_ptr = h->d_adj_ptr;
   a.adj_edge = h->d_adj_edge;
+  a.cap = h->d_cap;
   a.stats = h->d_stats;
   h->a = a;
   *out = h;
@@ -149,6 +168,7 @@ extern "C" int tsim_uf_info(tsim_uf *h, int64_t out[16]) {
   out[7] = (int64_t)st[1];
   out[8] = h->a.n_cols;
   out[9] = h->grid;
+  out[10] = h->max_cap;
   return TSIM_OK;
 }
 
@@ -183,7 +203,8 @@ extern "C" int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t 
     a.pred = d_pred ? reinterpret_cast<unsigned long long *>(d_pred) + r0 : nullptr;
     const int64_t tiles = (a.n + 63) / 64;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + a.waves - 1) / a.waves, h->grid));
-    hipLaunchKernelGGL(ufk::k_uf, dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    if (a.cap) hipLaunchKernelGGL(ufk::k_uf<true>, dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(ufk::k_uf<false>, dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
     UF_TRY(hipGetLastError());
     ++h->launches;
   }

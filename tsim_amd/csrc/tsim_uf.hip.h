@@ -16,10 +16,16 @@
 //                     ORs the half bit of every edge at such a node; the visit that finds it set (from an earlier round, or
 //                     from the other end in this round) ORs the full bit - grown + active(u) + active(v), capped at 2, in
 //                     any order of the visits
+//   cnt       uint32  (weighted growth, in the place of `half`) grown[e] as a 4-bit counter, eight edges to a word: a visit
+//                     adds 1 to the edge's nibble; the visit whose old nibble is cap[e] - 1 ORs the full bit.  An edge that
+//                     is not full starts a round at <= cap - 1 and is visited at most once from each end, so the nibble ends
+//                     at <= cap + 1 <= 15 (caps are 1 .. 14) and never carries; past the cap it means nothing, fullness is
+//                     the full bit - grown + active(u) + active(v), capped at cap[e], in any order of the visits
 //   wlist     uint16  the 32-bit words of `full` that are not zero (appended by the lane that set a word's first bit; the
 //                     order is arbitrary and nothing depends on it): labels, levels and peeling sweep these words only, a
 //                     lane per word, so no step of a shot sweeps all edges
-// The edge table (u | v << 16), the observable masks and the node adjacency (CSR) are read-only in global memory.
+// The edge table (u | v << 16), the observable masks, the caps (uint8, weighted growth only) and the node adjacency (CSR) are
+// read-only in global memory.
 // Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +37,7 @@ constexpr int kMaxWaves = 4;             // shots (waves) per block at most
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // lp of a node no level has reached
 constexpr int kLdsBlock = 64 * 1024;     // LDS a block may ask for
 constexpr int kLdsCU = 160 * 1024;
+constexpr int kMaxCap = 14;              // of an edge: its 4-bit counter may pass the cap by one
 
 struct Args {
   const uint8_t *rows;
@@ -41,6 +48,8 @@ struct Args {
   int n_nodes, n_edges, w32;  // w32: 32-bit words of an edge bitmap
   const uint32_t *edge_uv;    // [n_edges] u | v << 16
   const unsigned long long *edge_obs;
+  const uint8_t *cap;         // [n_edges] 1 .. 14, or NULL: every cap is 2 (the half / full bitmaps)
+  int w_cnt;                  // 32-bit words of the 4-bit counters (weighted growth), 0 without caps
   const uint32_t *adj_ptr;    // [n_nodes + 1]
   const uint16_t *adj_edge;   // the edges at a node
   int obs_lo, obs_hi;
@@ -59,7 +68,7 @@ __host__ inline long long layout(Args *a) {
   a->off_lp = (int)at, at += a16(4 * N);
   a->off_s = (int)at, at += a16(N);
   a->off_par = (int)at, at += a16(N);
-  a->off_half = (int)at, at += a16(4 * W);
+  a->off_half = (int)at, at += a16(4 * (a->w_cnt ? (long long)a->w_cnt : W));  // (the counters lie where `half` would)
   a->off_full = (int)at, at += a16(4 * W);
   a->off_wlist = (int)at, at += a16(2 * W);
   a->off_misc = (int)at, at += 16;
@@ -92,6 +101,7 @@ __device__ __forceinline__ uint64_t below(int b, int end) {
 struct State {
   uint16_t *label;
   uint32_t *lp, *s32, *par32, *half, *full, *misc;  // misc: [0] listed words [1] deepest level [2] [3] the prediction
+  //                                                   (half: the 4-bit counters when the growth is weighted)
   uint8_t *s, *par;
   uint16_t *wlist;
 };
@@ -112,6 +122,7 @@ __device__ __forceinline__ void full_edges(const Args &a, const State &st, int n
 }
 
 // one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform
+template <bool Weighted>
 __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds) {
   const int N = a.n_nodes;
   for (int v = lane; v < N; v += 64) {
@@ -125,7 +136,12 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
     st.s[v] = (uint8_t)bit;
     st.label[v] = (uint16_t)v;
   }
-  for (int i = lane; i < a.w32; i += 64) st.half[i] = 0, st.full[i] = 0;
+  if constexpr (Weighted) {
+    for (int i = lane; i < a.w_cnt; i += 64) st.half[i] = 0;
+    for (int i = lane; i < a.w32; i += 64) st.full[i] = 0;
+  } else {
+    for (int i = lane; i < a.w32; i += 64) st.half[i] = 0, st.full[i] = 0;
+  }
   if (lane < 4) st.misc[lane] = 0;
   wsync();
   *missed = false;
@@ -160,14 +176,24 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
         const int e = a.adj_edge[k], w = e >> 5;
         const uint32_t bit = 1u << (e & 31);
         if (st.full[w] & bit) continue;  // (bits are only ever set: a set bit read here is final)
-        if (!(atomicOr(&st.half[w], bit) & bit)) {
+        if constexpr (Weighted) {
+          const int sh = 4 * (e & 7);
+          const uint32_t old = (atomicAdd(&st.half[e >> 3], 1u << sh) >> sh) & 15u, cap = a.cap[e];
+          if (old >= cap) continue;  // (filled from the other end in this round)
           changed = true;
-          continue;
+          if (old + 1 < cap) continue;
+          // (old == cap - 1: one visit only sees it, so the bit is set once)
+          if (atomicOr(&st.full[w], bit) == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)w;
+        } else {
+          if (!(atomicOr(&st.half[w], bit) & bit)) {
+            changed = true;
+            continue;
+          }
+          const uint32_t was = atomicOr(&st.full[w], bit);
+          if (was & bit) continue;
+          changed = true;
+          if (was == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)w;  // (each word once: at most w32 entries)
         }
-        const uint32_t was = atomicOr(&st.full[w], bit);
-        if (was & bit) continue;
-        changed = true;
-        if (was == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)w;  // (each word once: at most w32 entries)
       }
     }
     wsync();
@@ -222,6 +248,7 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   return (uint64_t)st.misc[2] | (uint64_t)st.misc[3] << 32;
 }
 
+template <bool Weighted>
 __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
@@ -278,7 +305,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       work &= work - 1;
       bool m;
       int rounds;
-      const uint64_t p = decode_shot(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds);
+      const uint64_t p = decode_shot<Weighted>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds);
       if (lane == src) pred = p, missed = m;
       most_rounds = max(most_rounds, rounds);
       ++decoded_acc;

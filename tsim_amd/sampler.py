@@ -1251,7 +1251,8 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
         ``decoder`` is applied to every kept shot on the GPU: a :class:`tsim_amd.decode.LookupDecoder` (a table of
         syndromes from a training run: exact at d = 3, blind beyond d = 5) or a :class:`tsim_amd.decode.UnionFindDecoder`
         (cluster growth on the circuit's decoding graph, ``UnionFindDecoder.from_circuit(circuit)``: no training, any
-        distance whose graph fits).  ``decoded_errors``: kept shots whose observables differ from its prediction;
+        distance whose graph fits; ``from_circuit(circuit, weights="probability")`` grows likely edges sooner - fewer decoded
+        errors for about three times the growth rounds).  ``decoded_errors``: kept shots whose observables differ from its prediction;
         ``decoder_misses``: kept shots for which it has no prediction (an unknown syndrome; a cluster that cannot reach the
         boundary) and predicts no flip.  For a fresh sampler with the same seed and arguments this
         equals ``counts.tally_rows(sample(..., append_observables=True), ...)``, and the sampler's keys stand where that
