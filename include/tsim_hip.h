@@ -515,6 +515,30 @@ int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t first_shot, uin
  * [12] n_gaps, [13] n_cols, [14] sites of the largest class, [15] the most columns a window can have */
 int tsim_faults_info(const tsim_faults *h, int64_t out[16]);
 
+/* ---- fixed-weight fault sampling (compile_detector_sampler(method="faults", fault_weight=k)) on the same handle ------------
+ * Rows conditioned on exactly k noise sites firing: the strata of a stratified logical error rate (tsim_amd/fixed_weight.py
+ * documents the law and states the same function in numpy).  tsim_faults_set_split uploads the table of the class counts,
+ * split_thr uint32 [n_classes][kmax + 1][kmax + 1] (host array): row (c, r) is ceil(cdf 2^32) of P(class c takes m of the r
+ * sites still to place in the classes c, c + 1, ...), entries from min(r, n_c) upward 2^32 - 1; one table serves every
+ * k <= kmax.  Checked before any device call: kmax in 0 .. 32 and a non-NULL table, rows that do not decrease, and in every
+ * row a split can reach a zero wherever m would leave the later classes more sites than they hold (TSIM_EINVAL); a class
+ * with an all-zero gap row (p_fire = 1: no odds) is TSIM_ENOTSUP.  A second call replaces the table.
+ * tsim_faults_sample_weight_device has the contract of tsim_faults_sample_device (rows, col0 / n_cols, first_shot, stream,
+ * one launch, results a function of the key, k and g only).  Per shot g, r = k, the classes in order under the class keys of
+ * the noise key threefry2x32(key, (0x6E6F6973, 0x66697877)): draw 0 of class c, x0, picks k_c = the smallest m < min(r, n_c)
+ * with x0 < thr[m] of row (c, r), min(r, n_c) when there is none (the last class takes r without a draw), r -= k_c; draws
+ * j = 1, 2, ...: t = x0 n_c, pos = t >> 32, rejected when t mod 2^32 < 2^32 mod n_c or pos fired already in this shot and
+ * class, else site pos fires with the first outcome whose threshold exceeds x1; until k_c sites have fired.  k < 0, k > kmax
+ * and k > n_sites are TSIM_EINVAL, a call without a split table is TSIM_ESTATE. */
+int tsim_faults_set_split(tsim_faults *h, int32_t kmax, const uint32_t *split_thr);
+int tsim_faults_sample_weight_device(tsim_faults *h, int32_t k, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo,
+                                     uint8_t *d_out, int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols,
+                                     void *stream);
+/* out[0] kmax of the split table (-1: none, the rest then 0), [1] waves per block, [2] LDS bytes per block (tables, then per
+ * wave its rows and 8 KiB of fired positions), [3] 1 when the outcome tables and the split table live in LDS (together at
+ * most 32 KiB), [4] 32-bit words per LDS row, [5] columns per window, [6] windows of all outputs, [7] bytes of the table */
+int tsim_faults_weight_info(const tsim_faults *h, int64_t out[8]);
+
 /* ---- counts over bit-packed device rows (the samplers' count(): rates without moving the rows to the host) ---------------
  * Row r starts at byte r * row_bytes of d_rows and holds n_cols columns little-endian (row_bytes >= ceil(n_cols/8); the
  * buffer spans n * row_bytes bytes).  Optional rows of ceil(n_cols/8) bytes: d_xor is XORed into every row first, and a

@@ -141,6 +141,9 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_faults_destroy": (None, [_P]),
     "tsim_faults_sample_device": (C.c_int, [_P, _I64, _I64, _U32, _U32, _P, _I64, _I32, _I32, _I32, _P]),
     "tsim_faults_info": (C.c_int, [_P, C.POINTER(_I64)]),
+    "tsim_faults_set_split": (C.c_int, [_P, _I32, _P]),
+    "tsim_faults_sample_weight_device": (C.c_int, [_P, _I32, _I64, _I64, _U32, _U32, _P, _I64, _I32, _I32, _I32, _P]),
+    "tsim_faults_weight_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_tally_rows_device": (C.c_int, [_I32, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _P, _I32, _P, _P]),
     "tsim_pairs_create": (C.c_int, [_I32, _I32, _P, _I32, C.POINTER(_P)]),
     "tsim_pairs_destroy": (None, [_P]),

@@ -981,14 +981,22 @@ class CliffordCircuit:
                                           seed=seed, device=device, noise=noise, mode=mode)
 
     def compile_detector_sampler(self, *, seed: int | None = None, device: int = 0, noise: str = "host",
-                                 mode: str = "auto", method: str = "autoregressive"):
+                                 mode: str = "auto", method: str = "autoregressive", fault_weight: int | None = None):
         """Mirror of ``Circuit.compile_detector_sampler`` (src/tsim/circuit.py:836-867).  ``method="frame"``: the Pauli-frame
         sampler (:mod:`tsim_amd.frame`): the same law from another stream, linear in the circuit, and detectors whose random
         outcomes do not cancel are sampled instead of refused.  ``method="faults"``: the fault-driven sampler
         (:mod:`tsim_amd.faults`): the same law from a third stream, a shot draws which noise sites fire and XORs their
-        detectors; built from :meth:`analyze` alone, work per shot proportional to the faults that happened."""
+        detectors; built from :meth:`analyze` alone, work per shot proportional to the faults that happened.  With
+        ``fault_weight=k`` (``method="faults"`` only) every shot is drawn conditioned on exactly ``k`` noise sites firing
+        (:mod:`tsim_amd.fixed_weight`: the strata of ``stratified_error_rate``)."""
         if method not in ("autoregressive", "frame", "faults"):
             raise ValueError(f"method must be 'autoregressive', 'frame' or 'faults', got {method!r}")
+        if fault_weight is not None:
+            if method != "faults":
+                raise ValueError(f'fault_weight needs method="faults", got {method!r}')
+            from .fixed_weight import CompiledFixedWeightDetectorSampler
+
+            return CompiledFixedWeightDetectorSampler(self.compile_faults(), fault_weight, seed=seed, device=device, noise=noise)
         if method == "faults":
             from .faults import CompiledFaultDetectorSampler
 

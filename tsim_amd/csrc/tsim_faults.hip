@@ -1,8 +1,9 @@
 // tsim_faults.hip - the fault-driven detector sampler (tsim_faults_*): a handle of its own, bound to one device, holding the
 // compiled form of tsim_amd/faults.py (classes of noise sites, their tables, the error bit -> outputs CSR); the kernel is
-// csrc/tsim_faults.hip.h.
+// csrc/tsim_faults.hip.h.  The same handle draws rows conditioned on exactly k fired sites (tsim_amd/fixed_weight.py) once
+// tsim_faults_set_split gave it the table of the class counts; that kernel is csrc/tsim_faults_weight.hip.h.
 #include "../../include/tsim_hip.h"
-#include "tsim_faults.hip.h"
+#include "tsim_faults_weight.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,26 @@ namespace {
 constexpr int64_t kLds = 160 * 1024;          // all the LDS a workgroup may take
 constexpr int32_t kMaxClassSites = 1 << 25;   // the draw index has 26 bits: a class needs at most n_c + n_c / kGapK + 2 draws
 constexpr int64_t kMaxShot = 1ll << 38;
+
+// The LDS of a block: the tables (tab_bytes, 0 when they stay in global memory), then per wave one row of S 32-bit words per
+// lane plus wave_extra bytes.  S is the outputs' words made odd when one wave's share fits, and the block then has as many
+// waves (at most kMaxWaves) as fit; otherwise one wave with the widest odd row that fits, the outputs going through in windows
+// of 32 S columns.  k_faults: wave_extra = 0.  k_faults_weight: wave_extra = 4 * kListWords = 8 KiB, the fired-position list.
+void lds_rule(int64_t tab_bytes, int64_t wave_extra, int32_t n_out, int32_t *S_out, int32_t *waves_out, int32_t *win_out) {
+  const int64_t avail = kLds - tab_bytes;
+  const int64_t words_all = std::max<int64_t>(1, ((int64_t)n_out + 31) / 32);
+  int64_t S = words_all | 1;  // odd
+  int32_t waves = 1;
+  if (256 * S + wave_extra <= avail) {
+    waves = (int32_t)std::min<int64_t>(fltk::kMaxWaves, avail / (256 * S + wave_extra));
+  } else {  // windows: the widest odd row one wave can keep
+    S = (avail - wave_extra) / 256;
+    if (!(S & 1)) --S;
+  }
+  *S_out = (int32_t)S;
+  *waves_out = waves;
+  *win_out = (int32_t)std::min<int64_t>(32 * S, 32 * words_all);
+}
 }  // namespace
 
 struct tsim_faults {
@@ -33,12 +54,21 @@ struct tsim_faults {
   fltk::Form form{};
   hipStream_t stream = nullptr;
   bool attr_set = false;
+  // ---- fixed weight (tsim_faults_set_split)
+  std::vector<int32_t> class_n;   // sites per class
+  int32_t always_class = -1;      // the first class whose gap row is all zero (p_fire = 1), -1: none
+  int32_t kmax = -1;              // of the split table, -1: none
+  uint32_t *split = nullptr;      // device, [n_classes][kmax + 1][kmax + 1]
+  int32_t w_tab_lds = 0, w_S = 1, w_win = 32, w_waves = 1;
+  int64_t w_tab_bytes = 0, split_bytes = 0;
+  bool w_attr_set = false;
 };
 
 static void faults_release(tsim_faults *h) {
   if (h->device >= 0) (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void *p : h->bufs) (void)hipFree(p);
+  if (h->split) (void)hipFree(h->split);
   if (h->stream) (void)hipStreamDestroy(h->stream);
 }
 
@@ -98,17 +128,9 @@ extern "C" int tsim_faults_create(int32_t device, const tsim_faults_desc *d, tsi
   int64_t tab_bytes = ((int64_t)d->n_gaps * fltk::kGapK + 2ll * d->n_outcomes) * 4;
   const int32_t tab_lds = tab_bytes <= fltk::kTabLdsBytes;
   tab_bytes = tab_lds ? (tab_bytes + 15) / 16 * 16 : 0;
-  const int64_t avail = kLds - tab_bytes;
   const int64_t words_all = std::max<int64_t>(1, ((int64_t)n_out + 31) / 32);
-  int64_t S = words_all | 1;  // odd
-  int32_t waves = 1;
-  if (256 * S <= avail) {
-    waves = (int32_t)std::min<int64_t>(fltk::kMaxWaves, avail / (256 * S));
-  } else {  // windows: the widest odd row one wave can keep
-    S = avail / 256;
-    if (!(S & 1)) --S;
-  }
-  const int32_t win = (int32_t)std::min<int64_t>(32 * S, 32 * words_all);
+  int32_t S = 1, waves = 1, win = 32;
+  lds_rule(tab_bytes, 0, n_out, &S, &waves, &win);
   std::vector<uint32_t> cwords;
   try {
     cwords.assign((size_t)words_all + 2, 0u);
@@ -133,9 +155,19 @@ extern "C" int tsim_faults_create(int32_t device, const tsim_faults_desc *d, tsi
   h->max_class = max_class;
   h->tab_lds = tab_lds;
   h->tab_bytes = tab_bytes;
-  h->S = (int32_t)S;
+  h->S = S;
   h->win = win;
   h->waves = waves;
+  try {
+    h->class_n.resize((size_t)n_cls);
+  } catch (const std::bad_alloc &) {
+    delete h;
+    return tsim_fail(TSIM_ENOMEM, "out of host memory");
+  }
+  for (int32_t c = n_cls - 1; c >= 0; --c) {
+    h->class_n[c] = d->class_ptr[c + 1] - d->class_ptr[c];
+    if (d->gap_thr[(size_t)fltk::kGapK * d->table_gap[c]] == 0) h->always_class = c;  // (a gap row does not increase)
+  }
   fltk::Form &f = h->form;
   f.n_classes = n_cls;
   f.n_gaps = d->n_gaps;
@@ -162,9 +194,10 @@ extern "C" void tsim_faults_destroy(tsim_faults *h) {
   delete h;
 }
 
-extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo, uint8_t *d_out,
-                                         int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols, void *stream) {
-  if (!h) return tsim_fail(TSIM_EINVAL, "sampler is NULL");
+// The checks every request shares, before any device call; *run = false: nothing to do.
+static int check_request(const tsim_faults *h, int64_t B, int64_t first_shot, const uint8_t *d_out, int64_t out_row_bytes, int32_t out_packed,
+                         int32_t col0, int32_t n_cols, bool *run) {
+  *run = false;
   if (B < 0) return tsim_fail(TSIM_EINVAL, "negative B");
   if (first_shot < 0 || first_shot % 64 != 0)
     return tsim_fail(TSIM_EINVAL, "first_shot = %lld is not a non-negative multiple of 64", (long long)first_shot);
@@ -177,6 +210,33 @@ extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t firs
     return tsim_fail(TSIM_EINVAL, "out_row_bytes = %lld for %lld bytes per row", (long long)out_row_bytes, (long long)out_used);
   if (B == 0 || n_cols == 0) return TSIM_OK;
   if (!d_out) return tsim_fail(TSIM_EINVAL, "NULL buffer");
+  *run = true;
+  return TSIM_OK;
+}
+
+// The arguments both kernels take; the noise key is threefry2x32(key, (n0, n1)) of the counter given in A.n0, A.n1.
+static void fill_args(fltk::Args &A, const tsim_faults *h, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo, uint8_t *d_out,
+                      int64_t out_row_bytes, int32_t col0, int32_t n_cols, int32_t S, int32_t win) {
+  A.f = h->form;
+  A.B = B;
+  A.g0 = first_shot;
+  tsimk::threefry2x32(key_hi, key_lo, A.n0, A.n1);
+  A.out = d_out;
+  A.out_rb = out_row_bytes;
+  A.out_w4 = out_row_bytes % 4 == 0 && reinterpret_cast<uintptr_t>(d_out) % 4 == 0;
+  A.col0 = col0;
+  A.n_cols = n_cols;
+  A.S = S;
+  A.win = win;
+  A.n_win = (n_cols + win - 1) / win;
+}
+
+extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo, uint8_t *d_out,
+                                         int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols, void *stream) {
+  if (!h) return tsim_fail(TSIM_EINVAL, "sampler is NULL");
+  bool run = false;
+  const int rc = check_request(h, B, first_shot, d_out, out_row_bytes, out_packed, col0, n_cols, &run);
+  if (rc != TSIM_OK || !run) return rc;
   FLT_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   void (*k)(fltk::Args) = out_packed ? (h->tab_lds ? fltk::k_faults<true, true> : fltk::k_faults<true, false>)
@@ -189,26 +249,112 @@ extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t firs
     h->attr_set = true;
   }
   fltk::Args A;
-  A.f = h->form;
-  A.B = B;
-  A.g0 = first_shot;
   A.n0 = 0x6E6F6973u;  // the request's noise key: threefry2x32(key, ("nois", "falt"))
   A.n1 = 0x66616C74u;
-  tsimk::threefry2x32(key_hi, key_lo, A.n0, A.n1);
-  A.out = d_out;
-  A.out_rb = out_row_bytes;
-  A.out_w4 = out_row_bytes % 4 == 0 && reinterpret_cast<uintptr_t>(d_out) % 4 == 0;
-  A.col0 = col0;
-  A.n_cols = n_cols;
-  A.S = h->S;
-  A.win = h->win;
-  A.n_win = (n_cols + h->win - 1) / h->win;
+  fill_args(A, h, B, first_shot, key_hi, key_lo, d_out, out_row_bytes, col0, n_cols, h->S, h->win);
   const int64_t tiles = (B + 63) / 64;
   const int nw = (int)std::min<int64_t>(h->waves, tiles);
   const size_t lds = (size_t)h->tab_bytes + (size_t)nw * 256 * (size_t)h->S;
   const int64_t blocks = std::min<int64_t>((tiles + nw - 1) / nw, 256 * 8);
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * nw), lds, s, A);
   FLT_TRY(hipGetLastError());
+  return TSIM_OK;
+}
+
+// ---- fixed weight -----------------------------------------------------------------------------------------------------------
+
+extern "C" int tsim_faults_set_split(tsim_faults *h, int32_t kmax, const uint32_t *split_thr) {
+  if (!h) return tsim_fail(TSIM_EINVAL, "sampler is NULL");
+  if (kmax < 0 || kmax > fltk::kMaxWeight) return tsim_fail(TSIM_EINVAL, "kmax = %d (0 .. %d)", kmax, fltk::kMaxWeight);
+  if (!split_thr) return tsim_fail(TSIM_EINVAL, "NULL table");
+  if (h->always_class >= 0)
+    return tsim_fail(TSIM_ENOTSUP, "class %d fires with probability 1 (an all-zero gap row): it has no odds", h->always_class);
+  const int64_t kw = kmax + 1, n_cls = h->n_classes, n_words = n_cls * kw * kw;
+  if (n_words > 0x7FFFFFFF) return tsim_fail(TSIM_ENOTSUP, "a split table of %lld entries", (long long)n_words);
+  // ---- what keeps the kernel's walk inside the classes: rows do not decrease, and an entry m of row (c, r) that would leave
+  //      the later classes more than they hold is zero (never picked), for every row a split can reach
+  int64_t rest = 0;  // sites of the classes after c
+  for (int64_t c = n_cls - 1; c >= 0; --c) {
+    for (int64_t r = 0; r <= kmax; ++r) {
+      const uint32_t *row = split_thr + (c * kw + r) * kw;
+      for (int64_t m = 0; m + 1 < kw; ++m)
+        if (row[m + 1] < row[m]) return tsim_fail(TSIM_EINVAL, "split row (%lld, %lld) decreases", (long long)c, (long long)r);
+      if (r > rest + h->class_n[c]) continue;  // (no split can reach it)
+      for (int64_t m = 0; m < std::min<int64_t>(r, h->class_n[c]) && r - m > rest; ++m)
+        if (row[m] != 0)
+          return tsim_fail(TSIM_EINVAL, "split row (%lld, %lld): %lld sites here would leave %lld to the %lld sites of the later classes",
+                           (long long)c, (long long)r, (long long)m, (long long)(r - m), (long long)rest);
+    }
+    rest += h->class_n[c];
+  }
+  FLT_TRY(hipSetDevice(h->device));
+  if (h->split) {  // (hipFree waits for the launches that read it)
+    FLT_TRY(hipFree(h->split));
+    h->split = nullptr;
+    h->kmax = -1;
+  }
+  void *p = nullptr;
+  FLT_TRY(hipMalloc(&p, std::max<size_t>(1, (size_t)n_words) * 4));
+  h->split = static_cast<uint32_t *>(p);
+  if (n_words) FLT_TRY(hipMemcpy(p, split_thr, (size_t)n_words * 4, hipMemcpyHostToDevice));
+  // ---- LDS: the outcome tables and the split table when they are small (no gap rows here), then lds_rule with the list
+  int64_t tab_bytes = (2ll * h->form.n_outcomes + n_words) * 4;
+  h->w_tab_lds = tab_bytes <= fltk::kTabLdsBytes;
+  h->w_tab_bytes = h->w_tab_lds ? (tab_bytes + 15) / 16 * 16 : 0;
+  lds_rule(h->w_tab_bytes, 4 * fltk::kListWords, h->n_out, &h->w_S, &h->w_waves, &h->w_win);
+  h->split_bytes = n_words * 4;
+  h->kmax = kmax;
+  return TSIM_OK;
+}
+
+extern "C" int tsim_faults_sample_weight_device(tsim_faults *h, int32_t k, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo,
+                                                uint8_t *d_out, int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols,
+                                                void *stream) {
+  if (!h) return tsim_fail(TSIM_EINVAL, "sampler is NULL");
+  if (h->kmax < 0) return tsim_fail(TSIM_ESTATE, "no split table: call tsim_faults_set_split first");
+  if (k < 0 || k > h->kmax) return tsim_fail(TSIM_EINVAL, "k = %d: the split table serves 0 .. %d", k, h->kmax);
+  if (k > h->n_sites) return tsim_fail(TSIM_EINVAL, "k = %d of %d noise sites", k, h->n_sites);
+  bool run = false;
+  const int rc = check_request(h, B, first_shot, d_out, out_row_bytes, out_packed, col0, n_cols, &run);
+  if (rc != TSIM_OK || !run) return rc;
+  FLT_TRY(hipSetDevice(h->device));
+  hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+  void (*kern)(fltk::WeightArgs) = out_packed ? (h->w_tab_lds ? fltk::k_faults_weight<true, true> : fltk::k_faults_weight<true, false>)
+                                              : (h->w_tab_lds ? fltk::k_faults_weight<false, true> : fltk::k_faults_weight<false, false>);
+  if (!h->w_attr_set) {
+    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    h->w_attr_set = true;
+  }
+  fltk::WeightArgs W;
+  W.a.n0 = 0x6E6F6973u;  // the request's noise key: threefry2x32(key, ("nois", "fixw")), a stream of its own
+  W.a.n1 = 0x66697877u;
+  fill_args(W.a, h, B, first_shot, key_hi, key_lo, d_out, out_row_bytes, col0, n_cols, h->w_S, h->w_win);
+  W.split = h->split;
+  W.k = k;
+  W.kmax = h->kmax;
+  const int64_t tiles = (B + 63) / 64;
+  const int nw = (int)std::min<int64_t>(h->w_waves, tiles);
+  const size_t lds = (size_t)h->w_tab_bytes + (size_t)nw * (256 * (size_t)h->w_S + 4 * fltk::kListWords);
+  const int64_t blocks = std::min<int64_t>((tiles + nw - 1) / nw, 256 * 8);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * nw), lds, s, W);
+  FLT_TRY(hipGetLastError());
+  return TSIM_OK;
+}
+
+extern "C" int tsim_faults_weight_info(const tsim_faults *h, int64_t out[8]) {
+  if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
+  const bool have = h->kmax >= 0;
+  out[0] = h->kmax;
+  out[1] = have ? h->w_waves : 0;
+  out[2] = have ? h->w_tab_bytes + (int64_t)h->w_waves * (256ll * h->w_S + 4 * fltk::kListWords) : 0;
+  out[3] = have ? h->w_tab_lds : 0;
+  out[4] = have ? h->w_S : 0;
+  out[5] = have ? h->w_win : 0;
+  out[6] = have ? ((int64_t)h->n_out + h->w_win - 1) / h->w_win : 0;
+  out[7] = h->split_bytes;
   return TSIM_OK;
 }
 

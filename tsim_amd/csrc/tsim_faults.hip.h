@@ -48,6 +48,71 @@ struct Args {
   int win, n_win;         // columns per window (a multiple of 32), windows of this request
 };
 
+// ---- the pieces of a tile's work that k_faults and k_faults_weight (tsim_faults_weight.hip.h) share
+
+// the row starts as the constants of the outputs cb .. cb + wc - 1, pad bits zero
+__device__ __forceinline__ void row_init(uint32_t *mine, const Form &f, int cb, int wc) {
+  const uint32_t *cw = f.const_words + (cb >> 5);
+  const int sh = cb & 31, n_words = (wc + 31) >> 5;
+  for (int i = 0; i < n_words; ++i) {
+    uint32_t v = sh ? (cw[i] >> sh) | (cw[i + 1] << (32 - sh)) : cw[i];
+    const int left = wc - 32 * i;
+    if (left < 32) v &= (1u << left) - 1u;
+    mine[i] = v;
+  }
+}
+
+// a site with first error bit e0 fires under x1: the first outcome of its table (o0 .. o0 + no - 1; l_thr / l_val: the
+// tables in LDS) whose threshold exceeds x1, the last one when none does; the column lists of its error bits go into the row
+template <bool TAB_LDS>
+__device__ __forceinline__ void fire_site(uint32_t *mine, const Form &f, const uint32_t *l_thr, const uint32_t *l_val, int o0, int no,
+                                          uint32_t x1, int e0, int cb, int wc) {
+  int o = 0;
+  while (o < no - 1 && (TAB_LDS ? l_thr[o0 + o] : f.out_thr[o0 + o]) <= x1) ++o;
+  uint32_t v = TAB_LDS ? l_val[o0 + o] : f.out_vals[o0 + o];
+  while (v) {
+    const int e = e0 + __ffs((int)v) - 1;
+    v &= v - 1u;
+    const int t1 = f.col_ptr[e + 1];
+    for (int k = f.col_ptr[e]; k < t1; ++k) {
+      const uint32_t r = (uint32_t)(f.cols[k] - cb);
+      if (r < (uint32_t)wc) mine[r >> 5] ^= 1u << (r & 31);
+    }
+  }
+}
+
+// the store of `rows` rows of a tile (S words each), columns w0 .. w0 + wc - 1 of the request: lanes run over (row, dword)
+// pairs, the dword fastest
+template <bool OUT_PACKED>
+__device__ __forceinline__ void store_tile(const uint32_t *tile, int S, uint8_t *out, long long out_rb, int out_w4, long long r0, int rows,
+                                           int w0, int wc, int lane) {
+  if (OUT_PACKED) {
+    uint8_t *dst = out + r0 * out_rb + (w0 >> 3);
+    const int nb = (wc + 7) >> 3, nd = out_w4 ? nb >> 2 : 0, rem = nb - 4 * nd;
+    for (int i = lane; i < rows * nd; i += 64) {
+      const int r = i / nd, k = i - r * nd;
+      *reinterpret_cast<uint32_t *>(dst + (long long)r * out_rb + 4 * k) = tile[r * S + k];
+    }
+    for (int i = lane; i < rows * rem; i += 64) {
+      const int r = i / rem, k = 4 * nd + i - r * rem;
+      dst[(long long)r * out_rb + k] = (uint8_t)(tile[r * S + (k >> 2)] >> (8 * (k & 3)));
+    }
+  } else {
+    uint8_t *dst = out + r0 * out_rb + w0;
+    const int nq = out_w4 ? wc >> 2 : 0, rem = wc - 4 * nq;
+    for (int i = lane; i < rows * nq; i += 64) {
+      const int r = i / nq, q = i - r * nq;
+      const uint32_t b = tile[r * S + (q >> 3)] >> (4 * (q & 7));
+      *reinterpret_cast<uint32_t *>(dst + (long long)r * out_rb + 4 * q) =
+          (b & 1u) | ((b & 2u) << 7) | ((b & 4u) << 14) | ((b & 8u) << 21);
+    }
+    for (int i = lane; i < rows * rem; i += 64) {
+      const int r = i / rem, k = 4 * nq + i - r * rem;
+      dst[(long long)r * out_rb + k] = (uint8_t)((tile[r * S + (k >> 5)] >> (k & 31)) & 1u);
+    }
+  }
+}
+
 template <bool OUT_PACKED, bool TAB_LDS>
 __global__ void __launch_bounds__(64 * kMaxWaves) k_faults(Args A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -77,15 +142,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_faults(Args A) {
       const int w0 = w * A.win, wc = min(A.win, A.n_cols - w0), cb = A.col0 + w0;
       m2dk::wsync();  // (the store of the previous tile or window has read the rows)
       if (lane < rows) {
-        // ---- the row starts as the constants of the outputs cb .. cb + wc - 1, pad bits zero
-        const uint32_t *cw = f.const_words + (cb >> 5);
-        const int sh = cb & 31, n_words = (wc + 31) >> 5;
-        for (int i = 0; i < n_words; ++i) {
-          uint32_t v = sh ? (cw[i] >> sh) | (cw[i + 1] << (32 - sh)) : cw[i];
-          const int left = wc - 32 * i;
-          if (left < 32) v &= (1u << left) - 1u;
-          mine[i] = v;
-        }
+        row_init(mine, f, cb, wc);
         // ---- the walk
         for (int c = 0; c < f.n_classes; ++c) {
           const int s0 = f.class_ptr[c], n_c = f.class_ptr[c + 1] - s0;
@@ -109,49 +166,12 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_faults(Args A) {
             }
             pos += lo + 1;
             if (pos >= n_c) break;
-            int o = 0;
-            while (o < no - 1 && (TAB_LDS ? l_thr[o0 + o] : f.out_thr[o0 + o]) <= x1) ++o;
-            uint32_t v = TAB_LDS ? l_val[o0 + o] : f.out_vals[o0 + o];
-            const int e0 = f.site_e0[s0 + pos];
-            while (v) {
-              const int e = e0 + __ffs((int)v) - 1;
-              v &= v - 1u;
-              const int t1 = f.col_ptr[e + 1];
-              for (int k = f.col_ptr[e]; k < t1; ++k) {
-                const uint32_t r = (uint32_t)(f.cols[k] - cb);
-                if (r < (uint32_t)wc) mine[r >> 5] ^= 1u << (r & 31);
-              }
-            }
+            fire_site<TAB_LDS>(mine, f, l_thr, l_val, o0, no, x1, f.site_e0[s0 + pos], cb, wc);
           }
         }
       }
       m2dk::wsync();
-      // ---- the store: lanes run over (row, dword) pairs, the dword fastest
-      if (OUT_PACKED) {
-        uint8_t *dst = A.out + r0 * A.out_rb + (w0 >> 3);
-        const int nb = (wc + 7) >> 3, nd = A.out_w4 ? nb >> 2 : 0, rem = nb - 4 * nd;
-        for (int i = lane; i < rows * nd; i += 64) {
-          const int r = i / nd, k = i - r * nd;
-          *reinterpret_cast<uint32_t *>(dst + (long long)r * A.out_rb + 4 * k) = tile[r * A.S + k];
-        }
-        for (int i = lane; i < rows * rem; i += 64) {
-          const int r = i / rem, k = 4 * nd + i - r * rem;
-          dst[(long long)r * A.out_rb + k] = (uint8_t)(tile[r * A.S + (k >> 2)] >> (8 * (k & 3)));
-        }
-      } else {
-        uint8_t *dst = A.out + r0 * A.out_rb + w0;
-        const int nq = A.out_w4 ? wc >> 2 : 0, rem = wc - 4 * nq;
-        for (int i = lane; i < rows * nq; i += 64) {
-          const int r = i / nq, q = i - r * nq;
-          const uint32_t b = tile[r * A.S + (q >> 3)] >> (4 * (q & 7));
-          *reinterpret_cast<uint32_t *>(dst + (long long)r * A.out_rb + 4 * q) =
-              (b & 1u) | ((b & 2u) << 7) | ((b & 4u) << 14) | ((b & 8u) << 21);
-        }
-        for (int i = lane; i < rows * rem; i += 64) {
-          const int r = i / rem, k = 4 * nq + i - r * rem;
-          dst[(long long)r * A.out_rb + k] = (uint8_t)((tile[r * A.S + (k >> 5)] >> (k & 31)) & 1u);
-        }
-      }
+      store_tile<OUT_PACKED>(tile, A.S, A.out, A.out_rb, A.out_w4, r0, rows, w0, wc, lane);
     }
   }
 }

@@ -228,6 +228,18 @@ def fault_rows_host(form: FaultForm, first_shot: int, B: int, key, *, return_e: 
     the request key ``key``.  ``return_e=True``: also ``uint64[num_e, ceil(B / 64)]``, every error bit (numbered as
     ``analyze()`` numbers them) over the shots, bit ``g % 64`` of word ``g // 64 - first_shot // 64`` (the layout of
     ``frame.frame_rows_host``; ``frame.e_rows`` packs it into rows)."""
+    nkey = noise_key(key)
+
+    def fire(g):
+        fired = [_walk_class(form, c, nkey, g) for c in range(form.n_classes)] or [(np.zeros(0, np.int64),) * 2]
+        return tuple(np.concatenate(x) for x in zip(*fired))
+
+    return _rows_host(form, first_shot, B, fire, return_e)
+
+
+def _rows_host(form: FaultForm, first_shot: int, B: int, fire, return_e: bool):
+    """The rows of :func:`fault_rows_host` from ``fire(g) -> (shot index into g, error bit)`` of every error bit that fired in
+    the shots ``g`` (uint64): the error bits through the column lists, XOR the constants."""
     B, first_shot = int(B), int(first_shot)
     if B < 0 or first_shot < 0 or first_shot % 64 or first_shot + B > MAX_SHOT:
         raise ValueError(f"shots {first_shot} .. {first_shot} + {B}: first_shot must be a multiple of 64, all inside 0 .. 2^38")
@@ -235,7 +247,6 @@ def fault_rows_host(form: FaultForm, first_shot: int, B: int, key, *, return_e: 
     nw_all = (B + 63) // 64
     rows = np.empty((B, n_out), dtype=np.uint8)
     e_all = np.zeros((form.num_e, nw_all), np.uint64) if return_e else None
-    nkey = noise_key(key)
     lens = np.diff(form.col_ptr).astype(np.int64)
     step = max(1, (1 << 27) // max(1, 8 * (form.num_e + n_out)))  # words of shots at a time: 128 MiB of error and output words
     for w0 in range(0, nw_all, step):
@@ -243,9 +254,8 @@ def fault_rows_host(form: FaultForm, first_shot: int, B: int, key, *, return_e: 
         n = min(64 * nw, B - 64 * w0)
         g = (first_shot + 64 * w0 + np.arange(n, dtype=np.int64)).astype(np.uint64)
         e = np.zeros((form.num_e, nw), np.uint64)
-        for c in range(form.n_classes):
-            shot, bit = _walk_class(form, c, nkey, g)
-            np.bitwise_or.at(e, (bit, shot >> 6), np.uint64(1) << (shot & 63).astype(np.uint64))
+        shot, bit = fire(g)
+        np.bitwise_or.at(e, (bit, shot >> 6), np.uint64(1) << (shot & 63).astype(np.uint64))
         if return_e:
             e_all[:, w0:w0 + nw] = e
         ow = np.zeros((n_out, nw), np.uint64)
