@@ -641,14 +641,32 @@ int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf **out);
  * TSIM_EINVAL, checked with the other arguments before any device call.  A shot's state then holds 4 bits per edge in
  * the place of one of the two edge bitmaps (8 bytes per node, 6 + 16 bytes per 32 edges) for the 64 KiB limit. */
 int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, tsim_uf **out);
+/* Heralded erasures (DecodingGraph.from_form(form, heralds=True)): a row has n_det_cols detector columns, of which
+ * node_det[v - 1] (int32[n_nodes - 1], strictly ascending) is the column of node v and herald_det[i] (int32[n_heralds])
+ * the column of herald i; every column is a node or one herald, so n_det_cols == n_nodes - 1 + n_heralds, and
+ * desc->n_cols >= n_det_cols.  herald_edges[herald_ptr[i] .. herald_ptr[i + 1] - 1] (herald_ptr int32[n_heralds + 1] from 0,
+ * never falling; an empty list is allowed, an edge may be listed under several heralds) are the edges that start FULL in a
+ * row whose column herald_det[i] is set after d_xor.  A herald is no defect: a kept row whose node columns are all 0
+ * predicts 0, is not decoded and does not count in out[7] of tsim_uf_info, whatever its heralds say.  Growth, forest and
+ * peeling are those of the other handles; so are the state in LDS and its limits (heralds take no per-shot state and their
+ * number is bounded by int32 only).  edge_cap: as tsim_uf_create_weighted, NULL for unweighted growth.  her == NULL is
+ * tsim_uf_create_weighted.  Every column, the ordering, the lists and their edge indices are checked on the host before any
+ * device call (TSIM_EINVAL). */
+typedef struct tsim_uf_heralds {
+  int32_t n_det_cols, n_heralds;
+  const int32_t *node_det, *herald_det, *herald_ptr, *herald_edges;
+} tsim_uf_heralds;
+int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
+                           tsim_uf **out);
 void tsim_uf_destroy(tsim_uf *h);
 /* out[0] nodes, [1] edges, [2] LDS bytes per shot, [3] shots (waves) per block, [4] kernel launches so far, [5] the most
  * growth rounds a row took, [6] bytes of device memory, [7] rows decoded in LDS (kept rows with a defect), [8] n_cols,
- * [9] blocks of a full grid, [10] the largest cap (0: an unweighted handle); the rest 0.  Synchronises the device. */
+ * [9] blocks of a full grid, [10] the largest cap (0: an unweighted handle), [11] heralds, [12] detector columns of a row
+ * (n_nodes - 1 without heralds); the rest 0.  Synchronises the device. */
 int tsim_uf_info(tsim_uf *h, int64_t out[16]);
 /* Rows, d_xor, d_test, obs_lo, obs_hi and d_counters are those of tsim_rowtab_decode_device and mean the same (masks of
  * ceil(n_cols / 8) bytes): a row is KEPT iff (row ^ xor) & test == 0, its syndrome is row ^ xor at columns
- * 0 .. n_nodes - 2, the prediction is compared with its columns obs_lo .. obs_hi - 1, and the call ACCUMULATES into
+ * 0 .. n_nodes - 2 (with heralds: at the columns node_det, the heralds at herald_det), the prediction is compared with its columns obs_lo .. obs_hi - 1, and the call ACCUMULATES into
  * d_counters: [0] kept rows, [1] kept rows whose prediction differs from their observables, [2] kept rows that are a
  * miss (growth stopped with an active cluster left: no flip is predicted).  d_pred (NULL: not wanted; 8-byte aligned)
  * receives every row's prediction as uint64[n]: 0 for a row that is not kept, and for a miss.  Asynchronous on `stream`;

@@ -81,6 +81,13 @@ class UfDesc(C.Structure):
                 ("edge_obs", C.c_void_p)]
 
 
+class UfHeralds(C.Structure):
+    """``tsim_uf_heralds`` (include/tsim_hip.h)."""
+
+    _fields_ = [("n_det_cols", C.c_int32), ("n_heralds", C.c_int32), ("node_det", C.c_void_p), ("herald_det", C.c_void_p),
+                ("herald_ptr", C.c_void_p), ("herald_edges", C.c_void_p)]
+
+
 # every symbol include/tsim_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I32, _I64, _U32 = C.c_int32, C.c_int64, C.c_uint32
@@ -161,6 +168,7 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_rowtab_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P]),
     "tsim_uf_create": (C.c_int, [_I32, C.POINTER(UfDesc), C.POINTER(_P)]),
     "tsim_uf_create_weighted": (C.c_int, [_I32, C.POINTER(UfDesc), _P, C.POINTER(_P)]),
+    "tsim_uf_create_heralds": (C.c_int, [_I32, C.POINTER(UfDesc), _P, C.POINTER(UfHeralds), C.POINTER(_P)]),
     "tsim_uf_destroy": (None, [_P]),
     "tsim_uf_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_uf_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _P]),

@@ -457,26 +457,41 @@ class HipProgram:
         self._lib.tsim_rowtab_destroy(C.c_void_p(handle))
 
     UF_INFO = ("n_nodes", "n_edges", "lds_bytes_per_shot", "shots_per_block", "launches", "max_rounds", "device_bytes", "rows_decoded",
-               "n_cols", "grid_blocks", "max_cap")
+               "n_cols", "grid_blocks", "max_cap", "n_heralds", "n_det_cols")
 
     def uf_create(self, graph, n_cols: int, caps=None) -> int:
         """A union-find decoder over ``graph`` (:class:`tsim_amd.decode.DecodingGraph`) for rows of ``n_cols`` columns on this
         program's device (``tsim_uf_create``, include/tsim_hip.h): the handle, to be given back to :meth:`uf_destroy`.
-        ``caps``: ``None``, or an integer per edge in 1 .. 14 for weighted growth (``tsim_uf_create_weighted``)."""
+        ``caps``: ``None``, or an integer per edge in 1 .. 14 for weighted growth (``tsim_uf_create_weighted``).  A graph with
+        heralds (``graph.herald_det`` is not empty) goes to ``tsim_uf_create_heralds``."""
         eu = np.ascontiguousarray(graph.edge_u, dtype=np.int32)
         ev = np.ascontiguousarray(graph.edge_v, dtype=np.int32)
         eo = np.ascontiguousarray(graph.edge_obs, dtype=np.uint64)
         desc = _lib.UfDesc(int(graph.n_nodes), int(eu.size), int(n_cols), eu.ctypes.data, ev.ctypes.data, eo.ctypes.data)
         h = C.c_void_p()
-        if caps is None:
+        her = len(getattr(graph, "herald_det", ())) > 0
+        if caps is None and not her:
             _lib.check(self._lib.tsim_uf_create(self.device, C.byref(desc), C.byref(h)), "tsim_uf_create")
             return h.value
+        if caps is None:
+            return self._uf_create_heralds(graph, desc, None)
         ec = np.ascontiguousarray(caps)
         if ec.shape != (eu.size,) or not np.issubdtype(ec.dtype, np.integer) or (ec.size and (ec.min() < 0 or ec.max() > 255)):
             raise ValueError(f"caps: {eu.size} integers in 1 .. 14 expected")
         ec = np.concatenate([ec.astype(np.uint8), np.zeros(1, np.uint8)])  # (never an empty buffer: NULL means unweighted)
+        if her:
+            return self._uf_create_heralds(graph, desc, ec)
         _lib.check(self._lib.tsim_uf_create_weighted(self.device, C.byref(desc), C.c_void_p(ec.ctypes.data), C.byref(h)),
                    "tsim_uf_create_weighted")
+        return h.value
+
+    def _uf_create_heralds(self, graph, desc, ec) -> int:
+        arrays = [np.ascontiguousarray(np.concatenate([np.asarray(getattr(graph, k), dtype=np.int32), np.zeros(1, np.int32)]))
+                  for k in ("node_det", "herald_det", "herald_ptr", "herald_edges")]  # (never an empty buffer)
+        her = _lib.UfHeralds(int(graph.num_detectors), len(graph.herald_det), *(a.ctypes.data for a in arrays))
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_uf_create_heralds(self.device, C.byref(desc), None if ec is None else C.c_void_p(ec.ctypes.data),
+                                                    C.byref(her), C.byref(h)), "tsim_uf_create_heralds")
         return h.value
 
     def uf_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,

@@ -36,7 +36,8 @@ def rotated_surface_code_memory(distance: int, rounds: int, *, basis: str = "Z",
                                 after_clifford_depolarization: float = 0.0,
                                 before_round_data_depolarization: float = 0.0,
                                 before_measure_flip_probability: float = 0.0,
-                                after_reset_flip_probability: float = 0.0) -> str:
+                                after_reset_flip_probability: float = 0.0,
+                                after_clifford_heralded_erasure: float = 0.0) -> str:
     """Rotated surface code memory experiment in the Z or X basis.
 
     Data qubits sit at odd coordinates (2i+1, 2j+1), measure qubits at even coordinates; a measure
@@ -44,6 +45,10 @@ def rotated_surface_code_memory(distance: int, rounds: int, *, basis: str = "Z",
     left/right boundary columns and Z-type checks on the top/bottom boundary rows are dropped, which
     leaves d^2 - 1 checks.  The four CX layers visit the neighbours in an order whose two middle
     steps are swapped between X- and Z-type checks, so that all checks commute through each other.
+
+    ``after_clifford_heralded_erasure`` > 0 follows every CX layer (and its ``DEPOLARIZE2``, if any) by a
+    ``HERALDED_ERASE`` on the layer's targets and one ``DETECTOR`` per herald record, the erasure-conversion
+    noise of neutral atoms; the detectors of the checks then look back over a cycle's heralds as well.
     """
     d = distance
     basis = basis.upper()
@@ -85,6 +90,9 @@ def rotated_surface_code_memory(distance: int, rounds: int, *, basis: str = "Z",
         out = [f"CX {j(pairs)}"]
         if after_clifford_depolarization > 0:
             out.append(f"DEPOLARIZE2({after_clifford_depolarization}) {j(pairs)}")
+        if after_clifford_heralded_erasure > 0:
+            out.append(f"HERALDED_ERASE({after_clifford_heralded_erasure}) {j(pairs)}")
+            out += [f"DETECTOR rec[-{len(pairs) - i}]" for i in range(len(pairs))]
         return out
 
     def noisy1(name, qs):
@@ -109,6 +117,7 @@ def rotated_surface_code_memory(distance: int, rounds: int, *, basis: str = "Z",
         return out
 
     nm = len(mq)
+    nh = sum(map(len, layers)) if after_clifford_heralded_erasure > 0 else 0   # herald records of a cycle, before its MR
     pos = {q: k for k, q in enumerate(mq)}          # position of a measure qubit inside one MR
     chosen = zq if basis == "Z" else xq             # checks that are deterministic in the first round
     L = [f"R{'X' if basis == 'X' else ''} {j(dq)}", f"R {j(mq)}"]
@@ -119,7 +128,7 @@ def rotated_surface_code_memory(distance: int, rounds: int, *, basis: str = "Z",
     L += [f"DETECTOR rec[-{nm - pos[q]}]" for q in chosen]
     if rounds > 1:
         L += [f"REPEAT {rounds - 1} {{"] + cycle()
-        L += [f"DETECTOR rec[-{nm - pos[q]}] rec[-{2 * nm - pos[q]}]" for q in mq] + ["}"]
+        L += [f"DETECTOR rec[-{nm - pos[q]}] rec[-{2 * nm + nh - pos[q]}]" for q in mq] + ["}"]
     if before_measure_flip_probability > 0:
         L.append(f"{'Z' if basis == 'X' else 'X'}_ERROR({before_measure_flip_probability}) {j(dq)}")
     L.append(f"M{'X' if basis == 'X' else ''} {j(dq)}")

@@ -32,11 +32,15 @@ struct tsim_uf {
   uint16_t *d_adj_edge = nullptr;
   uint8_t *d_cap = nullptr;
   int max_cap = 0;  // 0: unweighted
+  int n_heralds = 0;
+  int32_t *d_her = nullptr;   // node_det, col_herald, herald_ptr, herald_edges: one allocation (heralds only)
+  uint8_t *d_masks = nullptr;  // dmask, hmask
 };
 
 static void uf_release(tsim_uf *h) {
   if (h->device >= 0) (void)hipSetDevice(h->device);
-  for (void *p : {(void *)h->d_edge_uv, (void *)h->d_adj_ptr, (void *)h->d_edge_obs, (void *)h->d_stats, (void *)h->d_adj_edge, (void *)h->d_cap})
+  for (void *p : {(void *)h->d_edge_uv, (void *)h->d_adj_ptr, (void *)h->d_edge_obs, (void *)h->d_stats, (void *)h->d_adj_edge, (void *)h->d_cap,
+                  (void *)h->d_her, (void *)h->d_masks})
     if (p) (void)hipFree(p);
 }
 
@@ -45,6 +49,11 @@ extern "C" int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf 
 }
 
 extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, tsim_uf **out) {
+  return tsim_uf_create_heralds(device, desc, edge_cap, nullptr, out);
+}
+
+extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
+                                      tsim_uf **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
   *out = nullptr;
   if (!desc) return tsim_fail(TSIM_EINVAL, "desc is NULL");
@@ -53,8 +62,11 @@ extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc,
   if (E < 0) return tsim_fail(TSIM_EINVAL, "n_edges = %d", E);
   if (N > kMaxGraph || E > kMaxGraph)
     return tsim_fail(TSIM_ENOTSUP, "%d nodes and %d edges (at most %d each: indices are uint16)", N, E, kMaxGraph);
-  if (desc->n_cols < N - 1 || desc->n_cols > (1 << 30))
-    return tsim_fail(TSIM_EINVAL, "n_cols = %d for %d detectors (up to 2^30)", desc->n_cols, N - 1);
+  const long long n_det = her ? (long long)N - 1 + her->n_heralds : N - 1;  // detector columns of a row
+  if (her && (her->n_heralds < 0 || her->n_det_cols != n_det))
+    return tsim_fail(TSIM_EINVAL, "n_det_cols = %d for %d nodes and %d heralds (nodes - 1 + heralds expected)", her->n_det_cols, N, her->n_heralds);
+  if (desc->n_cols < n_det || desc->n_cols > (1 << 30))
+    return tsim_fail(TSIM_EINVAL, "n_cols = %d for %lld detectors (up to 2^30)", desc->n_cols, n_det);
   if (E > 0 && (!desc->edge_u || !desc->edge_v || !desc->edge_obs)) return tsim_fail(TSIM_EINVAL, "an edge array is NULL");
   for (int e = 0; e < E; ++e) {
     const int32_t u = desc->edge_u[e], v = desc->edge_v[e];
@@ -70,10 +82,49 @@ extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc,
         return tsim_fail(TSIM_EINVAL, "edge %d has cap %d (1 .. %d: a 4-bit counter that may overshoot by one)", e, edge_cap[e], ufk::kMaxCap);
       max_cap = std::max<int>(max_cap, edge_cap[e]);
     }
+  // the heralds: every column a node or one herald, the lists inside the edges
+  const int H = her ? her->n_heralds : 0, mask_bytes = (desc->n_cols + 7) / 8;
+  int n_listed = 0;
+  std::vector<int32_t> her_tab;  // node_det [N - 1], col_herald [n_det], herald_ptr [H + 1], herald_edges [n_listed]
+  std::vector<uint8_t> masks;    // dmask, hmask: mask_bytes each
+  if (her) {
+    if (!her->node_det || !her->herald_ptr || (H > 0 && !her->herald_det)) return tsim_fail(TSIM_EINVAL, "a herald array is NULL");
+    std::vector<int32_t> col_herald((size_t)n_det, -1);
+    masks.assign(2 * (size_t)mask_bytes, 0);
+    for (int v = 0; v < N - 1; ++v) {
+      const int32_t c = her->node_det[v];
+      if (c < 0 || c >= n_det) return tsim_fail(TSIM_EINVAL, "node_det[%d] = %d leaves the columns 0 .. %lld", v, c, n_det - 1);
+      if (v > 0 && her->node_det[v - 1] >= c) return tsim_fail(TSIM_EINVAL, "node_det[%d] = %d: the columns of the nodes must be strictly ascending", v, c);
+      masks[c >> 3] |= (uint8_t)(1u << (c & 7));
+    }
+    for (int i = 0; i < H; ++i) {
+      const int32_t c = her->herald_det[i];
+      if (c < 0 || c >= n_det) return tsim_fail(TSIM_EINVAL, "herald_det[%d] = %d leaves the columns 0 .. %lld", i, c, n_det - 1);
+      if ((masks[c >> 3] | masks[(size_t)mask_bytes + (c >> 3)]) >> (c & 7) & 1)
+        return tsim_fail(TSIM_EINVAL, "column %d is named twice (a column is a node or one herald)", c);
+      masks[(size_t)mask_bytes + (c >> 3)] |= (uint8_t)(1u << (c & 7));
+      col_herald[c] = i;
+    }
+    if (her->herald_ptr[0] != 0) return tsim_fail(TSIM_EINVAL, "herald_ptr[0] = %d", her->herald_ptr[0]);
+    for (int i = 0; i < H; ++i)
+      if (her->herald_ptr[i + 1] < her->herald_ptr[i])
+        return tsim_fail(TSIM_EINVAL, "herald_ptr[%d] = %d after %d: it must not fall", i + 1, her->herald_ptr[i + 1], her->herald_ptr[i]);
+    n_listed = her->herald_ptr[H];
+    if (n_listed > 0 && !her->herald_edges) return tsim_fail(TSIM_EINVAL, "herald_edges is NULL");
+    for (int k = 0; k < n_listed; ++k)
+      if (her->herald_edges[k] < 0 || her->herald_edges[k] >= E)
+        return tsim_fail(TSIM_EINVAL, "herald_edges[%d] = %d of %d edges", k, her->herald_edges[k], E);
+    her_tab.insert(her_tab.end(), her->node_det, her->node_det + (N - 1));
+    her_tab.insert(her_tab.end(), col_herald.begin(), col_herald.end());
+    her_tab.insert(her_tab.end(), her->herald_ptr, her->herald_ptr + H + 1);
+    if (n_listed) her_tab.insert(her_tab.end(), her->herald_edges, her->herald_edges + n_listed);
+    her_tab.push_back(0);
+  }
   ufk::Args a{};
   a.n_nodes = N;
   a.n_edges = E;
   a.n_cols = desc->n_cols;
+  a.n_det_cols = (int)n_det;
   a.w32 = std::max(1, (E + 31) / 32);
   a.w_cnt = edge_cap ? std::max(1, (E + 7) / 8) : 0;
   const long long shot = ufk::layout(&a);
@@ -113,8 +164,14 @@ extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc,
   h->grid = std::max(1, cus) * per_cu;
   const size_t ne = uv.size(), na = adj.size();
   h->max_cap = max_cap;
-  h->bytes = (int64_t)(ne * 12 + ptr.size() * 4 + na * 2 + 16 + (edge_cap ? ne : 0));
+  h->n_heralds = H;
+  h->bytes = (int64_t)(ne * 12 + ptr.size() * 4 + na * 2 + 16 + (edge_cap ? ne : 0) + her_tab.size() * 4 + masks.size());
   hipError_t e = hipMalloc(&h->d_edge_uv, ne * 4);
+  if (e == hipSuccess && her) e = hipMalloc(&h->d_her, her_tab.size() * 4);
+  if (e == hipSuccess && her) e = hipMalloc(&h->d_masks, masks.size() + 8);
+  if (e == hipSuccess && her) e = hipMemcpy(h->d_her, her_tab.data(), her_tab.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && her) e = hipMemset(h->d_masks, 0, masks.size() + 8);
+  if (e == hipSuccess && her && !masks.empty()) e = hipMemcpy(h->d_masks, masks.data(), masks.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&h->d_edge_obs, ne * 8);
   if (e == hipSuccess) e = hipMalloc(&h->d_adj_ptr, ptr.size() * 4);
   if (e == hipSuccess) e = hipMalloc(&h->d_adj_edge, na * 2);
@@ -140,6 +197,14 @@ extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc,
   a.adj_edge = h->d_adj_edge;
   a.cap = h->d_cap;
   a.stats = h->d_stats;
+  if (her) {
+    a.node_det = h->d_her;
+    a.col_herald = a.node_det + (N - 1);
+    a.herald_ptr = a.col_herald + n_det;
+    a.herald_edges = a.herald_ptr + H + 1;
+    a.dmask = h->d_masks;
+    a.hmask = h->d_masks + mask_bytes;
+  }
   h->a = a;
   *out = h;
   return TSIM_OK;
@@ -169,6 +234,8 @@ extern "C" int tsim_uf_info(tsim_uf *h, int64_t out[16]) {
   out[8] = h->a.n_cols;
   out[9] = h->grid;
   out[10] = h->max_cap;
+  out[11] = h->n_heralds;
+  out[12] = h->a.n_det_cols;
   return TSIM_OK;
 }
 
@@ -203,8 +270,11 @@ extern "C" int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t 
     a.pred = d_pred ? reinterpret_cast<unsigned long long *>(d_pred) + r0 : nullptr;
     const int64_t tiles = (a.n + 63) / 64;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + a.waves - 1) / a.waves, h->grid));
-    if (a.cap) hipLaunchKernelGGL(ufk::k_uf<true>, dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(ufk::k_uf<false>, dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    if (a.node_det) {
+      if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((ufk::k_uf<false, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    } else if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((ufk::k_uf<false, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
     UF_TRY(hipGetLastError());
     ++h->launches;
   }

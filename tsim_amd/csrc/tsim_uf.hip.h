@@ -26,6 +26,11 @@
 //                     lane per word, so no step of a shot sweeps all edges
 // The edge table (u | v << 16), the observable masks, the caps (uint8, weighted growth only) and the node adjacency (CSR) are
 // read-only in global memory.
+// Heralded erasures (k_uf<Weighted, true>, tsim_uf_create_heralds): herald detectors are no nodes.  Pass 1 takes "has a defect"
+// from the columns of dmask (the non-herald detectors), so a row with heralds only is finished there; s[v] comes from column
+// node_det[v - 1]; and before the first round a pre-grow step sets the full bit of every edge listed under a herald whose
+// column is set (a lane per 8-byte word of the row, col_herald[c] -> herald_ptr -> herald_edges), appending a word of `full`
+// to wlist when it was zero: the append rule of the growth.  half and the counters stay zero: visits test `full` first.
 // Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,6 +63,13 @@ struct Args {
   unsigned long long *dec;    // [0] kept [1] wrong [2] missed
   unsigned long long *pred;   // [n] or NULL
   unsigned long long *stats;  // [0] most growth rounds [1] rows decoded in LDS
+  // heralded erasures (NULL / 0 on a handle without heralds)
+  int n_det_cols;              // detector columns of a row: the nodes but the boundary, and the heralds
+  const int32_t *node_det;     // [n_nodes - 1] the column of node v at v - 1
+  const uint8_t *dmask, *hmask;  // rows of ceil(n_cols / 8) bytes: the columns of the nodes, of the heralds
+  const int32_t *col_herald;   // [n_det_cols] the herald of a herald column
+  const int32_t *herald_ptr;   // [n_heralds + 1]
+  const int32_t *herald_edges;
 };
 
 // the layout of one wave's state, shared by the host (sizes, limits) and the kernel
@@ -122,13 +134,14 @@ __device__ __forceinline__ void full_edges(const Args &a, const State &st, int n
 }
 
 // one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform
-template <bool Weighted>
+template <bool Weighted, bool Heralds>
 __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds) {
   const int N = a.n_nodes;
   for (int v = lane; v < N; v += 64) {
     uint32_t bit = 0;
     if (v) {
-      const int c = v - 1;
+      int c = v - 1;
+      if constexpr (Heralds) c = a.node_det[c];
       uint32_t byte = row[c >> 3];
       if (a.xr) byte ^= a.xr[c >> 3];
       bit = (byte >> (c & 7)) & 1u;
@@ -144,6 +157,27 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   }
   if (lane < 4) st.misc[lane] = 0;
   wsync();
+  if constexpr (Heralds) {  // the edges of the heralds that are set start full
+    const int det_bytes = (a.n_det_cols + 7) >> 3;
+    for (int b = 8 * lane; b < det_bytes; b += 8 * 64) {
+      const uint64_t hw = mask_word(a.hmask, b, a.used);
+      if (hw == 0) continue;
+      uint64_t w = 0;
+      if (a.w8) w = *reinterpret_cast<const uint64_t *>(row + b);  // (rb is a multiple of 8: inside the row)
+      else
+        for (int q = 0; q < 8 && b + q < a.used; ++q) w |= (uint64_t)row[b + q] << (8 * q);
+      w = (w ^ mask_word(a.xr, b, a.used)) & hw;
+      while (w) {
+        const int h = a.col_herald[8 * b + __builtin_ctzll(w)];
+        w &= w - 1;
+        for (int k = a.herald_ptr[h]; k < a.herald_ptr[h + 1]; ++k) {
+          const int e = a.herald_edges[k], fw = e >> 5;
+          if (atomicOr(&st.full[fw], 1u << (e & 31)) == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)fw;  // (each word once)
+        }
+      }
+    }
+    wsync();
+  }
   *missed = false;
   *rounds = 0;
   // ---- growth
@@ -248,7 +282,7 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   return (uint64_t)st.misc[2] | (uint64_t)st.misc[3] << 32;
 }
 
-template <bool Weighted>
+template <bool Weighted, bool Heralds>
 __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
@@ -277,7 +311,8 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     const uint8_t *row = a.rows + (valid ? r : 0) * a.rb;
     uint64_t fail = 0, defects = 0;
     for (int b = 0; b < a.used; b += 8) {
-      const uint64_t tw = mask_word(a.test, b, a.used) & below(b, a.n_cols), dw = below(b, nd);  // (pad bits are not columns)
+      const uint64_t tw = mask_word(a.test, b, a.used) & below(b, a.n_cols),  // (pad bits are not columns)
+          dw = Heralds ? mask_word(a.dmask, b, a.used) : below(b, nd);
       if ((tw | dw) == 0) continue;
       uint64_t w = 0;
       if (valid) {
@@ -305,7 +340,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       work &= work - 1;
       bool m;
       int rounds;
-      const uint64_t p = decode_shot<Weighted>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds);
+      const uint64_t p = decode_shot<Weighted, Heralds>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds);
       if (lane == src) pred = p, missed = m;
       most_rounds = max(most_rounds, rounds);
       ++decoded_acc;

@@ -49,6 +49,30 @@ at 14: the device counts ``grown`` in 4 bits and may pass the cap by one).  The 
 caps {1, 2} and is WORSE than no weights (110 decoded errors against 12 at d = 3, p = 1e-3); a higher
 resolution costs growth rounds in proportion.  ``UnionFindDecoder.from_circuit(circuit, weights="probability")`` uses these
 caps; ``weights=None`` (caps of 2 everywhere, bit for bit) stays the default.
+
+Heralded erasures (``DecodingGraph.from_form(form, heralds=True)``, ``UnionFindDecoder.from_circuit(circuit, heralds=True)``;
+``heralds=False`` is the default and leaves every array, number and prediction what it is above).  A herald tells where an
+error may be, so the edges of the heralded site start fully grown and the herald itself is no syndrome bit.
+
+Herald bits are found from the ``FaultForm`` alone.  Within a site of ``k >= 2`` error bits with outcome table ``P``, bit ``i``
+is a HERALD BIT iff (a) every outcome ``o != 0`` with ``P[o] > 0`` has bit ``i`` set, and there is such an outcome; (b) its
+column list is exactly one output, a detector ``h < num_detectors`` with ``out_const[h] == 0``; (c) no other error bit of the
+circuit lists ``h``.  Then ``h`` is a HERALD DETECTOR: it is 1 exactly when the site fired.  Of several such bits of a site the
+lowest is the herald, the others are ordinary bits.  A detector that fails (c) - one that XORs two herald records, say -
+stays an ordinary detector.
+
+The graph with heralds.  Herald detectors are not nodes: node 0 is the boundary, node ``v >= 1`` is the ``v``-th non-herald
+detector in column order, ``node_det[v - 1]`` is its column (``arange`` without heralds) and ``num_detectors`` is the number of
+detector columns of a row, ``n_nodes - 1 + n_heralds``.  Herald bits give no edge; every other bit contributes as above, in
+the new node numbers, the non-herald bits of heralded sites included, with their unconditional marginals.  Per herald, in
+herald-column order, a CSR (``herald_det``, ``herald_ptr``, ``herald_edges``) lists the distinct edges, ascending, of the site's
+other bits that have marginal > 0 and flip one or two non-herald detectors; such bits with more than two detectors count in
+``info()["herald_bits_dropped"]``, bits without a detector are ignored, and a herald's list may be empty.
+
+The rule with heralds changes at its start only.  ``defect[v]`` is the bit of column ``node_det[v - 1]``; for every herald
+whose column is set, every listed edge starts at ``grown[e] = cap[e]``.  Growth, forest and peeling are as written (the
+clusters of the pre-grown edges exist in round 1).  A row whose non-herald detectors are all 0 predicts 0 and is not
+decoded, whatever its heralds say.
 """
 
 from __future__ import annotations
@@ -154,7 +178,8 @@ class DecodingGraph:
     """The decoding graph (module docstring): ``n_nodes`` (node 0 the boundary), ``edge_u < edge_v`` (int32, strictly
     ascending pairs), ``edge_obs`` (uint64 observable masks) and ``edge_p`` (float64; :meth:`growth_caps` makes edge caps of it)."""
 
-    def __init__(self, n_nodes: int, edge_u, edge_v, edge_obs, edge_p=None, *, dropped_bits: int = 0, undetectable_bits: int = 0):
+    def __init__(self, n_nodes: int, edge_u, edge_v, edge_obs, edge_p=None, *, dropped_bits: int = 0, undetectable_bits: int = 0,
+                 node_det=None, herald_det=None, herald_ptr=None, herald_edges=None, herald_bits_dropped: int = 0):
         u, v = np.asarray(edge_u), np.asarray(edge_v)
         if u.ndim != 1 or v.shape != u.shape or np.asarray(edge_obs).shape != u.shape:
             raise ValueError(f"edge_u, edge_v and edge_obs must be 1-D and equally long, got shapes {u.shape}, {v.shape} and "
@@ -181,16 +206,61 @@ class DecodingGraph:
         self.edge_obs = np.asarray(edge_obs).astype(np.uint64)
         self.edge_p = p.copy()
         self.dropped_bits, self.undetectable_bits = int(dropped_bits), int(undetectable_bits)
+        self._set_heralds(node_det, herald_det, herald_ptr, herald_edges)
+        self.herald_bits_dropped = int(herald_bits_dropped)
+
+    def _set_heralds(self, node_det, herald_det, herald_ptr, herald_edges):
+        """The columns of the nodes and the heralds' CSR (module docstring), checked; without them every column is a node."""
+        def ints(name, a, n=None):
+            a = np.zeros(0, np.int64) if a is None else np.asarray(a)
+            if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)) or (n is not None and a.size != n):
+                raise ValueError(f"{name} must be 1-D integers" + ("" if n is None else f", {n} of them"))
+            if a.size and (a.min() < 0 or a.max() > 0x7FFFFFFF):
+                raise ValueError(f"{name} must lie in 0 .. 2^31 - 1")
+            return a.astype(np.int64)
+
+        hd = ints("herald_det", herald_det)
+        nh = len(hd)
+        nd = self.n_nodes - 1 + nh
+        if nd > 0x7FFFFFFF:
+            raise ValueError(f"{nd} detector columns (at most 2^31 - 1)")
+        nodes = np.arange(self.n_nodes - 1, dtype=np.int64) if node_det is None else ints("node_det", node_det, self.n_nodes - 1)
+        hp = np.zeros(1, np.int64) if herald_ptr is None and nh == 0 else ints("herald_ptr", herald_ptr, nh + 1)
+        he = ints("herald_edges", herald_edges)
+        if (np.diff(nodes) <= 0).any():
+            raise ValueError(f"node_det[{int(np.flatnonzero(np.diff(nodes) <= 0)[0]) + 1}]: the columns of the nodes must be strictly ascending")
+        cols = np.concatenate([nodes, hd])
+        if len(cols) and cols.max() >= nd:
+            raise ValueError(f"column {int(cols.max())} of {nd} detector columns ({self.n_nodes - 1} nodes and {nh} heralds)")
+        seen = np.bincount(cols, minlength=nd)
+        if (seen > 1).any():
+            raise ValueError(f"column {int(np.flatnonzero(seen > 1)[0])} is named twice (a column is a node or one herald)")
+        if hp[0] != 0 or (np.diff(hp) < 0).any() or hp[-1] != len(he):
+            raise ValueError(f"herald_ptr must rise from 0 to len(herald_edges) = {len(he)}")
+        if len(he) and he.max() >= self.n_edges:
+            raise ValueError(f"herald_edges names edge {int(he.max())} of {self.n_edges}")
+        self.node_det, self.herald_det = nodes.astype(np.int32), hd.astype(np.int32)
+        self.herald_ptr, self.herald_edges = hp.astype(np.int32), he.astype(np.int32)
 
     @property
     def n_edges(self) -> int:
         return len(self.edge_u)
 
+    @property
+    def n_heralds(self) -> int:
+        return len(self.herald_det)
+
+    @property
+    def num_detectors(self) -> int:
+        """The detector columns of a row: the nodes but the boundary, and the heralds."""
+        return self.n_nodes - 1 + self.n_heralds
+
     def info(self) -> dict:
         deg = np.bincount(np.concatenate([self.edge_u, self.edge_v]), minlength=self.n_nodes)
         return dict(n_nodes=self.n_nodes, n_edges=self.n_edges, dropped_bits=self.dropped_bits,
                     undetectable_bits=self.undetectable_bits, boundary_degree=int(deg[0]),
-                    max_node_degree=int(deg[1:].max()) if self.n_nodes > 1 else 0)
+                    max_node_degree=int(deg[1:].max()) if self.n_nodes > 1 else 0, n_heralds=self.n_heralds,
+                    herald_bits_dropped=self.herald_bits_dropped)
 
     def growth_caps(self, resolution: int = 4) -> np.ndarray:
         """``uint8[n_edges]``: the caps of weighted growth from ``edge_p`` (module docstring), 1 .. ``2 * resolution``;
@@ -206,9 +276,32 @@ class DecodingGraph:
             return np.full(self.n_edges, top, np.uint8)
         return np.clip(np.rint(top * L / L.max()), 1, top).astype(np.uint8)
 
+    @staticmethod
+    def _herald_bits(form) -> dict:
+        """``{error bit: herald detector column}`` by the criterion of the module docstring."""
+        nd = int(form.num_detectors)
+        listed = np.bincount(np.asarray(form.cols, dtype=np.int64), minlength=int(form.n_out))
+        out, e0 = {}, 0
+        for probs in form.channel_probs:
+            probs = np.asarray(probs, dtype=np.float64)
+            k = int(len(probs)).bit_length() - 1
+            fired = np.flatnonzero(probs > 0)
+            fired = fired[fired != 0]
+            if k >= 2 and len(fired):
+                for i in range(k):
+                    if not ((fired >> i) & 1).all():
+                        continue
+                    cols = form.cols[form.col_ptr[e0 + i]:form.col_ptr[e0 + i + 1]]
+                    if len(cols) == 1 and cols[0] < nd and form.out_const[cols[0]] == 0 and listed[cols[0]] == 1:
+                        out[e0 + i] = int(cols[0])
+                        break  # (the lowest such bit is the herald, the others are ordinary bits)
+            e0 += k
+        return out
+
     @classmethod
-    def from_form(cls, form) -> "DecodingGraph":
-        """From the ``FaultForm`` of ``CliffordCircuit.compile_faults()`` (module docstring)."""
+    def from_form(cls, form, heralds: bool = False) -> "DecodingGraph":
+        """From the ``FaultForm`` of ``CliffordCircuit.compile_faults()`` (module docstring).  ``heralds``: herald detectors
+        are not nodes, their sites' edges are listed per herald."""
         if getattr(form, "kind", None) != "detectors":
             raise ValueError("the decoding graph needs the form of compile_faults()")
         nd, n_obs = int(form.num_detectors), int(form.n_out) - int(form.num_detectors)
@@ -216,22 +309,35 @@ class DecodingGraph:
             raise ValueError(f"at most 64 observables, got {n_obs}")
         if nd < 1:
             raise ValueError("a decoder needs at least one detector")
-        if nd + 1 > MAX_GRAPH:
-            raise NotImplementedError(f"{nd + 1} nodes (at most {MAX_GRAPH}: indices are uint16 on the device)")
+        herald_of = cls._herald_bits(form) if heralds else {}
+        herald_cols = np.array(sorted(herald_of.values()), np.int64)
+        node_det = np.setdiff1d(np.arange(nd), herald_cols)
+        if len(node_det) < 1:
+            raise ValueError("a decoder needs at least one detector that is not a herald")
+        if len(node_det) + 1 > MAX_GRAPH:
+            raise NotImplementedError(f"{len(node_det) + 1} nodes (at most {MAX_GRAPH}: indices are uint16 on the device)")
+        node_of = np.full(nd, -1, np.int64)   # detector column -> node
+        node_of[node_det] = np.arange(1, len(node_det) + 1)
         pairs: dict = {}   # (u, v) -> {mask: probability}
-        dropped = undetectable = 0
+        site_pairs: dict = {}   # herald column -> the pairs of its site's other bits
+        dropped = undetectable = herald_dropped = 0
         e0 = 0
         for probs in form.channel_probs:
             probs = np.asarray(probs, dtype=np.float64)
             k = int(len(probs)).bit_length() - 1
             outcomes = np.arange(len(probs))
+            site_herald = next((herald_of[e0 + i] for i in range(k) if e0 + i in herald_of), None)
+            if site_herald is not None:
+                site_pairs[site_herald] = set()
             for i in range(k):
                 e = e0 + i
+                if e in herald_of:
+                    continue
                 p = float(probs[((outcomes >> i) & 1).astype(np.bool_)].sum())
                 if p <= 0.0:
                     continue
                 cols = form.cols[form.col_ptr[e]:form.col_ptr[e + 1]]
-                dets = sorted(int(c) + 1 for c in cols if c < nd)
+                dets = sorted(int(node_of[c]) for c in cols if c < nd)
                 mask = 0
                 for c in cols:
                     if c >= nd:
@@ -241,8 +347,11 @@ class DecodingGraph:
                     continue
                 if len(dets) > 2:
                     dropped += 1
+                    herald_dropped += site_herald is not None
                     continue
                 pair = (0, dets[0]) if len(dets) == 1 else (dets[0], dets[1])
+                if site_herald is not None:
+                    site_pairs[site_herald].add(pair)
                 by_mask = pairs.setdefault(pair, {})
                 q = by_mask.get(mask, 0.0)
                 by_mask[mask] = p * (1.0 - q) + q * (1.0 - p)
@@ -251,9 +360,15 @@ class DecodingGraph:
             raise NotImplementedError(f"{len(pairs)} edges (at most {MAX_GRAPH}: indices are uint16 on the device)")
         order = sorted(pairs)
         best = [min(pairs[pr].items(), key=lambda mp: (-mp[1], mp[0])) for pr in order]   # the likelier mask, a tie to the smaller
-        return cls(nd + 1, np.array([pr[0] for pr in order], np.int32), np.array([pr[1] for pr in order], np.int32),
+        extra = {}
+        if heralds:
+            index = {pr: e for e, pr in enumerate(order)}
+            lists = [sorted(index[pr] for pr in site_pairs[h]) for h in herald_cols.tolist()]
+            extra = dict(node_det=node_det, herald_det=herald_cols, herald_ptr=np.cumsum([0] + [len(x) for x in lists]),
+                         herald_edges=np.array([e for x in lists for e in x], np.int64), herald_bits_dropped=herald_dropped)
+        return cls(len(node_det) + 1, np.array([pr[0] for pr in order], np.int32), np.array([pr[1] for pr in order], np.int32),
                    np.array([m for m, _ in best], np.uint64), np.array([p for _, p in best], np.float64),
-                   dropped_bits=dropped, undetectable_bits=undetectable)
+                   dropped_bits=dropped, undetectable_bits=undetectable, **extra)
 
 
 def uf_shot_bytes(n_nodes: int, n_edges: int, weighted: bool) -> int:
@@ -280,7 +395,7 @@ def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray
 
 
 class UnionFindDecoder:
-    """The union-find decoder of a :class:`DecodingGraph` (module docstring) for rows of ``graph.n_nodes - 1`` detectors and
+    """The union-find decoder of a :class:`DecodingGraph` (module docstring) for rows of ``graph.num_detectors`` detectors and
     ``num_observables`` observables (default: as many as the masks of the graph use, at least one; at most 64).
     ``decode`` / ``missed`` have the signatures of :class:`LookupDecoder`; they decode each distinct syndrome once.
     ``edge_caps``: an integer per edge in 1 .. 14 for weighted growth (kept as uint8 in ``self.edge_caps``), ``None`` for the
@@ -304,12 +419,13 @@ class UnionFindDecoder:
                 raise ValueError(f"edge {bad} has cap {int(caps[bad])} (1 .. {MAX_CAP})")
             edge_caps = caps.astype(np.uint8)
         self.graph, self._n_obs, self.edge_caps = graph, n_obs, edge_caps
-        self._cache: dict = {}   # packed syndrome -> (prediction, missed, flipped edges, rounds)
+        self._cache: dict = {}   # packed row of detectors -> (prediction, missed, flipped edges, rounds)
 
     @classmethod
-    def from_circuit(cls, circuit, weights: str | None = None, resolution: int = 4) -> "UnionFindDecoder":
+    def from_circuit(cls, circuit, weights: str | None = None, resolution: int = 4, heralds: bool = False) -> "UnionFindDecoder":
         """Of a :class:`tsim_amd.clifford.CliffordCircuit` with deterministic detectors (or its program text).  ``weights``:
-        ``None`` (unweighted) or ``"probability"``: the caps ``graph.growth_caps(resolution)`` (module docstring)."""
+        ``None`` (unweighted) or ``"probability"``: the caps ``graph.growth_caps(resolution)`` (module docstring).
+        ``heralds``: herald detectors pre-grow their site's edges and are no syndrome bits (module docstring)."""
         if weights not in (None, "probability"):
             raise ValueError(f'weights = {weights!r}: None or "probability"')
         if isinstance(circuit, str):
@@ -317,12 +433,12 @@ class UnionFindDecoder:
 
             circuit = CliffordCircuit(circuit)
         form = circuit.compile_faults()
-        graph = DecodingGraph.from_form(form)
+        graph = DecodingGraph.from_form(form, heralds=heralds)
         return cls(graph, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution))
 
     @property
     def num_detectors(self) -> int:
-        return self.graph.n_nodes - 1
+        return self.graph.num_detectors
 
     @property
     def num_observables(self) -> int:
@@ -332,14 +448,17 @@ class UnionFindDecoder:
         return self.graph.info()
 
     # -- the numpy statement ---------------------------------------------------------------------------------------------
-    def _decode_one(self, defects: np.ndarray):
-        """One syndrome (the defect NODES, ascending): ``(prediction, missed, flipped edges ascending, growth rounds)``."""
+    def _decode_one(self, defects: np.ndarray, erased_edges=()):
+        """One syndrome (the defect NODES, ascending; ``erased_edges`` start fully grown): ``(prediction, missed, flipped edges
+        ascending, growth rounds)``."""
         g = self.graph
         n, eu, ev = g.n_nodes, g.edge_u, g.edge_v
         defect = np.zeros(n, np.bool_)
         defect[defects] = True
         cap = np.full(g.n_edges, 2, np.int8) if self.edge_caps is None else self.edge_caps.astype(np.int8)
         grown = np.zeros(g.n_edges, np.int8)
+        erased = np.asarray(erased_edges, dtype=np.int64)
+        grown[erased] = cap[erased]
         label = np.arange(n)
         rounds = 0
         while True:
@@ -385,12 +504,13 @@ class UnionFindDecoder:
         return prediction, False, np.array(sorted(flipped), np.int64), rounds
 
     def _decoded(self, dets):
-        """Per row the cache entry of its syndrome (``None`` for a row without defects)."""
+        """Per row the cache entry of its detector columns (``None`` for a row without defects, whatever its heralds)."""
         d = np.asarray(dets, dtype=np.bool_)
         if d.ndim != 2 or d.shape[1] != self.num_detectors:
             raise ValueError(f"dets must be [n, {self.num_detectors}], got shape {d.shape}")
+        g = self.graph
         out = [None] * len(d)
-        rows = np.flatnonzero(d.any(axis=1))
+        rows = np.flatnonzero(d[:, g.node_det].any(axis=1))
         if not len(rows):
             return out
         uniq, inv = np.unique(_pack(d[rows]), axis=0, return_inverse=True)
@@ -400,7 +520,9 @@ class UnionFindDecoder:
             key = k.tobytes()
             if key not in self._cache:
                 bits = np.unpackbits(k, bitorder="little", count=self.num_detectors)
-                self._cache[key] = self._decode_one(np.flatnonzero(bits) + 1)
+                erased = [g.herald_edges[g.herald_ptr[h]:g.herald_ptr[h + 1]] for h in np.flatnonzero(bits[g.herald_det])]
+                self._cache[key] = self._decode_one(np.flatnonzero(bits[g.node_det]) + 1,
+                                                    np.unique(np.concatenate(erased)) if erased else ())
             entries.append(self._cache[key])
         for r, i in zip(rows, inv):
             out[r] = entries[i]
