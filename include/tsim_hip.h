@@ -675,6 +675,33 @@ int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t 
                           const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
                           void *stream);
 
+/* ---- sliding-window union-find decoding of long runs (count(decoder=WindowedUnionFindDecoder)) -----------------------
+ * `global` is a decoding graph as above without heralds, bounded by int32 only; edge_cap as tsim_uf_create_weighted (NULL:
+ * cap 2 everywhere); commit = C >= 1 and window = W > C are in detector columns.  The rule - the windows [k C, k C + W),
+ * the validity condition, the window graphs with their open future boundary, merged pairs, local edge order and COMMITTED
+ * edges, and a row decoded window after window with the committed flips carried on - is "Sliding-window decoding of long
+ * runs" in the module docstring of tsim_amd/decode.py; it fixes the prediction whatever the order of the lanes.  The
+ * library builds the windows itself, on the host.  Every index, the ordering, the caps and the validity condition (an edge
+ * whose upper end lies past the window that commits its lower end: the buffer W - C is too small) are checked before any
+ * device call (TSIM_EINVAL).  TSIM_ENOTSUP when a window has more than 65535 nodes or edges, and when one shot's state -
+ * that of tsim_uf_create / _weighted for the largest window, a carry bitmap of the smallest power of two >= W bits and 16
+ * bytes - does not fit a block's 64 KiB of LDS. */
+typedef struct tsim_ufw tsim_ufw;
+int tsim_ufw_create(int32_t device, const tsim_uf_desc *global, const uint8_t *edge_cap, int32_t commit, int32_t window,
+                    tsim_ufw **out);
+void tsim_ufw_destroy(tsim_ufw *h);
+/* out[0] nodes and [1] edges of the global graph, [2] windows, [3] the most nodes and [4] the most edges of a window,
+ * [5] LDS bytes per shot, [6] shots (waves) per block, [7] kernel launches so far, [8] the most growth rounds a window
+ * took, [9] bytes of device memory, [10] rows decoded in LDS (kept rows with a defect), [11] windows decoded (those with a
+ * defect, of such rows), [12] n_cols, [13] blocks of a full grid, [14] the largest cap (0: unweighted); the rest 0.
+ * Synchronises the device. */
+int tsim_ufw_info(tsim_ufw *h, int64_t out[16]);
+/* The arguments of tsim_uf_decode_device, with the same meaning: kept / wrong / missed ACCUMULATE into d_counters, a row
+ * with a miss in any window is a miss and predicts 0, d_pred is optional. */
+int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                           const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                           void *stream);
+
 /* ---- stim's shot-data formats on the device (stim.read_shot_data_file / write_shot_data_file, the samplers'
  *      sample_write, CompiledMeasurementsToDetectionEventsConverter.convert_file) ------------------------------------
  * format: 0 "01", 1 "b8", 2 "r8", 3 "ptb64", 4 "hits", 5 "dets" (layouts: tsim_amd/shotdata.py).  A handle of its own,

@@ -1,0 +1,189 @@
+"""Sliding-window union-find decoding next to the whole-graph decoder: surface code memory, one MI355X.
+
+    python scripts/windowed_uf_bench.py                                  # the three legs below, JSON lines
+    python scripts/windowed_uf_bench.py --legs rate --cases d9x27c9
+    python scripts/windowed_uf_bench.py --legs quality --shots 1000000
+
+A case ``d<D>x<R>c<C>`` is ``rotated_surface_code_memory(D, R)`` with all three noise options at ``--p``, decoded in windows
+of ``commit = C`` rounds and ``window = 2 C`` rounds (a round is ``D * D - 1`` detector columns), unweighted.
+
+``rate``: ``count(--shots, decoder=...)`` of the ``method="faults"`` sampler, in batches of ``--batch``, with the whole-graph
+``UnionFindDecoder`` and with the ``WindowedUnionFindDecoder``, alternating, each warmed up first, on the same seeded rows; a
+host clock around a call that returns the counters; the median and the spread of ``--reps`` calls.  A decoder that cannot be
+built (the graph passes 65535 nodes or edges, or its state passes a block's LDS) is reported as such and left out, and so is
+a sampler that does not build.  Then the decoders alone: ``--decode-rows`` rows of ``faults.fault_rows_host``, bit-packed and
+uploaded, through ``tsim_uf_decode_device`` / ``tsim_ufw_decode_device`` on handles of their own (a host clock around the call
+and a stream synchronise, median of ``--reps``), with what ``tsim_uf_info`` / ``tsim_ufw_info`` report.
+
+``quality``: ``decoded_errors`` of the whole-graph decoder and of the windowed one for each ``--commits`` (rounds) on the same
+``--quality-shots`` seeded shots of ``--quality-case`` at ``--quality-p``.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tsim_amd import _lib, circuits, faults, synth  # noqa: E402
+from tsim_amd.backend import HipProgram  # noqa: E402
+from tsim_amd.clifford import CliffordCircuit  # noqa: E402
+from tsim_amd.decode import DecodingGraph, UnionFindDecoder, WindowedUnionFindDecoder  # noqa: E402
+
+
+def memory(d: int, rounds: int, p: float) -> CliffordCircuit:
+    return CliffordCircuit(circuits.rotated_surface_code_memory(d, rounds, after_clifford_depolarization=p, before_measure_flip_probability=p,
+                                                                after_reset_flip_probability=p))
+
+
+def parse(case: str):
+    d, rest = case[1:].split("x")
+    rounds, commit = rest.split("c")
+    return int(d), int(rounds), int(commit)
+
+
+def spread(times) -> dict:
+    return dict(median_s=statistics.median(times), min_s=min(times), max_s=max(times))
+
+
+def decoders_of(form, d: int, commit: int) -> tuple:
+    """``({name: decoder}, {name: why it was not built})`` of the whole graph and of windows of ``commit`` + ``commit`` rounds."""
+    n_obs = int(form.n_out) - int(form.num_detectors)
+    built, refused = {}, {}
+    try:
+        built["whole"] = UnionFindDecoder(DecodingGraph.from_form(form), n_obs)
+    except NotImplementedError as e:
+        refused["whole"] = str(e)
+    cols = commit * (d * d - 1)
+    built["windowed"] = WindowedUnionFindDecoder(DecodingGraph.from_form(form, limit=None), cols, 2 * cols, n_obs)
+    return built, refused
+
+
+def decode_alone(hp, dec, rows: np.ndarray, reps: int) -> dict:
+    """The decode call alone on uploaded rows: its times and the handle's info."""
+    nd, n_cols = dec.num_detectors, dec.num_detectors + dec.num_observables
+    windowed = isinstance(dec, WindowedUnionFindDecoder)
+    h = hp.ufw_create(dec.graph, n_cols, dec.commit, dec.window, dec.edge_caps) if windowed else hp.uf_create(dec.graph, n_cols, dec.edge_caps)
+    run, info, destroy = (hp.ufw_decode_device, hp.ufw_info, hp.ufw_destroy) if windowed else (hp.uf_decode_device, hp.uf_info, hp.uf_destroy)
+    d_rows, d_cnt = hp.malloc(rows.nbytes + 16), hp.malloc(64)
+    try:
+        hp.h2d(d_rows, rows)
+        times = []
+        for i in range(reps + 1):  # (the first call warms up)
+            hp.h2d(d_cnt, np.zeros(3, np.uint64))
+            hp.stream_synchronize(0)
+            t0 = time.perf_counter()
+            run(h, d_rows.ptr, len(rows), rows.shape[1], (nd, n_cols), d_cnt.ptr)
+            hp.stream_synchronize(0)
+            times.append(time.perf_counter() - t0)
+        cnt = np.zeros(3, np.uint64)
+        hp.d2h(cnt, d_cnt)
+        out = spread(times[1:])
+        out.update(rows=len(rows), rows_per_s=len(rows) / out["median_s"], kept_wrong_missed=[int(x) for x in cnt], info=info(h))
+        return out
+    finally:
+        destroy(h)
+        d_rows.free()
+        d_cnt.free()
+
+
+def rate_leg(args, hp) -> None:
+    for case in args.cases.split(","):
+        d, rounds, commit = parse(case)
+        c = memory(d, rounds, args.p)
+        t0 = time.perf_counter()
+        form = c.compile_faults()
+        form_s = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        decoders, refused = decoders_of(form, d, commit)
+        out = dict(leg="rate", case=case, p=args.p, commit_rounds=commit, window_rounds=2 * commit, form_s=form_s,
+                   decoders_s=time.perf_counter() - t0, graph=decoders["windowed"].info(), not_built=refused)
+        # count(): sampling and decoding together
+        try:
+            def sampler():  # a fresh one per call: every call counts the same seeded rows
+                return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+            times, last = {m: [] for m in decoders}, {}
+            for m, dec in decoders.items():
+                sampler().count(args.shots, batch_size=args.batch, decoder=dec)  # warm-up at the timed size
+            for _ in range(args.reps):
+                for m, dec in decoders.items():
+                    s = sampler()
+                    t0 = time.perf_counter()
+                    last[m] = s.count(args.shots, batch_size=args.batch, decoder=dec)
+                    times[m].append(time.perf_counter() - t0)
+            out["count"] = {m: dict(spread(t), shots=args.shots, shots_per_s=args.shots / statistics.median(t), kept=last[m].kept,
+                                    raw_flips=last[m].kept_with_observable_flip, decoded_errors=last[m].decoded_errors,
+                                    misses=last[m].decoder_misses) for m, t in times.items()}
+        except (NotImplementedError, ValueError, MemoryError, _lib.HipBackendError) as e:
+            if "failed:" in str(e):  # (a HIP call failed: that is no refusal, and nothing more is started on the device)
+                raise
+            out["count"] = dict(not_run=f"{type(e).__name__}: {e}")
+        # the decoders alone, on the same uploaded rows
+        bits = faults.fault_rows_host(form, 0, args.decode_rows, (3, 4))
+        rows = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little"))
+        rows = np.ascontiguousarray(np.pad(rows, ((0, 0), (0, -rows.shape[1] % 8))))
+        out["mean_defects_per_row"] = float(bits[:, :int(form.num_detectors)].sum(axis=1).mean())
+        out["decode_alone"] = {}
+        for m, dec in decoders.items():
+            try:
+                out["decode_alone"][m] = decode_alone(hp, dec, rows, args.reps)
+            except _lib.HipBackendError as e:
+                if "failed:" in str(e):
+                    raise
+                out["decode_alone"][m] = dict(not_run=str(e))
+        print(json.dumps(out), flush=True)
+
+
+def quality_leg(args) -> None:
+    d, rounds, _ = parse(args.quality_case + "c1")
+    c = memory(d, rounds, args.quality_p)
+    form = c.compile_faults()
+    n_obs = int(form.n_out) - int(form.num_detectors)
+    g = DecodingGraph.from_form(form)
+    decoders = {"whole": UnionFindDecoder(g, n_obs)}
+    for k in (int(x) for x in args.commits.split(",")):
+        decoders[f"commit{k}"] = WindowedUnionFindDecoder(g, k * (d * d - 1), 2 * k * (d * d - 1), n_obs)
+    res = {}
+    for m, dec in decoders.items():
+        t0 = time.perf_counter()
+        r = c.compile_detector_sampler(seed=5, noise="device", method="faults").count(args.quality_shots, batch_size=args.batch, decoder=dec)
+        res[m] = dict(kept=r.kept, raw_flips=r.kept_with_observable_flip, decoded_errors=r.decoded_errors, misses=r.decoder_misses,
+                      seconds=time.perf_counter() - t0, windows=dec.info().get("n_windows", 1))
+    if len({(r["kept"], r["raw_flips"]) for r in res.values()}) != 1:
+        sys.exit("windowed_uf_bench: the decoders did not see the same rows")
+    print(json.dumps(dict(leg="quality", case=args.quality_case, p=args.quality_p, shots=args.quality_shots, graph=g.info(), results=res)), flush=True)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="rate,quality")
+    ap.add_argument("--cases", default="d9x27c9,d11x500c11")
+    ap.add_argument("--p", type=float, default=1e-3)
+    ap.add_argument("--shots", type=int, default=10**6)
+    ap.add_argument("--batch", type=int, default=10**5)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--decode-rows", type=int, default=4096)
+    ap.add_argument("--quality-case", default="d5x20")
+    ap.add_argument("--quality-p", type=float, default=2e-3)
+    ap.add_argument("--quality-shots", type=int, default=10**6)
+    ap.add_argument("--commits", default="2,5")
+    args = ap.parse_args()
+    _lib.load()
+    if _lib.device_count() < 1:
+        sys.exit("windowed_uf_bench: no HIP device - nothing is measured without one")
+    if "quality" in args.legs.split(","):
+        quality_leg(args)
+    if "rate" in args.legs.split(","):
+        rate_leg(args, HipProgram(synth.kat_h_m()))
+
+
+if __name__ == "__main__":
+    main()

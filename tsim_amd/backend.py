@@ -512,6 +512,48 @@ class HipProgram:
     def uf_destroy(self, handle: int) -> None:
         self._lib.tsim_uf_destroy(C.c_void_p(handle))
 
+    UFW_INFO = ("n_nodes", "n_edges", "n_windows", "max_window_nodes", "max_window_edges", "lds_bytes_per_shot", "shots_per_block",
+                "launches", "max_rounds", "device_bytes", "rows_decoded", "windows_decoded", "n_cols", "grid_blocks", "max_cap")
+
+    def ufw_create(self, graph, n_cols: int, commit: int, window: int, caps=None) -> int:
+        """A sliding-window union-find decoder over ``graph`` (a :class:`tsim_amd.decode.DecodingGraph` without heralds, of int32
+        sizes) for rows of ``n_cols`` columns on this program's device (``tsim_ufw_create``, include/tsim_hip.h; the library
+        builds the windows of ``commit`` / ``window`` columns itself): the handle, to be given back to :meth:`ufw_destroy`.
+        ``caps``: ``None``, or an integer per edge in 1 .. 14 for weighted growth."""
+        if len(getattr(graph, "herald_det", ())) > 0:
+            raise NotImplementedError("the windowed decoder takes a graph without heralds")
+        eu = np.ascontiguousarray(graph.edge_u, dtype=np.int32)
+        ev = np.ascontiguousarray(graph.edge_v, dtype=np.int32)
+        eo = np.ascontiguousarray(graph.edge_obs, dtype=np.uint64)
+        desc = _lib.UfDesc(int(graph.n_nodes), int(eu.size), int(n_cols), eu.ctypes.data, ev.ctypes.data, eo.ctypes.data)
+        ec = None
+        if caps is not None:
+            ec = np.ascontiguousarray(caps)
+            if ec.shape != (eu.size,) or not np.issubdtype(ec.dtype, np.integer) or (ec.size and (ec.min() < 0 or ec.max() > 255)):
+                raise ValueError(f"caps: {eu.size} integers in 1 .. 14 expected")
+            ec = np.concatenate([ec.astype(np.uint8), np.zeros(1, np.uint8)])  # (never an empty buffer: NULL means unweighted)
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_ufw_create(self.device, C.byref(desc), None if ec is None else C.c_void_p(ec.ctypes.data),
+                                             int(min(commit, 0x7FFFFFFF)), int(min(window, 0x7FFFFFFF)), C.byref(h)), "tsim_ufw_create")
+        return h.value
+
+    def ufw_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,
+                          d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
+        """:meth:`uf_decode_device` by a handle of :meth:`ufw_create` (``tsim_ufw_decode_device``)."""
+        _lib.check(self._lib.tsim_ufw_decode_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
+                                                    C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
+                                                    int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
+                                                    C.c_void_p(int(d_pred)) if d_pred else None,
+                                                    C.c_void_p(stream or self.stream_ptr())), "tsim_ufw_decode_device")
+
+    def ufw_info(self, handle: int) -> dict:
+        out = (C.c_int64 * 16)()
+        _lib.check(self._lib.tsim_ufw_info(C.c_void_p(handle), out), "tsim_ufw_info")
+        return {k: int(v) for k, v in zip(self.UFW_INFO, out)}
+
+    def ufw_destroy(self, handle: int) -> None:
+        self._lib.tsim_ufw_destroy(C.c_void_p(handle))
+
     def sample_batch_device(self, d_f: int, B: int, num_f: int, key, d_out: int, *,
                             shot_offset: int = 0, d_norm_dev: int = 0, stream: int = 0) -> None:
         """Asynchronous launch on the handle's stream (``stream``: a HIP stream of the caller instead); buffers are raw

@@ -16,7 +16,8 @@ caller owns (``m2d`` output, ``sample_steps_device`` rows).
 ``pattern_columns`` adds the joint statistic: the distinct patterns of the kept shots over those columns, each with its
 exact count (the row table, ``tsim_rowtab_*``, ``csrc/tsim_rowtab.hip.h``) - what ``np.unique(sample(), axis=0)`` gives
 without the rows crossing PCIe.  ``decoder`` (:class:`tsim_amd.decode.LookupDecoder`, a table of syndromes, or
-:class:`tsim_amd.decode.UnionFindDecoder`, cluster growth on the circuit's decoding graph, ``tsim_uf_*``) is applied to
+:class:`tsim_amd.decode.UnionFindDecoder`, cluster growth on the circuit's decoding graph, ``tsim_uf_*``, or
+:class:`tsim_amd.decode.WindowedUnionFindDecoder`, the same window after window for long runs, ``tsim_ufw_*``) is applied to
 every kept shot where it lies, and the wrong predictions are counted.
 """
 
@@ -450,6 +451,7 @@ class _DeviceTally:
         self._table = None       # the row table's handle (tsim_rowtab), when pattern columns are asked for
         self._lookup = None      # the decoder's row table, loaded from the host (a LookupDecoder)
         self._uf = None          # the decoder's graph handle (tsim_uf; a UnionFindDecoder)
+        self._ufw = None         # the decoder's windows handle (tsim_ufw; a WindowedUnionFindDecoder)
         self.d_decoded = None    # its three counters
         try:
             if self.pc:
@@ -457,10 +459,12 @@ class _DeviceTally:
             if self.tc:
                 self._table = hp.rowtab_create(self.n_cols, self.tc, pattern_capacity or DEFAULT_PATTERN_CAPACITY)
             if decoder is not None:
-                from .decode import UnionFindDecoder
+                from .decode import UnionFindDecoder, WindowedUnionFindDecoder
 
                 if isinstance(decoder, UnionFindDecoder):
                     self._uf = hp.uf_create(decoder.graph, self.n_cols, decoder.edge_caps)
+                elif isinstance(decoder, WindowedUnionFindDecoder):
+                    self._ufw = hp.ufw_create(decoder.graph, self.n_cols, decoder.commit, decoder.window, decoder.edge_caps)
                 else:
                     keys, values = decoder.table()
                     self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))
@@ -499,7 +503,7 @@ class _DeviceTally:
             self.hp.pairs_add_device(self._pairs, d_first + (a - r0) * row_bytes, b - a, row_bytes,
                                      d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
                                      d_test=self.d_test.ptr if self.d_test is not None else 0, stream=stream)
-        if self._table is not None or self._lookup is not None or self._uf is not None:
+        if self._table is not None or self._lookup is not None or self._uf is not None or self._ufw is not None:
             self._pairs_stream = stream
             masks = dict(d_xor=self.d_xor.ptr if self.d_xor is not None else 0, d_test=self.d_test.ptr if self.d_test is not None else 0,
                          stream=stream)
@@ -511,13 +515,16 @@ class _DeviceTally:
             if self._uf is not None:
                 self.hp.uf_decode_device(self._uf, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
                                          self.d_decoded.ptr, **masks)
+            if self._ufw is not None:
+                self.hp.ufw_decode_device(self._ufw, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
+                                          self.d_decoded.ptr, **masks)
 
     def result(self, shots: int) -> ShotCounts:
         """The counters, once every tally launch has completed (the caller has synchronised their streams)."""
         c = np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64)
         self.hp.d2h(c, self.d_counts)
         out = ShotCounts.from_counters(c, shots=shots, n_cols=self.n_cols, num_detectors=self.nd, histogram_columns=self.hc)
-        if self._pairs is None and self._table is None and self._lookup is None and self._uf is None:
+        if self._pairs is None and self._table is None and self._lookup is None and self._uf is None and self._ufw is None:
             return out
         pairs = self.hp.pairs_read(self._pairs, len(self.pc), stream=self._pairs_stream) if self._pairs is not None else None
         patterns = pattern_counts = errors = misses = None
@@ -526,7 +533,7 @@ class _DeviceTally:
             keys, cnt, info = self.hp.rowtab_read(self._table, len(self.tc), stream=self._pairs_stream)
             patterns, pattern_counts = ordered_patterns(keys, cnt, len(self.tc))
             overflow = int(info[4])
-        if self._lookup is not None or self._uf is not None:
+        if self._lookup is not None or self._uf is not None or self._ufw is not None:
             self.hp.stream_synchronize(self._pairs_stream)
             d = np.zeros(3, dtype=np.uint64)
             self.hp.d2h(d, self.d_decoded)
@@ -543,6 +550,9 @@ class _DeviceTally:
         if self._uf is not None:
             self.hp.uf_destroy(self._uf)
             self._uf = None
+        if self._ufw is not None:
+            self.hp.ufw_destroy(self._ufw)
+            self._ufw = None
         if self._pairs is not None:
             self.hp.pairs_destroy(self._pairs)
             self._pairs = None

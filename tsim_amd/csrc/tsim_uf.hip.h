@@ -110,6 +110,43 @@ __device__ __forceinline__ uint64_t below(int b, int end) {
   return left <= 0 ? 0ull : left >= 64 ? ~0ull : ~0ull >> (64 - left);
 }
 
+// bytes b .. b + 7 of a row (0 past its `used` bytes); `R` has used and w8 (Args here, the windowed decoder's in tsim_ufw.hip.h)
+template <class R>
+__device__ __forceinline__ uint64_t row_word(const R &a, const uint8_t *row, int b) {
+  if (a.w8) return *reinterpret_cast<const uint64_t *>(row + b);  // (rb is a multiple of 8: inside the row)
+  uint64_t w = 0;
+  for (int q = 0; q < 8 && b + q < a.used; ++q) w |= (uint64_t)row[b + q] << (8 * q);
+  return w;
+}
+
+// pass 1 of a lane's row: *fail = the test columns that are set, *defects = the detector columns that are set (after xor);
+// dmask: the detector columns as a mask row, NULL for the columns 0 .. nd - 1
+template <class R>
+__device__ __forceinline__ void scan_row(const R &a, const uint8_t *row, bool valid, const uint8_t *dmask, int nd, uint64_t *fail,
+                                         uint64_t *defects) {
+  *fail = 0, *defects = 0;
+  for (int b = 0; b < a.used; b += 8) {
+    const uint64_t tw = mask_word(a.test, b, a.used) & below(b, a.n_cols),  // (pad bits are not columns)
+        dw = dmask ? mask_word(dmask, b, a.used) : below(b, nd);
+    if ((tw | dw) == 0) continue;
+    const uint64_t w = (valid ? row_word(a, row, b) : 0ull) ^ mask_word(a.xr, b, a.used);
+    *fail |= w & tw;
+    *defects |= w & dw;
+  }
+}
+
+// the observable columns obs_lo .. obs_hi - 1 of a row, bit i = column obs_lo + i
+template <class R>
+__device__ __forceinline__ uint64_t row_obs(const R &a, const uint8_t *row) {
+  uint64_t obs = 0;
+  for (int c = a.obs_lo; c < a.obs_hi; ++c) {
+    uint32_t byte = row[c >> 3];
+    if (a.xr) byte ^= a.xr[c >> 3];
+    obs |= (uint64_t)((byte >> (c & 7)) & 1u) << (c - a.obs_lo);
+  }
+  return obs;
+}
+
 struct State {
   uint16_t *label;
   uint32_t *lp, *s32, *par32, *half, *full, *misc;  // misc: [0] listed words [1] deepest level [2] [3] the prediction
@@ -118,9 +155,29 @@ struct State {
   uint16_t *wlist;
 };
 
+// a wave's state at `base`, by the offsets layout() has put into `a`
+template <class L>
+__device__ __forceinline__ State state_at(const L &a, uint8_t *base) {
+  State st;
+  st.label = reinterpret_cast<uint16_t *>(base);
+  st.lp = reinterpret_cast<uint32_t *>(base + a.off_lp);
+  st.s = base + a.off_s;
+  st.s32 = reinterpret_cast<uint32_t *>(st.s);
+  st.par = base + a.off_par;
+  st.par32 = reinterpret_cast<uint32_t *>(st.par);
+  st.half = reinterpret_cast<uint32_t *>(base + a.off_half);
+  st.full = reinterpret_cast<uint32_t *>(base + a.off_full);
+  st.wlist = reinterpret_cast<uint16_t *>(base + a.off_wlist);
+  st.misc = reinterpret_cast<uint32_t *>(base + a.off_misc);
+  return st;
+}
+
+// The steps of one shot, each by the whole wave.  `G` is the graph they run on: Args here, one window's tables in
+// tsim_ufw.hip.h (n_nodes, w32, w_cnt, edge_uv, edge_obs, cap, adj_ptr, adj_edge).  decode_shot below is their order.
+
 // f(e, u, v) for every full edge, a lane per listed word
-template <class F>
-__device__ __forceinline__ void full_edges(const Args &a, const State &st, int n_words, int lane, F f) {
+template <class G, class F>
+__device__ __forceinline__ void full_edges(const G &a, const State &st, int n_words, int lane, F f) {
   for (int i = lane; i < n_words; i += 64) {
     const int w = st.wlist[i];
     uint32_t bits = st.full[w];
@@ -133,9 +190,9 @@ __device__ __forceinline__ void full_edges(const Args &a, const State &st, int n
   }
 }
 
-// one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform
-template <bool Weighted, bool Heralds>
-__device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds) {
+// s[v] = the defect of node v, from the row; every node its own cluster
+template <bool Heralds>
+__device__ __forceinline__ void load_defects(const Args &a, const State &st, const uint8_t *row, int lane) {
   const int N = a.n_nodes;
   for (int v = lane; v < N; v += 64) {
     uint32_t bit = 0;
@@ -149,6 +206,11 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
     st.s[v] = (uint8_t)bit;
     st.label[v] = (uint16_t)v;
   }
+}
+
+// no edge has grown, no word is listed, the prediction is 0
+template <bool Weighted, class G>
+__device__ __forceinline__ void clear_edges(const G &a, const State &st, int lane) {
   if constexpr (Weighted) {
     for (int i = lane; i < a.w_cnt; i += 64) st.half[i] = 0;
     for (int i = lane; i < a.w32; i += 64) st.full[i] = 0;
@@ -157,30 +219,31 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   }
   if (lane < 4) st.misc[lane] = 0;
   wsync();
-  if constexpr (Heralds) {  // the edges of the heralds that are set start full
-    const int det_bytes = (a.n_det_cols + 7) >> 3;
-    for (int b = 8 * lane; b < det_bytes; b += 8 * 64) {
-      const uint64_t hw = mask_word(a.hmask, b, a.used);
-      if (hw == 0) continue;
-      uint64_t w = 0;
-      if (a.w8) w = *reinterpret_cast<const uint64_t *>(row + b);  // (rb is a multiple of 8: inside the row)
-      else
-        for (int q = 0; q < 8 && b + q < a.used; ++q) w |= (uint64_t)row[b + q] << (8 * q);
-      w = (w ^ mask_word(a.xr, b, a.used)) & hw;
-      while (w) {
-        const int h = a.col_herald[8 * b + __builtin_ctzll(w)];
-        w &= w - 1;
-        for (int k = a.herald_ptr[h]; k < a.herald_ptr[h + 1]; ++k) {
-          const int e = a.herald_edges[k], fw = e >> 5;
-          if (atomicOr(&st.full[fw], 1u << (e & 31)) == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)fw;  // (each word once)
-        }
+}
+
+// the edges of the heralds that are set start full
+__device__ __forceinline__ void pregrow_heralds(const Args &a, const State &st, const uint8_t *row, int lane) {
+  const int det_bytes = (a.n_det_cols + 7) >> 3;
+  for (int b = 8 * lane; b < det_bytes; b += 8 * 64) {
+    const uint64_t hw = mask_word(a.hmask, b, a.used);
+    if (hw == 0) continue;
+    const uint64_t w0 = (row_word(a, row, b) ^ mask_word(a.xr, b, a.used)) & hw;
+    for (uint64_t w = w0; w; w &= w - 1) {
+      const int h = a.col_herald[8 * b + __builtin_ctzll(w)];
+      for (int k = a.herald_ptr[h]; k < a.herald_ptr[h + 1]; ++k) {
+        const int e = a.herald_edges[k], fw = e >> 5;
+        if (atomicOr(&st.full[fw], 1u << (e & 31)) == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)fw;  // (each word once)
       }
     }
-    wsync();
   }
-  *missed = false;
+  wsync();
+}
+
+// growth to its end: true for a miss; *rounds is wave-uniform
+template <bool Weighted, class G>
+__device__ __forceinline__ bool grow(const G &a, const State &st, int lane, int *rounds) {
+  const int N = a.n_nodes;
   *rounds = 0;
-  // ---- growth
   for (;;) {
     const int n_words = (int)st.misc[0];
     for (;;) {  // the clusters: labels to their fixpoint (they stay upper bounds from round to round: clusters only merge)
@@ -231,14 +294,16 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
       }
     }
     wsync();
-    if (!__builtin_amdgcn_ballot_w64(active)) break;
-    if (!__builtin_amdgcn_ballot_w64(changed)) {
-      *missed = true;
-      return 0;
-    }
+    if (!__builtin_amdgcn_ballot_w64(active)) return false;
+    if (!__builtin_amdgcn_ballot_w64(changed)) return true;
     ++*rounds;
   }
-  // ---- the forest
+}
+
+// the forest: lp[v] = level << 16 | parent edge, the deepest level in misc[1]
+template <class G>
+__device__ __forceinline__ void forest(const G &a, const State &st, int lane) {
+  const int N = a.n_nodes;
   const int n_words = (int)st.misc[0];
   for (int v = lane; v < N; v += 64) st.lp[v] = st.label[v] == v ? 0u : kNone;
   wsync();
@@ -260,7 +325,13 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   }
   full_edges(a, st, n_words, lane, [&](int, int u, int v) { atomicMax(&st.misc[1], max(st.lp[u], st.lp[v]) >> 16); });
   wsync();
-  // ---- peeling: an edge is looked at by the level of the end whose parent edge it is
+}
+
+// peeling: an edge is looked at by the level of the end whose parent edge it is.  flip(e, u, v) is called by the lane that
+// flips edge e = (u, v) and returns the observables this flips; the return value is this lane's XOR of them.
+template <class G, class F>
+__device__ __forceinline__ uint64_t peel(const G &a, const State &st, int lane, F flip) {
+  const int n_words = (int)st.misc[0];
   uint64_t flips = 0;
   for (int level = (int)st.misc[1]; level >= 1; --level) {
     full_edges(a, st, n_words, lane, [&](int e, int u, int v) {
@@ -270,16 +341,34 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
       else if (st.lp[u] == want) child = u, parent = v;
       if (child < 0 || !st.s[child]) return;
       atomicXor(&st.s32[parent >> 2], 1u << (8 * (parent & 3)));  // (the parent is of the level above: nobody reads it in this pass)
-      flips ^= a.edge_obs[e];
+      flips ^= flip(e, u, v);
     });
     wsync();
   }
+  return flips;
+}
+
+// the wave's XOR of the lanes' flips, kept in two 32-bit words of LDS (zero, or what earlier calls left)
+__device__ __forceinline__ uint64_t fold_flips(uint32_t *words, uint64_t flips) {
   if (flips) {
-    atomicXor(&st.misc[2], (uint32_t)flips);
-    atomicXor(&st.misc[3], (uint32_t)(flips >> 32));
+    atomicXor(&words[0], (uint32_t)flips);
+    atomicXor(&words[1], (uint32_t)(flips >> 32));
   }
   wsync();
-  return (uint64_t)st.misc[2] | (uint64_t)st.misc[3] << 32;
+  return (uint64_t)words[0] | (uint64_t)words[1] << 32;
+}
+
+// one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform
+template <bool Weighted, bool Heralds>
+__device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds) {
+  load_defects<Heralds>(a, st, row, lane);
+  clear_edges<Weighted>(a, st, lane);
+  if constexpr (Heralds) pregrow_heralds(a, st, row, lane);
+  *missed = grow<Weighted>(a, st, lane, rounds);
+  if (*missed) return 0;
+  forest(a, st, lane);
+  const uint64_t flips = peel(a, st, lane, [&](int e, int, int) { return a.edge_obs[e]; });
+  return fold_flips(&st.misc[2], flips);
 }
 
 template <bool Weighted, bool Heralds>
@@ -288,17 +377,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
-  State st;
-  st.label = reinterpret_cast<uint16_t *>(base);
-  st.lp = reinterpret_cast<uint32_t *>(base + a.off_lp);
-  st.s = base + a.off_s;
-  st.s32 = reinterpret_cast<uint32_t *>(st.s);
-  st.par = base + a.off_par;
-  st.par32 = reinterpret_cast<uint32_t *>(st.par);
-  st.half = reinterpret_cast<uint32_t *>(base + a.off_half);
-  st.full = reinterpret_cast<uint32_t *>(base + a.off_full);
-  st.wlist = reinterpret_cast<uint16_t *>(base + a.off_wlist);
-  st.misc = reinterpret_cast<uint32_t *>(base + a.off_misc);
+  const State st = state_at(a, base);
   if (threadIdx.x < 4) stat[threadIdx.x] = 0;
   __syncthreads();
   uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
@@ -309,29 +388,10 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     const long long r = (t << 6) + lane;
     const bool valid = r < a.n;
     const uint8_t *row = a.rows + (valid ? r : 0) * a.rb;
-    uint64_t fail = 0, defects = 0;
-    for (int b = 0; b < a.used; b += 8) {
-      const uint64_t tw = mask_word(a.test, b, a.used) & below(b, a.n_cols),  // (pad bits are not columns)
-          dw = Heralds ? mask_word(a.dmask, b, a.used) : below(b, nd);
-      if ((tw | dw) == 0) continue;
-      uint64_t w = 0;
-      if (valid) {
-        if (a.w8) w = *reinterpret_cast<const uint64_t *>(row + b);  // (rb is a multiple of 8: inside the row)
-        else
-          for (int q = 0; q < 8 && b + q < a.used; ++q) w |= (uint64_t)row[b + q] << (8 * q);
-      }
-      w ^= mask_word(a.xr, b, a.used);
-      fail |= w & tw;
-      defects |= w & dw;
-    }
+    uint64_t fail, defects;
+    scan_row(a, row, valid, Heralds ? a.dmask : nullptr, nd, &fail, &defects);
     const bool kept = valid && fail == 0;
-    uint64_t obs = 0;
-    if (kept)
-      for (int c = a.obs_lo; c < a.obs_hi; ++c) {
-        uint32_t byte = row[c >> 3];
-        if (a.xr) byte ^= a.xr[c >> 3];
-        obs |= (uint64_t)((byte >> (c & 7)) & 1u) << (c - a.obs_lo);
-      }
+    const uint64_t obs = kept ? row_obs(a, row) : 0;
     uint64_t pred = 0;
     bool missed = false;
     uint64_t work = __builtin_amdgcn_ballot_w64(kept && defects != 0);

@@ -1,0 +1,322 @@
+// tsim_ufw.hip - sliding-window union-find decoding over bit-packed device rows (tsim_ufw_*): a handle of its own, bound to
+// one device.  tsim_ufw_create builds the windows of the global decoding graph on the host, by the rule in the module
+// docstring of tsim_amd/decode.py ("Sliding-window decoding of long runs") - a second statement of that construction,
+// independent of the numpy one - and holds their tables; the kernel is csrc/tsim_ufw.hip.h.
+#include "../../include/tsim_hip.h"
+#include "tsim_ufw.hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define UFW_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+namespace {
+constexpr int kMaxWindow = 65535;              // nodes, and edges, of a window: uint16 indices
+constexpr int64_t kRowsPerLaunch = 1ll << 30;  // a block's uint32 partials cannot overflow
+constexpr int64_t kMaxTable = 0x7FFFFFFF;      // entries of a concatenated table: int32 offsets
+
+struct Tables {
+  std::vector<ufwk::WinDesc> desc;
+  std::vector<uint32_t> uv, adj_ptr, commit;
+  std::vector<uint64_t> obs;
+  std::vector<uint8_t> cap;
+  std::vector<uint16_t> adj;
+  int max_nodes = 0, max_edges = 0, max_w32 = 1, max_w_cnt = 0;
+};
+}  // namespace
+
+struct tsim_ufw {
+  int device = -1;
+  ufwk::Args a{};  // the windows' part of the kernel's arguments
+  int grid = 1;
+  int n_nodes = 0, n_edges = 0, max_nodes = 0, max_edges = 0, max_cap = 0;
+  int64_t launches = 0, bytes = 0;
+  void *d_desc = nullptr, *d_uv = nullptr, *d_obs = nullptr, *d_cap = nullptr, *d_adj_ptr = nullptr, *d_adj = nullptr, *d_commit = nullptr,
+       *d_stats = nullptr;
+};
+
+static void ufw_release(tsim_ufw *h) {
+  if (h->device >= 0) (void)hipSetDevice(h->device);
+  for (void *p : {h->d_desc, h->d_uv, h->d_obs, h->d_cap, h->d_adj_ptr, h->d_adj, h->d_commit, h->d_stats})
+    if (p) (void)hipFree(p);
+}
+
+// The windows of the graph (checked by the caller: u < v inside the nodes, pairs strictly ascending) with `commit` = C and
+// `window` = W columns.  0, or an error code after tsim_fail.
+static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t C, int64_t W, Tables *t) {
+  const int64_t nd = (int64_t)g->n_nodes - 1, E = g->n_edges;
+  const int64_t K = nd <= W ? 1 : (nd - W + C - 1) / C + 1;  // the smallest K >= 1 with (K - 1) C + W >= nd
+  auto hi_of = [&](int64_t k) { return k == K - 1 ? nd : k * C + W; };
+  auto cap_of = [&](int64_t e) { return edge_cap ? edge_cap[e] : (uint8_t)2; };
+  // validity: the column a of an edge's lower end is committed in window min(a / C, K - 1), which must hold its upper end
+  std::vector<int32_t> outer, inner;  // the boundary edges, ascending in their column; the others, ascending in the lower column
+  for (int64_t e = 0; e < E; ++e) {
+    if (g->edge_u[e] == 0) {
+      outer.push_back((int32_t)e);
+      continue;
+    }
+    inner.push_back((int32_t)e);
+    const int64_t a = g->edge_u[e] - 1, b = g->edge_v[e] - 1, k = std::min(a / C, K - 1);
+    if (b >= hi_of(k))
+      return tsim_fail(TSIM_EINVAL,
+                       "edge %lld = (%d, %d): column %lld is committed in window %lld, which ends before column %lld (at %lld): the buffer "
+                       "window - commit = %lld is too small",
+                       (long long)e, g->edge_u[e], g->edge_v[e], (long long)a, (long long)k, (long long)b, (long long)hi_of(k), (long long)(W - C));
+  }
+  if (std::min(W, nd) + 1 > kMaxWindow)
+    return tsim_fail(TSIM_ENOTSUP, "a window of %lld nodes (at most %d: indices are uint16)", (long long)(std::min(W, nd) + 1), kMaxWindow);
+  const size_t n_max = (size_t)std::min(W, nd) + 1;
+  std::vector<uint8_t> b_cap(n_max), b_kind(n_max);  // per local node x the pair (0, x): its cap; 0 none, 1 virtual only, 2 real
+  std::vector<int32_t> b_edge(n_max);                // the real boundary edge
+  std::vector<int32_t> kept;                         // the window's edges between two of its columns
+  std::vector<uint32_t> lu, lv, at;
+  size_t po = 0, pi = 0;
+  for (int64_t k = 0; k < K; ++k) {
+    const int64_t lo = k * C, hi = hi_of(k);
+    const int N = (int)(hi - lo + 1);
+    const bool last = k == K - 1;
+    std::fill(b_kind.begin(), b_kind.begin() + N, 0);
+    std::fill(b_cap.begin(), b_cap.begin() + N, 255);
+    while (po < outer.size() && g->edge_v[outer[po]] - 1 < lo) ++po;
+    for (size_t i = po; i < outer.size() && g->edge_v[outer[i]] - 1 < hi; ++i) {
+      const int32_t e = outer[i];
+      const int x = (int)(g->edge_v[e] - lo);
+      b_kind[x] = 2, b_edge[x] = e, b_cap[x] = cap_of(e);
+    }
+    kept.clear();
+    while (pi < inner.size() && g->edge_u[inner[pi]] - 1 < lo) ++pi;
+    for (size_t i = pi; i < inner.size() && g->edge_u[inner[i]] - 1 < hi; ++i) {
+      const int32_t e = inner[i];
+      if (g->edge_v[e] - 1 < hi) {
+        kept.push_back(e);
+        continue;
+      }
+      const int x = (int)(g->edge_u[e] - lo);  // to the open future boundary
+      b_kind[x] = std::max<uint8_t>(b_kind[x], 1), b_cap[x] = std::min(b_cap[x], cap_of(e));
+    }
+    lu.clear(), lv.clear();
+    ufwk::WinDesc d{};
+    d.lo = (int32_t)lo, d.n_nodes = N, d.last = last;
+    d.off_edge = (int32_t)t->uv.size(), d.off_ptr = (int32_t)t->adj_ptr.size(), d.off_adj = (int32_t)t->adj.size();
+    d.off_commit = (int32_t)t->commit.size();
+    for (int x = 1; x < N; ++x)
+      if (b_kind[x]) {
+        lu.push_back(0), lv.push_back((uint32_t)x);
+        t->obs.push_back(b_kind[x] == 2 ? g->edge_obs[b_edge[x]] : 0);
+        t->cap.push_back(b_cap[x]);
+      }
+    for (int32_t e : kept) {
+      lu.push_back((uint32_t)(g->edge_u[e] - lo)), lv.push_back((uint32_t)(g->edge_v[e] - lo));
+      t->obs.push_back(g->edge_obs[e]);
+      t->cap.push_back(cap_of(e));
+    }
+    const size_t n_e = lu.size();
+    if (n_e > (size_t)kMaxWindow)
+      return tsim_fail(TSIM_ENOTSUP, "window %lld has %zu edges (at most %d: indices are uint16)", (long long)k, n_e, kMaxWindow);
+    d.n_edges = (int32_t)n_e;
+    d.w32 = std::max(1, ((int)n_e + 31) / 32);
+    d.w_cnt = edge_cap ? std::max(1, ((int)n_e + 7) / 8) : 0;
+    t->commit.resize(t->commit.size() + d.w32, 0);
+    at.assign((size_t)N + 1, 0);
+    for (size_t e = 0; e < n_e; ++e) {
+      if (!(lu[e] < lv[e] && lv[e] < (uint32_t)N)) return tsim_fail(TSIM_EINVAL, "window %lld: local edge %zu leaves its nodes", (long long)k, e);
+      t->uv.push_back(lu[e] | lv[e] << 16);
+      if (last || lv[e] <= C || (lu[e] >= 1 && lu[e] <= C)) t->commit[d.off_commit + (e >> 5)] |= 1u << (e & 31);
+      ++at[lu[e] + 1], ++at[lv[e] + 1];
+    }
+    for (int v = 0; v < N; ++v) at[v + 1] += at[v];
+    t->adj_ptr.insert(t->adj_ptr.end(), at.begin(), at.end());
+    t->adj.resize(t->adj.size() + 2 * n_e);
+    for (size_t e = 0; e < n_e; ++e) {
+      t->adj[d.off_adj + at[lu[e]]++] = (uint16_t)e;
+      t->adj[d.off_adj + at[lv[e]]++] = (uint16_t)e;
+    }
+    t->desc.push_back(d);
+    t->max_nodes = std::max(t->max_nodes, N), t->max_edges = std::max(t->max_edges, (int)n_e);
+    t->max_w32 = std::max(t->max_w32, d.w32), t->max_w_cnt = std::max(t->max_w_cnt, d.w_cnt);
+    if ((int64_t)t->adj.size() > kMaxTable || (int64_t)t->adj_ptr.size() > kMaxTable)
+      return tsim_fail(TSIM_ENOTSUP, "the windows' tables pass 2^31 entries at window %lld of %lld", (long long)k, (long long)K);
+  }
+  return TSIM_OK;
+}
+
+extern "C" int tsim_ufw_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, int32_t commit, int32_t window,
+                               tsim_ufw **out) {
+  if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!desc) return tsim_fail(TSIM_EINVAL, "desc is NULL");
+  const int N = desc->n_nodes, E = desc->n_edges;
+  if (N < 2) return tsim_fail(TSIM_EINVAL, "n_nodes = %d (the boundary and at least one detector)", N);
+  if (E < 0) return tsim_fail(TSIM_EINVAL, "n_edges = %d", E);
+  if (commit < 1 || window <= commit) return tsim_fail(TSIM_EINVAL, "commit = %d, window = %d: 1 <= commit < window expected", commit, window);
+  if (desc->n_cols < N - 1 || desc->n_cols > (1 << 30)) return tsim_fail(TSIM_EINVAL, "n_cols = %d for %d detectors (up to 2^30)", desc->n_cols, N - 1);
+  if (E > 0 && (!desc->edge_u || !desc->edge_v || !desc->edge_obs)) return tsim_fail(TSIM_EINVAL, "an edge array is NULL");
+  for (int e = 0; e < E; ++e) {
+    const int32_t u = desc->edge_u[e], v = desc->edge_v[e];
+    if (u < 0 || v >= N) return tsim_fail(TSIM_EINVAL, "edge %d = (%d, %d) leaves the nodes 0 .. %d", e, u, v, N - 1);
+    if (u >= v) return tsim_fail(TSIM_EINVAL, "edge %d = (%d, %d): u < v expected", e, u, v);
+    if (e > 0 && (desc->edge_u[e - 1] > u || (desc->edge_u[e - 1] == u && desc->edge_v[e - 1] >= v)))
+      return tsim_fail(TSIM_EINVAL, "edge %d = (%d, %d) does not come after edge %d: the pairs must be strictly ascending", e, u, v, e - 1);
+  }
+  int max_cap = 0;
+  if (edge_cap)
+    for (int e = 0; e < E; ++e) {
+      if (edge_cap[e] < 1 || edge_cap[e] > ufk::kMaxCap)
+        return tsim_fail(TSIM_EINVAL, "edge %d has cap %d (1 .. %d: a 4-bit counter that may overshoot by one)", e, edge_cap[e], ufk::kMaxCap);
+      max_cap = std::max<int>(max_cap, edge_cap[e]);
+    }
+  Tables t;
+  if (const int rc = build_windows(desc, edge_cap, commit, window, &t)) return rc;
+  // the state of a wave: that of the largest window, the carry bitmap, the prediction
+  ufk::Args lay{};
+  lay.n_nodes = t.max_nodes, lay.w32 = t.max_w32, lay.w_cnt = t.max_w_cnt;
+  long long shot = ufk::layout(&lay);
+  int carry_words = 1;
+  while (32ll * carry_words < std::min<long long>(window, N - 1)) carry_words *= 2;
+  ufwk::Args a{};
+  a.off_lp = lay.off_lp, a.off_s = lay.off_s, a.off_par = lay.off_par, a.off_half = lay.off_half, a.off_full = lay.off_full;
+  a.off_wlist = lay.off_wlist, a.off_misc = lay.off_misc;
+  a.off_carry = (int)shot, shot += ufk::a16(4ll * carry_words);
+  a.off_pred = (int)shot, shot += 16;
+  if (16 + shot > ufk::kLdsBlock)
+    return tsim_fail(TSIM_ENOTSUP, "one shot's state takes %lld bytes of LDS (windows of up to %d nodes, %d edges), a block has %d", shot,
+                     t.max_nodes, t.max_edges, ufk::kLdsBlock - 16);
+  a.shot_bytes = (int)shot;
+  a.carry_words = carry_words;
+  a.n_windows = (int)t.desc.size();
+  a.commit = commit;
+  a.nd = N - 1;
+  a.n_cols = desc->n_cols;
+  int best = 0, per_cu = 1;  // the waves of a block: as many shots on a CU as its LDS holds, in the fewest blocks
+  for (int w = 1; w <= ufk::kMaxWaves; ++w) {
+    const long long block = 16 + w * shot;
+    if (block > ufk::kLdsBlock) break;
+    const int blocks = (int)std::min<long long>(ufk::kLdsCU / block, 32 / w);
+    if (blocks * w >= best) best = blocks * w, a.waves = w, per_cu = blocks;
+  }
+  if (t.uv.empty()) t.uv.push_back(0), t.obs.push_back(0), t.cap.push_back(1);
+  if (t.adj.empty()) t.adj.push_back(0);
+  int count = 0;
+  UFW_TRY(hipGetDeviceCount(&count));
+  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
+  UFW_TRY(hipSetDevice(device));
+  int cus = 0;
+  UFW_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  tsim_ufw *h = new (std::nothrow) tsim_ufw();
+  if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
+  h->device = device;
+  h->grid = std::max(1, cus) * per_cu;
+  h->n_nodes = N, h->n_edges = E, h->max_nodes = t.max_nodes, h->max_edges = t.max_edges, h->max_cap = max_cap;
+  hipError_t e = hipSuccess;
+  auto upload = [&](void **dst, const void *src, size_t bytes) {
+    if (e == hipSuccess) e = hipMalloc(dst, bytes);
+    if (e == hipSuccess) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    h->bytes += (int64_t)bytes;
+  };
+  upload(&h->d_desc, t.desc.data(), t.desc.size() * sizeof(ufwk::WinDesc));
+  upload(&h->d_uv, t.uv.data(), t.uv.size() * 4);
+  upload(&h->d_obs, t.obs.data(), t.obs.size() * 8);
+  if (edge_cap) upload(&h->d_cap, t.cap.data(), t.cap.size());
+  upload(&h->d_adj_ptr, t.adj_ptr.data(), t.adj_ptr.size() * 4);
+  upload(&h->d_adj, t.adj.data(), t.adj.size() * 2);
+  upload(&h->d_commit, t.commit.data(), t.commit.size() * 4);
+  const uint64_t zero[4] = {0, 0, 0, 0};
+  upload(&h->d_stats, zero, sizeof zero);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    ufw_release(h);
+    delete h;
+    return tsim_fail(e == hipErrorOutOfMemory ? TSIM_ENOMEM : TSIM_EHIP, "%zu windows of a graph of %d nodes, %d edges: %s", t.desc.size(), N, E,
+                     hipGetErrorString(e));
+  }
+  a.desc = static_cast<const ufwk::WinDesc *>(h->d_desc);
+  a.edge_uv = static_cast<const uint32_t *>(h->d_uv);
+  a.edge_obs = static_cast<const unsigned long long *>(h->d_obs);
+  a.cap = static_cast<const uint8_t *>(h->d_cap);
+  a.adj_ptr = static_cast<const uint32_t *>(h->d_adj_ptr);
+  a.adj_edge = static_cast<const uint16_t *>(h->d_adj);
+  a.commit_bits = static_cast<const uint32_t *>(h->d_commit);
+  a.stats = static_cast<unsigned long long *>(h->d_stats);
+  h->a = a;
+  *out = h;
+  return TSIM_OK;
+}
+
+extern "C" void tsim_ufw_destroy(tsim_ufw *h) {
+  if (!h) return;
+  ufw_release(h);
+  delete h;
+}
+
+extern "C" int tsim_ufw_info(tsim_ufw *h, int64_t out[16]) {
+  if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
+  UFW_TRY(hipSetDevice(h->device));
+  UFW_TRY(hipDeviceSynchronize());  // (the statistics live on the device: every decode so far is waited for)
+  uint64_t st[3];
+  UFW_TRY(hipMemcpy(st, h->d_stats, sizeof st, hipMemcpyDeviceToHost));
+  std::fill(out, out + 16, 0);
+  out[0] = h->n_nodes;
+  out[1] = h->n_edges;
+  out[2] = h->a.n_windows;
+  out[3] = h->max_nodes;
+  out[4] = h->max_edges;
+  out[5] = h->a.shot_bytes;
+  out[6] = h->a.waves;
+  out[7] = h->launches;
+  out[8] = (int64_t)st[0];
+  out[9] = h->bytes;
+  out[10] = (int64_t)st[1];
+  out[11] = (int64_t)st[2];
+  out[12] = h->a.n_cols;
+  out[13] = h->grid;
+  out[14] = h->max_cap;
+  return TSIM_OK;
+}
+
+extern "C" int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                      const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                      void *stream) {
+  if (!h) return tsim_fail(TSIM_EINVAL, "decoder is NULL");
+  if (n < 0) return tsim_fail(TSIM_EINVAL, "negative n");
+  ufwk::Args a = h->a;
+  const int64_t used = ((int64_t)a.n_cols + 7) / 8;
+  if (row_bytes < used || row_bytes > 0x7FFFFFFF)
+    return tsim_fail(TSIM_EINVAL, "row_bytes = %lld for %lld bytes per row", (long long)row_bytes, (long long)used);
+  if (n > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
+  if (obs_lo < 0 || obs_hi < obs_lo || obs_hi > a.n_cols || obs_hi - obs_lo > 64)
+    return tsim_fail(TSIM_EINVAL, "observable columns %d .. %d of %d (at most 64)", obs_lo, obs_hi, a.n_cols);
+  if (!d_counters || reinterpret_cast<uintptr_t>(d_counters) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_counters is NULL or not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_pred) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_pred is not 8-byte aligned");
+  if (n == 0) return TSIM_OK;
+  UFW_TRY(hipSetDevice(h->device));
+  a.rb = row_bytes;
+  a.used = (int)used;
+  a.xr = d_xor;
+  a.test = d_test;
+  a.w8 = reinterpret_cast<uintptr_t>(d_rows) % 8 == 0 && row_bytes % 8 == 0;
+  a.obs_lo = obs_lo;
+  a.obs_hi = obs_hi;
+  a.dec = reinterpret_cast<unsigned long long *>(d_counters);
+  const size_t lds = 16 + (size_t)a.waves * a.shot_bytes;
+  for (int64_t r0 = 0; r0 < n; r0 += kRowsPerLaunch) {
+    a.n = std::min(kRowsPerLaunch, n - r0);
+    a.rows = d_rows + r0 * row_bytes;
+    a.pred = d_pred ? reinterpret_cast<unsigned long long *>(d_pred) + r0 : nullptr;
+    const int64_t tiles = (a.n + 63) / 64;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + a.waves - 1) / a.waves, h->grid));
+    if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((ufwk::k_ufw<false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    UFW_TRY(hipGetLastError());
+    ++h->launches;
+  }
+  return TSIM_OK;
+}

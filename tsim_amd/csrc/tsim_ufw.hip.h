@@ -1,0 +1,199 @@
+// tsim_ufw.hip.h - sliding-window union-find decoding over bit-packed device rows (tsim_ufw_*); the rule is "Sliding-window
+// decoding of long runs" in the module docstring of tsim_amd/decode.py, which is also its numpy statement.  Rows, xor and
+// test are those of k_uf (tsim_uf.hip.h), and so are the grid and the passes: one wave owns a tile of 64 rows; pass 1
+// finishes the rows without a defect straight from the row; pass 2 decodes each kept row with a defect by the whole wave in the
+// wave's own state in LDS - here window after window, each by the steps of tsim_uf.hip.h (clear_edges, grow, forest, peel) on
+// that window's tables.
+//
+// The windows' tables lie concatenated in global memory (tsim_ufw_create builds and checks them on the host); WinDesc says
+// where a window's part of each begins: edge_uv (u | v << 16, LOCAL nodes: 0 the boundary, c - lo + 1 column c), edge_obs,
+// cap (weighted growth only), adj_ptr (n_nodes + 1 entries, relative to the window's part of adj_edge), adj_edge, and commit
+// (a bitmap over the local edges: the COMMITTED ones).  The global column of a local node v >= 1 is lo + v - 1, so the ends'
+// columns need no table of their own.
+//
+// A wave's state is ufk::layout() of the largest window (the most nodes, the most edge words, taken separately), then
+//   carry   uint32[P / 32]  bit (c mod P) = the toggles that committed flips of earlier windows left at column c, P the
+//                           smallest power of two >= max(window, 32).  Window k starts from s[v] = row bit ^ xor bit ^ carry
+//                           bit of column lo + v - 1; a committed edge that flips in peeling toggles the bits of its
+//                           non-boundary ends (32-bit LDS XOR); when the window advances, the slots of its commit region
+//                           [lo, lo + commit) are cleared (a lane per word, plain stores: nobody else touches carry then),
+//                           and these are the slots the columns [hi, hi + commit) of the next window use, since P >= window
+//   pred    uint32[2]       the prediction so far: the XOR of the masks of the committed flips
+// Every index into LDS and into the tables comes from tables tsim_ufw_create has built and checked; every address is formed
+// in 64 bits.
+#pragma once
+#include "tsim_uf.hip.h"
+
+namespace ufwk {
+
+struct WinDesc {
+  int32_t lo, n_nodes, n_edges, w32;                 // the first column; local nodes and edges; words of an edge bitmap
+  int32_t w_cnt, off_edge, off_ptr, off_adj;         // words of the 4-bit counters (0: unweighted); where its tables begin
+  int32_t off_commit, last, pad0, pad1;              // last: the run's last window (no slots to clear after it)
+};
+
+// what the steps of tsim_uf.hip.h read of a graph: one window's
+struct Win {
+  int n_nodes, n_edges, w32, w_cnt;
+  const uint32_t *edge_uv;
+  const unsigned long long *edge_obs;
+  const uint8_t *cap;
+  const uint32_t *adj_ptr;
+  const uint16_t *adj_edge;
+};
+
+struct Args {
+  const uint8_t *rows;
+  long long n, rb;           // rows, row stride in bytes
+  int n_cols, used;          // columns; bytes of a row that hold them
+  const uint8_t *xr, *test;  // optional rows of `used` bytes (NULL: none)
+  int w8;                    // the row pointer and rb are multiples of 8
+  int nd;                    // detector columns: the global graph's nodes but the boundary
+  int obs_lo, obs_hi;
+  int waves, shot_bytes;     // waves of a block; LDS bytes of one wave's state
+  int off_lp, off_s, off_par, off_half, off_full, off_wlist, off_misc, off_carry, off_pred;
+  int n_windows, commit, carry_words;  // carry_words * 32 = P
+  const WinDesc *desc;
+  const uint32_t *edge_uv;
+  const unsigned long long *edge_obs;
+  const uint8_t *cap;        // NULL: every cap is 2
+  const uint32_t *adj_ptr;
+  const uint16_t *adj_edge;
+  const uint32_t *commit_bits;
+  unsigned long long *dec;    // [0] kept [1] wrong [2] missed
+  unsigned long long *pred;   // [n] or NULL
+  unsigned long long *stats;  // [0] most growth rounds of a window [1] rows decoded in LDS [2] windows decoded
+};
+
+// the bits j of word w of a bitmap whose index 32 w + j lies in [s, e)
+__host__ __device__ inline uint32_t bits_between(int w, int s, int e) {
+  const int lo = s - 32 * w > 0 ? s - 32 * w : 0, hi = e - 32 * w < 32 ? e - 32 * w : 32;
+  if (hi <= lo) return 0;
+  return (hi == 32 ? ~0u : (1u << hi) - 1u) & ~((1u << lo) - 1u);
+}
+
+// one kept row with a defect, by the whole wave, window after window: the prediction (0 for a miss); *missed, *rounds (the most
+// of a window) and *windows (those decoded) are wave-uniform
+template <bool Weighted>
+__device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &st, uint32_t *carry, uint32_t *pred, const uint8_t *row,
+                                               int lane, bool *missed, int *rounds, int *windows) {
+  using ufk::wsync;
+  for (int i = lane; i < a.carry_words; i += 64) carry[i] = 0;
+  if (lane < 2) pred[lane] = 0;
+  wsync();
+  *missed = false, *rounds = 0, *windows = 0;
+  const int P = 32 * a.carry_words;
+  for (int k = 0; k < a.n_windows; ++k) {
+    const WinDesc d = a.desc[k];
+    const int N = d.n_nodes;
+    bool any = false;
+    for (int v = lane; v < N; v += 64) {
+      uint32_t bit = 0;
+      if (v) {
+        const int c = d.lo + v - 1, slot = c & (P - 1);
+        uint32_t byte = row[c >> 3];
+        if (a.xr) byte ^= a.xr[c >> 3];
+        bit = ((byte >> (c & 7)) ^ (carry[slot >> 5] >> (slot & 31))) & 1u;
+      }
+      st.s[v] = (uint8_t)bit;
+      st.label[v] = (uint16_t)v;
+      any |= bit != 0;
+    }
+    if (__builtin_amdgcn_ballot_w64(any)) {  // (a window without a defect is skipped)
+      Win w;
+      w.n_nodes = N, w.n_edges = d.n_edges, w.w32 = d.w32, w.w_cnt = d.w_cnt;
+      w.edge_uv = a.edge_uv + d.off_edge;
+      w.edge_obs = a.edge_obs + d.off_edge;
+      w.cap = Weighted ? a.cap + d.off_edge : nullptr;
+      w.adj_ptr = a.adj_ptr + d.off_ptr;
+      w.adj_edge = a.adj_edge + d.off_adj;
+      const uint32_t *committed = a.commit_bits + d.off_commit;
+      ufk::clear_edges<Weighted>(w, st, lane);
+      int r;
+      const bool miss = ufk::grow<Weighted>(w, st, lane, &r);
+      *rounds = max(*rounds, r);
+      ++*windows;
+      if (miss) {
+        *missed = true;
+        return 0;
+      }
+      ufk::forest(w, st, lane);
+      const uint64_t flips = ufk::peel(w, st, lane, [&](int e, int u, int v) -> uint64_t {
+        if (!((committed[e >> 5] >> (e & 31)) & 1u)) return 0;
+        if (u) {
+          const int slot = (d.lo + u - 1) & (P - 1);
+          atomicXor(&carry[slot >> 5], 1u << (slot & 31));
+        }
+        const int slot = (d.lo + v - 1) & (P - 1);
+        atomicXor(&carry[slot >> 5], 1u << (slot & 31));
+        return w.edge_obs[e];
+      });
+      ufk::fold_flips(pred, flips);
+    }
+    wsync();
+    if (!d.last) {  // the window advances: the slots of its commit region are free for the columns that come in
+      const int s = d.lo & (P - 1), e = s + a.commit;
+      for (int i = lane; i < a.carry_words; i += 64) {
+        const uint32_t gone = bits_between(i, s, e) | bits_between(i, 0, e - P);
+        if (gone) carry[i] &= ~gone;
+      }
+      wsync();
+    }
+  }
+  return (uint64_t)pred[0] | (uint64_t)pred[1] << 32;
+}
+
+template <bool Weighted>
+__global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
+  const ufk::State st = ufk::state_at(a, base);
+  uint32_t *carry = reinterpret_cast<uint32_t *>(base + a.off_carry), *predw = reinterpret_cast<uint32_t *>(base + a.off_pred);
+  if (threadIdx.x < 4) stat[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
+  unsigned long long windows_acc = 0;
+  int most_rounds = 0;
+  const long long tiles = (a.n + 63) >> 6;
+  for (long long t = (long long)blockIdx.x * a.waves + wave; t < tiles; t += (long long)gridDim.x * a.waves) {
+    const long long r = (t << 6) + lane;
+    const bool valid = r < a.n;
+    const uint8_t *row = a.rows + (valid ? r : 0) * a.rb;
+    uint64_t fail, defects;
+    ufk::scan_row(a, row, valid, nullptr, a.nd, &fail, &defects);
+    const bool kept = valid && fail == 0;
+    const uint64_t obs = kept ? ufk::row_obs(a, row) : 0;
+    uint64_t pred = 0;
+    bool missed = false;
+    uint64_t work = __builtin_amdgcn_ballot_w64(kept && defects != 0);
+    while (work) {
+      const int src = __builtin_ctzll(work);
+      work &= work - 1;
+      bool m;
+      int rounds, windows;
+      const uint64_t p = decode_row<Weighted>(a, st, carry, predw, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, &windows);
+      if (lane == src) pred = p, missed = m;
+      most_rounds = max(most_rounds, rounds);
+      windows_acc += (unsigned)windows;
+      ++decoded_acc;
+    }
+    kept_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept));
+    wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
+    miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && missed));
+    if (a.pred && valid) a.pred[r] = pred;  // (0 for a row that is not kept, and for a miss)
+  }
+  if (lane == 0) {
+    if (kept_acc) atomicAdd(&stat[0], kept_acc);
+    if (wrong_acc) atomicAdd(&stat[1], wrong_acc);
+    if (miss_acc) atomicAdd(&stat[2], miss_acc);
+    if (most_rounds) atomicMax(&a.stats[0], (unsigned long long)most_rounds);
+    if (decoded_acc) atomicAdd(&a.stats[1], (unsigned long long)decoded_acc);
+    if (windows_acc) atomicAdd(&a.stats[2], windows_acc);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && stat[threadIdx.x]) atomicAdd(&a.dec[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
+}
+
+}  // namespace ufwk

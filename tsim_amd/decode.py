@@ -73,16 +73,64 @@ The rule with heralds changes at its start only.  ``defect[v]`` is the bit of co
 whose column is set, every listed edge starts at ``grown[e] = cap[e]``.  Growth, forest and peeling are as written (the
 clusters of the pre-grown edges exist in round 1).  A row whose non-herald detectors are all 0 predicts 0 and is not
 decoded, whatever its heralds say.
+
+Sliding-window decoding of long runs (:class:`WindowedUnionFindDecoder`; ``tsim_ufw_*``, ``csrc/tsim_ufw.hip.h``)
+---------------------------------------------------------------------------------------------------------------------
+A shot's state of the rule above must fit a block's 64 KiB of LDS (about 7000 nodes) and a :class:`DecodingGraph` has at most
+65535 nodes and edges, so a memory experiment of many rounds does not decode whole.  The windowed decoder decodes a window of
+the next columns, commits only the corrections of its oldest part and hands the defects this leaves to the next window: the
+state is that of one window whatever the length of the run, and the graph may have int32 sizes
+(``DecodingGraph(..., limit=None)``, ``from_form(form, limit=None)``; the default limit is the one above).
+
+The decoder takes a graph without heralds (node ``v >= 1`` is detector column ``v - 1``, ``nd = n_nodes - 1``), optional edge
+caps as above (without caps every cap is 2) and two integers in detector columns, ``commit = C >= 1`` and ``window = W > C``.
+Windowing is by column index, not by coordinates: the detectors of a memory circuit are declared in time order, and a round of
+``rotated_surface_code_memory(d, ...)`` is ``d * d - 1`` columns.
+
+Windows.  ``K`` is the smallest integer >= 1 with ``(K - 1) C + W >= nd``.  Window ``k`` covers the columns ``[lo_k, hi_k)``,
+``lo_k = k C`` and ``hi_k = lo_k + W``, the last one ``hi_{K-1} = nd``.  The COMMIT REGION of window ``k < K - 1`` is
+``[lo_k, lo_k + C)``; the last window commits everything.
+
+Validity.  For an edge with non-boundary ends at columns ``a < b``, ``a`` is committed in window ``k(a) = min(a // C, K - 1)``,
+and ``b < hi_{k(a)}`` is required: otherwise the constructor raises ``ValueError``, naming the edge (the buffer ``W - C`` is
+too small).  It is checked once, on the host.
+
+The window graph ``G_k``.  Local node 0 is the boundary, local node ``c - lo_k + 1`` is column ``c``.  Of the global edges, one
+with a non-boundary end below ``lo_k`` is left out (an earlier window has decided it); one with both ends in
+``{boundary} | [lo_k, hi_k)`` is kept as it is; one from a window column ``a`` to a column ``>= hi_k`` becomes the pair
+``(0, a - lo_k + 1)``, the open future boundary; one without a column in the window does not appear.  Edges that land on one
+pair merge into one edge: its cap is the smallest cap among them, its mask that of the real boundary edge if there is one,
+otherwise 0, and it is REAL iff a real edge is among them.  Local edges are numbered in ascending ``(u, v)``.  A local edge is
+COMMITTED iff ``k = K - 1`` or one of its non-boundary ends lies in the commit region; by the validity check a committed edge
+is always a real, unmerged global edge.
+
+Decoding a row.  ``r`` is the syndrome and the prediction is 0.  For ``k = 0 .. K - 1``: a window whose ``r[lo_k:hi_k]`` is all
+zero is skipped; otherwise the rule above (growth, forest, peeling) runs on ``G_k`` with the defects ``r[lo_k:hi_k]``.  A miss
+there makes the row a miss: it predicts 0 and decoding stops.  Otherwise every flipped edge that is committed XORs its mask
+into the prediction and toggles ``r`` at its non-boundary ends.  After window ``k``, ``r`` is zero on its commit region, after
+the last window everywhere (both asserted in the numpy statement).  ``growth_rounds`` is the most rounds of any window.  With
+``W >= nd`` there is one window and every number equals :class:`UnionFindDecoder`'s.
 """
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
-__all__ = ["LookupDecoder", "DecodingGraph", "UnionFindDecoder"]
+__all__ = ["LookupDecoder", "DecodingGraph", "UnionFindDecoder", "UnionFindWindow", "WindowedUnionFindDecoder"]
 
 MAX_GRAPH = 65535  # nodes, and edges: uint16 indices on the device
 MAX_CAP = 14       # of an edge: the device counts grown[e] in 4 bits and may pass the cap by one
+
+
+def _graph_limit(limit) -> int:
+    """The most nodes, and edges, of a :class:`DecodingGraph`: ``limit``, or int32 sizes for ``None``."""
+    if limit is None:
+        return 0x7FFFFFFF
+    if isinstance(limit, (bool, np.bool_)) or not isinstance(limit, (int, np.integer)) or not 2 <= limit <= 0x7FFFFFFF:
+        raise ValueError(f"limit = {limit!r}: an int in 2 .. 2^31 - 1, or None")
+    return int(limit)
 
 
 def _pack(bits: np.ndarray) -> np.ndarray:
@@ -179,15 +227,18 @@ class DecodingGraph:
     ascending pairs), ``edge_obs`` (uint64 observable masks) and ``edge_p`` (float64; :meth:`growth_caps` makes edge caps of it)."""
 
     def __init__(self, n_nodes: int, edge_u, edge_v, edge_obs, edge_p=None, *, dropped_bits: int = 0, undetectable_bits: int = 0,
-                 node_det=None, herald_det=None, herald_ptr=None, herald_edges=None, herald_bits_dropped: int = 0):
+                 node_det=None, herald_det=None, herald_ptr=None, herald_edges=None, herald_bits_dropped: int = 0,
+                 limit: int | None = MAX_GRAPH):
         u, v = np.asarray(edge_u), np.asarray(edge_v)
         if u.ndim != 1 or v.shape != u.shape or np.asarray(edge_obs).shape != u.shape:
             raise ValueError(f"edge_u, edge_v and edge_obs must be 1-D and equally long, got shapes {u.shape}, {v.shape} and "
                              f"{np.asarray(edge_obs).shape}")
         if int(n_nodes) != n_nodes or n_nodes < 2:
             raise ValueError(f"n_nodes = {n_nodes!r}: the boundary and at least one detector")
-        if n_nodes > MAX_GRAPH or len(u) > MAX_GRAPH:
-            raise NotImplementedError(f"{n_nodes} nodes and {len(u)} edges (at most {MAX_GRAPH} each: indices are uint16 on the device)")
+        limit = _graph_limit(limit)
+        if n_nodes > limit or len(u) > limit:
+            raise NotImplementedError(f"{n_nodes} nodes and {len(u)} edges (at most {limit} each" +
+                                      (": indices are uint16 on the device)" if limit == MAX_GRAPH else ")"))
         if len(u) and not (np.issubdtype(u.dtype, np.integer) and np.issubdtype(v.dtype, np.integer)):
             raise ValueError("edge_u and edge_v must be integers")
         u, v = u.astype(np.int64), v.astype(np.int64)
@@ -299,9 +350,11 @@ class DecodingGraph:
         return out
 
     @classmethod
-    def from_form(cls, form, heralds: bool = False) -> "DecodingGraph":
+    def from_form(cls, form, heralds: bool = False, limit: int | None = MAX_GRAPH) -> "DecodingGraph":
         """From the ``FaultForm`` of ``CliffordCircuit.compile_faults()`` (module docstring).  ``heralds``: herald detectors
-        are not nodes, their sites' edges are listed per herald."""
+        are not nodes, their sites' edges are listed per herald.  ``limit``: the most nodes, and edges (``None``: int32 sizes,
+        for :class:`WindowedUnionFindDecoder`)."""
+        limit = _graph_limit(limit)
         if getattr(form, "kind", None) != "detectors":
             raise ValueError("the decoding graph needs the form of compile_faults()")
         nd, n_obs = int(form.num_detectors), int(form.n_out) - int(form.num_detectors)
@@ -314,8 +367,8 @@ class DecodingGraph:
         node_det = np.setdiff1d(np.arange(nd), herald_cols)
         if len(node_det) < 1:
             raise ValueError("a decoder needs at least one detector that is not a herald")
-        if len(node_det) + 1 > MAX_GRAPH:
-            raise NotImplementedError(f"{len(node_det) + 1} nodes (at most {MAX_GRAPH}: indices are uint16 on the device)")
+        if len(node_det) + 1 > limit:
+            raise NotImplementedError(f"{len(node_det) + 1} nodes (at most {limit}" + (": indices are uint16 on the device)" if limit == MAX_GRAPH else ")"))
         node_of = np.full(nd, -1, np.int64)   # detector column -> node
         node_of[node_det] = np.arange(1, len(node_det) + 1)
         pairs: dict = {}   # (u, v) -> {mask: probability}
@@ -356,8 +409,8 @@ class DecodingGraph:
                 q = by_mask.get(mask, 0.0)
                 by_mask[mask] = p * (1.0 - q) + q * (1.0 - p)
             e0 += k
-        if len(pairs) > MAX_GRAPH:
-            raise NotImplementedError(f"{len(pairs)} edges (at most {MAX_GRAPH}: indices are uint16 on the device)")
+        if len(pairs) > limit:
+            raise NotImplementedError(f"{len(pairs)} edges (at most {limit}" + (": indices are uint16 on the device)" if limit == MAX_GRAPH else ")"))
         order = sorted(pairs)
         best = [min(pairs[pr].items(), key=lambda mp: (-mp[1], mp[0])) for pr in order]   # the likelier mask, a tie to the smaller
         extra = {}
@@ -368,7 +421,7 @@ class DecodingGraph:
                          herald_edges=np.array([e for x in lists for e in x], np.int64), herald_bits_dropped=herald_dropped)
         return cls(len(node_det) + 1, np.array([pr[0] for pr in order], np.int32), np.array([pr[1] for pr in order], np.int32),
                    np.array([m for m, _ in best], np.uint64), np.array([p for _, p in best], np.float64),
-                   dropped_bits=dropped, undetectable_bits=undetectable, **extra)
+                   dropped_bits=dropped, undetectable_bits=undetectable, limit=limit, **extra)
 
 
 def uf_shot_bytes(n_nodes: int, n_edges: int, weighted: bool) -> int:
@@ -576,5 +629,222 @@ class UnionFindDecoder:
             return pred, tuple(int(x) for x in cnt)
         finally:
             hp.uf_destroy(h)
+            for b in bufs:
+                b.free()
+
+
+class UnionFindWindow(NamedTuple):
+    """One window of a :class:`WindowedUnionFindDecoder` (module docstring): the columns ``[lo, hi)``, the window graph, its
+    caps (uint8, 2 everywhere without weights), per local edge the global edge it is (-1 for a purely virtual edge to the open
+    future boundary) and whether it is committed."""
+
+    lo: int
+    hi: int
+    graph: DecodingGraph
+    caps: np.ndarray
+    global_edge: np.ndarray
+    committed: np.ndarray
+
+
+class WindowedUnionFindDecoder:
+    """Sliding-window union-find decoding of a :class:`DecodingGraph` without heralds (module docstring): windows of ``window``
+    detector columns that advance by ``commit`` columns, each decoded by the rule of :class:`UnionFindDecoder`; only the flips
+    of committed edges are kept and the defects they leave go to the next window.  The per-shot state on the device is that of
+    one window, so the graph may have int32 sizes (``DecodingGraph(..., limit=None)``).  ``edge_caps`` as in
+    :class:`UnionFindDecoder`.  ``decode`` / ``missed`` / ``predictions`` / ``growth_rounds`` have its signatures and decode each
+    distinct row once; with ``window >= num_detectors`` there is one window and every number is :class:`UnionFindDecoder`'s."""
+
+    def __init__(self, graph: DecodingGraph, commit: int, window: int, num_observables: int | None = None, edge_caps=None):
+        if graph.n_heralds:
+            raise NotImplementedError("the windowed decoder takes a graph without heralds")
+        whole = UnionFindDecoder(graph, num_observables, edge_caps)  # (checks the observables and the caps)
+        for name, x in (("commit", commit), ("window", window)):
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                raise ValueError(f"{name} = {x!r}: an int (detector columns)")
+        if commit < 1 or window <= commit:
+            raise ValueError(f"commit = {commit}, window = {window}: 1 <= commit < window expected")
+        self.graph, self._n_obs, self.edge_caps = graph, whole.num_observables, whole.edge_caps
+        self.commit, self.window = int(commit), int(min(window, 0x7FFFFFFF))
+        self._windows = self._build_windows()
+        self._decoders = [UnionFindDecoder(w.graph, self._n_obs, None if self.edge_caps is None else w.caps) for w in self._windows]
+        self._cache: dict = {}         # packed row of detectors -> (prediction, missed, flipped global edges, rounds)
+        self._window_cache: dict = {}  # (window, its packed defects) -> what _decode_one gave
+
+    @classmethod
+    def from_circuit(cls, circuit, commit: int, window: int, weights: str | None = None, resolution: int = 4) -> "WindowedUnionFindDecoder":
+        """Of a :class:`tsim_amd.clifford.CliffordCircuit` with deterministic detectors (or its program text); ``commit`` and
+        ``window`` in detector columns (a round of ``rotated_surface_code_memory(d, ...)`` is ``d * d - 1`` columns), ``weights``
+        and ``resolution`` as in :meth:`UnionFindDecoder.from_circuit`."""
+        if weights not in (None, "probability"):
+            raise ValueError(f'weights = {weights!r}: None or "probability"')
+        if isinstance(circuit, str):
+            from .clifford import CliffordCircuit
+
+            circuit = CliffordCircuit(circuit)
+        form = circuit.compile_faults()
+        graph = DecodingGraph.from_form(form, limit=None)
+        return cls(graph, commit, window, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution))
+
+    # -- the windows -----------------------------------------------------------------------------------------------------
+    def _build_windows(self) -> list:
+        g, C, W = self.graph, self.commit, self.window
+        nd = g.n_nodes - 1
+        K = max(1, -(-(nd - W) // C) + 1)
+        eu, ev = g.edge_u.astype(np.int64), g.edge_v.astype(np.int64)
+        cap = np.full(g.n_edges, 2, np.uint8) if self.edge_caps is None else self.edge_caps
+        hi_of = lambda k: np.where(k == K - 1, nd, k * C + W)  # noqa: E731
+        inner = np.flatnonzero(eu > 0)       # ascending in the column of the lower end, a = eu - 1
+        a, b = eu[inner] - 1, ev[inner] - 1
+        bad = b >= hi_of(np.minimum(a // C, K - 1))
+        if bad.any():
+            e = int(inner[np.flatnonzero(bad)[0]])
+            k = int(min((eu[e] - 1) // C, K - 1))
+            raise ValueError(f"edge {e} = ({int(eu[e])}, {int(ev[e])}): column {int(eu[e]) - 1} is committed in window {k}, which ends before "
+                             f"column {int(ev[e]) - 1} (at {int(hi_of(np.int64(k)))}): the buffer window - commit = {W - C} is too small")
+        outer = np.flatnonzero(eu == 0)      # the boundary edges, ascending in the column ev - 1
+        c = ev[outer] - 1
+        out = []
+        for k in range(K):
+            lo, hi = k * C, int(hi_of(np.int64(k)))
+            n_local = hi - lo + 1
+            last = k == K - 1
+            # the pairs (0, x): the real boundary edges of the window's columns and the edges that leave it for the future
+            o = outer[np.searchsorted(c, lo):np.searchsorted(c, hi)]
+            i = slice(np.searchsorted(a, lo), np.searchsorted(a, hi))
+            ie, ia, ib = inner[i], a[i], b[i]
+            away = ib >= hi
+            b_cap = np.full(n_local, 255, np.uint8)
+            b_edge = np.full(n_local, -1, np.int64)
+            has = np.zeros(n_local, np.bool_)
+            x = ev[o] - lo
+            b_cap[x], b_edge[x], has[x] = cap[o], o, True
+            x = ia[away] - lo + 1
+            np.minimum.at(b_cap, x, cap[ie[away]])
+            has[x] = True
+            x = np.flatnonzero(has)
+            real = b_edge[x] >= 0
+            keep = ie[~away]
+            lu = np.concatenate([np.zeros(len(x), np.int64), eu[keep] - lo])
+            lv = np.concatenate([x, ev[keep] - lo])
+            ge = np.concatenate([b_edge[x], keep])
+            obs = np.where(ge >= 0, g.edge_obs[np.maximum(ge, 0)], np.uint64(0))
+            obs[:len(x)][~real] = 0
+            p = np.where(ge >= 0, g.edge_p[np.maximum(ge, 0)], 0.0)
+            committed = np.ones(len(ge), np.bool_) if last else (lv <= C) | ((lu >= 1) & (lu <= C))
+            out.append(UnionFindWindow(lo, hi, DecodingGraph(n_local, lu, lv, obs, p, limit=None), np.concatenate([b_cap[x], cap[keep]]),
+                                       ge, committed))
+        return out
+
+    def windows(self) -> list:
+        """Per window a :class:`UnionFindWindow`: what the device tables are compared with, and what a reader inspects."""
+        return list(self._windows)
+
+    @property
+    def num_detectors(self) -> int:
+        return self.graph.num_detectors
+
+    @property
+    def num_observables(self) -> int:
+        return self._n_obs
+
+    def info(self) -> dict:
+        return dict(self.graph.info(), n_windows=len(self._windows), max_window_nodes=max(w.graph.n_nodes for w in self._windows),
+                    max_window_edges=max(w.graph.n_edges for w in self._windows))
+
+    # -- the numpy statement ---------------------------------------------------------------------------------------------
+    def _decode_row(self, syndrome: np.ndarray):
+        """One syndrome (bool ``[num_detectors]``): ``(prediction, missed, committed flipped global edges ascending, the most
+        growth rounds of a window)``."""
+        g = self.graph
+        r = syndrome.copy()
+        prediction, flipped, most = 0, [], 0
+        for k, (w, uf) in enumerate(zip(self._windows, self._decoders)):
+            if not r[w.lo:w.hi].any():
+                continue
+            key = (k, np.packbits(r[w.lo:w.hi]).tobytes())
+            if key not in self._window_cache:
+                self._window_cache[key] = uf._decode_one(np.flatnonzero(r[w.lo:w.hi]) + 1)
+            _, miss, local, rounds = self._window_cache[key]
+            most = max(most, rounds)
+            if miss:
+                return 0, True, np.zeros(0, np.int64), most
+            for e in local[w.committed[local]]:
+                ge = int(w.global_edge[e])
+                assert ge >= 0, "a committed edge is a real edge"
+                prediction ^= int(g.edge_obs[ge])
+                if g.edge_u[ge]:
+                    r[g.edge_u[ge] - 1] ^= True
+                r[g.edge_v[ge] - 1] ^= True
+                flipped.append(ge)
+            assert not r[w.lo:min(w.lo + self.commit, w.hi)].any(), "the commit region is not clean"
+        assert not r.any(), "the correction does not reproduce the syndrome"
+        return prediction, False, np.array(sorted(flipped), np.int64), most
+
+    def _decoded(self, dets):
+        """Per row the cache entry of its syndrome (``None`` for a row without defects)."""
+        d = np.asarray(dets, dtype=np.bool_)
+        if d.ndim != 2 or d.shape[1] != self.num_detectors:
+            raise ValueError(f"dets must be [n, {self.num_detectors}], got shape {d.shape}")
+        out = [None] * len(d)
+        rows = np.flatnonzero(d.any(axis=1))
+        if not len(rows):
+            return out
+        uniq, inv = np.unique(_pack(d[rows]), axis=0, return_inverse=True)
+        inv = np.asarray(inv).reshape(-1)
+        entries = []
+        for k in uniq:
+            key = k.tobytes()
+            if key not in self._cache:
+                self._cache[key] = self._decode_row(np.unpackbits(k, bitorder="little", count=self.num_detectors).astype(np.bool_))
+            entries.append(self._cache[key])
+        for r, i in zip(rows, inv):
+            out[r] = entries[i]
+        return out
+
+    def predictions(self, dets) -> np.ndarray:
+        """uint64 ``[n]``: the predicted observable mask of every row (0 for a miss) - what the device kernel writes to ``d_pred``."""
+        return np.array([0 if e is None else e[0] for e in self._decoded(dets)], dtype=np.uint64)
+
+    def decode(self, dets) -> np.ndarray:
+        """bool ``[n, num_observables]``: the predicted observable flips of detector rows bool ``[n, num_detectors]``."""
+        p = self.predictions(dets)
+        return ((p[:, None] >> np.arange(self._n_obs, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.bool_)
+
+    def missed(self, dets) -> np.ndarray:
+        """bool ``[n]``: the rows with a window whose growth stopped with an active cluster left (they predict no flip)."""
+        return np.array([e is not None and e[1] for e in self._decoded(dets)], dtype=np.bool_)
+
+    def flipped_edges(self, dets) -> list:
+        """Per row the committed edges of its correction, as edges of ``graph`` (int64, ascending; empty for a miss)."""
+        return [np.zeros(0, np.int64) if e is None else e[2] for e in self._decoded(dets)]
+
+    def growth_rounds(self, dets) -> np.ndarray:
+        """int64 ``[n]``: per row the most growth rounds any of its windows took."""
+        return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
+
+    # -- the device side -------------------------------------------------------------------------------------------------
+    def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
+                      stream: int = 0):
+        """:meth:`UnionFindDecoder.decode_device`, by one ``tsim_ufw`` handle on ``hp``'s device (the library builds the windows
+        itself), created and destroyed here."""
+        nd = self.num_detectors
+        n_cols = nd + self._n_obs if n_cols is None else int(n_cols)
+        h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps)
+        bufs = []
+        try:
+            pred = np.zeros(int(n), np.uint64)
+            cnt = np.zeros(3, np.uint64)
+            d_pred, d_cnt = hp.malloc(pred.nbytes + 16), hp.malloc(cnt.nbytes + 16)
+            bufs += [d_pred, d_cnt]
+            hp.h2d(d_cnt, cnt)
+            hp.ufw_decode_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, d_pred=d_pred.ptr, d_xor=d_xor,
+                                 d_test=d_test, stream=stream)
+            hp.stream_synchronize(stream)
+            if n:
+                hp.d2h(pred, d_pred)
+            hp.d2h(cnt, d_cnt)
+            return pred, tuple(int(x) for x in cnt)
+        finally:
+            hp.ufw_destroy(h)
             for b in bufs:
                 b.free()

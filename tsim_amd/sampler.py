@@ -1252,7 +1252,8 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
         syndromes from a training run: exact at d = 3, blind beyond d = 5) or a :class:`tsim_amd.decode.UnionFindDecoder`
         (cluster growth on the circuit's decoding graph, ``UnionFindDecoder.from_circuit(circuit)``: no training, any
         distance whose graph fits; ``from_circuit(circuit, weights="probability")`` grows likely edges sooner - fewer decoded
-        errors for about three times the growth rounds).  ``decoded_errors``: kept shots whose observables differ from its prediction;
+        errors for about three times the growth rounds; :class:`tsim_amd.decode.WindowedUnionFindDecoder` decodes a long run
+        window after window where the whole graph does not fit).  ``decoded_errors``: kept shots whose observables differ from its prediction;
         ``decoder_misses``: kept shots for which it has no prediction (an unknown syndrome; a cluster that cannot reach the
         boundary) and predicts no flip.  For a fresh sampler with the same seed and arguments this
         equals ``counts.tally_rows(sample(..., append_observables=True), ...)``, and the sampler's keys stand where that
