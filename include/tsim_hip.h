@@ -674,6 +674,19 @@ int tsim_uf_info(tsim_uf *h, int64_t out[16]);
 int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
                           const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
                           void *stream);
+/* tsim_uf_decode_device with the decoder's soft outputs ("Soft outputs" in the module docstring of tsim_amd/decode.py).
+ * Everything up to d_pred means the same and accumulates the same.  Four values per row, from the state in which growth
+ * ends (a miss included): [0] rounds, [1] full_edges, [2] largest_cluster, [3] correction_weight (0 for a miss); all four are
+ * 0 for a row that is not kept and for a kept row without a defect.  metric (0 .. 3, in that order) is the value that is
+ * binned, into n_bins (2 .. 1024) bins: the bin of x is min(x, n_bins - 1).  d_hist (uint64[2 * n_bins], 8-byte aligned,
+ * required, never zeroed here): [b] ACCUMULATES the kept rows of bin b, [n_bins + b] those of them whose prediction differs
+ * from their observables.  d_soft: NULL, or uint32[4 * n] (16-byte aligned) for the four values of every row.  Every kind
+ * of handle takes it (plain, weighted, heralds); a shot's state in LDS and the limits of tsim_uf_create are unchanged.  A bad
+ * metric or n_bins, or a NULL d_hist, is TSIM_EINVAL before any device call; n == 0 returns 0 without a launch; the
+ * launches count in out[4] of tsim_uf_info. */
+int tsim_uf_decode_soft_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                               const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                               int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream);
 
 /* ---- sliding-window union-find decoding of long runs (count(decoder=WindowedUnionFindDecoder)) -----------------------
  * `global` is a decoding graph as above without heralds, bounded by int32 only; edge_cap as tsim_uf_create_weighted (NULL:

@@ -3,6 +3,7 @@
     python scripts/uf_bench.py                       # the table: per distance, JSON lines
     python scripts/uf_bench.py --circuits d15 --shots 1000000
     python scripts/uf_bench.py --resolution 4        # weighted against unweighted growth: d = 5, 9, 15
+    python scripts/uf_bench.py --soft largest_cluster  # the price of a soft output: d = 5, 9
 
 Per distance the ``method="faults"`` sampler counts ``--shots`` shots per call in batches of 10^6, once without a decoder and
 once with ``decoder=UnionFindDecoder.from_circuit(circuit)``, alternating, each warmed up first; the time is a host clock
@@ -16,6 +17,11 @@ the same ``count()`` call with ``UnionFindDecoder.from_circuit(circuit)`` and wi
 weights="probability", resolution=R)``, alternating; both rates with the spread of the calls, both decoded error counts and
 misses, and per decoder the most growth rounds ``tsim_uf_info`` reports after decoding ``--info-rows`` sampled rows on a
 handle of its own.
+
+``--soft METRIC`` is a leg of its own too (``--circuits`` then defaults to d5,d9): the same ``count()`` call with
+``UnionFindDecoder.from_circuit(circuit)`` and with its ``with_soft_output(METRIC, --bins)``, alternating over the same seeded
+rows (with ``--resolution R`` both are the weighted decoder): both rates, their ratio, the two histograms and the rejection
+curve.  The leg stops when the two calls disagree on a counter or the histograms do not add up to them.
 """
 
 from __future__ import annotations
@@ -96,6 +102,42 @@ def weighted_leg(args) -> None:
             flush=True)
 
 
+def soft_leg(args) -> None:
+    for name in (args.circuits or "d5,d9").split(","):
+        d = int(name[1:])
+        c = memory(d, args.p)
+        plain = (UnionFindDecoder.from_circuit(c) if args.resolution is None
+                 else UnionFindDecoder.from_circuit(c, weights="probability", resolution=args.resolution))
+        decoders = {"plain": plain, "soft": plain.with_soft_output(args.soft, args.bins)}
+        def sampler():  # a fresh one per call: every call counts the same seeded rows
+            return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+        times, last = {m: [] for m in decoders}, {}
+        for m, uf in decoders.items():
+            sampler().count(args.shots, batch_size=10**6, decoder=uf)  # warm-up at the timed size
+        for _ in range(args.reps):
+            for m, uf in decoders.items():
+                s = sampler()
+                t0 = time.perf_counter()
+                last[m] = s.count(args.shots, batch_size=10**6, decoder=uf)
+                times[m].append(time.perf_counter() - t0)
+        a, b = last["plain"], last["soft"]
+        if (a.kept, a.kept_with_observable_flip, a.decoded_errors, a.decoder_misses) != (b.kept, b.kept_with_observable_flip, b.decoded_errors,
+                                                                                         b.decoder_misses):
+            sys.exit("uf_bench: the soft decoder did not count what the plain one counted")
+        if int(b.soft_kept.sum()) != b.kept or int(b.soft_errors.sum()) != b.decoded_errors:
+            sys.exit("uf_bench: the histograms do not add up to the counters")
+        rate = {m: args.shots / statistics.median(t) for m, t in times.items()}
+        accepted, errors = b.rejection_curve()
+        print(json.dumps(dict(
+            case=name, leg="soft", metric=args.soft, bins=args.bins, resolution=args.resolution, p=args.p, shots=args.shots, reps=args.reps,
+            graph=plain.info(), median_s={m: statistics.median(t) for m, t in times.items()}, min_s={m: min(t) for m, t in times.items()},
+            max_s={m: max(t) for m, t in times.items()}, shots_per_s=rate, soft_over_plain=rate["soft"] / rate["plain"], kept=b.kept,
+            raw_flips=b.kept_with_observable_flip, decoded_errors=b.decoded_errors, misses=b.decoder_misses,
+            soft_kept=b.soft_kept.tolist(), soft_errors=b.soft_errors.tolist(), accepted=accepted.tolist(), errors_accepted=errors.tolist())),
+            flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shots", type=int, default=10**7)
@@ -105,10 +147,15 @@ def main() -> None:
     ap.add_argument("--train", type=int, default=10**8)
     ap.add_argument("--resolution", type=int, default=None, help="the leg that runs weighted against unweighted growth")
     ap.add_argument("--info-rows", type=int, default=20000)
+    ap.add_argument("--soft", default=None, metavar="METRIC",
+                    help="the leg that runs a decoder with this soft output against the same decoder without (weighted with --resolution)")
+    ap.add_argument("--bins", type=int, default=64, help="the bins of --soft")
     args = ap.parse_args()
     _lib.load()
     if _lib.device_count() < 1:
         sys.exit("uf_bench: no HIP device - nothing is measured without one")
+    if args.soft is not None:
+        return soft_leg(args)
     if args.resolution is not None:
         return weighted_leg(args)
     for name in (args.circuits or "d3,d5,d7,d11,d15").split(","):

@@ -504,6 +504,23 @@ class HipProgram:
                                                    C.c_void_p(int(d_pred)) if d_pred else None,
                                                    C.c_void_p(stream or self.stream_ptr())), "tsim_uf_decode_device")
 
+    UF_SOFT_METRICS = ("rounds", "full_edges", "largest_cluster", "correction_weight")
+
+    def uf_decode_soft_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, metric,
+                              n_bins: int, d_hist: int, *, d_soft: int = 0, d_pred: int = 0, d_xor: int = 0, d_test: int = 0,
+                              stream: int = 0) -> None:
+        """:meth:`uf_decode_device` with the soft outputs (``tsim_uf_decode_soft_device``): ``metric`` (one of
+        ``UF_SOFT_METRICS``, or its index) is binned into ``n_bins`` bins, the kept rows and the wrong ones among them ACCUMULATE
+        into ``uint64[2 * n_bins]`` at ``d_hist``; ``d_soft``: ``uint32[4 * n]`` (16-byte aligned) for the four values of every row."""
+        m = self.UF_SOFT_METRICS.index(metric) if isinstance(metric, str) else int(metric)
+        _lib.check(self._lib.tsim_uf_decode_soft_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
+                                                        C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
+                                                        int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
+                                                        C.c_void_p(int(d_pred)) if d_pred else None, m, int(n_bins),
+                                                        C.c_void_p(int(d_hist)) if d_hist else None,
+                                                        C.c_void_p(int(d_soft)) if d_soft else None,
+                                                        C.c_void_p(stream or self.stream_ptr())), "tsim_uf_decode_soft_device")
+
     def uf_info(self, handle: int) -> dict:
         out = (C.c_int64 * 16)()
         _lib.check(self._lib.tsim_uf_info(C.c_void_p(handle), out), "tsim_uf_info")

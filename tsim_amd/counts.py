@@ -52,7 +52,11 @@ class ShotCounts:
     descending, ties by the bit-packed (little-endian) pattern bytes ascending; ``pattern_overflow``: kept shots whose
     pattern found no room (``sum(pattern_counts) + pattern_overflow == kept``; the patterns present are exact).
     ``decoded_errors`` / ``decoder_misses`` (``None`` without a decoder): kept shots whose observables differ from the
-    decoder's prediction, and kept shots whose syndrome the decoder does not know (it predicts no flip for them)."""
+    decoder's prediction, and kept shots whose syndrome the decoder does not know (it predicts no flip for them).
+    ``soft_output`` (``None`` unless the decoder is a ``UnionFindDecoder.with_soft_output(metric, bins)``): the metric's name;
+    then ``soft_kept[b]`` (int64 ``[bins]``) are the kept shots whose metric falls into bin ``b = min(value, bins - 1)`` and
+    ``soft_errors[b]`` those of them that count in ``decoded_errors`` (``soft_kept.sum() == kept``,
+    ``soft_errors.sum() == decoded_errors``); :meth:`rejection_curve` sums them up."""
 
     shots: int
     kept: int
@@ -69,6 +73,9 @@ class ShotCounts:
     pattern_overflow: int = 0
     decoded_errors: int | None = None
     decoder_misses: int | None = None
+    soft_output: str | None = None
+    soft_kept: np.ndarray | None = None
+    soft_errors: np.ndarray | None = None
 
     @property
     def detector_counts(self) -> np.ndarray:
@@ -97,7 +104,12 @@ class ShotCounts:
                 and (self.patterns is None or (np.array_equal(self.patterns, other.patterns)
                                                and np.array_equal(self.pattern_counts, other.pattern_counts)))
                 and self.pattern_overflow == other.pattern_overflow
-                and self.decoded_errors == other.decoded_errors and self.decoder_misses == other.decoder_misses)
+                and self.decoded_errors == other.decoded_errors and self.decoder_misses == other.decoder_misses
+                and self.soft_output == other.soft_output
+                and (self.soft_kept is None) == (other.soft_kept is None)
+                and (self.soft_kept is None or np.array_equal(self.soft_kept, other.soft_kept))
+                and (self.soft_errors is None) == (other.soft_errors is None)
+                and (self.soft_errors is None or np.array_equal(self.soft_errors, other.soft_errors)))
 
     def pair_correlations(self) -> np.ndarray:
         """The float64 ``[k, k]`` matrix of the p_ij estimator over ``pair_columns`` (diagonal NaN):
@@ -108,6 +120,14 @@ class ShotCounts:
         if self.kept == 0:
             return np.full(n.shape, np.nan)
         return pair_correlations_from_moments(np.diagonal(n) / self.kept, n / self.kept)
+
+    def rejection_curve(self):
+        """``(accepted int64[bins], errors int64[bins])``: entry ``t`` is what is left when the shots of a bin above ``t`` are
+        discarded - the kept shots of the bins ``0 .. t`` and the decoded errors among them (the running sums of ``soft_kept``
+        and ``soft_errors``; the last entry is ``(kept, decoded_errors)``)."""
+        if self.soft_output is None or self.soft_kept is None or self.soft_errors is None:
+            raise ValueError("no soft output: give count() a UnionFindDecoder.with_soft_output(metric, bins)")
+        return np.cumsum(np.asarray(self.soft_kept, dtype=np.int64)), np.cumsum(np.asarray(self.soft_errors, dtype=np.int64))
 
     __hash__ = None
 
@@ -248,6 +268,8 @@ class _HostTally:
         self.overflow = 0
         self.decoder = decoder
         self.errors = self.misses = 0
+        self.soft = _soft_choice(decoder)   # (metric, bins) of a UnionFindDecoder.with_soft_output, or None
+        self.soft_hist = np.zeros((2, self.soft[1]), dtype=np.int64) if self.soft else None
         self.pc = tuple(pair_columns)
         self.pairs = np.zeros((len(self.pc), len(self.pc)), dtype=np.int64) if self.pc else None
         self.mask = None if postselection_mask is None else np.asarray(postselection_mask, dtype=np.bool_)
@@ -284,8 +306,13 @@ class _HostTally:
                     self.overflow += int(cnt[i])
         if self.decoder is not None and len(rows):
             dets, obs = rows[:, : self.nd], rows[:, self.nd:]
-            self.errors += int((self.decoder.decode(dets) != obs).any(axis=1).sum())
+            wrong = (self.decoder.decode(dets) != obs).any(axis=1)
+            self.errors += int(wrong.sum())
             self.misses += int(self.decoder.missed(dets).sum())
+            if self.soft:
+                kept, errors = self.decoder.soft_bin_counts(dets, wrong)
+                self.soft_hist[0] += kept
+                self.soft_hist[1] += errors
 
     def result(self) -> ShotCounts:
         patterns = pattern_counts = None
@@ -295,7 +322,8 @@ class _HostTally:
             patterns, pattern_counts = ordered_patterns(keys, np.fromiter(self.table.values(), np.int64, len(self.table)), len(self.tc))
         return ShotCounts(self.shots, self.kept, self.kept_obs, self.cols.copy(), self.nd, self.hc, self.hist.copy(), self.pc,
                           None if self.pairs is None else self.pairs.copy(), self.tc, patterns, pattern_counts, self.overflow,
-                          None if self.decoder is None else self.errors, None if self.decoder is None else self.misses)
+                          None if self.decoder is None else self.errors, None if self.decoder is None else self.misses,
+                          *((self.soft[0], self.soft_hist[0].copy(), self.soft_hist[1].copy()) if self.soft else ()))
 
 
 def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_columns=(), pair_columns=(), pattern_columns=(),
@@ -306,7 +334,8 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
     (:func:`check_pattern_columns`): the distinct patterns of the kept rows (``np.unique``) with their counts, in the order
     of :class:`ShotCounts`; ``pattern_capacity`` (default: no limit) admits that many patterns in the order of first
     appearance and counts the rows of the others in ``pattern_overflow``.  ``decoder``: a
-    :class:`tsim_amd.decode.LookupDecoder` or :class:`tsim_amd.decode.UnionFindDecoder` applied to the kept rows."""
+    :class:`tsim_amd.decode.LookupDecoder` or :class:`tsim_amd.decode.UnionFindDecoder` applied to the kept rows; one with a
+    soft output (``with_soft_output``) also fills ``soft_kept`` / ``soft_errors``, from its ``soft_outputs()``."""
     rows = np.asarray(rows, dtype=np.bool_)
     if rows.ndim != 2:
         raise ValueError(f"rows must be 2-D, got shape {rows.shape}")
@@ -321,6 +350,15 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
                    check_decoder(decoder, n_cols, num_detectors))
     t.add(rows)
     return t.result()
+
+
+def _soft_choice(decoder):
+    """``(metric, bins)`` of a :class:`tsim_amd.decode.UnionFindDecoder` that carries a soft output, else ``None``."""
+    from .decode import UnionFindDecoder
+
+    if isinstance(decoder, UnionFindDecoder) and decoder.soft_output is not None:
+        return decoder.soft_output, int(decoder.soft_bins)
+    return None
 
 
 def check_decoder(decoder, n_cols: int, num_detectors: int):
@@ -453,6 +491,8 @@ class _DeviceTally:
         self._uf = None          # the decoder's graph handle (tsim_uf; a UnionFindDecoder)
         self._ufw = None         # the decoder's windows handle (tsim_ufw; a WindowedUnionFindDecoder)
         self.d_decoded = None    # its three counters
+        self.soft = _soft_choice(decoder)   # (metric, bins): the union-find decoder's soft output, binned on the device
+        self.d_soft_hist = None  # its two histograms, uint64[2 * bins]
         try:
             if self.pc:
                 self._pairs = hp.pairs_create(self.n_cols, self.pc)
@@ -470,6 +510,8 @@ class _DeviceTally:
                     self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))
                     hp.rowtab_load(self._lookup, keys, values)
                 self.d_decoded = self._upload(np.zeros(3, dtype=np.uint64))
+                if self.soft:
+                    self.d_soft_hist = self._upload(np.zeros(2 * self.soft[1], dtype=np.uint64))
             self.d_counts = self._upload(np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64))
             self.d_xor = self._upload(self._row(xor_bits)) if xor_bits is not None and np.any(xor_bits) else None
             self.d_test = self._upload(self._row(test_bits)) if test_bits is not None else None
@@ -512,7 +554,10 @@ class _DeviceTally:
             if self._lookup is not None:
                 self.hp.rowtab_decode_device(self._lookup, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
                                              self.d_decoded.ptr, **masks)
-            if self._uf is not None:
+            if self._uf is not None and self.soft:
+                self.hp.uf_decode_soft_device(self._uf, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
+                                              self.d_decoded.ptr, self.soft[0], self.soft[1], self.d_soft_hist.ptr, **masks)
+            elif self._uf is not None:
                 self.hp.uf_decode_device(self._uf, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
                                          self.d_decoded.ptr, **masks)
             if self._ufw is not None:
@@ -538,9 +583,15 @@ class _DeviceTally:
             d = np.zeros(3, dtype=np.uint64)
             self.hp.d2h(d, self.d_decoded)
             errors, misses = int(d[1]), int(d[2])
+        soft = ()
+        if self.soft:
+            hist = np.zeros(2 * self.soft[1], dtype=np.uint64)
+            self.hp.d2h(hist, self.d_soft_hist)
+            hist = hist.astype(np.int64)
+            soft = (self.soft[0], hist[:self.soft[1]].copy(), hist[self.soft[1]:].copy())
         return ShotCounts(out.shots, out.kept, out.kept_with_observable_flip, out.column_counts, out.num_detectors,
                           out.histogram_columns, out.histogram, self.pc, pairs, self.tc, patterns, pattern_counts, overflow,
-                          errors, misses)
+                          errors, misses, *soft)
 
     def release(self) -> None:
         for name in ("_table", "_lookup"):

@@ -239,9 +239,26 @@ extern "C" int tsim_uf_info(tsim_uf *h, int64_t out[16]) {
   return TSIM_OK;
 }
 
-extern "C" int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
-                                     const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
-                                     void *stream) {
+namespace {
+struct SoftOut {  // what tsim_uf_decode_soft_device adds to tsim_uf_decode_device
+  int metric, n_bins;
+  uint64_t *d_hist;
+  uint32_t *d_soft;
+};
+
+template <bool Soft>
+void uf_launch(const ufk::Args &a, unsigned blocks, size_t lds, hipStream_t stream) {
+  if (a.node_det) {
+    if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, true, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+    else hipLaunchKernelGGL((ufk::k_uf<false, true, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+  } else if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, false, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+  else hipLaunchKernelGGL((ufk::k_uf<false, false, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+}
+}  // namespace
+
+// both decode entry points; soft == NULL: tsim_uf_decode_device
+static int uf_decode(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor, const uint8_t *d_test,
+                     int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred, const SoftOut *soft, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "decoder is NULL");
   if (n < 0) return tsim_fail(TSIM_EINVAL, "negative n");
   ufk::Args a = h->a;
@@ -253,6 +270,15 @@ extern "C" int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t 
     return tsim_fail(TSIM_EINVAL, "observable columns %d .. %d of %d (at most 64)", obs_lo, obs_hi, a.n_cols);
   if (!d_counters || reinterpret_cast<uintptr_t>(d_counters) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_counters is NULL or not 8-byte aligned");
   if (reinterpret_cast<uintptr_t>(d_pred) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_pred is not 8-byte aligned");
+  if (soft) {
+    if (soft->metric < 0 || soft->metric > 3) return tsim_fail(TSIM_EINVAL, "metric = %d (0 rounds, 1 full_edges, 2 largest_cluster, 3 correction_weight)", soft->metric);
+    if (soft->n_bins < 2 || soft->n_bins > 1024) return tsim_fail(TSIM_EINVAL, "n_bins = %d (2 .. 1024)", soft->n_bins);
+    if (!soft->d_hist || reinterpret_cast<uintptr_t>(soft->d_hist) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_hist is NULL or not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(soft->d_soft) % 16 != 0) return tsim_fail(TSIM_EINVAL, "d_soft is not 16-byte aligned");
+    a.metric = soft->metric;
+    a.n_bins = soft->n_bins;
+    a.hist = reinterpret_cast<unsigned long long *>(soft->d_hist);
+  }
   if (n == 0) return TSIM_OK;
   UF_TRY(hipSetDevice(h->device));
   a.rb = row_bytes;
@@ -270,13 +296,27 @@ extern "C" int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t 
     a.pred = d_pred ? reinterpret_cast<unsigned long long *>(d_pred) + r0 : nullptr;
     const int64_t tiles = (a.n + 63) / 64;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + a.waves - 1) / a.waves, h->grid));
-    if (a.node_det) {
-      if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((ufk::k_uf<false, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-    } else if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((ufk::k_uf<false, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    if (soft) {
+      a.soft = soft->d_soft ? soft->d_soft + 4 * r0 : nullptr;
+      uf_launch<true>(a, blocks, lds, (hipStream_t)stream);
+    } else {
+      uf_launch<false>(a, blocks, lds, (hipStream_t)stream);
+    }
     UF_TRY(hipGetLastError());
     ++h->launches;
   }
   return TSIM_OK;
+}
+
+extern "C" int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                     const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                     void *stream) {
+  return uf_decode(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, d_pred, nullptr, stream);
+}
+
+extern "C" int tsim_uf_decode_soft_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                          const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                          int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream) {
+  const SoftOut soft{metric, n_bins, d_hist, d_soft};
+  return uf_decode(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, d_pred, &soft, stream);
 }

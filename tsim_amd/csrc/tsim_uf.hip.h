@@ -31,6 +31,13 @@
 // node_det[v - 1]; and before the first round a pre-grow step sets the full bit of every edge listed under a herald whose
 // column is set (a lane per 8-byte word of the row, col_herald[c] -> herald_ptr -> herald_edges), appending a word of `full`
 // to wlist when it was zero: the append rule of the growth.  half and the counters stay zero: visits test `full` first.
+// Soft outputs (k_uf<Weighted, Heralds, true>, tsim_uf_decode_soft_device; "Soft outputs" in the docstring): four numbers of a
+// decoded row, read off the state above when growth ends, miss or not, without a byte of LDS of their own.  rounds: grow()
+// counts them.  full_edges: the popcount of the listed words of `full`.  largest_cluster: lp[] is dead between grow() and
+// forest(), so every end of a full edge adds 1 to lp[label[x]], once, and the largest count is taken.  correction_weight: counted
+// by the lane that flips an edge, in the function handed to peel().  The three per-lane numbers are reduced over the wave in
+// registers.  Of a tile's rows those of bin 0 (every kept row without a defect among them) are counted by ballot into
+// registers and flushed once per wave; the others go to the histogram by global 64-bit adds, one per distinct bin of the tile.
 // Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,6 +77,10 @@ struct Args {
   const int32_t *col_herald;   // [n_det_cols] the herald of a herald column
   const int32_t *herald_ptr;   // [n_heralds + 1]
   const int32_t *herald_edges;
+  // soft outputs (k_uf<., ., true> only)
+  int metric, n_bins;          // 0 rounds 1 full_edges 2 largest_cluster 3 correction_weight; the bin of x is min(x, n_bins - 1)
+  unsigned long long *hist;    // [2 * n_bins] kept rows per bin, then the wrong ones among them
+  uint32_t *soft;              // [4 * n] the four values of every row (16-byte aligned), or NULL
 };
 
 // the layout of one wave's state, shared by the host (sizes, limits) and the kernel
@@ -358,23 +369,71 @@ __device__ __forceinline__ uint64_t fold_flips(uint32_t *words, uint64_t flips) 
   return (uint64_t)words[0] | (uint64_t)words[1] << 32;
 }
 
-// one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform
-template <bool Weighted, bool Heralds>
-__device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds) {
+// the wave's sum / maximum of a value per lane, in every lane (a butterfly in registers)
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += (uint32_t)__shfl_xor((int)x, m, 64);
+  return x;
+}
+// the same for a sum in the high and a maximum in the low 16 bits (the sum stays below 2^16), in one butterfly
+__device__ __forceinline__ uint32_t wave_sum_max(uint32_t x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const uint32_t y = (uint32_t)__shfl_xor((int)x, m, 64);
+    x = ((x >> 16) + (y >> 16)) << 16 | max(x & 0xFFFFu, y & 0xFFFFu);
+  }
+  return x;
+}
+
+// the soft outputs of the state growth has left, miss or not: soft[0] full edges, soft[1] the nodes of the largest cluster
+// (wave-uniform).  The labels are the clusters of the full edges (grow() ends on a round that changed no edge); lp[] is free
+// until forest() fills it.
+// A cluster of more than one node is made of ends of full edges, its root among them, so only those are visited, in two sweeps
+// of the full edges: lp[x] = 0 at every end (and the edges are counted); then the first visit of an end sets bit 31 of lp[x]
+// and adds 1 to lp[label[x]], whose low bits so count the cluster's nodes: the add that completes a cluster reads its size
+// less one, so the largest value any add has read, plus one, is the largest cluster (1 when no edge is full).
+template <class G>
+__device__ __forceinline__ void soft_of_growth(const G &a, const State &st, int lane, uint32_t *soft) {
+  constexpr uint32_t kSeen = 0x80000000u;
+  const int n_words = (int)st.misc[0];
+  uint32_t full = 0, most = 1;  // (both at most 65535: edges, nodes)
+  full_edges(a, st, n_words, lane, [&](int, int u, int v) { st.lp[u] = 0, st.lp[v] = 0, ++full; });
+  wsync();
+  full_edges(a, st, n_words, lane, [&](int, int u, int v) {
+    if (!(atomicOr(&st.lp[u], kSeen) & kSeen)) most = max(most, (atomicAdd(&st.lp[st.label[u]], 1u) & ~kSeen) + 1u);
+    if (!(atomicOr(&st.lp[v], kSeen) & kSeen)) most = max(most, (atomicAdd(&st.lp[st.label[v]], 1u) & ~kSeen) + 1u);
+  });
+  wsync();  // (forest() writes lp[] next)
+  const uint32_t both = wave_sum_max(full << 16 | most);
+  soft[0] = both >> 16;
+  soft[1] = both & 0xFFFFu;
+}
+
+// one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform, and so
+// are, with Soft, soft[0 .. 2]: full edges, largest cluster, correction weight
+template <bool Weighted, bool Heralds, bool Soft>
+__device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds,
+                                                uint32_t *soft) {
   load_defects<Heralds>(a, st, row, lane);
   clear_edges<Weighted>(a, st, lane);
   if constexpr (Heralds) pregrow_heralds(a, st, row, lane);
   *missed = grow<Weighted>(a, st, lane, rounds);
+  if constexpr (Soft) soft_of_growth(a, st, lane, soft), soft[2] = 0;
   if (*missed) return 0;
   forest(a, st, lane);
-  const uint64_t flips = peel(a, st, lane, [&](int e, int, int) { return a.edge_obs[e]; });
+  uint32_t flipped = 0;  // by this lane
+  const uint64_t flips = peel(a, st, lane, [&](int e, int, int) {
+    if constexpr (Soft) ++flipped;
+    return a.edge_obs[e];
+  });
+  if constexpr (Soft) soft[2] = wave_sum(flipped);
   return fold_flips(&st.misc[2], flips);
 }
 
-template <bool Weighted, bool Heralds>
+template <bool Weighted, bool Heralds, bool Soft = false>
 __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
+  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed; with Soft: the kept rows of bin 0
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
   const State st = state_at(a, base);
@@ -382,6 +441,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   __syncthreads();
   uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
   int most_rounds = 0;
+  uint32_t bin0_acc = 0, bin0_wrong_acc = 0;  // (Soft) wave-uniform: the kept rows of bin 0, the wrong ones among them
   const int nd = a.n_nodes - 1;
   const long long tiles = (a.n + 63) >> 6;
   for (long long t = (long long)blockIdx.x * a.waves + wave; t < tiles; t += (long long)gridDim.x * a.waves) {
@@ -394,14 +454,18 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     const uint64_t obs = kept ? row_obs(a, row) : 0;
     uint64_t pred = 0;
     bool missed = false;
+    uint32_t mine[4] = {0, 0, 0, 0};  // (Soft) this lane's row: rounds, full edges, largest cluster, correction weight
     uint64_t work = __builtin_amdgcn_ballot_w64(kept && defects != 0);
     while (work) {
       const int src = __builtin_ctzll(work);
       work &= work - 1;
       bool m;
       int rounds;
-      const uint64_t p = decode_shot<Weighted, Heralds>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds);
+      uint32_t soft[3];
+      const uint64_t p = decode_shot<Weighted, Heralds, Soft>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, soft);
       if (lane == src) pred = p, missed = m;
+      if constexpr (Soft)
+        if (lane == src) mine[0] = (uint32_t)rounds, mine[1] = soft[0], mine[2] = soft[1], mine[3] = soft[2];
       most_rounds = max(most_rounds, rounds);
       ++decoded_acc;
     }
@@ -409,6 +473,24 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
     miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && missed));
     if (a.pred && valid) a.pred[r] = pred;  // (0 for a row that is not kept, and for a miss)
+    if constexpr (Soft) {
+      const uint32_t x = a.metric == 0 ? mine[0] : a.metric == 1 ? mine[1] : a.metric == 2 ? mine[2] : mine[3];
+      const uint32_t bin = min(x, (uint32_t)a.n_bins - 1u);
+      const bool wrong = kept && pred != obs;
+      bin0_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && bin == 0));
+      bin0_wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(wrong && bin == 0));
+      uint64_t todo = __builtin_amdgcn_ballot_w64(kept && bin != 0);
+      while (todo) {  // one add per distinct bin of the tile (and one for its wrong rows)
+        const uint32_t b = (uint32_t)__shfl((int)bin, __builtin_ctzll(todo), 64);
+        const uint64_t same = __builtin_amdgcn_ballot_w64(kept && bin == b), bad = __builtin_amdgcn_ballot_w64(wrong && bin == b);
+        if (lane == 0) {
+          atomicAdd(&a.hist[b], (unsigned long long)__popcll(same));
+          if (bad) atomicAdd(&a.hist[(size_t)a.n_bins + b], (unsigned long long)__popcll(bad));
+        }
+        todo &= ~same;
+      }
+      if (a.soft && valid) reinterpret_cast<uint4 *>(a.soft)[r] = make_uint4(mine[0], mine[1], mine[2], mine[3]);  // (zeros for a row that is not kept)
+    }
   }
   if (lane == 0) {
     if (kept_acc) atomicAdd(&stat[0], kept_acc);
@@ -416,9 +498,15 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     if (miss_acc) atomicAdd(&stat[2], miss_acc);
     if (most_rounds) atomicMax(&a.stats[0], (unsigned long long)most_rounds);
     if (decoded_acc) atomicAdd(&a.stats[1], (unsigned long long)decoded_acc);
+    if constexpr (Soft) {
+      if (bin0_acc) atomicAdd(&stat[3], bin0_acc);
+      if (bin0_wrong_acc) atomicAdd(&a.hist[a.n_bins], (unsigned long long)bin0_wrong_acc);  // (rare: wrong without a defect, or in bin 0)
+    }
   }
   __syncthreads();
   if (threadIdx.x < 3 && stat[threadIdx.x]) atomicAdd(&a.dec[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
+  if constexpr (Soft)
+    if (threadIdx.x == 3 && stat[3]) atomicAdd(&a.hist[0], (unsigned long long)stat[3]);
 }
 
 }  // namespace ufk

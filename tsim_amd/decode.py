@@ -74,6 +74,26 @@ whose column is set, every listed edge starts at ``grown[e] = cap[e]``.  Growth,
 clusters of the pre-grown edges exist in round 1).  A row whose non-herald detectors are all 0 predicts 0 and is not
 decoded, whatever its heralds say.
 
+Soft outputs (:meth:`UnionFindDecoder.soft_outputs`, :meth:`UnionFindDecoder.with_soft_output`; ``tsim_uf_decode_soft_device``).
+Post-selected protocols discard the shots the decoder is least sure of, and cluster growth knows how hard a shot was.  Four
+integers per row, each defined on the state the rule above fixes, so no lane order can change them:
+
+``rounds``             the growth rounds the row took (:meth:`UnionFindDecoder.growth_rounds`);
+``full_edges``         the edges with ``grown[e] == cap[e]`` when growth ends, those pre-grown by heralds included;
+``largest_cluster``    the most nodes in one cluster when growth ends: the clusters are the components under the full edges,
+                       node 0 counts as a node of its cluster and a cluster of one node counts 1;
+``correction_weight``  the edges peeling flips (``len(flipped_edges)``), 0 for a miss.
+
+"When growth ends" includes a miss: the state after the round that changed nothing gives a miss its ``rounds``,
+``full_edges`` and ``largest_cluster``.  All four are 0 for a row that is not kept and for a kept row without a defect (with
+heralds: without a defect on a non-herald detector, whatever its heralds say - such a row is not decoded).  Under
+``bins = B`` the bin of a value ``x`` is ``min(x, B - 1)``.  ``uf.with_soft_output(metric, bins)`` is the same decoder with
+``soft_output = metric`` and ``soft_bins = bins`` (2 .. 1024); given to ``count(decoder=...)`` it fills
+``ShotCounts.soft_kept[b]``, the kept shots of bin ``b``, and ``ShotCounts.soft_errors[b]``, those of them that are decoded
+wrongly (``soft_kept.sum() == kept``, ``soft_errors.sum() == decoded_errors``); :meth:`ShotCounts.rejection_curve` is their
+running sum, the error count against the shots accepted.  A soft output of the windowed decoder (below) is out of scope:
+its windows have no common final state.
+
 Sliding-window decoding of long runs (:class:`WindowedUnionFindDecoder`; ``tsim_ufw_*``, ``csrc/tsim_ufw.hip.h``)
 ---------------------------------------------------------------------------------------------------------------------
 A shot's state of the rule above must fit a block's 64 KiB of LDS (about 7000 nodes) and a :class:`DecodingGraph` has at most
@@ -122,6 +142,8 @@ __all__ = ["LookupDecoder", "DecodingGraph", "UnionFindDecoder", "UnionFindWindo
 
 MAX_GRAPH = 65535  # nodes, and edges: uint16 indices on the device
 MAX_CAP = 14       # of an edge: the device counts grown[e] in 4 bits and may pass the cap by one
+SOFT_OUTPUTS = ("rounds", "full_edges", "largest_cluster", "correction_weight")  # the columns of soft_outputs(), the device's metric 0 .. 3
+MAX_SOFT_BINS = 1024
 
 
 def _graph_limit(limit) -> int:
@@ -472,7 +494,8 @@ class UnionFindDecoder:
                 raise ValueError(f"edge {bad} has cap {int(caps[bad])} (1 .. {MAX_CAP})")
             edge_caps = caps.astype(np.uint8)
         self.graph, self._n_obs, self.edge_caps = graph, n_obs, edge_caps
-        self._cache: dict = {}   # packed row of detectors -> (prediction, missed, flipped edges, rounds)
+        self.soft_output, self.soft_bins = None, None   # the metric count() bins, and into how many bins (with_soft_output)
+        self._cache: dict = {}   # packed row of detectors -> (prediction, missed, flipped edges, rounds, full edges, largest cluster)
 
     @classmethod
     def from_circuit(cls, circuit, weights: str | None = None, resolution: int = 4, heralds: bool = False) -> "UnionFindDecoder":
@@ -489,6 +512,19 @@ class UnionFindDecoder:
         graph = DecodingGraph.from_form(form, heralds=heralds)
         return cls(graph, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution))
 
+    def with_soft_output(self, metric: str, bins: int = 64) -> "UnionFindDecoder":
+        """The same decoder (graph, caps and observables are shared) with ``soft_output = metric``, one of ``"rounds"``,
+        ``"full_edges"``, ``"largest_cluster"`` and ``"correction_weight"``, and ``soft_bins = bins``, an int in 2 .. 1024:
+        ``count(decoder=...)`` then fills ``ShotCounts.soft_kept`` / ``soft_errors`` ("Soft outputs" in the module docstring)."""
+        if metric not in SOFT_OUTPUTS:
+            raise ValueError(f"metric = {metric!r}: one of {', '.join(SOFT_OUTPUTS)}")
+        if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= MAX_SOFT_BINS:
+            raise ValueError(f"bins = {bins!r}: an int in 2 .. {MAX_SOFT_BINS}")
+        out = object.__new__(UnionFindDecoder)
+        out.__dict__.update(self.__dict__)  # (the cache too: what a syndrome decodes to does not depend on the metric)
+        out.soft_output, out.soft_bins = metric, int(bins)
+        return out
+
     @property
     def num_detectors(self) -> int:
         return self.graph.num_detectors
@@ -504,6 +540,10 @@ class UnionFindDecoder:
     def _decode_one(self, defects: np.ndarray, erased_edges=()):
         """One syndrome (the defect NODES, ascending; ``erased_edges`` start fully grown): ``(prediction, missed, flipped edges
         ascending, growth rounds)``."""
+        return self._decode_one_soft(defects, erased_edges)[:4]
+
+    def _decode_one_soft(self, defects: np.ndarray, erased_edges=()):
+        """:meth:`_decode_one`, followed by the full edges and the nodes of the largest cluster when growth ends."""
         g = self.graph
         n, eu, ev = g.n_nodes, g.edge_u, g.edge_v
         defect = np.zeros(n, np.bool_)
@@ -524,8 +564,9 @@ class UnionFindDecoder:
                 break
             new = np.minimum(cap, grown + active[eu] + active[ev]).astype(np.int8)
             if np.array_equal(new, grown):
-                return 0, True, np.zeros(0, np.int64), rounds
+                return 0, True, np.zeros(0, np.int64), rounds, int(f.sum()), int(np.bincount(label).max())
             grown, rounds = new, rounds + 1
+        soft = (int((grown == cap).sum()), int(np.bincount(label).max()))  # (label: the clusters of the full edges)
         # the forest: levels from the roots, the parent edge the smallest-index edge to the level above
         fe = np.flatnonzero(grown == cap)
         fu, fv = eu[fe], ev[fe]
@@ -554,7 +595,7 @@ class UnionFindDecoder:
                 prediction ^= int(g.edge_obs[e])
                 flipped.append(e)
         assert not s[1:].any(), "the correction does not reproduce the syndrome"
-        return prediction, False, np.array(sorted(flipped), np.int64), rounds
+        return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft
 
     def _decoded(self, dets):
         """Per row the cache entry of its detector columns (``None`` for a row without defects, whatever its heralds)."""
@@ -574,8 +615,8 @@ class UnionFindDecoder:
             if key not in self._cache:
                 bits = np.unpackbits(k, bitorder="little", count=self.num_detectors)
                 erased = [g.herald_edges[g.herald_ptr[h]:g.herald_ptr[h + 1]] for h in np.flatnonzero(bits[g.herald_det])]
-                self._cache[key] = self._decode_one(np.flatnonzero(bits[g.node_det]) + 1,
-                                                    np.unique(np.concatenate(erased)) if erased else ())
+                self._cache[key] = self._decode_one_soft(np.flatnonzero(bits[g.node_det]) + 1,
+                                                         np.unique(np.concatenate(erased)) if erased else ())
             entries.append(self._cache[key])
         for r, i in zip(rows, inv):
             out[r] = entries[i]
@@ -603,13 +644,35 @@ class UnionFindDecoder:
         """int64 ``[n]``: the growth rounds every row took."""
         return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
 
+    def soft_outputs(self, dets) -> np.ndarray:
+        """int64 ``[n, 4]``: per row ``rounds``, ``full_edges``, ``largest_cluster`` and ``correction_weight`` ("Soft outputs" in
+        the module docstring); a row without defects is all zero."""
+        out = np.zeros((len(np.asarray(dets)), 4), dtype=np.int64)
+        for r, e in enumerate(self._decoded(dets)):
+            if e is not None:
+                out[r] = e[3], e[4], e[5], len(e[2])
+        return out
+
+    def soft_bin_counts(self, dets, wrong):
+        """``(kept int64[soft_bins], errors int64[soft_bins])`` of kept rows: the rows per bin of ``soft_output``, and those of
+        them that are ``wrong`` (bool ``[n]``) - what the device adds to ``d_hist``."""
+        if self.soft_output is None:
+            raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
+        bins = np.minimum(self.soft_outputs(dets)[:, SOFT_OUTPUTS.index(self.soft_output)], self.soft_bins - 1)
+        return (np.bincount(bins, minlength=self.soft_bins).astype(np.int64),
+                np.bincount(bins[np.asarray(wrong, dtype=np.bool_)], minlength=self.soft_bins).astype(np.int64))
+
     # -- the device side -------------------------------------------------------------------------------------------------
     def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
-                      stream: int = 0):
+                      stream: int = 0, soft: bool = False):
         """``(predictions uint64[n], (kept, wrong, missed))`` for ``n`` bit-packed rows already in HBM (detectors, then
         observables; ``n_cols`` columns, default ``num_detectors + num_observables``; ``d_xor`` / ``d_test``: device masks of
         ``ceil(n_cols / 8)`` bytes) by one ``tsim_uf`` handle on ``hp``'s device, created and destroyed here.  A row that is
-        not kept and a miss predict 0.  Returns when the results are on the host."""
+        not kept and a miss predict 0.  Returns when the results are on the host.  ``soft`` (the decoder of
+        :meth:`with_soft_output`; ``tsim_uf_decode_soft_device``): two more results, the soft outputs of every row as uint32
+        ``[n, 4]`` (zeros for a row that is not kept) and ``(kept int64[soft_bins], errors int64[soft_bins])``."""
+        if soft and self.soft_output is None:
+            raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
         nd = self.num_detectors
         n_cols = nd + self._n_obs if n_cols is None else int(n_cols)
         h = hp.uf_create(self.graph, n_cols, self.edge_caps)
@@ -620,13 +683,28 @@ class UnionFindDecoder:
             d_pred, d_cnt = hp.malloc(pred.nbytes + 16), hp.malloc(cnt.nbytes + 16)
             bufs += [d_pred, d_cnt]
             hp.h2d(d_cnt, cnt)
-            hp.uf_decode_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, d_pred=d_pred.ptr, d_xor=d_xor,
-                                d_test=d_test, stream=stream)
+            if soft:
+                values = np.zeros((int(n), 4), np.uint32)
+                hist = np.zeros(2 * self.soft_bins, np.uint64)
+                d_values, d_hist = hp.malloc(values.nbytes + 16), hp.malloc(hist.nbytes + 16)
+                bufs += [d_values, d_hist]
+                hp.h2d(d_hist, hist)
+                hp.uf_decode_soft_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, self.soft_output, self.soft_bins,
+                                         d_hist.ptr, d_soft=d_values.ptr, d_pred=d_pred.ptr, d_xor=d_xor, d_test=d_test, stream=stream)
+            else:
+                hp.uf_decode_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, d_pred=d_pred.ptr, d_xor=d_xor,
+                                    d_test=d_test, stream=stream)
             hp.stream_synchronize(stream)
             if n:
                 hp.d2h(pred, d_pred)
             hp.d2h(cnt, d_cnt)
-            return pred, tuple(int(x) for x in cnt)
+            if not soft:
+                return pred, tuple(int(x) for x in cnt)
+            if n:
+                hp.d2h(values, d_values)
+            hp.d2h(hist, d_hist)
+            hist = hist.astype(np.int64)
+            return pred, tuple(int(x) for x in cnt), values, (hist[:self.soft_bins].copy(), hist[self.soft_bins:].copy())
         finally:
             hp.uf_destroy(h)
             for b in bufs:

@@ -1255,7 +1255,9 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
         errors for about three times the growth rounds; :class:`tsim_amd.decode.WindowedUnionFindDecoder` decodes a long run
         window after window where the whole graph does not fit).  ``decoded_errors``: kept shots whose observables differ from its prediction;
         ``decoder_misses``: kept shots for which it has no prediction (an unknown syndrome; a cluster that cannot reach the
-        boundary) and predicts no flip.  For a fresh sampler with the same seed and arguments this
+        boundary) and predicts no flip.  A ``UnionFindDecoder.with_soft_output(metric, bins)`` also fills ``soft_kept`` /
+        ``soft_errors``: the kept shots and the decoded errors per bin of the decoder's confidence in the shot
+        (``ShotCounts.rejection_curve()``).  For a fresh sampler with the same seed and arguments this
         equals ``counts.tally_rows(sample(..., append_observables=True), ...)``, and the sampler's keys stand where that
         ``sample()`` would leave them."""
         nd = self._num_detectors
