@@ -689,7 +689,7 @@ int tsim_uf_decode_soft_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int
                                int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream);
 
 /* ---- sliding-window union-find decoding of long runs (count(decoder=WindowedUnionFindDecoder)) -----------------------
- * `global` is a decoding graph as above without heralds, bounded by int32 only; edge_cap as tsim_uf_create_weighted (NULL:
+ * `global` is a decoding graph as above without heralds (with heralds: tsim_ufw_create_heralds below), bounded by int32 only; edge_cap as tsim_uf_create_weighted (NULL:
  * cap 2 everywhere); commit = C >= 1 and window = W > C are in detector columns.  The rule - the windows [k C, k C + W),
  * the validity condition, the window graphs with their open future boundary, merged pairs, local edge order and COMMITTED
  * edges, and a row decoded window after window with the committed flips carried on - is "Sliding-window decoding of long
@@ -702,12 +702,28 @@ int tsim_uf_decode_soft_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int
 typedef struct tsim_ufw tsim_ufw;
 int tsim_ufw_create(int32_t device, const tsim_uf_desc *global, const uint8_t *edge_cap, int32_t commit, int32_t window,
                     tsim_ufw **out);
+/* Sliding windows over a graph with heralds ("Sliding windows with heralds" in the same docstring).  `her` is the struct of
+ * tsim_uf_create_heralds and means the same: a row has her->n_det_cols detector columns, node v sits in column
+ * node_det[v - 1], herald i in column herald_det[i], and global->n_cols >= n_det_cols.  commit and window count NODES (the
+ * non-herald detectors): the windows, the validity condition, the window graphs and the committed edges are those of
+ * tsim_ufw_create over the nodes and edges of `global`; herald columns are never windowed.  In window k herald i lists the
+ * distinct local edges of its global edges that are present there - an edge that leaves the window for the future as the
+ * local boundary pair of its lower end - and in a row whose column herald_det[i] is set after d_xor those local edges start
+ * FULL in that window.  The library builds these lists itself, on the host, with the windows.  A herald is no defect: "has
+ * a defect", of a row and of a window, is taken from the node columns alone.  Everything tsim_ufw_create checks, and
+ * everything tsim_uf_create_heralds checks of `her` (every column in range, node_det strictly ascending, each column a node
+ * or exactly one herald, n_det_cols == n_nodes - 1 + n_heralds, herald_ptr from 0 and never falling, the edge indices), is
+ * checked before any device call (TSIM_EINVAL).  TSIM_ENOTSUP as tsim_ufw_create: heralds take no per-shot LDS, their
+ * tables lie in global memory.  her == NULL is tsim_ufw_create. */
+int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *global, const uint8_t *edge_cap, int32_t commit,
+                            int32_t window, const tsim_uf_heralds *her, tsim_ufw **out);
 void tsim_ufw_destroy(tsim_ufw *h);
 /* out[0] nodes and [1] edges of the global graph, [2] windows, [3] the most nodes and [4] the most edges of a window,
  * [5] LDS bytes per shot, [6] shots (waves) per block, [7] kernel launches so far, [8] the most growth rounds a window
- * took, [9] bytes of device memory, [10] rows decoded in LDS (kept rows with a defect), [11] windows decoded (those with a
- * defect, of such rows), [12] n_cols, [13] blocks of a full grid, [14] the largest cap (0: unweighted); the rest 0.
- * Synchronises the device. */
+ * took, [9] bytes of device memory, [10] rows decoded in LDS (kept rows with a defect on a node column), [11] windows
+ * decoded (those with a defect, of such rows), [12] n_cols, [13] blocks of a full grid, [14] the largest cap (0:
+ * unweighted), [15] heralds (0 for a handle of tsim_ufw_create).  That was the last free slot: the detector columns of a
+ * row are out[0] - 1 + out[15] and have none of their own.  Synchronises the device. */
 int tsim_ufw_info(tsim_ufw *h, int64_t out[16]);
 /* The arguments of tsim_uf_decode_device, with the same meaning: kept / wrong / missed ACCUMULATE into d_counters, a row
  * with a miss in any window is a miss and predicts 0, d_pred is optional. */

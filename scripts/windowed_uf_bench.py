@@ -17,6 +17,11 @@ and a stream synchronise, median of ``--reps``), with what ``tsim_uf_info`` / ``
 
 ``quality``: ``decoded_errors`` of the whole-graph decoder and of the windowed one for each ``--commits`` (rounds) on the same
 ``--quality-shots`` seeded shots of ``--quality-case`` at ``--quality-p``.
+
+``erasure``: the ``--erasure-cases`` with ``after_clifford_depolarization = before_measure_flip_probability =
+--p`` and ``after_clifford_heralded_erasure = --pe``; ``count(--erasure-shots, decoder=...)`` as in ``rate``, of the whole-graph
+decoder with heralds (where it is built and fits), of the windowed decoder with heralds, and of the same windows over heralds
+that list no edge (what ignoring the heralds costs in decoded errors), on the same seeded rows.
 """
 
 from __future__ import annotations
@@ -162,9 +167,67 @@ def quality_leg(args) -> None:
     print(json.dumps(dict(leg="quality", case=args.quality_case, p=args.quality_p, shots=args.quality_shots, graph=g.info(), results=res)), flush=True)
 
 
+def erasure_memory(d: int, rounds: int, p: float, pe: float) -> CliffordCircuit:
+    return CliffordCircuit(circuits.rotated_surface_code_memory(d, rounds, after_clifford_depolarization=p, before_measure_flip_probability=p,
+                                                                after_clifford_heralded_erasure=pe))
+
+
+def erasure_leg(args) -> None:
+    """``count(--erasure-shots, decoder=...)`` on the same seeded rows of the heralded memory: the whole graph with heralds (where
+    it is built and fits), windows with heralds, and the same windows with the heralds ignored (their decoded errors only)."""
+    for case in args.erasure_cases.split(","):
+        d, rounds, commit = parse(case)
+        c = erasure_memory(d, rounds, args.p, args.pe)
+        t0 = time.perf_counter()
+        form = c.compile_faults()
+        form_s = time.perf_counter() - t0
+        n_obs = int(form.n_out) - int(form.num_detectors)
+        cols = commit * (d * d - 1)
+        t0 = time.perf_counter()
+        g = DecodingGraph.from_form(form, heralds=True, limit=None)
+        decoders, refused = {}, {}
+        try:
+            decoders["whole"] = UnionFindDecoder(DecodingGraph.from_form(form, heralds=True), n_obs)
+        except NotImplementedError as e:
+            refused["whole"] = str(e)
+        decoders["windowed"] = WindowedUnionFindDecoder(g, cols, 2 * cols, n_obs, heralds=True)
+        blind = DecodingGraph(g.n_nodes, g.edge_u, g.edge_v, g.edge_obs, g.edge_p, node_det=g.node_det, herald_det=g.herald_det,
+                              herald_ptr=np.zeros(g.n_heralds + 1, np.int64), herald_edges=[], limit=None)   # the heralds list nothing
+        decoders["windowed_heralds_ignored"] = WindowedUnionFindDecoder(blind, cols, 2 * cols, n_obs, heralds=True)
+        out = dict(leg="erasure", case=case, p=args.p, pe=args.pe, commit_rounds=commit, window_rounds=2 * commit, form_s=form_s,
+                   decoders_s=time.perf_counter() - t0, graph=decoders["windowed"].info(), n_cols=int(form.n_out), not_built=refused,
+                   heralds_per_window=[len(w.heralds) for w in decoders["windowed"].windows()][:8])
+
+        def sampler():  # a fresh one per call: every call counts the same seeded rows
+            return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+        times, last = {}, {}
+        for m, dec in list(decoders.items()):
+            try:
+                last[m] = sampler().count(args.erasure_shots, batch_size=args.batch, decoder=dec)  # warm-up at the timed size
+                times[m] = []
+            except (NotImplementedError, ValueError, MemoryError, _lib.HipBackendError) as e:
+                if "failed:" in str(e):  # (a HIP call failed: that is no refusal, and nothing more is started on the device)
+                    raise
+                refused[m] = f"{type(e).__name__}: {e}"
+        for _ in range(args.reps):
+            for m in times:
+                s = sampler()
+                t0 = time.perf_counter()
+                last[m] = s.count(args.erasure_shots, batch_size=args.batch, decoder=decoders[m])
+                times[m].append(time.perf_counter() - t0)
+        out["count"] = {m: dict(spread(t), shots=args.erasure_shots, shots_per_s=args.erasure_shots / statistics.median(t), kept=last[m].kept,
+                                raw_flips=last[m].kept_with_observable_flip, decoded_errors=last[m].decoded_errors,
+                                misses=last[m].decoder_misses) for m, t in times.items()}
+        print(json.dumps(out), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="rate,quality")
+    ap.add_argument("--legs", default="rate,quality,erasure")
+    ap.add_argument("--erasure-cases", default="d5x20c5,d9x27c9")
+    ap.add_argument("--erasure-shots", type=int, default=200000)
+    ap.add_argument("--pe", type=float, default=1e-2)
     ap.add_argument("--cases", default="d9x27c9,d11x500c11")
     ap.add_argument("--p", type=float, default=1e-3)
     ap.add_argument("--shots", type=int, default=10**6)
@@ -183,6 +246,8 @@ def main() -> None:
         quality_leg(args)
     if "rate" in args.legs.split(","):
         rate_leg(args, HipProgram(synth.kat_h_m()))
+    if "erasure" in args.legs.split(","):
+        erasure_leg(args)
 
 
 if __name__ == "__main__":

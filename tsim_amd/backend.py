@@ -530,14 +530,17 @@ class HipProgram:
         self._lib.tsim_uf_destroy(C.c_void_p(handle))
 
     UFW_INFO = ("n_nodes", "n_edges", "n_windows", "max_window_nodes", "max_window_edges", "lds_bytes_per_shot", "shots_per_block",
-                "launches", "max_rounds", "device_bytes", "rows_decoded", "windows_decoded", "n_cols", "grid_blocks", "max_cap")
+                "launches", "max_rounds", "device_bytes", "rows_decoded", "windows_decoded", "n_cols", "grid_blocks", "max_cap",
+                "n_heralds")
 
-    def ufw_create(self, graph, n_cols: int, commit: int, window: int, caps=None) -> int:
-        """A sliding-window union-find decoder over ``graph`` (a :class:`tsim_amd.decode.DecodingGraph` without heralds, of int32
-        sizes) for rows of ``n_cols`` columns on this program's device (``tsim_ufw_create``, include/tsim_hip.h; the library
-        builds the windows of ``commit`` / ``window`` columns itself): the handle, to be given back to :meth:`ufw_destroy`.
-        ``caps``: ``None``, or an integer per edge in 1 .. 14 for weighted growth."""
-        if len(getattr(graph, "herald_det", ())) > 0:
+    def ufw_create(self, graph, n_cols: int, commit: int, window: int, caps=None, heralds: bool = False) -> int:
+        """A sliding-window union-find decoder over ``graph`` (a :class:`tsim_amd.decode.DecodingGraph` of int32 sizes) for rows
+        of ``n_cols`` columns on this program's device (``tsim_ufw_create``, include/tsim_hip.h; the library builds the windows
+        of ``commit`` / ``window`` columns itself): the handle, to be given back to :meth:`ufw_destroy`.  ``caps``: ``None``, or
+        an integer per edge in 1 .. 14 for weighted growth.  ``heralds``: ``False`` refuses a graph with heralds; with ``True``
+        such a graph goes to ``tsim_ufw_create_heralds`` (the library builds the windows' herald lists too)."""
+        her = len(getattr(graph, "herald_det", ())) > 0
+        if her and not heralds:
             raise NotImplementedError("the windowed decoder takes a graph without heralds")
         eu = np.ascontiguousarray(graph.edge_u, dtype=np.int32)
         ev = np.ascontiguousarray(graph.edge_v, dtype=np.int32)
@@ -550,6 +553,14 @@ class HipProgram:
                 raise ValueError(f"caps: {eu.size} integers in 1 .. 14 expected")
             ec = np.concatenate([ec.astype(np.uint8), np.zeros(1, np.uint8)])  # (never an empty buffer: NULL means unweighted)
         h = C.c_void_p()
+        if her:
+            arrays = [np.ascontiguousarray(np.concatenate([np.asarray(getattr(graph, k), dtype=np.int32), np.zeros(1, np.int32)]))
+                      for k in ("node_det", "herald_det", "herald_ptr", "herald_edges")]  # (never an empty buffer)
+            hd = _lib.UfHeralds(int(graph.num_detectors), len(graph.herald_det), *(a.ctypes.data for a in arrays))
+            _lib.check(self._lib.tsim_ufw_create_heralds(self.device, C.byref(desc), None if ec is None else C.c_void_p(ec.ctypes.data),
+                                                         int(min(commit, 0x7FFFFFFF)), int(min(window, 0x7FFFFFFF)), C.byref(hd), C.byref(h)),
+                       "tsim_ufw_create_heralds")
+            return h.value
         _lib.check(self._lib.tsim_ufw_create(self.device, C.byref(desc), None if ec is None else C.c_void_p(ec.ctypes.data),
                                              int(min(commit, 0x7FFFFFFF)), int(min(window, 0x7FFFFFFF)), C.byref(h)), "tsim_ufw_create")
         return h.value
@@ -566,7 +577,9 @@ class HipProgram:
     def ufw_info(self, handle: int) -> dict:
         out = (C.c_int64 * 16)()
         _lib.check(self._lib.tsim_ufw_info(C.c_void_p(handle), out), "tsim_ufw_info")
-        return {k: int(v) for k, v in zip(self.UFW_INFO, out)}
+        info = {k: int(v) for k, v in zip(self.UFW_INFO, out)}
+        info["n_det_cols"] = info["n_nodes"] - 1 + info["n_heralds"]  # (the 16 slots are taken: a column is a node or one herald)
+        return info
 
     def ufw_destroy(self, handle: int) -> None:
         self._lib.tsim_ufw_destroy(C.c_void_p(handle))

@@ -17,8 +17,9 @@ caller owns (``m2d`` output, ``sample_steps_device`` rows).
 exact count (the row table, ``tsim_rowtab_*``, ``csrc/tsim_rowtab.hip.h``) - what ``np.unique(sample(), axis=0)`` gives
 without the rows crossing PCIe.  ``decoder`` (:class:`tsim_amd.decode.LookupDecoder`, a table of syndromes, or
 :class:`tsim_amd.decode.UnionFindDecoder`, cluster growth on the circuit's decoding graph, ``tsim_uf_*``, or
-:class:`tsim_amd.decode.WindowedUnionFindDecoder`, the same window after window for long runs, ``tsim_ufw_*``) is applied to
-every kept shot where it lies, and the wrong predictions are counted.
+:class:`tsim_amd.decode.WindowedUnionFindDecoder`, the same window after window for long runs, ``tsim_ufw_*``, with heralded
+erasures too when the decoder has ``heralds=True``) is applied to every kept shot where it lies, and the wrong predictions are
+counted.
 """
 
 from __future__ import annotations
@@ -504,7 +505,8 @@ class _DeviceTally:
                 if isinstance(decoder, UnionFindDecoder):
                     self._uf = hp.uf_create(decoder.graph, self.n_cols, decoder.edge_caps)
                 elif isinstance(decoder, WindowedUnionFindDecoder):
-                    self._ufw = hp.ufw_create(decoder.graph, self.n_cols, decoder.commit, decoder.window, decoder.edge_caps)
+                    self._ufw = hp.ufw_create(decoder.graph, self.n_cols, decoder.commit, decoder.window, decoder.edge_caps,
+                                              heralds=decoder.heralds)
                 else:
                     keys, values = decoder.table()
                     self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))

@@ -1,7 +1,8 @@
 // tsim_ufw.hip - sliding-window union-find decoding over bit-packed device rows (tsim_ufw_*): a handle of its own, bound to
 // one device.  tsim_ufw_create builds the windows of the global decoding graph on the host, by the rule in the module
 // docstring of tsim_amd/decode.py ("Sliding-window decoding of long runs") - a second statement of that construction,
-// independent of the numpy one - and holds their tables; the kernel is csrc/tsim_ufw.hip.h.
+// independent of the numpy one - and holds their tables; the kernel is csrc/tsim_ufw.hip.h.  tsim_ufw_create_heralds takes a
+// graph with heralds and builds, with the windows, every window's herald lists ("Sliding windows with heralds" there).
 #include "../../include/tsim_hip.h"
 #include "tsim_ufw.hip.h"
 
@@ -9,6 +10,7 @@
 
 #include <algorithm>
 #include <new>
+#include <utility>
 #include <vector>
 
 int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -31,6 +33,16 @@ struct Tables {
   std::vector<uint8_t> cap;
   std::vector<uint16_t> adj;
   int max_nodes = 0, max_edges = 0, max_w32 = 1, max_w_cnt = 0;
+  // heralds: per window the heralds with a local edge there, one CSR over the concatenation, the local edges
+  std::vector<int32_t> win_herald;
+  std::vector<uint32_t> win_her_ptr;
+  std::vector<uint16_t> win_her_edges;
+};
+
+// the heralds that list a global edge: the transpose of the heralds' CSR (built once, read per window)
+struct EdgeHeralds {
+  std::vector<int64_t> ptr;  // [n_edges + 1]
+  std::vector<int32_t> her;
 };
 }  // namespace
 
@@ -42,17 +54,23 @@ struct tsim_ufw {
   int64_t launches = 0, bytes = 0;
   void *d_desc = nullptr, *d_uv = nullptr, *d_obs = nullptr, *d_cap = nullptr, *d_adj_ptr = nullptr, *d_adj = nullptr, *d_commit = nullptr,
        *d_stats = nullptr;
+  int n_heralds = 0;
+  void *d_node_det = nullptr, *d_herald_det = nullptr, *d_dmask = nullptr, *d_win_herald = nullptr, *d_win_her_ptr = nullptr,
+       *d_win_her_edges = nullptr;  // heralds only
 };
 
 static void ufw_release(tsim_ufw *h) {
   if (h->device >= 0) (void)hipSetDevice(h->device);
-  for (void *p : {h->d_desc, h->d_uv, h->d_obs, h->d_cap, h->d_adj_ptr, h->d_adj, h->d_commit, h->d_stats})
+  for (void *p : {h->d_desc, h->d_uv, h->d_obs, h->d_cap, h->d_adj_ptr, h->d_adj, h->d_commit, h->d_stats, h->d_node_det, h->d_herald_det,
+                  h->d_dmask, h->d_win_herald, h->d_win_her_ptr, h->d_win_her_edges})
     if (p) (void)hipFree(p);
 }
 
 // The windows of the graph (checked by the caller: u < v inside the nodes, pairs strictly ascending) with `commit` = C and
-// `window` = W columns.  0, or an error code after tsim_fail.
-static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t C, int64_t W, Tables *t) {
+// `window` = W columns.  0, or an error code after tsim_fail.  `eh` (NULL: a graph without heralds): the heralds of every global
+// edge, for the windows' herald lists - per window and herald the distinct local edges loc_k(e) of the herald's edges that are
+// present there ("Sliding windows with heralds" in the docstring).
+static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t C, int64_t W, const EdgeHeralds *eh, Tables *t) {
   const int64_t nd = (int64_t)g->n_nodes - 1, E = g->n_edges;
   const int64_t K = nd <= W ? 1 : (nd - W + C - 1) / C + 1;  // the smallest K >= 1 with (K - 1) C + W >= nd
   auto hi_of = [&](int64_t k) { return k == K - 1 ? nd : k * C + W; };
@@ -79,6 +97,8 @@ static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t
   std::vector<int32_t> b_edge(n_max);                // the real boundary edge
   std::vector<int32_t> kept;                         // the window's edges between two of its columns
   std::vector<uint32_t> lu, lv, at;
+  std::vector<int32_t> b_index(eh ? n_max : 0);      // (heralds) per local node x the local edge that is the pair (0, x)
+  std::vector<std::pair<int32_t, int32_t>> listed;   // (heralds) (herald, local edge) of the window
   size_t po = 0, pi = 0;
   for (int64_t k = 0; k < K; ++k) {
     const int64_t lo = k * C, hi = hi_of(k);
@@ -110,6 +130,7 @@ static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t
     d.off_commit = (int32_t)t->commit.size();
     for (int x = 1; x < N; ++x)
       if (b_kind[x]) {
+        if (eh) b_index[x] = (int32_t)lu.size();
         lu.push_back(0), lv.push_back((uint32_t)x);
         t->obs.push_back(b_kind[x] == 2 ? g->edge_obs[b_edge[x]] : 0);
         t->cap.push_back(b_cap[x]);
@@ -123,6 +144,34 @@ static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t
     if (n_e > (size_t)kMaxWindow)
       return tsim_fail(TSIM_ENOTSUP, "window %lld has %zu edges (at most %d: indices are uint16)", (long long)k, n_e, kMaxWindow);
     d.n_edges = (int32_t)n_e;
+    if (eh) {  // the herald lists: every global edge that is present, under its local edge, for each herald that lists it
+      listed.clear();
+      auto list = [&](int32_t e, int32_t local) {
+        for (int64_t q = eh->ptr[e]; q < eh->ptr[e + 1]; ++q) listed.emplace_back(eh->her[q], local);
+      };
+      for (size_t i = po; i < outer.size() && g->edge_v[outer[i]] - 1 < hi; ++i) list(outer[i], b_index[g->edge_v[outer[i]] - lo]);
+      int32_t next_kept = (int32_t)(n_e - kept.size());  // (the kept edges follow the boundary pairs, in their order)
+      for (size_t i = pi; i < inner.size() && g->edge_u[inner[i]] - 1 < hi; ++i) {
+        const int32_t e = inner[i];
+        if (g->edge_v[e] - 1 < hi) list(e, next_kept++);
+        else list(e, b_index[g->edge_u[e] - lo]);  // as the open future boundary of its lower end
+      }
+      std::sort(listed.begin(), listed.end());
+      listed.erase(std::unique(listed.begin(), listed.end()), listed.end());
+      d.off_her = (int32_t)t->win_herald.size();
+      for (size_t i = 0; i < listed.size(); ++i) {
+        if (listed[i].second < 0 || (size_t)listed[i].second >= n_e)
+          return tsim_fail(TSIM_EINVAL, "window %lld: a herald's local edge %d leaves its %zu edges", (long long)k, listed[i].second, n_e);
+        if (i == 0 || listed[i].first != listed[i - 1].first) {
+          t->win_herald.push_back(listed[i].first);
+          t->win_her_ptr.push_back((uint32_t)t->win_her_edges.size());
+        }
+        t->win_her_edges.push_back((uint16_t)listed[i].second);
+      }
+      d.n_her = (int32_t)(t->win_herald.size() - (size_t)d.off_her);
+      if ((int64_t)t->win_herald.size() > kMaxTable || (int64_t)t->win_her_edges.size() > kMaxTable)
+        return tsim_fail(TSIM_ENOTSUP, "the windows' herald lists pass 2^31 entries at window %lld of %lld", (long long)k, (long long)K);
+    }
     d.w32 = std::max(1, ((int)n_e + 31) / 32);
     d.w_cnt = edge_cap ? std::max(1, ((int)n_e + 7) / 8) : 0;
     t->commit.resize(t->commit.size() + d.w32, 0);
@@ -146,11 +195,17 @@ static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t
     if ((int64_t)t->adj.size() > kMaxTable || (int64_t)t->adj_ptr.size() > kMaxTable)
       return tsim_fail(TSIM_ENOTSUP, "the windows' tables pass 2^31 entries at window %lld of %lld", (long long)k, (long long)K);
   }
+  if (eh) t->win_her_ptr.push_back((uint32_t)t->win_her_edges.size());  // (one CSR over all windows: the end of the last list)
   return TSIM_OK;
 }
 
 extern "C" int tsim_ufw_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, int32_t commit, int32_t window,
                                tsim_ufw **out) {
+  return tsim_ufw_create_heralds(device, desc, edge_cap, commit, window, nullptr, out);
+}
+
+extern "C" int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, int32_t commit, int32_t window,
+                                       const tsim_uf_heralds *her, tsim_ufw **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
   *out = nullptr;
   if (!desc) return tsim_fail(TSIM_EINVAL, "desc is NULL");
@@ -158,7 +213,10 @@ extern "C" int tsim_ufw_create(int32_t device, const tsim_uf_desc *desc, const u
   if (N < 2) return tsim_fail(TSIM_EINVAL, "n_nodes = %d (the boundary and at least one detector)", N);
   if (E < 0) return tsim_fail(TSIM_EINVAL, "n_edges = %d", E);
   if (commit < 1 || window <= commit) return tsim_fail(TSIM_EINVAL, "commit = %d, window = %d: 1 <= commit < window expected", commit, window);
-  if (desc->n_cols < N - 1 || desc->n_cols > (1 << 30)) return tsim_fail(TSIM_EINVAL, "n_cols = %d for %d detectors (up to 2^30)", desc->n_cols, N - 1);
+  const long long n_det = her ? (long long)N - 1 + her->n_heralds : N - 1;  // detector columns of a row
+  if (her && (her->n_heralds < 0 || her->n_det_cols != n_det))
+    return tsim_fail(TSIM_EINVAL, "n_det_cols = %d for %d nodes and %d heralds (nodes - 1 + heralds expected)", her->n_det_cols, N, her->n_heralds);
+  if (desc->n_cols < n_det || desc->n_cols > (1 << 30)) return tsim_fail(TSIM_EINVAL, "n_cols = %d for %lld detectors (up to 2^30)", desc->n_cols, n_det);
   if (E > 0 && (!desc->edge_u || !desc->edge_v || !desc->edge_obs)) return tsim_fail(TSIM_EINVAL, "an edge array is NULL");
   for (int e = 0; e < E; ++e) {
     const int32_t u = desc->edge_u[e], v = desc->edge_v[e];
@@ -174,8 +232,46 @@ extern "C" int tsim_ufw_create(int32_t device, const tsim_uf_desc *desc, const u
         return tsim_fail(TSIM_EINVAL, "edge %d has cap %d (1 .. %d: a 4-bit counter that may overshoot by one)", e, edge_cap[e], ufk::kMaxCap);
       max_cap = std::max<int>(max_cap, edge_cap[e]);
     }
+  // the heralds: every column a node or one herald, the lists inside the edges (the checks of tsim_uf_create_heralds)
+  const int H = her ? her->n_heralds : 0, mask_bytes = (desc->n_cols + 7) / 8;
+  std::vector<uint8_t> dmask;
+  EdgeHeralds eh;
+  if (her) {
+    if (!her->node_det || !her->herald_ptr || (H > 0 && !her->herald_det)) return tsim_fail(TSIM_EINVAL, "a herald array is NULL");
+    dmask.assign((size_t)mask_bytes, 0);
+    std::vector<uint8_t> hmask((size_t)mask_bytes, 0);
+    for (int v = 0; v < N - 1; ++v) {
+      const int32_t c = her->node_det[v];
+      if (c < 0 || c >= n_det) return tsim_fail(TSIM_EINVAL, "node_det[%d] = %d leaves the columns 0 .. %lld", v, c, n_det - 1);
+      if (v > 0 && her->node_det[v - 1] >= c) return tsim_fail(TSIM_EINVAL, "node_det[%d] = %d: the columns of the nodes must be strictly ascending", v, c);
+      dmask[c >> 3] |= (uint8_t)(1u << (c & 7));
+    }
+    for (int i = 0; i < H; ++i) {
+      const int32_t c = her->herald_det[i];
+      if (c < 0 || c >= n_det) return tsim_fail(TSIM_EINVAL, "herald_det[%d] = %d leaves the columns 0 .. %lld", i, c, n_det - 1);
+      if ((dmask[c >> 3] | hmask[c >> 3]) >> (c & 7) & 1)
+        return tsim_fail(TSIM_EINVAL, "column %d is named twice (a column is a node or one herald)", c);
+      hmask[c >> 3] |= (uint8_t)(1u << (c & 7));
+    }
+    if (her->herald_ptr[0] != 0) return tsim_fail(TSIM_EINVAL, "herald_ptr[0] = %d", her->herald_ptr[0]);
+    for (int i = 0; i < H; ++i)
+      if (her->herald_ptr[i + 1] < her->herald_ptr[i])
+        return tsim_fail(TSIM_EINVAL, "herald_ptr[%d] = %d after %d: it must not fall", i + 1, her->herald_ptr[i + 1], her->herald_ptr[i]);
+    const int n_listed = her->herald_ptr[H];
+    if (n_listed > 0 && !her->herald_edges) return tsim_fail(TSIM_EINVAL, "herald_edges is NULL");
+    for (int k = 0; k < n_listed; ++k)
+      if (her->herald_edges[k] < 0 || her->herald_edges[k] >= E)
+        return tsim_fail(TSIM_EINVAL, "herald_edges[%d] = %d of %d edges", k, her->herald_edges[k], E);
+    eh.ptr.assign((size_t)E + 1, 0);
+    for (int k = 0; k < n_listed; ++k) ++eh.ptr[her->herald_edges[k] + 1];
+    for (int e = 0; e < E; ++e) eh.ptr[e + 1] += eh.ptr[e];
+    eh.her.resize((size_t)n_listed);
+    std::vector<int64_t> at(eh.ptr.begin(), eh.ptr.end() - 1);
+    for (int i = 0; i < H; ++i)
+      for (int k = her->herald_ptr[i]; k < her->herald_ptr[i + 1]; ++k) eh.her[at[her->herald_edges[k]]++] = i;
+  }
   Tables t;
-  if (const int rc = build_windows(desc, edge_cap, commit, window, &t)) return rc;
+  if (const int rc = build_windows(desc, edge_cap, commit, window, her ? &eh : nullptr, &t)) return rc;
   // the state of a wave: that of the largest window, the carry bitmap, the prediction
   ufk::Args lay{};
   lay.n_nodes = t.max_nodes, lay.w32 = t.max_w32, lay.w_cnt = t.max_w_cnt;
@@ -229,6 +325,19 @@ extern "C" int tsim_ufw_create(int32_t device, const tsim_uf_desc *desc, const u
   upload(&h->d_adj_ptr, t.adj_ptr.data(), t.adj_ptr.size() * 4);
   upload(&h->d_adj, t.adj.data(), t.adj.size() * 2);
   upload(&h->d_commit, t.commit.data(), t.commit.size() * 4);
+  if (her) {
+    h->n_heralds = H;
+    std::vector<int32_t> herald_det(1, 0);  // (never an empty buffer)
+    if (H) herald_det.assign(her->herald_det, her->herald_det + H);
+    if (t.win_herald.empty()) t.win_herald.push_back(0);
+    if (t.win_her_edges.empty()) t.win_her_edges.push_back(0);
+    upload(&h->d_node_det, her->node_det, (size_t)(N - 1) * 4);
+    upload(&h->d_herald_det, herald_det.data(), herald_det.size() * 4);
+    upload(&h->d_dmask, dmask.data(), dmask.size());
+    upload(&h->d_win_herald, t.win_herald.data(), t.win_herald.size() * 4);
+    upload(&h->d_win_her_ptr, t.win_her_ptr.data(), t.win_her_ptr.size() * 4);
+    upload(&h->d_win_her_edges, t.win_her_edges.data(), t.win_her_edges.size() * 2);
+  }
   const uint64_t zero[4] = {0, 0, 0, 0};
   upload(&h->d_stats, zero, sizeof zero);
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -246,6 +355,12 @@ extern "C" int tsim_ufw_create(int32_t device, const tsim_uf_desc *desc, const u
   a.adj_edge = static_cast<const uint16_t *>(h->d_adj);
   a.commit_bits = static_cast<const uint32_t *>(h->d_commit);
   a.stats = static_cast<unsigned long long *>(h->d_stats);
+  a.node_det = static_cast<const int32_t *>(h->d_node_det);
+  a.dmask = static_cast<const uint8_t *>(h->d_dmask);
+  a.herald_det = static_cast<const int32_t *>(h->d_herald_det);
+  a.win_herald = static_cast<const int32_t *>(h->d_win_herald);
+  a.win_her_ptr = static_cast<const uint32_t *>(h->d_win_her_ptr);
+  a.win_her_edges = static_cast<const uint16_t *>(h->d_win_her_edges);
   h->a = a;
   *out = h;
   return TSIM_OK;
@@ -279,6 +394,7 @@ extern "C" int tsim_ufw_info(tsim_ufw *h, int64_t out[16]) {
   out[12] = h->a.n_cols;
   out[13] = h->grid;
   out[14] = h->max_cap;
+  out[15] = h->n_heralds;
   return TSIM_OK;
 }
 
@@ -313,8 +429,11 @@ extern "C" int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_
     a.pred = d_pred ? reinterpret_cast<unsigned long long *>(d_pred) + r0 : nullptr;
     const int64_t tiles = (a.n + 63) / 64;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + a.waves - 1) / a.waves, h->grid));
-    if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((ufwk::k_ufw<false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    if (a.node_det) {
+      if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL((ufwk::k_ufw<false, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    } else if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((ufwk::k_ufw<false, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
     UFW_TRY(hipGetLastError());
     ++h->launches;
   }

@@ -19,6 +19,15 @@
 //                           [lo, lo + commit) are cleared (a lane per word, plain stores: nobody else touches carry then),
 //                           and these are the slots the columns [hi, hi + commit) of the next window use, since P >= window
 //   pred    uint32[2]       the prediction so far: the XOR of the masks of the committed flips
+// Heralded erasures (k_ufw<Weighted, true>, tsim_ufw_create_heralds; "Sliding windows with heralds" in the docstring): herald
+// detectors are no nodes and are never windowed.  Pass 1 takes "has a defect" from the columns of dmask (the nodes'), so a row
+// with heralds only is finished there.  Local node v >= 1 of a window reads row column node_det[lo + v - 1]; its carry slot
+// stays that of the node index lo + v - 1.  After clear_edges and before grow a pre-grow step strides over the window's own
+// herald list - win_herald[off_her .. off_her + n_her), the heralds with a local edge in this window, so the cost follows the
+// window, not the row: a lane tests the row bit (after xor) at herald_det[i] and, when it is set, ORs the full bit of the
+// local edges win_her_edges[win_her_ptr[j] .. win_her_ptr[j + 1]), appending a word of `full` to wlist when it was zero (the
+// idiom of ufk::pregrow_heralds; half and the counters stay zero: visits test `full` first).  The three tables are in global
+// memory, concatenated over the windows like the others; win_her_ptr is one CSR over the concatenation, absolute.
 // Every index into LDS and into the tables comes from tables tsim_ufw_create has built and checked; every address is formed
 // in 64 bits.
 #pragma once
@@ -29,7 +38,8 @@ namespace ufwk {
 struct WinDesc {
   int32_t lo, n_nodes, n_edges, w32;                 // the first column; local nodes and edges; words of an edge bitmap
   int32_t w_cnt, off_edge, off_ptr, off_adj;         // words of the 4-bit counters (0: unweighted); where its tables begin
-  int32_t off_commit, last, pad0, pad1;              // last: the run's last window (no slots to clear after it)
+  int32_t off_commit, last, off_her, n_her;          // last: the run's last window (no slots to clear after it); where its
+                                                     // heralds begin in win_herald / win_her_ptr, and how many (0 without heralds)
 };
 
 // what the steps of tsim_uf.hip.h read of a graph: one window's
@@ -63,6 +73,13 @@ struct Args {
   unsigned long long *dec;    // [0] kept [1] wrong [2] missed
   unsigned long long *pred;   // [n] or NULL
   unsigned long long *stats;  // [0] most growth rounds of a window [1] rows decoded in LDS [2] windows decoded
+  // heralded erasures (NULL on a handle without heralds)
+  const int32_t *node_det;    // [nd] the row column of node v at v - 1
+  const uint8_t *dmask;       // a row of ceil(n_cols / 8) bytes: the columns of the nodes
+  const int32_t *herald_det;  // [n_heralds] the row column of a herald
+  const int32_t *win_herald;  // per window (WinDesc.off_her, n_her) the heralds with a local edge there
+  const uint32_t *win_her_ptr;     // [entries of win_herald + 1] where the list of entry j begins in win_her_edges
+  const uint16_t *win_her_edges;   // LOCAL edges
 };
 
 // the bits j of word w of a bitmap whose index 32 w + j lies in [s, e)
@@ -72,9 +89,25 @@ __host__ __device__ inline uint32_t bits_between(int w, int s, int e) {
   return (hi == 32 ? ~0u : (1u << hi) - 1u) & ~((1u << lo) - 1u);
 }
 
+// the local edges of the window's heralds that are set in the row start full
+__device__ __forceinline__ void pregrow_window(const Args &a, const WinDesc &d, const ufk::State &st, const uint8_t *row, int lane) {
+  for (int j = lane; j < d.n_her; j += 64) {
+    const long long at = (long long)d.off_her + j;
+    const int c = a.herald_det[a.win_herald[at]];
+    uint32_t byte = row[c >> 3];
+    if (a.xr) byte ^= a.xr[c >> 3];
+    if (!((byte >> (c & 7)) & 1u)) continue;
+    for (uint32_t q = a.win_her_ptr[at]; q < a.win_her_ptr[at + 1]; ++q) {
+      const int e = a.win_her_edges[q], fw = e >> 5;
+      if (atomicOr(&st.full[fw], 1u << (e & 31)) == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)fw;  // (each word once)
+    }
+  }
+  ufk::wsync();
+}
+
 // one kept row with a defect, by the whole wave, window after window: the prediction (0 for a miss); *missed, *rounds (the most
 // of a window) and *windows (those decoded) are wave-uniform
-template <bool Weighted>
+template <bool Weighted, bool Heralds>
 __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &st, uint32_t *carry, uint32_t *pred, const uint8_t *row,
                                                int lane, bool *missed, int *rounds, int *windows) {
   using ufk::wsync;
@@ -90,7 +123,9 @@ __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &
     for (int v = lane; v < N; v += 64) {
       uint32_t bit = 0;
       if (v) {
-        const int c = d.lo + v - 1, slot = c & (P - 1);
+        int c = d.lo + v - 1;
+        const int slot = c & (P - 1);
+        if constexpr (Heralds) c = a.node_det[c];
         uint32_t byte = row[c >> 3];
         if (a.xr) byte ^= a.xr[c >> 3];
         bit = ((byte >> (c & 7)) ^ (carry[slot >> 5] >> (slot & 31))) & 1u;
@@ -109,6 +144,7 @@ __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &
       w.adj_edge = a.adj_edge + d.off_adj;
       const uint32_t *committed = a.commit_bits + d.off_commit;
       ufk::clear_edges<Weighted>(w, st, lane);
+      if constexpr (Heralds) pregrow_window(a, d, st, row, lane);
       int r;
       const bool miss = ufk::grow<Weighted>(w, st, lane, &r);
       *rounds = max(*rounds, r);
@@ -143,7 +179,7 @@ __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &
   return (uint64_t)pred[0] | (uint64_t)pred[1] << 32;
 }
 
-template <bool Weighted>
+template <bool Weighted, bool Heralds>
 __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
@@ -162,7 +198,7 @@ __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
     const bool valid = r < a.n;
     const uint8_t *row = a.rows + (valid ? r : 0) * a.rb;
     uint64_t fail, defects;
-    ufk::scan_row(a, row, valid, nullptr, a.nd, &fail, &defects);
+    ufk::scan_row(a, row, valid, Heralds ? a.dmask : nullptr, a.nd, &fail, &defects);
     const bool kept = valid && fail == 0;
     const uint64_t obs = kept ? ufk::row_obs(a, row) : 0;
     uint64_t pred = 0;
@@ -173,7 +209,7 @@ __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
       work &= work - 1;
       bool m;
       int rounds, windows;
-      const uint64_t p = decode_row<Weighted>(a, st, carry, predw, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, &windows);
+      const uint64_t p = decode_row<Weighted, Heralds>(a, st, carry, predw, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, &windows);
       if (lane == src) pred = p, missed = m;
       most_rounds = max(most_rounds, rounds);
       windows_acc += (unsigned)windows;

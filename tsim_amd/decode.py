@@ -102,8 +102,9 @@ the next columns, commits only the corrections of its oldest part and hands the 
 state is that of one window whatever the length of the run, and the graph may have int32 sizes
 (``DecodingGraph(..., limit=None)``, ``from_form(form, limit=None)``; the default limit is the one above).
 
-The decoder takes a graph without heralds (node ``v >= 1`` is detector column ``v - 1``, ``nd = n_nodes - 1``), optional edge
-caps as above (without caps every cap is 2) and two integers in detector columns, ``commit = C >= 1`` and ``window = W > C``.
+The decoder takes a graph without heralds (node ``v >= 1`` is detector column ``v - 1``, ``nd = n_nodes - 1``; a graph with
+heralds is the section "Sliding windows with heralds" below), optional edge caps as above (without caps every cap is 2) and
+two integers in detector columns, ``commit = C >= 1`` and ``window = W > C``.
 Windowing is by column index, not by coordinates: the detectors of a memory circuit are declared in time order, and a round of
 ``rotated_surface_code_memory(d, ...)`` is ``d * d - 1`` columns.
 
@@ -130,6 +131,35 @@ there makes the row a miss: it predicts 0 and decoding stops.  Otherwise every f
 into the prediction and toggles ``r`` at its non-boundary ends.  After window ``k``, ``r`` is zero on its commit region, after
 the last window everywhere (both asserted in the numpy statement).  ``growth_rounds`` is the most rounds of any window.  With
 ``W >= nd`` there is one window and every number equals :class:`UnionFindDecoder`'s.
+
+Sliding windows with heralds (``WindowedUnionFindDecoder(..., heralds=True)``, ``from_circuit(..., heralds=True)``;
+``tsim_ufw_create_heralds``).  ``heralds=False`` is the default and refuses a graph with heralds, as before.  Let ``g`` be a
+:class:`DecodingGraph` with heralds and ``nd = g.n_nodes - 1``: node ``v >= 1`` is the ``v``-th non-herald detector and sits in
+row column ``g.node_det[v - 1]``.
+
+Windows, validity, the window graphs ``G_k``, merged pairs, the local edge order and the COMMITTED edges are exactly those
+above, applied to the nodes and edges of ``g`` with "column ``c``" read as "node ``c + 1``".  ``commit`` and ``window`` therefore
+count non-herald detectors (a round of the rotated memory is still ``d * d - 1``).  Herald columns are never windowed: the
+whole row is known, so every window sees every herald.
+
+``loc_k(e)``, the local edge of the global edge ``e = (u, v)`` in window ``k``.  For ``u == 0`` it is present iff
+``lo_k <= v - 1 < hi_k``, as the local pair ``(0, v - lo_k)``.  For ``u >= 1``, with ``a = u - 1`` and ``b = v - 1``, it is present
+iff ``lo_k <= a < hi_k``: for ``b < hi_k`` it is the local pair ``(u - lo_k, v - lo_k)``, otherwise the local pair
+``(0, a - lo_k + 1)``, the open future boundary.  Several global edges may share one local edge: the merged pairs.
+
+``L_k(i)``, the list of herald ``i`` in window ``k``: the distinct ``loc_k(e)``, ascending, over the edges ``e`` of
+``g.herald_edges[g.herald_ptr[i]:g.herald_ptr[i + 1]]`` that are present in ``G_k``.  It may be empty; a herald may have
+non-empty lists in several windows; an edge pre-grown towards the future boundary in window ``k`` is pre-grown as itself in
+window ``k + 1``.  :meth:`WindowedUnionFindDecoder.windows` gives, per window, the heralds with a non-empty list and their
+lists as a CSR (``UnionFindWindow.heralds``, ``herald_ptr``, ``herald_edges``).
+
+A row.  ``r[c]`` is the bit of column ``node_det[c]`` and ``H`` the set of heralds whose column ``herald_det[i]`` is set, both
+after the xor mask.  A row with ``r == 0`` predicts 0 and is not decoded, whatever ``H`` is.  For ``k = 0 .. K - 1``: a window with
+``r[lo_k:hi_k] == 0`` is skipped, whatever ``H`` is; otherwise the union-find rule runs on ``G_k`` with the defects
+``r[lo_k:hi_k]``, and every edge of the union of ``L_k(i)`` over ``i`` in ``H`` starts at ``grown = cap``, the local edge's cap.
+Growth, forest, peeling, the committed flips, the carry into ``r`` and a miss are as written above.  With ``W >= nd`` there is
+one window and every number - prediction, miss, flipped edges, growth rounds - equals that of :class:`UnionFindDecoder` over
+``g``.  The rule is the one above plus a fixed set of edges that start full, so it stays independent of any parallel order.
 """
 
 from __future__ import annotations
@@ -714,7 +744,9 @@ class UnionFindDecoder:
 class UnionFindWindow(NamedTuple):
     """One window of a :class:`WindowedUnionFindDecoder` (module docstring): the columns ``[lo, hi)``, the window graph, its
     caps (uint8, 2 everywhere without weights), per local edge the global edge it is (-1 for a purely virtual edge to the open
-    future boundary) and whether it is committed."""
+    future boundary) and whether it is committed.  Of a decoder with ``heralds=True`` also the window's herald lists
+    ("Sliding windows with heralds"): ``heralds`` (int64, ascending) are the heralds ``i`` of the graph whose ``L_k(i)`` is not
+    empty, and ``herald_edges[herald_ptr[j]:herald_ptr[j + 1]]`` (int64, ascending LOCAL edges) is the list of ``heralds[j]``."""
 
     lo: int
     hi: int
@@ -722,19 +754,29 @@ class UnionFindWindow(NamedTuple):
     caps: np.ndarray
     global_edge: np.ndarray
     committed: np.ndarray
+    heralds: np.ndarray | None = None
+    herald_ptr: np.ndarray | None = None
+    herald_edges: np.ndarray | None = None
 
 
 class WindowedUnionFindDecoder:
-    """Sliding-window union-find decoding of a :class:`DecodingGraph` without heralds (module docstring): windows of ``window``
-    detector columns that advance by ``commit`` columns, each decoded by the rule of :class:`UnionFindDecoder`; only the flips
-    of committed edges are kept and the defects they leave go to the next window.  The per-shot state on the device is that of
-    one window, so the graph may have int32 sizes (``DecodingGraph(..., limit=None)``).  ``edge_caps`` as in
-    :class:`UnionFindDecoder`.  ``decode`` / ``missed`` / ``predictions`` / ``growth_rounds`` have its signatures and decode each
-    distinct row once; with ``window >= num_detectors`` there is one window and every number is :class:`UnionFindDecoder`'s."""
+    """Sliding-window union-find decoding of a :class:`DecodingGraph` (module docstring): windows of ``window`` detector columns
+    that advance by ``commit`` columns, each decoded by the rule of :class:`UnionFindDecoder`; only the flips of committed edges
+    are kept and the defects they leave go to the next window.  The per-shot state on the device is that of one window, so the
+    graph may have int32 sizes (``DecodingGraph(..., limit=None)``).  ``edge_caps`` as in :class:`UnionFindDecoder`.
+    ``heralds``: ``False`` takes a graph without heralds only; ``True`` also one with heralds, whose windows are over its
+    non-herald detectors and pre-grow, each, the local edges of the heralds that are set ("Sliding windows with heralds"); it is
+    kept in ``self.heralds``.  ``decode`` / ``missed`` / ``predictions`` / ``growth_rounds`` have :class:`UnionFindDecoder`'s
+    signatures and decode each distinct row once; with ``window >= graph.n_nodes - 1`` there is one window and every number is
+    :class:`UnionFindDecoder`'s."""
 
-    def __init__(self, graph: DecodingGraph, commit: int, window: int, num_observables: int | None = None, edge_caps=None):
-        if graph.n_heralds:
+    def __init__(self, graph: DecodingGraph, commit: int, window: int, num_observables: int | None = None, edge_caps=None,
+                 heralds: bool = False):
+        if not isinstance(heralds, (bool, np.bool_)):
+            raise ValueError(f"heralds = {heralds!r}: a bool")
+        if graph.n_heralds and not heralds:
             raise NotImplementedError("the windowed decoder takes a graph without heralds")
+        self.heralds = bool(heralds)
         whole = UnionFindDecoder(graph, num_observables, edge_caps)  # (checks the observables and the caps)
         for name, x in (("commit", commit), ("window", window)):
             if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
@@ -744,15 +786,19 @@ class WindowedUnionFindDecoder:
         self.graph, self._n_obs, self.edge_caps = graph, whole.num_observables, whole.edge_caps
         self.commit, self.window = int(commit), int(min(window, 0x7FFFFFFF))
         self._windows = self._build_windows()
+        if self.heralds:
+            self._windows = [w._replace(**self._herald_lists(w)) for w in self._windows]
         self._decoders = [UnionFindDecoder(w.graph, self._n_obs, None if self.edge_caps is None else w.caps) for w in self._windows]
         self._cache: dict = {}         # packed row of detectors -> (prediction, missed, flipped global edges, rounds)
-        self._window_cache: dict = {}  # (window, its packed defects) -> what _decode_one gave
+        self._window_cache: dict = {}  # (window, its packed defects, its erased local edges) -> what _decode_one gave
 
     @classmethod
-    def from_circuit(cls, circuit, commit: int, window: int, weights: str | None = None, resolution: int = 4) -> "WindowedUnionFindDecoder":
+    def from_circuit(cls, circuit, commit: int, window: int, weights: str | None = None, resolution: int = 4,
+                     heralds: bool = False) -> "WindowedUnionFindDecoder":
         """Of a :class:`tsim_amd.clifford.CliffordCircuit` with deterministic detectors (or its program text); ``commit`` and
         ``window`` in detector columns (a round of ``rotated_surface_code_memory(d, ...)`` is ``d * d - 1`` columns), ``weights``
-        and ``resolution`` as in :meth:`UnionFindDecoder.from_circuit`."""
+        and ``resolution`` as in :meth:`UnionFindDecoder.from_circuit`.  ``heralds``: the graph is built with heralds
+        (``DecodingGraph.from_form(form, heralds=True, limit=None)``); ``commit`` and ``window`` then count non-herald detectors."""
         if weights not in (None, "probability"):
             raise ValueError(f'weights = {weights!r}: None or "probability"')
         if isinstance(circuit, str):
@@ -760,8 +806,9 @@ class WindowedUnionFindDecoder:
 
             circuit = CliffordCircuit(circuit)
         form = circuit.compile_faults()
-        graph = DecodingGraph.from_form(form, limit=None)
-        return cls(graph, commit, window, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution))
+        graph = DecodingGraph.from_form(form, heralds=True, limit=None) if heralds else DecodingGraph.from_form(form, limit=None)
+        return cls(graph, commit, window, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution),
+                   heralds=heralds)
 
     # -- the windows -----------------------------------------------------------------------------------------------------
     def _build_windows(self) -> list:
@@ -813,6 +860,27 @@ class WindowedUnionFindDecoder:
                                        ge, committed))
         return out
 
+    def _herald_lists(self, w: UnionFindWindow) -> dict:
+        """The herald lists ``L_k(i)`` of window ``w`` ("Sliding windows with heralds"), by ``loc_k`` as the docstring states it
+        and a search of the local pair among the window graph's edges: the three herald fields of :class:`UnionFindWindow`."""
+        g = self.graph
+        e = g.herald_edges.astype(np.int64)
+        i = np.repeat(np.arange(g.n_heralds, dtype=np.int64), np.diff(g.herald_ptr))
+        u, v = g.edge_u[e].astype(np.int64), g.edge_v[e].astype(np.int64)
+        outer = u == 0
+        present = np.where(outer, (v - 1 >= w.lo) & (v - 1 < w.hi), (u - 1 >= w.lo) & (u - 1 < w.hi))
+        away = ~outer & (v - 1 >= w.hi)   # to the open future boundary: the pair (0, a - lo + 1) = (0, u - lo)
+        lu = np.where(outer | away, 0, u - w.lo)[present]
+        lv = np.where(away, u - w.lo, v - w.lo)[present]
+        n = w.graph.n_nodes
+        keys = w.graph.edge_u.astype(np.int64) * n + w.graph.edge_v.astype(np.int64)   # (strictly ascending)
+        loc = np.searchsorted(keys, lu * n + lv)
+        assert (loc < len(keys)).all() and (keys[loc] == lu * n + lv).all(), "an edge that is present has a local edge"
+        pairs = np.unique(i[present] * max(1, len(keys)) + loc)   # (herald, local edge): distinct, ascending
+        hi, le = pairs // max(1, len(keys)), pairs % max(1, len(keys))
+        heralds, counts = np.unique(hi, return_counts=True)
+        return dict(heralds=heralds, herald_ptr=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), herald_edges=le)
+
     def windows(self) -> list:
         """Per window a :class:`UnionFindWindow`: what the device tables are compared with, and what a reader inspects."""
         return list(self._windows)
@@ -830,18 +898,24 @@ class WindowedUnionFindDecoder:
                     max_window_edges=max(w.graph.n_edges for w in self._windows))
 
     # -- the numpy statement ---------------------------------------------------------------------------------------------
-    def _decode_row(self, syndrome: np.ndarray):
-        """One syndrome (bool ``[num_detectors]``): ``(prediction, missed, committed flipped global edges ascending, the most
-        growth rounds of a window)``."""
+    def _decode_row(self, bits: np.ndarray):
+        """One row's detector bits (bool ``[num_detectors]``): ``(prediction, missed, committed flipped global edges ascending,
+        the most growth rounds of a window)``."""
         g = self.graph
-        r = syndrome.copy()
+        r = bits[g.node_det].copy()   # the syndrome, by node (every column without heralds)
+        fired = np.flatnonzero(bits[g.herald_det]) if self.heralds else ()   # the heralds that are set
         prediction, flipped, most = 0, [], 0
         for k, (w, uf) in enumerate(zip(self._windows, self._decoders)):
             if not r[w.lo:w.hi].any():
                 continue
-            key = (k, np.packbits(r[w.lo:w.hi]).tobytes())
+            erased = np.zeros(0, np.int64)   # the union of L_k(i) over the heralds that are set
+            if len(fired):
+                j = np.flatnonzero(np.isin(w.heralds, fired))
+                if len(j):
+                    erased = np.unique(np.concatenate([w.herald_edges[w.herald_ptr[x]:w.herald_ptr[x + 1]] for x in j]))
+            key = (k, np.packbits(r[w.lo:w.hi]).tobytes(), erased.tobytes())
             if key not in self._window_cache:
-                self._window_cache[key] = uf._decode_one(np.flatnonzero(r[w.lo:w.hi]) + 1)
+                self._window_cache[key] = uf._decode_one(np.flatnonzero(r[w.lo:w.hi]) + 1, erased)
             _, miss, local, rounds = self._window_cache[key]
             most = max(most, rounds)
             if miss:
@@ -859,12 +933,12 @@ class WindowedUnionFindDecoder:
         return prediction, False, np.array(sorted(flipped), np.int64), most
 
     def _decoded(self, dets):
-        """Per row the cache entry of its syndrome (``None`` for a row without defects)."""
+        """Per row the cache entry of its detector columns (``None`` for a row without defects, whatever its heralds)."""
         d = np.asarray(dets, dtype=np.bool_)
         if d.ndim != 2 or d.shape[1] != self.num_detectors:
             raise ValueError(f"dets must be [n, {self.num_detectors}], got shape {d.shape}")
         out = [None] * len(d)
-        rows = np.flatnonzero(d.any(axis=1))
+        rows = np.flatnonzero((d[:, self.graph.node_det] if self.graph.n_heralds else d).any(axis=1))
         if not len(rows):
             return out
         uniq, inv = np.unique(_pack(d[rows]), axis=0, return_inverse=True)
@@ -907,7 +981,7 @@ class WindowedUnionFindDecoder:
         itself), created and destroyed here."""
         nd = self.num_detectors
         n_cols = nd + self._n_obs if n_cols is None else int(n_cols)
-        h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps)
+        h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps, heralds=self.heralds)
         bufs = []
         try:
             pred = np.zeros(int(n), np.uint64)
