@@ -158,7 +158,7 @@ def test_create_weighted_refuses_without_a_device():
         else:
             caps = np.asarray(caps, np.uint8)
             rc = lib.tsim_uf_create_weighted(0, C.byref(desc), C.c_void_p(caps.ctypes.data), C.byref(h))
-        msg = lib.tsim_last_error()
+        msg = lib.tsim_last_error() if rc else b""  # (a call that succeeds leaves the text of the last failure)
         if rc == 0:  # (a device is there and the graph is fine: give the handle back)
             lib.tsim_uf_destroy(h)
             h.value = None

@@ -254,6 +254,58 @@ def test_create_heralds_refuses_without_a_device():
         assert rc in (0, -5) or (rc == -22 and b"device 0 of 0" in msg), (kw, rc, msg)
 
 
+def test_both_handles_refuse_a_graph_its_caps_and_its_heralds_alike():
+    """The bad graphs, caps and herald structs of the refusal tests of ``tsim_uf_create`` / ``_weighted`` / ``_heralds``: the
+    whole-graph handle and the windowed one (``commit`` 2 < ``window`` 4) give the same code and the same text, before any
+    device call - a check of one handle is a check of the other."""
+    lib = _lib.load()
+
+    def both(n_nodes, u, v, n_cols=None, caps=None, heralds=None, n_det_cols=None):
+        u, v = np.asarray(u, np.int32), np.asarray(v, np.int32)
+        obs = np.zeros(len(u), np.uint64)
+        desc = _lib.UfDesc(n_nodes, len(u), n_nodes if n_cols is None else n_cols, u.ctypes.data, v.ctypes.data, obs.ctypes.data)
+        caps = None if caps is None else np.asarray(caps, np.uint8)
+        d_caps = None if caps is None else C.c_void_p(caps.ctypes.data)
+        her = None
+        if heralds is not None:
+            arrays = {k: np.array(x + [0], np.int32) for k, x in heralds.items()}
+            her = C.byref(_lib.UfHeralds(n_det_cols, len(heralds["herald_det"]),
+                                         *(arrays[k].ctypes.data for k in ("node_det", "herald_det", "herald_ptr", "herald_edges"))))
+        h = C.c_void_p()
+        whole = lib.tsim_uf_create_heralds(99, C.byref(desc), d_caps, her, C.byref(h)), lib.tsim_last_error()
+        assert not h.value
+        windowed = lib.tsim_ufw_create_heralds(99, C.byref(desc), d_caps, 2, 4, her, C.byref(h)), lib.tsim_last_error()
+        assert not h.value
+        assert whole == windowed
+        assert whole[0] == -22 and b"device" not in whole[1], whole
+        return whole[1]
+
+    # the graph (test_unionfind.py)
+    for nodes, u, v, what in ((4, [0, 0], [2, 1], b"strictly ascending"), (4, [0, 0], [1, 1], b"strictly ascending"),
+                              (4, [2], [1], b"u < v"), (4, [1], [4], b"leaves the nodes"), (4, [-1], [2], b"leaves the nodes"),
+                              (1, [], [], b"n_nodes")):
+        assert what in both(nodes, u, v)
+    assert b"n_cols" in both(4, [0], [1], n_cols=2)
+    # the caps (test_unionfind_weighted.py); the graph's own checks come first
+    u = np.arange(69)
+    for caps, what in (([2] * 68 + [0], b"edge 68 has cap 0"), ([15] + [2] * 68, b"edge 0 has cap 15"), ([2, 2, 255] + [2] * 66, b"edge 2 has cap 255")):
+        assert what in both(70, u, u + 1, caps=caps)
+    assert b"strictly ascending" in both(4, [0, 0], [2, 1], caps=[2, 0])
+    # the herald struct (test_unionfind_erasure.py, and the cases of the test above)
+    for kw, what in ((dict(herald_det=[1, 3]), b"named twice"), (dict(herald_det=[4, 4]), b"named twice"),
+                     (dict(herald_edges=[3, 0, 4]), b"of 4 edges"), (dict(herald_edges=[3, -1, 0]), b"of 4 edges"),
+                     (dict(herald_edges=[-1, 0, 3]), b"of 4 edges"), (dict(herald_ptr=[0, 2, 1]), b"must not fall"),
+                     (dict(herald_ptr=[1, 1, 3]), b"herald_ptr[0] = 1"), (dict(n_cols=5), b"n_cols = 5"),
+                     (dict(n_det_cols=7), b"n_det_cols = 7"), (dict(n_det_cols=4), b"n_det_cols = 4"),
+                     (dict(node_det=[0, 3, 2, 5]), b"strictly ascending"), (dict(node_det=[0, 2, 3, 6]), b"leaves the columns"),
+                     (dict(herald_det=[1, -4]), b"leaves the columns"), (dict(herald_det=[1, 6]), b"leaves the columns"),
+                     (dict(herald_det=[-1, 4]), b"leaves the columns"), (dict(caps=[1, 2, 15, 1]), b"edge 2 has cap 15")):
+        kw = dict(kw)
+        scalars = {k: kw.pop(k) for k in ("n_cols", "n_det_cols", "caps") if k in kw}
+        heralds = dict(dict(node_det=[0, 2, 3, 5], herald_det=[1, 4], herald_ptr=[0, 1, 3], herald_edges=[3, 0, 3]), **kw)
+        assert what in both(5, np.arange(4), np.arange(4) + 1, heralds=heralds, **dict(dict(n_cols=7, n_det_cols=6), **scalars))
+
+
 # ---- count() on the host path ----------------------------------------------------------------------------------------------
 
 def test_host_count_equals_the_tally_of_sample_and_decode(monkeypatch):

@@ -464,45 +464,53 @@ class HipProgram:
         program's device (``tsim_uf_create``, include/tsim_hip.h): the handle, to be given back to :meth:`uf_destroy`.
         ``caps``: ``None``, or an integer per edge in 1 .. 14 for weighted growth (``tsim_uf_create_weighted``).  A graph with
         heralds (``graph.herald_det`` is not empty) goes to ``tsim_uf_create_heralds``."""
+        desc, d_caps, her, _keep = self._uf_graph_args(graph, n_cols, caps)
+        h = C.c_void_p()
+        if her is not None:
+            rc, name = self._lib.tsim_uf_create_heralds(self.device, C.byref(desc), d_caps, C.byref(her), C.byref(h)), "tsim_uf_create_heralds"
+        elif d_caps is not None:
+            rc, name = self._lib.tsim_uf_create_weighted(self.device, C.byref(desc), d_caps, C.byref(h)), "tsim_uf_create_weighted"
+        else:
+            rc, name = self._lib.tsim_uf_create(self.device, C.byref(desc), C.byref(h)), "tsim_uf_create"
+        _lib.check(rc, name)
+        return h.value
+
+    @staticmethod
+    def _uf_graph_args(graph, n_cols: int, caps):
+        """What a create call of either union-find handle takes of a graph: ``(UfDesc, the caps' pointer or None, UfHeralds
+        or None for a graph without heralds, the arrays they point into)``; the last must outlive the call."""
         eu = np.ascontiguousarray(graph.edge_u, dtype=np.int32)
         ev = np.ascontiguousarray(graph.edge_v, dtype=np.int32)
         eo = np.ascontiguousarray(graph.edge_obs, dtype=np.uint64)
         desc = _lib.UfDesc(int(graph.n_nodes), int(eu.size), int(n_cols), eu.ctypes.data, ev.ctypes.data, eo.ctypes.data)
-        h = C.c_void_p()
-        her = len(getattr(graph, "herald_det", ())) > 0
-        if caps is None and not her:
-            _lib.check(self._lib.tsim_uf_create(self.device, C.byref(desc), C.byref(h)), "tsim_uf_create")
-            return h.value
-        if caps is None:
-            return self._uf_create_heralds(graph, desc, None)
-        ec = np.ascontiguousarray(caps)
-        if ec.shape != (eu.size,) or not np.issubdtype(ec.dtype, np.integer) or (ec.size and (ec.min() < 0 or ec.max() > 255)):
-            raise ValueError(f"caps: {eu.size} integers in 1 .. 14 expected")
-        ec = np.concatenate([ec.astype(np.uint8), np.zeros(1, np.uint8)])  # (never an empty buffer: NULL means unweighted)
-        if her:
-            return self._uf_create_heralds(graph, desc, ec)
-        _lib.check(self._lib.tsim_uf_create_weighted(self.device, C.byref(desc), C.c_void_p(ec.ctypes.data), C.byref(h)),
-                   "tsim_uf_create_weighted")
-        return h.value
+        keep, d_caps, her = [eu, ev, eo], None, None
+        if caps is not None:
+            ec = np.ascontiguousarray(caps)
+            if ec.shape != (eu.size,) or not np.issubdtype(ec.dtype, np.integer) or (ec.size and (ec.min() < 0 or ec.max() > 255)):
+                raise ValueError(f"caps: {eu.size} integers in 1 .. 14 expected")
+            ec = np.concatenate([ec.astype(np.uint8), np.zeros(1, np.uint8)])  # (never an empty buffer: NULL means unweighted)
+            keep.append(ec)
+            d_caps = C.c_void_p(ec.ctypes.data)
+        if len(getattr(graph, "herald_det", ())) > 0:
+            arrays = [np.ascontiguousarray(np.concatenate([np.asarray(getattr(graph, k), dtype=np.int32), np.zeros(1, np.int32)]))
+                      for k in ("node_det", "herald_det", "herald_ptr", "herald_edges")]  # (never an empty buffer)
+            keep += arrays
+            her = _lib.UfHeralds(int(graph.num_detectors), len(graph.herald_det), *(a.ctypes.data for a in arrays))
+        return desc, d_caps, her, keep
 
-    def _uf_create_heralds(self, graph, desc, ec) -> int:
-        arrays = [np.ascontiguousarray(np.concatenate([np.asarray(getattr(graph, k), dtype=np.int32), np.zeros(1, np.int32)]))
-                  for k in ("node_det", "herald_det", "herald_ptr", "herald_edges")]  # (never an empty buffer)
-        her = _lib.UfHeralds(int(graph.num_detectors), len(graph.herald_det), *(a.ctypes.data for a in arrays))
-        h = C.c_void_p()
-        _lib.check(self._lib.tsim_uf_create_heralds(self.device, C.byref(desc), None if ec is None else C.c_void_p(ec.ctypes.data),
-                                                    C.byref(her), C.byref(h)), "tsim_uf_create_heralds")
-        return h.value
+    def _uf_decode(self, entry: str, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, d_pred: int,
+                   d_xor: int, d_test: int, stream: int, *extra) -> None:
+        """The decode entry point ``entry`` of either handle; ``extra``: what it takes between ``d_pred`` and the stream."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        _lib.check(getattr(self._lib, entry)(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes), ptr(d_xor), ptr(d_test),
+                                             int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)), ptr(d_pred), *extra,
+                                             C.c_void_p(stream or self.stream_ptr())), entry)
 
     def uf_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,
                          d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
         """Decode the rows' syndromes and count kept / wrong / missed into ``d_counters``; ``d_pred``: ``uint64[n]`` for the
         predictions (``tsim_uf_decode_device``); asynchronous on ``stream`` (0: the handle's stream)."""
-        _lib.check(self._lib.tsim_uf_decode_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
-                                                   C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
-                                                   int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
-                                                   C.c_void_p(int(d_pred)) if d_pred else None,
-                                                   C.c_void_p(stream or self.stream_ptr())), "tsim_uf_decode_device")
+        self._uf_decode("tsim_uf_decode_device", handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test, stream)
 
     UF_SOFT_METRICS = ("rounds", "full_edges", "largest_cluster", "correction_weight")
 
@@ -513,13 +521,9 @@ class HipProgram:
         ``UF_SOFT_METRICS``, or its index) is binned into ``n_bins`` bins, the kept rows and the wrong ones among them ACCUMULATE
         into ``uint64[2 * n_bins]`` at ``d_hist``; ``d_soft``: ``uint32[4 * n]`` (16-byte aligned) for the four values of every row."""
         m = self.UF_SOFT_METRICS.index(metric) if isinstance(metric, str) else int(metric)
-        _lib.check(self._lib.tsim_uf_decode_soft_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
-                                                        C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
-                                                        int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
-                                                        C.c_void_p(int(d_pred)) if d_pred else None, m, int(n_bins),
-                                                        C.c_void_p(int(d_hist)) if d_hist else None,
-                                                        C.c_void_p(int(d_soft)) if d_soft else None,
-                                                        C.c_void_p(stream or self.stream_ptr())), "tsim_uf_decode_soft_device")
+        ptr = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        self._uf_decode("tsim_uf_decode_soft_device", handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test, stream,
+                        m, int(n_bins), ptr(d_hist), ptr(d_soft))
 
     def uf_info(self, handle: int) -> dict:
         out = (C.c_int64 * 16)()
@@ -542,37 +546,20 @@ class HipProgram:
         her = len(getattr(graph, "herald_det", ())) > 0
         if her and not heralds:
             raise NotImplementedError("the windowed decoder takes a graph without heralds")
-        eu = np.ascontiguousarray(graph.edge_u, dtype=np.int32)
-        ev = np.ascontiguousarray(graph.edge_v, dtype=np.int32)
-        eo = np.ascontiguousarray(graph.edge_obs, dtype=np.uint64)
-        desc = _lib.UfDesc(int(graph.n_nodes), int(eu.size), int(n_cols), eu.ctypes.data, ev.ctypes.data, eo.ctypes.data)
-        ec = None
-        if caps is not None:
-            ec = np.ascontiguousarray(caps)
-            if ec.shape != (eu.size,) or not np.issubdtype(ec.dtype, np.integer) or (ec.size and (ec.min() < 0 or ec.max() > 255)):
-                raise ValueError(f"caps: {eu.size} integers in 1 .. 14 expected")
-            ec = np.concatenate([ec.astype(np.uint8), np.zeros(1, np.uint8)])  # (never an empty buffer: NULL means unweighted)
+        desc, d_caps, hd, _keep = self._uf_graph_args(graph, n_cols, caps)
+        cw = int(min(commit, 0x7FFFFFFF)), int(min(window, 0x7FFFFFFF))
         h = C.c_void_p()
-        if her:
-            arrays = [np.ascontiguousarray(np.concatenate([np.asarray(getattr(graph, k), dtype=np.int32), np.zeros(1, np.int32)]))
-                      for k in ("node_det", "herald_det", "herald_ptr", "herald_edges")]  # (never an empty buffer)
-            hd = _lib.UfHeralds(int(graph.num_detectors), len(graph.herald_det), *(a.ctypes.data for a in arrays))
-            _lib.check(self._lib.tsim_ufw_create_heralds(self.device, C.byref(desc), None if ec is None else C.c_void_p(ec.ctypes.data),
-                                                         int(min(commit, 0x7FFFFFFF)), int(min(window, 0x7FFFFFFF)), C.byref(hd), C.byref(h)),
-                       "tsim_ufw_create_heralds")
-            return h.value
-        _lib.check(self._lib.tsim_ufw_create(self.device, C.byref(desc), None if ec is None else C.c_void_p(ec.ctypes.data),
-                                             int(min(commit, 0x7FFFFFFF)), int(min(window, 0x7FFFFFFF)), C.byref(h)), "tsim_ufw_create")
+        if hd is not None:
+            rc, name = self._lib.tsim_ufw_create_heralds(self.device, C.byref(desc), d_caps, *cw, C.byref(hd), C.byref(h)), "tsim_ufw_create_heralds"
+        else:
+            rc, name = self._lib.tsim_ufw_create(self.device, C.byref(desc), d_caps, *cw, C.byref(h)), "tsim_ufw_create"
+        _lib.check(rc, name)
         return h.value
 
     def ufw_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,
                           d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
         """:meth:`uf_decode_device` by a handle of :meth:`ufw_create` (``tsim_ufw_decode_device``)."""
-        _lib.check(self._lib.tsim_ufw_decode_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
-                                                    C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
-                                                    int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
-                                                    C.c_void_p(int(d_pred)) if d_pred else None,
-                                                    C.c_void_p(stream or self.stream_ptr())), "tsim_ufw_decode_device")
+        self._uf_decode("tsim_ufw_decode_device", handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test, stream)
 
     def ufw_info(self, handle: int) -> dict:
         out = (C.c_int64 * 16)()

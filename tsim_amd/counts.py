@@ -488,9 +488,8 @@ class _DeviceTally:
         self._pairs = None       # the pair counter's handle (tsim_pairs), when pair columns are asked for
         self._pairs_stream = 0   # the stream its launches went to
         self._table = None       # the row table's handle (tsim_rowtab), when pattern columns are asked for
-        self._lookup = None      # the decoder's row table, loaded from the host (a LookupDecoder)
-        self._uf = None          # the decoder's graph handle (tsim_uf; a UnionFindDecoder)
-        self._ufw = None         # the decoder's windows handle (tsim_ufw; a WindowedUnionFindDecoder)
+        self._dec = None         # the decoder's (handle, what decodes rows by it, what destroys it): a row table loaded from the
+        #                          host (a LookupDecoder), a tsim_uf (a UnionFindDecoder) or a tsim_ufw (a WindowedUnionFindDecoder)
         self.d_decoded = None    # its three counters
         self.soft = _soft_choice(decoder)   # (metric, bins): the union-find decoder's soft output, binned on the device
         self.d_soft_hist = None  # its two histograms, uint64[2 * bins]
@@ -502,18 +501,16 @@ class _DeviceTally:
             if decoder is not None:
                 from .decode import UnionFindDecoder, WindowedUnionFindDecoder
 
-                if isinstance(decoder, UnionFindDecoder):
-                    self._uf = hp.uf_create(decoder.graph, self.n_cols, decoder.edge_caps)
-                elif isinstance(decoder, WindowedUnionFindDecoder):
-                    self._ufw = hp.ufw_create(decoder.graph, self.n_cols, decoder.commit, decoder.window, decoder.edge_caps,
-                                              heralds=decoder.heralds)
+                if isinstance(decoder, (UnionFindDecoder, WindowedUnionFindDecoder)):
+                    self._dec = decoder._handle(hp, self.n_cols)
                 else:
                     keys, values = decoder.table()
-                    self._lookup = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values)))
-                    hp.rowtab_load(self._lookup, keys, values)
+                    self._dec = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values))), hp.rowtab_decode_device, hp.rowtab_destroy
+                    hp.rowtab_load(self._dec[0], keys, values)
                 self.d_decoded = self._upload(np.zeros(3, dtype=np.uint64))
                 if self.soft:
                     self.d_soft_hist = self._upload(np.zeros(2 * self.soft[1], dtype=np.uint64))
+                    self._dec = (self._dec[0], lambda *a, **k: hp.uf_decode_soft_device(*a, *self.soft, self.d_soft_hist.ptr, **k), self._dec[2])
             self.d_counts = self._upload(np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64))
             self.d_xor = self._upload(self._row(xor_bits)) if xor_bits is not None and np.any(xor_bits) else None
             self.d_test = self._upload(self._row(test_bits)) if test_bits is not None else None
@@ -547,31 +544,21 @@ class _DeviceTally:
             self.hp.pairs_add_device(self._pairs, d_first + (a - r0) * row_bytes, b - a, row_bytes,
                                      d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
                                      d_test=self.d_test.ptr if self.d_test is not None else 0, stream=stream)
-        if self._table is not None or self._lookup is not None or self._uf is not None or self._ufw is not None:
+        if self._table is not None or self._dec is not None:
             self._pairs_stream = stream
             masks = dict(d_xor=self.d_xor.ptr if self.d_xor is not None else 0, d_test=self.d_test.ptr if self.d_test is not None else 0,
                          stream=stream)
             if self._table is not None:
                 self.hp.rowtab_add_device(self._table, d_first + (a - r0) * row_bytes, b - a, row_bytes, **masks)
-            if self._lookup is not None:
-                self.hp.rowtab_decode_device(self._lookup, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
-                                             self.d_decoded.ptr, **masks)
-            if self._uf is not None and self.soft:
-                self.hp.uf_decode_soft_device(self._uf, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
-                                              self.d_decoded.ptr, self.soft[0], self.soft[1], self.d_soft_hist.ptr, **masks)
-            elif self._uf is not None:
-                self.hp.uf_decode_device(self._uf, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
-                                         self.d_decoded.ptr, **masks)
-            if self._ufw is not None:
-                self.hp.ufw_decode_device(self._ufw, d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols),
-                                          self.d_decoded.ptr, **masks)
+            if self._dec is not None:
+                self._dec[1](self._dec[0], d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols), self.d_decoded.ptr, **masks)
 
     def result(self, shots: int) -> ShotCounts:
         """The counters, once every tally launch has completed (the caller has synchronised their streams)."""
         c = np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64)
         self.hp.d2h(c, self.d_counts)
         out = ShotCounts.from_counters(c, shots=shots, n_cols=self.n_cols, num_detectors=self.nd, histogram_columns=self.hc)
-        if self._pairs is None and self._table is None and self._lookup is None and self._uf is None and self._ufw is None:
+        if self._pairs is None and self._table is None and self._dec is None:
             return out
         pairs = self.hp.pairs_read(self._pairs, len(self.pc), stream=self._pairs_stream) if self._pairs is not None else None
         patterns = pattern_counts = errors = misses = None
@@ -580,7 +567,7 @@ class _DeviceTally:
             keys, cnt, info = self.hp.rowtab_read(self._table, len(self.tc), stream=self._pairs_stream)
             patterns, pattern_counts = ordered_patterns(keys, cnt, len(self.tc))
             overflow = int(info[4])
-        if self._lookup is not None or self._uf is not None or self._ufw is not None:
+        if self._dec is not None:
             self.hp.stream_synchronize(self._pairs_stream)
             d = np.zeros(3, dtype=np.uint64)
             self.hp.d2h(d, self.d_decoded)
@@ -596,16 +583,12 @@ class _DeviceTally:
                           errors, misses, *soft)
 
     def release(self) -> None:
-        for name in ("_table", "_lookup"):
-            if getattr(self, name) is not None:
-                self.hp.rowtab_destroy(getattr(self, name))
-                setattr(self, name, None)
-        if self._uf is not None:
-            self.hp.uf_destroy(self._uf)
-            self._uf = None
-        if self._ufw is not None:
-            self.hp.ufw_destroy(self._ufw)
-            self._ufw = None
+        if self._table is not None:
+            self.hp.rowtab_destroy(self._table)
+            self._table = None
+        if self._dec is not None:
+            self._dec[2](self._dec[0])
+            self._dec = None
         if self._pairs is not None:
             self.hp.pairs_destroy(self._pairs)
             self._pairs = None

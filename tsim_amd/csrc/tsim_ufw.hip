@@ -3,28 +3,14 @@
 // docstring of tsim_amd/decode.py ("Sliding-window decoding of long runs") - a second statement of that construction,
 // independent of the numpy one - and holds their tables; the kernel is csrc/tsim_ufw.hip.h.  tsim_ufw_create_heralds takes a
 // graph with heralds and builds, with the windows, every window's herald lists ("Sliding windows with heralds" there).
-#include "../../include/tsim_hip.h"
+#include "tsim_uf_host.hip.h"
 #include "tsim_ufw.hip.h"
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <new>
 #include <utility>
-#include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define UFW_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
-constexpr int kMaxWindow = 65535;              // nodes, and edges, of a window: uint16 indices
-constexpr int64_t kRowsPerLaunch = 1ll << 30;  // a block's uint32 partials cannot overflow
-constexpr int64_t kMaxTable = 0x7FFFFFFF;      // entries of a concatenated table: int32 offsets
+constexpr int64_t kMaxTable = 0x7FFFFFFF;  // entries of a concatenated table: int32 offsets
 
 struct Tables {
   std::vector<ufwk::WinDesc> desc;
@@ -51,20 +37,10 @@ struct tsim_ufw {
   ufwk::Args a{};  // the windows' part of the kernel's arguments
   int grid = 1;
   int n_nodes = 0, n_edges = 0, max_nodes = 0, max_edges = 0, max_cap = 0;
-  int64_t launches = 0, bytes = 0;
-  void *d_desc = nullptr, *d_uv = nullptr, *d_obs = nullptr, *d_cap = nullptr, *d_adj_ptr = nullptr, *d_adj = nullptr, *d_commit = nullptr,
-       *d_stats = nullptr;
+  int64_t launches = 0;
   int n_heralds = 0;
-  void *d_node_det = nullptr, *d_herald_det = nullptr, *d_dmask = nullptr, *d_win_herald = nullptr, *d_win_her_ptr = nullptr,
-       *d_win_her_edges = nullptr;  // heralds only
+  ufh::Uploads up;  // the tables a points to
 };
-
-static void ufw_release(tsim_ufw *h) {
-  if (h->device >= 0) (void)hipSetDevice(h->device);
-  for (void *p : {h->d_desc, h->d_uv, h->d_obs, h->d_cap, h->d_adj_ptr, h->d_adj, h->d_commit, h->d_stats, h->d_node_det, h->d_herald_det,
-                  h->d_dmask, h->d_win_herald, h->d_win_her_ptr, h->d_win_her_edges})
-    if (p) (void)hipFree(p);
-}
 
 // The windows of the graph (checked by the caller: u < v inside the nodes, pairs strictly ascending) with `commit` = C and
 // `window` = W columns.  0, or an error code after tsim_fail.  `eh` (NULL: a graph without heralds): the heralds of every global
@@ -90,8 +66,8 @@ static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t
                        "window - commit = %lld is too small",
                        (long long)e, g->edge_u[e], g->edge_v[e], (long long)a, (long long)k, (long long)b, (long long)hi_of(k), (long long)(W - C));
   }
-  if (std::min(W, nd) + 1 > kMaxWindow)
-    return tsim_fail(TSIM_ENOTSUP, "a window of %lld nodes (at most %d: indices are uint16)", (long long)(std::min(W, nd) + 1), kMaxWindow);
+  if (std::min(W, nd) + 1 > ufh::kMaxIndex)
+    return tsim_fail(TSIM_ENOTSUP, "a window of %lld nodes (at most %d: indices are uint16)", (long long)(std::min(W, nd) + 1), ufh::kMaxIndex);
   const size_t n_max = (size_t)std::min(W, nd) + 1;
   std::vector<uint8_t> b_cap(n_max), b_kind(n_max);  // per local node x the pair (0, x): its cap; 0 none, 1 virtual only, 2 real
   std::vector<int32_t> b_edge(n_max);                // the real boundary edge
@@ -141,8 +117,8 @@ static int build_windows(const tsim_uf_desc *g, const uint8_t *edge_cap, int64_t
       t->cap.push_back(cap_of(e));
     }
     const size_t n_e = lu.size();
-    if (n_e > (size_t)kMaxWindow)
-      return tsim_fail(TSIM_ENOTSUP, "window %lld has %zu edges (at most %d: indices are uint16)", (long long)k, n_e, kMaxWindow);
+    if (n_e > (size_t)ufh::kMaxIndex)
+      return tsim_fail(TSIM_ENOTSUP, "window %lld has %zu edges (at most %d: indices are uint16)", (long long)k, n_e, ufh::kMaxIndex);
     d.n_edges = (int32_t)n_e;
     if (eh) {  // the herald lists: every global edge that is present, under its local edge, for each herald that lists it
       listed.clear();
@@ -213,55 +189,17 @@ extern "C" int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *desc,
   if (N < 2) return tsim_fail(TSIM_EINVAL, "n_nodes = %d (the boundary and at least one detector)", N);
   if (E < 0) return tsim_fail(TSIM_EINVAL, "n_edges = %d", E);
   if (commit < 1 || window <= commit) return tsim_fail(TSIM_EINVAL, "commit = %d, window = %d: 1 <= commit < window expected", commit, window);
-  const long long n_det = her ? (long long)N - 1 + her->n_heralds : N - 1;  // detector columns of a row
-  if (her && (her->n_heralds < 0 || her->n_det_cols != n_det))
-    return tsim_fail(TSIM_EINVAL, "n_det_cols = %d for %d nodes and %d heralds (nodes - 1 + heralds expected)", her->n_det_cols, N, her->n_heralds);
-  if (desc->n_cols < n_det || desc->n_cols > (1 << 30)) return tsim_fail(TSIM_EINVAL, "n_cols = %d for %lld detectors (up to 2^30)", desc->n_cols, n_det);
-  if (E > 0 && (!desc->edge_u || !desc->edge_v || !desc->edge_obs)) return tsim_fail(TSIM_EINVAL, "an edge array is NULL");
-  for (int e = 0; e < E; ++e) {
-    const int32_t u = desc->edge_u[e], v = desc->edge_v[e];
-    if (u < 0 || v >= N) return tsim_fail(TSIM_EINVAL, "edge %d = (%d, %d) leaves the nodes 0 .. %d", e, u, v, N - 1);
-    if (u >= v) return tsim_fail(TSIM_EINVAL, "edge %d = (%d, %d): u < v expected", e, u, v);
-    if (e > 0 && (desc->edge_u[e - 1] > u || (desc->edge_u[e - 1] == u && desc->edge_v[e - 1] >= v)))
-      return tsim_fail(TSIM_EINVAL, "edge %d = (%d, %d) does not come after edge %d: the pairs must be strictly ascending", e, u, v, e - 1);
-  }
+  long long n_det = 0;
   int max_cap = 0;
-  if (edge_cap)
-    for (int e = 0; e < E; ++e) {
-      if (edge_cap[e] < 1 || edge_cap[e] > ufk::kMaxCap)
-        return tsim_fail(TSIM_EINVAL, "edge %d has cap %d (1 .. %d: a 4-bit counter that may overshoot by one)", e, edge_cap[e], ufk::kMaxCap);
-      max_cap = std::max<int>(max_cap, edge_cap[e]);
-    }
-  // the heralds: every column a node or one herald, the lists inside the edges (the checks of tsim_uf_create_heralds)
+  if (const int rc = ufh::check_graph(desc, edge_cap, her, &n_det, &max_cap)) return rc;
   const int H = her ? her->n_heralds : 0, mask_bytes = (desc->n_cols + 7) / 8;
   std::vector<uint8_t> dmask;
   EdgeHeralds eh;
   if (her) {
-    if (!her->node_det || !her->herald_ptr || (H > 0 && !her->herald_det)) return tsim_fail(TSIM_EINVAL, "a herald array is NULL");
     dmask.assign((size_t)mask_bytes, 0);
     std::vector<uint8_t> hmask((size_t)mask_bytes, 0);
-    for (int v = 0; v < N - 1; ++v) {
-      const int32_t c = her->node_det[v];
-      if (c < 0 || c >= n_det) return tsim_fail(TSIM_EINVAL, "node_det[%d] = %d leaves the columns 0 .. %lld", v, c, n_det - 1);
-      if (v > 0 && her->node_det[v - 1] >= c) return tsim_fail(TSIM_EINVAL, "node_det[%d] = %d: the columns of the nodes must be strictly ascending", v, c);
-      dmask[c >> 3] |= (uint8_t)(1u << (c & 7));
-    }
-    for (int i = 0; i < H; ++i) {
-      const int32_t c = her->herald_det[i];
-      if (c < 0 || c >= n_det) return tsim_fail(TSIM_EINVAL, "herald_det[%d] = %d leaves the columns 0 .. %lld", i, c, n_det - 1);
-      if ((dmask[c >> 3] | hmask[c >> 3]) >> (c & 7) & 1)
-        return tsim_fail(TSIM_EINVAL, "column %d is named twice (a column is a node or one herald)", c);
-      hmask[c >> 3] |= (uint8_t)(1u << (c & 7));
-    }
-    if (her->herald_ptr[0] != 0) return tsim_fail(TSIM_EINVAL, "herald_ptr[0] = %d", her->herald_ptr[0]);
-    for (int i = 0; i < H; ++i)
-      if (her->herald_ptr[i + 1] < her->herald_ptr[i])
-        return tsim_fail(TSIM_EINVAL, "herald_ptr[%d] = %d after %d: it must not fall", i + 1, her->herald_ptr[i + 1], her->herald_ptr[i]);
+    if (const int rc = ufh::check_heralds(desc, her, n_det, dmask.data(), hmask.data(), nullptr)) return rc;
     const int n_listed = her->herald_ptr[H];
-    if (n_listed > 0 && !her->herald_edges) return tsim_fail(TSIM_EINVAL, "herald_edges is NULL");
-    for (int k = 0; k < n_listed; ++k)
-      if (her->herald_edges[k] < 0 || her->herald_edges[k] >= E)
-        return tsim_fail(TSIM_EINVAL, "herald_edges[%d] = %d of %d edges", k, her->herald_edges[k], E);
     eh.ptr.assign((size_t)E + 1, 0);
     for (int k = 0; k < n_listed; ++k) ++eh.ptr[her->herald_edges[k] + 1];
     for (int e = 0; e < E; ++e) eh.ptr[e + 1] += eh.ptr[e];
@@ -292,75 +230,47 @@ extern "C" int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *desc,
   a.commit = commit;
   a.nd = N - 1;
   a.n_cols = desc->n_cols;
-  int best = 0, per_cu = 1;  // the waves of a block: as many shots on a CU as its LDS holds, in the fewest blocks
-  for (int w = 1; w <= ufk::kMaxWaves; ++w) {
-    const long long block = 16 + w * shot;
-    if (block > ufk::kLdsBlock) break;
-    const int blocks = (int)std::min<long long>(ufk::kLdsCU / block, 32 / w);
-    if (blocks * w >= best) best = blocks * w, a.waves = w, per_cu = blocks;
-  }
+  int per_cu = 1;
+  ufh::choose_waves(shot, &a.waves, &per_cu);
   if (t.uv.empty()) t.uv.push_back(0), t.obs.push_back(0), t.cap.push_back(1);
   if (t.adj.empty()) t.adj.push_back(0);
-  int count = 0;
-  UFW_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  UFW_TRY(hipSetDevice(device));
   int cus = 0;
-  UFW_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  if (const int rc = ufh::open_device(device, &cus)) return rc;
   tsim_ufw *h = new (std::nothrow) tsim_ufw();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
   h->grid = std::max(1, cus) * per_cu;
   h->n_nodes = N, h->n_edges = E, h->max_nodes = t.max_nodes, h->max_edges = t.max_edges, h->max_cap = max_cap;
-  hipError_t e = hipSuccess;
-  auto upload = [&](void **dst, const void *src, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(dst, bytes);
-    if (e == hipSuccess) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    h->bytes += (int64_t)bytes;
-  };
-  upload(&h->d_desc, t.desc.data(), t.desc.size() * sizeof(ufwk::WinDesc));
-  upload(&h->d_uv, t.uv.data(), t.uv.size() * 4);
-  upload(&h->d_obs, t.obs.data(), t.obs.size() * 8);
-  if (edge_cap) upload(&h->d_cap, t.cap.data(), t.cap.size());
-  upload(&h->d_adj_ptr, t.adj_ptr.data(), t.adj_ptr.size() * 4);
-  upload(&h->d_adj, t.adj.data(), t.adj.size() * 2);
-  upload(&h->d_commit, t.commit.data(), t.commit.size() * 4);
+  ufh::Uploads &up = h->up;
+  a.desc = up.put(t.desc);
+  a.edge_uv = up.put(t.uv);
+  a.edge_obs = reinterpret_cast<const unsigned long long *>(up.put(t.obs));
+  if (edge_cap) a.cap = up.put(t.cap);
+  a.adj_ptr = up.put(t.adj_ptr);
+  a.adj_edge = up.put(t.adj);
+  a.commit_bits = up.put(t.commit);
   if (her) {
     h->n_heralds = H;
     std::vector<int32_t> herald_det(1, 0);  // (never an empty buffer)
     if (H) herald_det.assign(her->herald_det, her->herald_det + H);
     if (t.win_herald.empty()) t.win_herald.push_back(0);
     if (t.win_her_edges.empty()) t.win_her_edges.push_back(0);
-    upload(&h->d_node_det, her->node_det, (size_t)(N - 1) * 4);
-    upload(&h->d_herald_det, herald_det.data(), herald_det.size() * 4);
-    upload(&h->d_dmask, dmask.data(), dmask.size());
-    upload(&h->d_win_herald, t.win_herald.data(), t.win_herald.size() * 4);
-    upload(&h->d_win_her_ptr, t.win_her_ptr.data(), t.win_her_ptr.size() * 4);
-    upload(&h->d_win_her_edges, t.win_her_edges.data(), t.win_her_edges.size() * 2);
+    a.node_det = up.put(her->node_det, (size_t)(N - 1));
+    a.herald_det = up.put(herald_det);
+    a.dmask = up.put(dmask);
+    a.win_herald = up.put(t.win_herald);
+    a.win_her_ptr = up.put(t.win_her_ptr);
+    a.win_her_edges = up.put(t.win_her_edges);
   }
   const uint64_t zero[4] = {0, 0, 0, 0};
-  upload(&h->d_stats, zero, sizeof zero);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    ufw_release(h);
-    delete h;
+  a.stats = reinterpret_cast<unsigned long long *>(up.put(zero, 4));
+  if (up.err == hipSuccess) up.err = hipDeviceSynchronize();
+  if (up.err != hipSuccess) {
+    const hipError_t e = up.err;
+    tsim_ufw_destroy(h);
     return tsim_fail(e == hipErrorOutOfMemory ? TSIM_ENOMEM : TSIM_EHIP, "%zu windows of a graph of %d nodes, %d edges: %s", t.desc.size(), N, E,
                      hipGetErrorString(e));
   }
-  a.desc = static_cast<const ufwk::WinDesc *>(h->d_desc);
-  a.edge_uv = static_cast<const uint32_t *>(h->d_uv);
-  a.edge_obs = static_cast<const unsigned long long *>(h->d_obs);
-  a.cap = static_cast<const uint8_t *>(h->d_cap);
-  a.adj_ptr = static_cast<const uint32_t *>(h->d_adj_ptr);
-  a.adj_edge = static_cast<const uint16_t *>(h->d_adj);
-  a.commit_bits = static_cast<const uint32_t *>(h->d_commit);
-  a.stats = static_cast<unsigned long long *>(h->d_stats);
-  a.node_det = static_cast<const int32_t *>(h->d_node_det);
-  a.dmask = static_cast<const uint8_t *>(h->d_dmask);
-  a.herald_det = static_cast<const int32_t *>(h->d_herald_det);
-  a.win_herald = static_cast<const int32_t *>(h->d_win_herald);
-  a.win_her_ptr = static_cast<const uint32_t *>(h->d_win_her_ptr);
-  a.win_her_edges = static_cast<const uint16_t *>(h->d_win_her_edges);
   h->a = a;
   *out = h;
   return TSIM_OK;
@@ -368,16 +278,16 @@ extern "C" int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *desc,
 
 extern "C" void tsim_ufw_destroy(tsim_ufw *h) {
   if (!h) return;
-  ufw_release(h);
+  h->up.release(h->device);
   delete h;
 }
 
 extern "C" int tsim_ufw_info(tsim_ufw *h, int64_t out[16]) {
   if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
-  UFW_TRY(hipSetDevice(h->device));
-  UFW_TRY(hipDeviceSynchronize());  // (the statistics live on the device: every decode so far is waited for)
+  UF_TRY(hipSetDevice(h->device));
+  UF_TRY(hipDeviceSynchronize());  // (the statistics live on the device: every decode so far is waited for)
   uint64_t st[3];
-  UFW_TRY(hipMemcpy(st, h->d_stats, sizeof st, hipMemcpyDeviceToHost));
+  UF_TRY(hipMemcpy(st, h->a.stats, sizeof st, hipMemcpyDeviceToHost));
   std::fill(out, out + 16, 0);
   out[0] = h->n_nodes;
   out[1] = h->n_edges;
@@ -388,7 +298,7 @@ extern "C" int tsim_ufw_info(tsim_ufw *h, int64_t out[16]) {
   out[6] = h->a.waves;
   out[7] = h->launches;
   out[8] = (int64_t)st[0];
-  out[9] = h->bytes;
+  out[9] = h->up.bytes;
   out[10] = (int64_t)st[1];
   out[11] = (int64_t)st[2];
   out[12] = h->a.n_cols;
@@ -402,40 +312,16 @@ extern "C" int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_
                                       const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
                                       void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "decoder is NULL");
-  if (n < 0) return tsim_fail(TSIM_EINVAL, "negative n");
   ufwk::Args a = h->a;
-  const int64_t used = ((int64_t)a.n_cols + 7) / 8;
-  if (row_bytes < used || row_bytes > 0x7FFFFFFF)
-    return tsim_fail(TSIM_EINVAL, "row_bytes = %lld for %lld bytes per row", (long long)row_bytes, (long long)used);
-  if (n > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
-  if (obs_lo < 0 || obs_hi < obs_lo || obs_hi > a.n_cols || obs_hi - obs_lo > 64)
-    return tsim_fail(TSIM_EINVAL, "observable columns %d .. %d of %d (at most 64)", obs_lo, obs_hi, a.n_cols);
-  if (!d_counters || reinterpret_cast<uintptr_t>(d_counters) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_counters is NULL or not 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_pred) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_pred is not 8-byte aligned");
+  if (const int rc = ufh::check_rows(a, d_rows, n, row_bytes, obs_lo, obs_hi, d_counters, d_pred)) return rc;
   if (n == 0) return TSIM_OK;
-  UFW_TRY(hipSetDevice(h->device));
-  a.rb = row_bytes;
-  a.used = (int)used;
-  a.xr = d_xor;
-  a.test = d_test;
-  a.w8 = reinterpret_cast<uintptr_t>(d_rows) % 8 == 0 && row_bytes % 8 == 0;
-  a.obs_lo = obs_lo;
-  a.obs_hi = obs_hi;
-  a.dec = reinterpret_cast<unsigned long long *>(d_counters);
-  const size_t lds = 16 + (size_t)a.waves * a.shot_bytes;
-  for (int64_t r0 = 0; r0 < n; r0 += kRowsPerLaunch) {
-    a.n = std::min(kRowsPerLaunch, n - r0);
-    a.rows = d_rows + r0 * row_bytes;
-    a.pred = d_pred ? reinterpret_cast<unsigned long long *>(d_pred) + r0 : nullptr;
-    const int64_t tiles = (a.n + 63) / 64;
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + a.waves - 1) / a.waves, h->grid));
+  UF_TRY(hipSetDevice(h->device));
+  ufh::fill_rows(a, d_rows, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters);
+  return ufh::launch_rows(a, d_rows, n, d_pred, h->grid, &h->launches, [&](ufwk::Args &a, int64_t, unsigned blocks, size_t lds) {
     if (a.node_det) {
       if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
       else hipLaunchKernelGGL((ufwk::k_ufw<false, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
     } else if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((ufwk::k_ufw<false, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-    UFW_TRY(hipGetLastError());
-    ++h->launches;
-  }
-  return TSIM_OK;
+  });
 }

@@ -499,7 +499,111 @@ def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray
     return label
 
 
-class UnionFindDecoder:
+class _RowDecoder:
+    """What :class:`UnionFindDecoder` and :class:`WindowedUnionFindDecoder` share: rows to cache entries, the entries' readers
+    and the plain device call.  A subclass has ``graph``, ``_n_obs``, ``edge_caps`` and ``_cache``, decodes one row's detector
+    bits in ``_decode_bits`` (a cache entry: prediction, missed, flipped edges, rounds, ...) and opens its handle in ``_handle``."""
+
+    @staticmethod
+    def _of_circuit(circuit, weights, resolution, heralds, limit):
+        """The head of both ``from_circuit``: ``(graph, observables, caps)``."""
+        if weights not in (None, "probability"):
+            raise ValueError(f'weights = {weights!r}: None or "probability"')
+        if isinstance(circuit, str):
+            from .clifford import CliffordCircuit
+
+            circuit = CliffordCircuit(circuit)
+        form = circuit.compile_faults()
+        graph = DecodingGraph.from_form(form, heralds=heralds, limit=limit)
+        return graph, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution)
+
+    @property
+    def num_detectors(self) -> int:
+        return self.graph.num_detectors
+
+    @property
+    def num_observables(self) -> int:
+        return self._n_obs
+
+    def _decoded(self, dets):
+        """Per row the cache entry of its detector columns (``None`` for a row without defects, whatever its heralds)."""
+        d = np.asarray(dets, dtype=np.bool_)
+        if d.ndim != 2 or d.shape[1] != self.num_detectors:
+            raise ValueError(f"dets must be [n, {self.num_detectors}], got shape {d.shape}")
+        out = [None] * len(d)
+        rows = np.flatnonzero(d[:, self.graph.node_det].any(axis=1))
+        if not len(rows):
+            return out
+        uniq, inv = np.unique(_pack(d[rows]), axis=0, return_inverse=True)
+        inv = np.asarray(inv).reshape(-1)
+        entries = []
+        for k in uniq:
+            key = k.tobytes()
+            if key not in self._cache:
+                self._cache[key] = self._decode_bits(np.unpackbits(k, bitorder="little", count=self.num_detectors).astype(np.bool_))
+            entries.append(self._cache[key])
+        for r, i in zip(rows, inv):
+            out[r] = entries[i]
+        return out
+
+    def predictions(self, dets) -> np.ndarray:
+        """uint64 ``[n]``: the predicted observable mask of every row (bit ``k`` = observable ``k``; 0 for a miss) - what the
+        device kernel writes to ``d_pred``."""
+        return np.array([0 if e is None else e[0] for e in self._decoded(dets)], dtype=np.uint64)
+
+    def decode(self, dets) -> np.ndarray:
+        """bool ``[n, num_observables]``: the predicted observable flips of detector rows bool ``[n, num_detectors]``."""
+        p = self.predictions(dets)
+        return ((p[:, None] >> np.arange(self._n_obs, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.bool_)
+
+    def missed(self, dets) -> np.ndarray:
+        """bool ``[n]``: the rows whose growth (in a window, of the windowed decoder) stopped with an active cluster left (no
+        flip is predicted for them)."""
+        return np.array([e is not None and e[1] for e in self._decoded(dets)], dtype=np.bool_)
+
+    def flipped_edges(self, dets) -> list:
+        """Per row the edges of its correction, as edges of ``graph`` (int64, ascending; empty for a row without defects and
+        for a miss); of the windowed decoder the committed ones."""
+        return [np.zeros(0, np.int64) if e is None else e[2] for e in self._decoded(dets)]
+
+    def growth_rounds(self, dets) -> np.ndarray:
+        """int64 ``[n]``: the growth rounds every row took (of the windowed decoder: the most of any of its windows)."""
+        return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
+
+    def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
+                      stream: int = 0):
+        """``(predictions uint64[n], (kept, wrong, missed))`` for ``n`` bit-packed rows already in HBM (detectors, then
+        observables; ``n_cols`` columns, default ``num_detectors + num_observables``; ``d_xor`` / ``d_test``: device masks of
+        ``ceil(n_cols / 8)`` bytes) by one handle on ``hp``'s device, created and destroyed here: a ``tsim_uf``, or a
+        ``tsim_ufw`` (the library builds the windows itself).  A row that is not kept and a miss predict 0.  Returns when the
+        results are on the host."""
+        return self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream)
+
+    def _decode_device(self, hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream, call=None):
+        """:meth:`decode_device`; ``call``: what decodes instead of the handle's plain call, with its arguments."""
+        nd = self.num_detectors
+        h, decode, destroy = self._handle(hp, nd + self._n_obs if n_cols is None else int(n_cols))
+        bufs = []
+        try:
+            pred = np.zeros(int(n), np.uint64)
+            cnt = np.zeros(3, np.uint64)
+            d_pred, d_cnt = hp.malloc(pred.nbytes + 16), hp.malloc(cnt.nbytes + 16)
+            bufs += [d_pred, d_cnt]
+            hp.h2d(d_cnt, cnt)
+            (call or decode)(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, d_pred=d_pred.ptr, d_xor=d_xor, d_test=d_test,
+                             stream=stream)
+            hp.stream_synchronize(stream)
+            if n:
+                hp.d2h(pred, d_pred)
+            hp.d2h(cnt, d_cnt)
+            return pred, tuple(int(x) for x in cnt)
+        finally:
+            destroy(h)
+            for b in bufs:
+                b.free()
+
+
+class UnionFindDecoder(_RowDecoder):
     """The union-find decoder of a :class:`DecodingGraph` (module docstring) for rows of ``graph.num_detectors`` detectors and
     ``num_observables`` observables (default: as many as the masks of the graph use, at least one; at most 64).
     ``decode`` / ``missed`` have the signatures of :class:`LookupDecoder`; they decode each distinct syndrome once.
@@ -532,15 +636,7 @@ class UnionFindDecoder:
         """Of a :class:`tsim_amd.clifford.CliffordCircuit` with deterministic detectors (or its program text).  ``weights``:
         ``None`` (unweighted) or ``"probability"``: the caps ``graph.growth_caps(resolution)`` (module docstring).
         ``heralds``: herald detectors pre-grow their site's edges and are no syndrome bits (module docstring)."""
-        if weights not in (None, "probability"):
-            raise ValueError(f'weights = {weights!r}: None or "probability"')
-        if isinstance(circuit, str):
-            from .clifford import CliffordCircuit
-
-            circuit = CliffordCircuit(circuit)
-        form = circuit.compile_faults()
-        graph = DecodingGraph.from_form(form, heralds=heralds)
-        return cls(graph, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution))
+        return cls(*cls._of_circuit(circuit, weights, resolution, heralds, MAX_GRAPH))
 
     def with_soft_output(self, metric: str, bins: int = 64) -> "UnionFindDecoder":
         """The same decoder (graph, caps and observables are shared) with ``soft_output = metric``, one of ``"rounds"``,
@@ -554,14 +650,6 @@ class UnionFindDecoder:
         out.__dict__.update(self.__dict__)  # (the cache too: what a syndrome decodes to does not depend on the metric)
         out.soft_output, out.soft_bins = metric, int(bins)
         return out
-
-    @property
-    def num_detectors(self) -> int:
-        return self.graph.num_detectors
-
-    @property
-    def num_observables(self) -> int:
-        return self._n_obs
 
     def info(self) -> dict:
         return self.graph.info()
@@ -627,52 +715,11 @@ class UnionFindDecoder:
         assert not s[1:].any(), "the correction does not reproduce the syndrome"
         return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft
 
-    def _decoded(self, dets):
-        """Per row the cache entry of its detector columns (``None`` for a row without defects, whatever its heralds)."""
-        d = np.asarray(dets, dtype=np.bool_)
-        if d.ndim != 2 or d.shape[1] != self.num_detectors:
-            raise ValueError(f"dets must be [n, {self.num_detectors}], got shape {d.shape}")
+    def _decode_bits(self, bits: np.ndarray):
+        """One row's detector bits: the defects of its nodes, the edges of its heralds that are set erased."""
         g = self.graph
-        out = [None] * len(d)
-        rows = np.flatnonzero(d[:, g.node_det].any(axis=1))
-        if not len(rows):
-            return out
-        uniq, inv = np.unique(_pack(d[rows]), axis=0, return_inverse=True)
-        inv = np.asarray(inv).reshape(-1)
-        entries = []
-        for k in uniq:
-            key = k.tobytes()
-            if key not in self._cache:
-                bits = np.unpackbits(k, bitorder="little", count=self.num_detectors)
-                erased = [g.herald_edges[g.herald_ptr[h]:g.herald_ptr[h + 1]] for h in np.flatnonzero(bits[g.herald_det])]
-                self._cache[key] = self._decode_one_soft(np.flatnonzero(bits[g.node_det]) + 1,
-                                                         np.unique(np.concatenate(erased)) if erased else ())
-            entries.append(self._cache[key])
-        for r, i in zip(rows, inv):
-            out[r] = entries[i]
-        return out
-
-    def predictions(self, dets) -> np.ndarray:
-        """uint64 ``[n]``: the predicted observable mask of every row (bit ``k`` = observable ``k``; 0 for a miss) - what the
-        device kernel writes to ``d_pred``."""
-        return np.array([0 if e is None else e[0] for e in self._decoded(dets)], dtype=np.uint64)
-
-    def decode(self, dets) -> np.ndarray:
-        """bool ``[n, num_observables]``: the predicted observable flips of detector rows bool ``[n, num_detectors]``."""
-        p = self.predictions(dets)
-        return ((p[:, None] >> np.arange(self._n_obs, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.bool_)
-
-    def missed(self, dets) -> np.ndarray:
-        """bool ``[n]``: the rows whose growth stopped with an active cluster left (no flip is predicted for them)."""
-        return np.array([e is not None and e[1] for e in self._decoded(dets)], dtype=np.bool_)
-
-    def flipped_edges(self, dets) -> list:
-        """Per row the edges of its correction (int64, ascending; empty for a row without defects and for a miss)."""
-        return [np.zeros(0, np.int64) if e is None else e[2] for e in self._decoded(dets)]
-
-    def growth_rounds(self, dets) -> np.ndarray:
-        """int64 ``[n]``: the growth rounds every row took."""
-        return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
+        erased = [g.herald_edges[g.herald_ptr[h]:g.herald_ptr[h + 1]] for h in np.flatnonzero(bits[g.herald_det])]
+        return self._decode_one_soft(np.flatnonzero(bits[g.node_det]) + 1, np.unique(np.concatenate(erased)) if erased else ())
 
     def soft_outputs(self, dets) -> np.ndarray:
         """int64 ``[n, 4]``: per row ``rounds``, ``full_edges``, ``largest_cluster`` and ``correction_weight`` ("Soft outputs" in
@@ -693,52 +740,35 @@ class UnionFindDecoder:
                 np.bincount(bins[np.asarray(wrong, dtype=np.bool_)], minlength=self.soft_bins).astype(np.int64))
 
     # -- the device side -------------------------------------------------------------------------------------------------
+    def _handle(self, hp, n_cols: int):
+        return hp.uf_create(self.graph, n_cols, self.edge_caps), hp.uf_decode_device, hp.uf_destroy
+
     def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
                       stream: int = 0, soft: bool = False):
-        """``(predictions uint64[n], (kept, wrong, missed))`` for ``n`` bit-packed rows already in HBM (detectors, then
-        observables; ``n_cols`` columns, default ``num_detectors + num_observables``; ``d_xor`` / ``d_test``: device masks of
-        ``ceil(n_cols / 8)`` bytes) by one ``tsim_uf`` handle on ``hp``'s device, created and destroyed here.  A row that is
-        not kept and a miss predict 0.  Returns when the results are on the host.  ``soft`` (the decoder of
-        :meth:`with_soft_output`; ``tsim_uf_decode_soft_device``): two more results, the soft outputs of every row as uint32
-        ``[n, 4]`` (zeros for a row that is not kept) and ``(kept int64[soft_bins], errors int64[soft_bins])``."""
-        if soft and self.soft_output is None:
+        """``(predictions uint64[n], (kept, wrong, missed))`` of ``n`` bit-packed rows already in HBM by one ``tsim_uf`` handle on
+        ``hp``'s device, created and destroyed here: every argument and result as the base class states them.  ``soft`` (the
+        decoder of :meth:`with_soft_output`; ``tsim_uf_decode_soft_device``): two more results, the soft outputs of every row as
+        uint32 ``[n, 4]`` (zeros for a row that is not kept) and ``(kept int64[soft_bins], errors int64[soft_bins])``."""
+        if not soft:
+            return self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream)
+        if self.soft_output is None:
             raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
-        nd = self.num_detectors
-        n_cols = nd + self._n_obs if n_cols is None else int(n_cols)
-        h = hp.uf_create(self.graph, n_cols, self.edge_caps)
-        bufs = []
+        values = np.zeros((int(n), 4), np.uint32)
+        hist = np.zeros(2 * self.soft_bins, np.uint64)
+        d_values, d_hist = hp.malloc(values.nbytes + 16), hp.malloc(hist.nbytes + 16)
         try:
-            pred = np.zeros(int(n), np.uint64)
-            cnt = np.zeros(3, np.uint64)
-            d_pred, d_cnt = hp.malloc(pred.nbytes + 16), hp.malloc(cnt.nbytes + 16)
-            bufs += [d_pred, d_cnt]
-            hp.h2d(d_cnt, cnt)
-            if soft:
-                values = np.zeros((int(n), 4), np.uint32)
-                hist = np.zeros(2 * self.soft_bins, np.uint64)
-                d_values, d_hist = hp.malloc(values.nbytes + 16), hp.malloc(hist.nbytes + 16)
-                bufs += [d_values, d_hist]
-                hp.h2d(d_hist, hist)
-                hp.uf_decode_soft_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, self.soft_output, self.soft_bins,
-                                         d_hist.ptr, d_soft=d_values.ptr, d_pred=d_pred.ptr, d_xor=d_xor, d_test=d_test, stream=stream)
-            else:
-                hp.uf_decode_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, d_pred=d_pred.ptr, d_xor=d_xor,
-                                    d_test=d_test, stream=stream)
-            hp.stream_synchronize(stream)
-            if n:
-                hp.d2h(pred, d_pred)
-            hp.d2h(cnt, d_cnt)
-            if not soft:
-                return pred, tuple(int(x) for x in cnt)
+            hp.h2d(d_hist, hist)
+            pred, cnt = self._decode_device(
+                hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream,
+                lambda *a, **k: hp.uf_decode_soft_device(*a, self.soft_output, self.soft_bins, d_hist.ptr, d_soft=d_values.ptr, **k))
             if n:
                 hp.d2h(values, d_values)
             hp.d2h(hist, d_hist)
             hist = hist.astype(np.int64)
-            return pred, tuple(int(x) for x in cnt), values, (hist[:self.soft_bins].copy(), hist[self.soft_bins:].copy())
+            return pred, cnt, values, (hist[:self.soft_bins].copy(), hist[self.soft_bins:].copy())
         finally:
-            hp.uf_destroy(h)
-            for b in bufs:
-                b.free()
+            d_values.free()
+            d_hist.free()
 
 
 class UnionFindWindow(NamedTuple):
@@ -759,7 +789,7 @@ class UnionFindWindow(NamedTuple):
     herald_edges: np.ndarray | None = None
 
 
-class WindowedUnionFindDecoder:
+class WindowedUnionFindDecoder(_RowDecoder):
     """Sliding-window union-find decoding of a :class:`DecodingGraph` (module docstring): windows of ``window`` detector columns
     that advance by ``commit`` columns, each decoded by the rule of :class:`UnionFindDecoder`; only the flips of committed edges
     are kept and the defects they leave go to the next window.  The per-shot state on the device is that of one window, so the
@@ -799,16 +829,8 @@ class WindowedUnionFindDecoder:
         ``window`` in detector columns (a round of ``rotated_surface_code_memory(d, ...)`` is ``d * d - 1`` columns), ``weights``
         and ``resolution`` as in :meth:`UnionFindDecoder.from_circuit`.  ``heralds``: the graph is built with heralds
         (``DecodingGraph.from_form(form, heralds=True, limit=None)``); ``commit`` and ``window`` then count non-herald detectors."""
-        if weights not in (None, "probability"):
-            raise ValueError(f'weights = {weights!r}: None or "probability"')
-        if isinstance(circuit, str):
-            from .clifford import CliffordCircuit
-
-            circuit = CliffordCircuit(circuit)
-        form = circuit.compile_faults()
-        graph = DecodingGraph.from_form(form, heralds=True, limit=None) if heralds else DecodingGraph.from_form(form, limit=None)
-        return cls(graph, commit, window, int(form.n_out) - int(form.num_detectors), None if weights is None else graph.growth_caps(resolution),
-                   heralds=heralds)
+        graph, n_obs, caps = cls._of_circuit(circuit, weights, resolution, heralds, None)
+        return cls(graph, commit, window, n_obs, caps, heralds=heralds)
 
     # -- the windows -----------------------------------------------------------------------------------------------------
     def _build_windows(self) -> list:
@@ -885,14 +907,6 @@ class WindowedUnionFindDecoder:
         """Per window a :class:`UnionFindWindow`: what the device tables are compared with, and what a reader inspects."""
         return list(self._windows)
 
-    @property
-    def num_detectors(self) -> int:
-        return self.graph.num_detectors
-
-    @property
-    def num_observables(self) -> int:
-        return self._n_obs
-
     def info(self) -> dict:
         return dict(self.graph.info(), n_windows=len(self._windows), max_window_nodes=max(w.graph.n_nodes for w in self._windows),
                     max_window_edges=max(w.graph.n_edges for w in self._windows))
@@ -932,71 +946,9 @@ class WindowedUnionFindDecoder:
         assert not r.any(), "the correction does not reproduce the syndrome"
         return prediction, False, np.array(sorted(flipped), np.int64), most
 
-    def _decoded(self, dets):
-        """Per row the cache entry of its detector columns (``None`` for a row without defects, whatever its heralds)."""
-        d = np.asarray(dets, dtype=np.bool_)
-        if d.ndim != 2 or d.shape[1] != self.num_detectors:
-            raise ValueError(f"dets must be [n, {self.num_detectors}], got shape {d.shape}")
-        out = [None] * len(d)
-        rows = np.flatnonzero((d[:, self.graph.node_det] if self.graph.n_heralds else d).any(axis=1))
-        if not len(rows):
-            return out
-        uniq, inv = np.unique(_pack(d[rows]), axis=0, return_inverse=True)
-        inv = np.asarray(inv).reshape(-1)
-        entries = []
-        for k in uniq:
-            key = k.tobytes()
-            if key not in self._cache:
-                self._cache[key] = self._decode_row(np.unpackbits(k, bitorder="little", count=self.num_detectors).astype(np.bool_))
-            entries.append(self._cache[key])
-        for r, i in zip(rows, inv):
-            out[r] = entries[i]
-        return out
-
-    def predictions(self, dets) -> np.ndarray:
-        """uint64 ``[n]``: the predicted observable mask of every row (0 for a miss) - what the device kernel writes to ``d_pred``."""
-        return np.array([0 if e is None else e[0] for e in self._decoded(dets)], dtype=np.uint64)
-
-    def decode(self, dets) -> np.ndarray:
-        """bool ``[n, num_observables]``: the predicted observable flips of detector rows bool ``[n, num_detectors]``."""
-        p = self.predictions(dets)
-        return ((p[:, None] >> np.arange(self._n_obs, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.bool_)
-
-    def missed(self, dets) -> np.ndarray:
-        """bool ``[n]``: the rows with a window whose growth stopped with an active cluster left (they predict no flip)."""
-        return np.array([e is not None and e[1] for e in self._decoded(dets)], dtype=np.bool_)
-
-    def flipped_edges(self, dets) -> list:
-        """Per row the committed edges of its correction, as edges of ``graph`` (int64, ascending; empty for a miss)."""
-        return [np.zeros(0, np.int64) if e is None else e[2] for e in self._decoded(dets)]
-
-    def growth_rounds(self, dets) -> np.ndarray:
-        """int64 ``[n]``: per row the most growth rounds any of its windows took."""
-        return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
+    _decode_bits = _decode_row
 
     # -- the device side -------------------------------------------------------------------------------------------------
-    def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
-                      stream: int = 0):
-        """:meth:`UnionFindDecoder.decode_device`, by one ``tsim_ufw`` handle on ``hp``'s device (the library builds the windows
-        itself), created and destroyed here."""
-        nd = self.num_detectors
-        n_cols = nd + self._n_obs if n_cols is None else int(n_cols)
+    def _handle(self, hp, n_cols: int):
         h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps, heralds=self.heralds)
-        bufs = []
-        try:
-            pred = np.zeros(int(n), np.uint64)
-            cnt = np.zeros(3, np.uint64)
-            d_pred, d_cnt = hp.malloc(pred.nbytes + 16), hp.malloc(cnt.nbytes + 16)
-            bufs += [d_pred, d_cnt]
-            hp.h2d(d_cnt, cnt)
-            hp.ufw_decode_device(h, d_rows, n, row_bytes, (nd, nd + self._n_obs), d_cnt.ptr, d_pred=d_pred.ptr, d_xor=d_xor,
-                                 d_test=d_test, stream=stream)
-            hp.stream_synchronize(stream)
-            if n:
-                hp.d2h(pred, d_pred)
-            hp.d2h(cnt, d_cnt)
-            return pred, tuple(int(x) for x in cnt)
-        finally:
-            hp.ufw_destroy(h)
-            for b in bufs:
-                b.free()
+        return h, hp.ufw_decode_device, hp.ufw_destroy
