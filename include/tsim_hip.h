@@ -542,7 +542,9 @@ int tsim_faults_weight_info(const tsim_faults *h, int64_t out[8]);
 /* ---- counts over bit-packed device rows (the samplers' count(): rates without moving the rows to the host) ---------------
  * Row r starts at byte r * row_bytes of d_rows and holds n_cols columns little-endian (row_bytes >= ceil(n_cols/8); the
  * buffer spans n * row_bytes bytes).  Optional rows of ceil(n_cols/8) bytes: d_xor is XORed into every row first, and a
- * row is KEPT iff (row ^ xor) & test == 0 (d_test NULL: every row is kept).  ACCUMULATED into d_counts (uint64, 8-byte
+ * row is KEPT iff (row ^ xor) & test == 0 (d_test NULL: every row is kept).  The pad bits of d_test (columns n_cols and up of
+ * its last byte) MUST BE ZERO here: this entry point compares the mask's whole bytes, so a set pad bit tests a bit of the row
+ * that is no column (the handles below cut the mask's pad bits away themselves).  ACCUMULATED into d_counts (uint64, 8-byte
  * aligned, never zeroed here; 2 + n_cols + 2^n_hist entries):
  *   [0] kept rows;  [1] kept rows with a set bit in columns obs_lo .. obs_hi - 1;  [2 + c] kept rows with column c set;
  *   [2 + n_cols + b] kept rows whose bits at hist_cols[0 .. n_hist-1] (host array, distinct columns, n_hist <= 16) spell

@@ -1,21 +1,11 @@
 // tsim_affine.hip - the affine measurement sampler (tsim_affine_*): a handle of its own, bound to one device, holding the
 // CSR of the outputs' column lists over [f | random symbols] and their constant bits; the kernel is csrc/tsim_affine.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_affine.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
 #include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define AFF_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int kLdsBudget = 64 * 1024;             // dynamic LDS per block
@@ -95,10 +85,7 @@ extern "C" int tsim_affine_create(int32_t device, int32_t num_f, int32_t n_rando
   } catch (const std::bad_alloc &) {
     return tsim_fail(TSIM_ENOMEM, "out of host memory for the per-window CSR");
   }
-  int count = 0;
-  AFF_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  AFF_TRY(hipSetDevice(device));
+  if (const int rc = tsimh::open_device(device, nullptr)) return rc;
   tsim_affine *h = new (std::nothrow) tsim_affine();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -149,7 +136,7 @@ extern "C" int tsim_affine_sample_device(tsim_affine *h, const uint64_t *d_f, in
     return tsim_fail(TSIM_EINVAL, "out_row_bytes = %lld for %lld bytes per row", (long long)out_row_bytes, (long long)out_used);
   if (B == 0 || n_cols == 0) return TSIM_OK;
   if (!d_out || (h->num_f > 0 && !d_f)) return tsim_fail(TSIM_EINVAL, "NULL buffer");
-  AFF_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   const uint8_t *f = reinterpret_cast<const uint8_t *>(d_f);
   affk::Args A;
   m2dk::Args &a = A.m;
@@ -184,7 +171,7 @@ extern "C" int tsim_affine_sample_device(tsim_affine *h, const uint64_t *d_f, in
   const size_t lds = (size_t)nw * per_wave;
   void (*k)(affk::Args) = out_packed ? affk::k_affine<true> : affk::k_affine<false>;
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * nw), lds, stream ? (hipStream_t)stream : h->stream, A);
-  AFF_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return TSIM_OK;
 }
 

@@ -2,22 +2,12 @@
 // compiled form of tsim_amd/faults.py (classes of noise sites, their tables, the error bit -> outputs CSR); the kernel is
 // csrc/tsim_faults.hip.h.  The same handle draws rows conditioned on exactly k fired sites (tsim_amd/fixed_weight.py) once
 // tsim_faults_set_split gave it the table of the class counts; that kernel is csrc/tsim_faults_weight.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_faults_weight.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
 #include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define FLT_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int64_t kLds = 160 * 1024;          // all the LDS a workgroup may take
@@ -139,10 +129,7 @@ extern "C" int tsim_faults_create(int32_t device, const tsim_faults_desc *d, tsi
   }
   for (int32_t j = 0; j < n_out; ++j)
     if (d->out_const[j] & 1) cwords[j >> 5] |= 1u << (j & 31);
-  int count = 0;
-  FLT_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  FLT_TRY(hipSetDevice(device));
+  if (const int rc = tsimh::open_device(device, nullptr)) return rc;
   tsim_faults *h = new (std::nothrow) tsim_faults();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -237,15 +224,15 @@ extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t firs
   bool run = false;
   const int rc = check_request(h, B, first_shot, d_out, out_row_bytes, out_packed, col0, n_cols, &run);
   if (rc != TSIM_OK || !run) return rc;
-  FLT_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   void (*k)(fltk::Args) = out_packed ? (h->tab_lds ? fltk::k_faults<true, true> : fltk::k_faults<true, false>)
                                      : (h->tab_lds ? fltk::k_faults<false, true> : fltk::k_faults<false, false>);
   if (!h->attr_set) {
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
     h->attr_set = true;
   }
   fltk::Args A;
@@ -257,7 +244,7 @@ extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t firs
   const size_t lds = (size_t)h->tab_bytes + (size_t)nw * 256 * (size_t)h->S;
   const int64_t blocks = std::min<int64_t>((tiles + nw - 1) / nw, 256 * 8);
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * nw), lds, s, A);
-  FLT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return TSIM_OK;
 }
 
@@ -287,16 +274,16 @@ extern "C" int tsim_faults_set_split(tsim_faults *h, int32_t kmax, const uint32_
     }
     rest += h->class_n[c];
   }
-  FLT_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   if (h->split) {  // (hipFree waits for the launches that read it)
-    FLT_TRY(hipFree(h->split));
+    HIP_TRY(hipFree(h->split));
     h->split = nullptr;
     h->kmax = -1;
   }
   void *p = nullptr;
-  FLT_TRY(hipMalloc(&p, std::max<size_t>(1, (size_t)n_words) * 4));
+  HIP_TRY(hipMalloc(&p, std::max<size_t>(1, (size_t)n_words) * 4));
   h->split = static_cast<uint32_t *>(p);
-  if (n_words) FLT_TRY(hipMemcpy(p, split_thr, (size_t)n_words * 4, hipMemcpyHostToDevice));
+  if (n_words) HIP_TRY(hipMemcpy(p, split_thr, (size_t)n_words * 4, hipMemcpyHostToDevice));
   // ---- LDS: the outcome tables and the split table when they are small (no gap rows here), then lds_rule with the list
   int64_t tab_bytes = (2ll * h->form.n_outcomes + n_words) * 4;
   h->w_tab_lds = tab_bytes <= fltk::kTabLdsBytes;
@@ -317,15 +304,15 @@ extern "C" int tsim_faults_sample_weight_device(tsim_faults *h, int32_t k, int64
   bool run = false;
   const int rc = check_request(h, B, first_shot, d_out, out_row_bytes, out_packed, col0, n_cols, &run);
   if (rc != TSIM_OK || !run) return rc;
-  FLT_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   void (*kern)(fltk::WeightArgs) = out_packed ? (h->w_tab_lds ? fltk::k_faults_weight<true, true> : fltk::k_faults_weight<true, false>)
                                               : (h->w_tab_lds ? fltk::k_faults_weight<false, true> : fltk::k_faults_weight<false, false>);
   if (!h->w_attr_set) {
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    FLT_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
     h->w_attr_set = true;
   }
   fltk::WeightArgs W;
@@ -340,7 +327,7 @@ extern "C" int tsim_faults_sample_weight_device(tsim_faults *h, int32_t k, int64
   const size_t lds = (size_t)h->w_tab_bytes + (size_t)nw * (256 * (size_t)h->w_S + 4 * fltk::kListWords);
   const int64_t blocks = std::min<int64_t>((tiles + nw - 1) / nw, 256 * 8);
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * nw), lds, s, W);
-  FLT_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return TSIM_OK;
 }
 

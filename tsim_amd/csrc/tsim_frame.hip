@@ -1,22 +1,12 @@
 // tsim_frame.hip - the Pauli-frame sampler (tsim_frame_*): a handle of its own, bound to one device, holding the compiled
 // form of tsim_amd/frame.py (operation batches, noise sites and their tables, output lists) and the record-flip scratch; the
 // kernels are csrc/tsim_frame.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_frame.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
 #include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define FRM_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int64_t kFrameLds = 160 * 1024;         // the frames of a tile: all the LDS a workgroup may take
@@ -205,10 +195,7 @@ extern "C" int tsim_frame_create(int32_t device, const tsim_frame_desc *d, tsim_
   } catch (const std::bad_alloc &) {
     return tsim_fail(TSIM_ENOMEM, "out of host memory for the per-window CSR");
   }
-  int count = 0;
-  FRM_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  FRM_TRY(hipSetDevice(device));
+  if (const int rc = tsimh::open_device(device, nullptr)) return rc;
   tsim_frame *h = new (std::nothrow) tsim_frame();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -282,14 +269,14 @@ extern "C" int tsim_frame_sample_device(tsim_frame *h, int64_t B, int64_t first_
     return tsim_fail(TSIM_EINVAL, "out_row_bytes = %lld for %lld bytes per row", (long long)out_row_bytes, (long long)out_used);
   if (B == 0 || n_cols == 0) return TSIM_OK;
   if (!d_out) return tsim_fail(TSIM_EINVAL, "NULL buffer");
-  FRM_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const int T = 1 << h->log2T;
   const size_t frame_lds = 16 * (size_t)h->nq * T;
   // threads of a block: what the largest batch keeps busy, 4 .. 16 waves (a block is often alone on its CU: waves hide latency)
   const int threads = (int)std::min<int64_t>(frmk::kMaxThreads, std::max<int64_t>(256, ((int64_t)h->max_items * T + 63) / 64 * 64));
   if (!h->attr_set) {
-    FRM_TRY(hipFuncSetAttribute((const void *)frmk::k_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFrameLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)frmk::k_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFrameLds));
     h->attr_set = true;
   }
   uint32_t n0 = 0x6E6F6973u, n1 = 0x6672616Du;  // the request's noise key: threefry2x32(key, ("nois", "fram"))
@@ -308,7 +295,7 @@ extern "C" int tsim_frame_sample_device(tsim_frame *h, int64_t B, int64_t first_
     A.n0 = n0;
     A.n1 = n1;
     hipLaunchKernelGGL(frmk::k_frame, dim3((unsigned)((words + T - 1) / T)), dim3(threads), frame_lds, s, A);
-    FRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     uint8_t *dst = d_out + done * out_row_bytes;
     frmk::OutArgs O;
     m2dk::Args &a = O.m;
@@ -341,7 +328,7 @@ extern "C" int tsim_frame_sample_device(tsim_frame *h, int64_t B, int64_t first_
     const int64_t blocks = std::min<int64_t>((words + nw - 1) / nw, 256 * 8 * 4 / nw);
     void (*k)(frmk::OutArgs) = out_packed ? frmk::k_frame_out<true> : frmk::k_frame_out<false>;
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * nw), (size_t)nw * per_wave, s, O);
-    FRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   return TSIM_OK;
 }

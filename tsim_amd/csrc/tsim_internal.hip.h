@@ -12,7 +12,7 @@
 //   tsim_pcg.cpp       numpy-stream-exact host channel sampler (PCG64 + ziggurat), no HIP
 //   tsim_dist.hip      RCCL communicator (shot sharding over the GPUs of a node)
 #pragma once
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"  // tsim_fail, HIP_TRY
 #include "tsim_kernels.hip.h"
 #include "tsim_kernel4.hip.h"
 #ifndef TSIM_HARD_NW
@@ -44,17 +44,6 @@ constexpr int kMinLists = 4;
 constexpr int kHardLdsKb = 128;      // k_sample4h: a first-pass block still fits next to a hard-row block
 constexpr int kV4Block = 256;        // k_sample4 block
 constexpr int kWideGlobGraphs = 48;  // components of up to this many graphs whose column tables do not fit the LDS run k_sample_wide with the tables in the L2
-
-// ---------------------------------------------------------------------------
-// errors: every entry point returns 0 or a negative TSIM_E* code; the message is thread-local
-// ---------------------------------------------------------------------------
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 // fn(0) .. fn(n - 1) on the process-wide worker pool (tsim_pool.cpp): at most max_threads threads work on the call, the caller
 // among them; bounded however many components a program has, and safe to nest (a thread per level, created

@@ -1,22 +1,12 @@
 // tsim_m2d.hip - the measurements -> detection events converter (tsim_m2d_*): a handle of its own, bound to one device,
 // holding the CSR of the outputs' record lists and their reference bits; the kernel is csrc/tsim_m2d.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_m2d.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define M2D_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int kLdsBudget = 64 * 1024;             // dynamic LDS per block
@@ -101,10 +91,7 @@ extern "C" int tsim_m2d_create(int32_t device, int32_t num_measurements, int32_t
   } catch (const std::bad_alloc &) {
     return tsim_fail(TSIM_ENOMEM, "out of host memory for the per-window CSR");
   }
-  int count = 0;
-  M2D_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  M2D_TRY(hipSetDevice(device));
+  if (const int rc = tsimh::open_device(device, nullptr)) return rc;
   tsim_m2d *h = new (std::nothrow) tsim_m2d();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -182,7 +169,7 @@ static int m2d_launch(tsim_m2d *h, const uint8_t *d_meas, int64_t B, int64_t in_
   void (*k)(m2dk::Args) = in_packed ? (out_packed ? m2dk::k_m2d<true, true> : m2dk::k_m2d<true, false>)
                                     : (out_packed ? m2dk::k_m2d<false, true> : m2dk::k_m2d<false, false>);
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * nw), lds, s, a);
-  M2D_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return TSIM_OK;
 }
 
@@ -192,7 +179,7 @@ extern "C" int tsim_m2d_convert_device(tsim_m2d *h, const uint8_t *d_meas, int64
   if (int r = m2d_check(h, B, in_row_bytes, in_packed, out_row_bytes, out_packed, col0, n_cols)) return r;
   if (B == 0 || n_cols == 0) return TSIM_OK;
   if (!d_out || (h->M > 0 && !d_meas)) return tsim_fail(TSIM_EINVAL, "NULL buffer");
-  M2D_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   return m2d_launch(h, d_meas, B, in_row_bytes, in_packed, d_out, out_row_bytes, out_packed, col0, n_cols,
                     stream ? (hipStream_t)stream : h->stream);
 }
@@ -203,8 +190,8 @@ static int m2d_grow(tsim_m2d *h, int64_t in_bytes, int64_t out_bytes) {
     if (h->h_in) (void)hipHostFree(h->h_in);
     h->d_in = h->h_in = nullptr;
     h->in_cap = 0;
-    M2D_TRY(hipMalloc(&h->d_in, (size_t)in_bytes));
-    M2D_TRY(hipHostMalloc(&h->h_in, (size_t)in_bytes, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&h->d_in, (size_t)in_bytes));
+    HIP_TRY(hipHostMalloc(&h->h_in, (size_t)in_bytes, hipHostMallocDefault));
     h->in_cap = in_bytes;
   }
   if (out_bytes > h->out_cap) {
@@ -212,8 +199,8 @@ static int m2d_grow(tsim_m2d *h, int64_t in_bytes, int64_t out_bytes) {
     if (h->h_out) (void)hipHostFree(h->h_out);
     h->d_out = h->h_out = nullptr;
     h->out_cap = 0;
-    M2D_TRY(hipMalloc(&h->d_out, (size_t)out_bytes));
-    M2D_TRY(hipHostMalloc(&h->h_out, (size_t)out_bytes, hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&h->d_out, (size_t)out_bytes));
+    HIP_TRY(hipHostMalloc(&h->h_out, (size_t)out_bytes, hipHostMallocDefault));
     h->out_cap = out_bytes;
   }
   return TSIM_OK;
@@ -224,7 +211,7 @@ extern "C" int tsim_m2d_convert(tsim_m2d *h, const uint8_t *meas, int64_t B, int
   if (int r = m2d_check(h, B, in_row_bytes, in_packed, out_row_bytes, out_packed, col0, n_cols)) return r;
   if (B == 0 || n_cols == 0) return TSIM_OK;
   if (!out || (h->M > 0 && !meas)) return tsim_fail(TSIM_EINVAL, "NULL buffer");
-  M2D_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   // chunks of whole 64-row tiles, about kChunkBytes of input + output each: device memory stays bounded for any B
   int64_t rows = kChunkBytes / std::max<int64_t>(1, in_row_bytes + out_row_bytes);
   rows = std::max<int64_t>(64, rows / 64 * 64);
@@ -235,12 +222,12 @@ extern "C" int tsim_m2d_convert(tsim_m2d *h, const uint8_t *meas, int64_t B, int
     const size_t ib = (size_t)(n * in_row_bytes), ob = (size_t)(n * out_row_bytes);
     if (ib) {
       std::memcpy(h->h_in, meas + r0 * in_row_bytes, ib);
-      M2D_TRY(hipMemcpyAsync(h->d_in, h->h_in, ib, hipMemcpyHostToDevice, h->stream));
+      HIP_TRY(hipMemcpyAsync(h->d_in, h->h_in, ib, hipMemcpyHostToDevice, h->stream));
     }
     if (int r = m2d_launch(h, h->d_in, n, in_row_bytes, in_packed, h->d_out, out_row_bytes, out_packed, col0, n_cols, h->stream))
       return r;
-    M2D_TRY(hipMemcpyAsync(h->h_out, h->d_out, ob, hipMemcpyDeviceToHost, h->stream));
-    M2D_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(h->h_out, h->d_out, ob, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     std::memcpy(out + r0 * out_row_bytes, h->h_out, ob);
   }
   return TSIM_OK;

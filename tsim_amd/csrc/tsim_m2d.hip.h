@@ -15,8 +15,7 @@
 // Every address is formed in 64 bits (B x row bytes may exceed 2^31).  Phase 2 is a function of its own (outputs): the affine
 // measurement sampler (tsim_affine.hip.h) builds its masks differently and shares it.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "tsim_bitrows.hip.h"
 
 namespace m2dk {
 
@@ -40,12 +39,7 @@ struct Args {
   int win, n_win;         // columns per window (masks per wave, a multiple of 512 when n_win > 1), windows
 };
 
-// keeps the compiler from moving LDS accesses of this wave across the point (the wave's LDS operations execute in order)
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using bitrows::wsync;  // (csrc/tsim_bitrows.hip.h; the samplers that share this file call it as m2dk::wsync)
 
 // n contiguous bytes global -> LDS (dwords when w4: src and dst 4-aligned)
 __device__ __forceinline__ void load_span(uint8_t *stage, const uint8_t *src, int n, int w4, int lane) {

@@ -1,23 +1,13 @@
 // tsim_pairs.hip - pair counts over bit-packed device rows (tsim_pairs_*): a handle of its own, bound to one device,
 // holding the selected columns, the bit-plane workspace of one slab of rows and the uint64 counter matrix; the kernels
 // are csrc/tsim_pairs.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_pairs.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
 #include <numeric>
 #include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define PAIRS_TRY(expr)                                                                      \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int kMaxPairCols = 4096;
@@ -65,10 +55,7 @@ extern "C" int tsim_pairs_create(int32_t device, int32_t n_cols, const int32_t *
     }
   }
   aoff.push_back(n_pair);
-  int count = 0;
-  PAIRS_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  PAIRS_TRY(hipSetDevice(device));
+  if (const int rc = tsimh::open_device(device, nullptr)) return rc;
   tsim_pairs *h = new (std::nothrow) tsim_pairs();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -112,12 +99,11 @@ extern "C" int tsim_pairs_add_device(tsim_pairs *h, const uint8_t *d_rows, int64
                                      const uint8_t *d_test, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "pair counter is NULL");
   if (n < 0) return tsim_fail(TSIM_EINVAL, "negative n");
-  const int64_t used = ((int64_t)h->n_cols + 7) / 8;
-  if (row_bytes < used || row_bytes > 0x7FFFFFFF)
-    return tsim_fail(TSIM_EINVAL, "row_bytes = %lld for %lld bytes per row", (long long)row_bytes, (long long)used);
+  const int64_t used = tsimh::row_used(h->n_cols, row_bytes);
+  if (used < 0) return (int)used;
   if (n > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
   if (n == 0) return TSIM_OK;
-  PAIRS_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
 
   pairsk::PlaneArgs p{};
   p.rb = row_bytes;
@@ -147,12 +133,12 @@ extern "C" int tsim_pairs_add_device(tsim_pairs *h, const uint8_t *d_rows, int64
     p.rows = d_rows + r0 * row_bytes;
     const int64_t groups = (p.n + kGroupRows - 1) / kGroupRows;
     hipLaunchKernelGGL(pairsk::k_planes, dim3((unsigned)(groups * pairsk::kGroup / pairsk::kWaves)), dim3(64 * pairsk::kWaves), 0, s, p);
-    PAIRS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     g.groups = (int)groups;
     const int64_t split = std::max<int64_t>(1, std::min<int64_t>(kTargetBlocks / n_tiles,
                                                                  (groups + kMinGroupsPerBlock - 1) / kMinGroupsPerBlock));
     hipLaunchKernelGGL(pairsk::k_gemm, dim3((unsigned)n_tiles, (unsigned)split), dim3(256), 0, s, g);
-    PAIRS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     h->launches += 2;
   }
   return TSIM_OK;
@@ -160,10 +146,10 @@ extern "C" int tsim_pairs_add_device(tsim_pairs *h, const uint8_t *d_rows, int64
 
 extern "C" int tsim_pairs_read(tsim_pairs *h, uint64_t *out, void *stream) {
   if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
-  PAIRS_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   const size_t k = (size_t)h->k;
-  PAIRS_TRY(hipMemcpyAsync(out, h->d_counts, sizeof(uint64_t) * k * k, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  PAIRS_TRY(hipStreamSynchronize((hipStream_t)stream));
+  HIP_TRY(hipMemcpyAsync(out, h->d_counts, sizeof(uint64_t) * k * k, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   // the kernel fills [a][b] for tile(a) <= tile(b) only: the rest is the mirror image
   for (size_t a = pairsk::kTile; a < k; ++a) {
     const size_t lim = a / pairsk::kTile * pairsk::kTile;
@@ -174,8 +160,8 @@ extern "C" int tsim_pairs_read(tsim_pairs *h, uint64_t *out, void *stream) {
 
 extern "C" int tsim_pairs_reset(tsim_pairs *h, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "pair counter is NULL");
-  PAIRS_TRY(hipSetDevice(h->device));
-  PAIRS_TRY(hipMemsetAsync(h->d_counts, 0, sizeof(uint64_t) * (size_t)h->k * h->k, (hipStream_t)stream));
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemsetAsync(h->d_counts, 0, sizeof(uint64_t) * (size_t)h->k * h->k, (hipStream_t)stream));
   return TSIM_OK;
 }
 

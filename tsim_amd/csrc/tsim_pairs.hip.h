@@ -1,6 +1,6 @@
 // tsim_pairs.hip.h - pair counts over bit-packed rows: N[a][b] = kept rows with selected columns a and b both set, a
-// binary X^T X.  A row is kept iff (row ^ xor) & test == 0 and the counts are taken over row ^ xor, as in k_tally
-// (csrc/tsim_tally.hip.h): the diagonal is the tally's column counts.  Two kernels per slab of rows:
+// binary X^T X.  Rows, xor, test and the keep rule are the row contract of tsim_bitrows.hip.h and the counts are taken over
+// row ^ xor, as in k_tally (csrc/tsim_tally.hip.h): the diagonal is the tally's column counts.  Two kernels per slab of rows:
 //   k_planes  one wave owns a tile of 64 rows (row r = lane r).  The rows go through LDS in chunks of kChunk bytes
 //             (coalesced loads, dwords where the pointer and the stride allow).  Pass 1, only with a test mask: lane r
 //             ORs (row ^ xor) & test over the chunks the mask touches.  Pass 2: per selected column one ballot turns
@@ -18,15 +18,13 @@
 //             integer adds commute, the counts do not depend on the schedule.  A launch covers at most 2^20 rows, so a
 //             uint32 accumulator cannot overflow.  Tiles (ti, tj) with ti < tj are written at [a][b] only; the host
 //             mirrors them on read.
-// Every address is formed in 64 bits.
+// k_planes keeps a stager of its own (stage_chunk): bitrows::stage_rows in its place compiles to another kernel.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "tsim_bitrows.hip.h"
 
 namespace pairsk {
 
-constexpr int kChunk = 128;         // bytes of a row staged at a time (1024 columns)
-constexpr int kStage = kChunk + 4;  // LDS bytes per staged row (33 dwords: lanes fall on distinct banks)
+using namespace bitrows;            // kChunk, kStage, wsync, mask_word, cut_pad (the stager is this file's own: stage_chunk)
 constexpr int kWaves = 4;           // waves per k_planes block
 constexpr int kGroup = 16;          // tiles per group: 1024 rows, 32 dwords per plane
 constexpr int kWords = 2 * kGroup;  // dwords of a plane per group
@@ -52,13 +50,6 @@ struct GemmArgs {
   unsigned long long *counts;  // [k][k]
 };
 
-// keeps the compiler from moving LDS accesses of this wave across the point (the wave's LDS operations execute in order)
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // bytes b0 .. b0 + nb - 1 of `rows` rows -> one LDS row of kStage bytes each
 __device__ __forceinline__ void stage_chunk(uint8_t *stage, const uint8_t *src, int rows, int b0, int nb, long long rb, int w4, int lane) {
   if (w4) {  // (b0 is a multiple of 4; a dword that starts before nb ends inside the row: rb is a multiple of 4)
@@ -71,16 +62,6 @@ __device__ __forceinline__ void stage_chunk(uint8_t *stage, const uint8_t *src, 
     for (int r = 0; r < rows; ++r)
       for (int q = lane; q < nb; q += 64) stage[r * kStage + q] = src[r * rb + b0 + q];
   }
-}
-
-// bytes b .. b + 7 of a mask row of `used` bytes (0 past its end, 0 for no mask); b is wave-uniform
-__device__ __forceinline__ uint64_t mask_word(const uint8_t *m, int b, int used) {
-  if (!m) return 0;
-  uint64_t w = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q)
-    if (b + q < used) w |= (uint64_t)m[b + q] << (8 * q);
-  return w;
 }
 
 __global__ void __launch_bounds__(64 * kWaves) k_planes(PlaneArgs a) {
@@ -110,8 +91,7 @@ __global__ void __launch_bounds__(64 * kWaves) k_planes(PlaneArgs a) {
         const int b = b0 + g * 8;
         uint64_t tw = mask_word(a.test, b, a.used);
         if (tw == 0) continue;
-        const int past = (b + 8) * 8 - a.n_cols;  // pad bits of the last byte are not columns
-        if (past > 0) tw &= past >= 64 ? 0ull : (~0ull >> past);
+        tw = cut_pad(tw, b, a.n_cols);
         const uint64_t v = ((uint64_t)reinterpret_cast<const uint32_t *>(mine + g * 8)[0] |
                             ((uint64_t)reinterpret_cast<const uint32_t *>(mine + g * 8)[1] << 32)) ^ mask_word(a.xr, b, a.used);
         fail |= v & tw;

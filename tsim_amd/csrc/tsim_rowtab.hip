@@ -1,23 +1,13 @@
 // tsim_rowtab.hip - the distinct patterns of bit-packed device rows with exact counts, and a lookup decoder over such a
 // table (tsim_rowtab_*): a handle of its own, bound to one device, holding the key columns, the slots and the counters;
 // the kernels are csrc/tsim_rowtab.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_rowtab.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define ROWTAB_TRY(expr)                                                                     \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int64_t kMaxCapacity = 1ll << 30;
@@ -60,12 +50,8 @@ extern "C" int tsim_rowtab_create(int32_t device, int32_t n_cols, const int32_t 
   std::sort(sorted.begin(), sorted.end());
   for (int i = 1; i < n_key; ++i)
     if (sorted[i] == sorted[i - 1]) return tsim_fail(TSIM_EINVAL, "key column %d is listed twice", sorted[i]);
-  int count = 0;
-  ROWTAB_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  ROWTAB_TRY(hipSetDevice(device));
   int cus = 0;
-  ROWTAB_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  if (const int rc = tsimh::open_device(device, &cus)) return rc;
   tsim_rowtab *h = new (std::nothrow) tsim_rowtab();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -110,9 +96,8 @@ static int rowtab_args(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t
                        rowtabk::Args *a) {
   if (!h) return tsim_fail(TSIM_EINVAL, "row table is NULL");
   if (n < 0) return tsim_fail(TSIM_EINVAL, "negative n");
-  const int64_t used = ((int64_t)h->n_cols + 7) / 8;
-  if (row_bytes < used || row_bytes > 0x7FFFFFFF)
-    return tsim_fail(TSIM_EINVAL, "row_bytes = %lld for %lld bytes per row", (long long)row_bytes, (long long)used);
+  const int64_t used = tsimh::row_used(h->n_cols, row_bytes);
+  if (used < 0) return (int)used;
   if (n > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
   a->rb = row_bytes;
   a->n_cols = h->n_cols;
@@ -124,10 +109,7 @@ static int rowtab_args(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t
   a->direct = h->direct;
   a->kcol = h->d_kcol;
   a->exact = h->exact;
-  a->contig = row_bytes <= rowtabk::kChunk;
-  const bool p4 = reinterpret_cast<uintptr_t>(d_rows) % 4 == 0;
-  a->w4 = p4 && (a->contig || row_bytes % 4 == 0);
-  a->stage_bytes = a->contig ? (int)(64 * row_bytes + 8 + 7) / 8 * 8 : 64 * rowtabk::kStage;
+  tsimh::choose_staging(*a, d_rows, row_bytes);
   a->tags = h->d_tags;
   a->counts = h->d_counts;
   a->keys = h->d_keys;
@@ -148,7 +130,7 @@ extern "C" int tsim_rowtab_add_device(tsim_rowtab *h, const uint8_t *d_rows, int
   rowtabk::Args a{};
   if (int rc = rowtab_args(h, d_rows, n, row_bytes, d_xor, d_test, &a)) return rc;
   if (n == 0) return TSIM_OK;
-  ROWTAB_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   const size_t stage = (size_t)rowtabk::kWaves * a.stage_bytes;
   for (int64_t r0 = 0; r0 < n; r0 += kRowsPerLaunch) {
@@ -156,11 +138,11 @@ extern "C" int tsim_rowtab_add_device(tsim_rowtab *h, const uint8_t *d_rows, int
     a.rows = d_rows + r0 * row_bytes;
     const unsigned blocks = rowtab_blocks(h, a.n);
     hipLaunchKernelGGL(rowtabk::k_claim, dim3(blocks), dim3(64 * rowtabk::kWaves), rowtabk::kCache * 16 + 16 + stage, s, a);
-    ROWTAB_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     ++h->launches;
     if (!h->exact) {  // (the next launch of the stream: every key k_claim stored is visible)
       hipLaunchKernelGGL(rowtabk::k_verify, dim3(blocks), dim3(64 * rowtabk::kWaves), 16 + stage, s, a);
-      ROWTAB_TRY(hipGetLastError());
+      HIP_TRY(hipGetLastError());
       ++h->launches;
     }
   }
@@ -169,9 +151,9 @@ extern "C" int tsim_rowtab_add_device(tsim_rowtab *h, const uint8_t *d_rows, int
 }
 
 static int rowtab_stats(tsim_rowtab *h, uint64_t st[4], hipStream_t s) {
-  ROWTAB_TRY(hipSetDevice(h->device));
-  ROWTAB_TRY(hipMemcpyAsync(st, h->d_stats, 32, hipMemcpyDeviceToHost, s));
-  ROWTAB_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemcpyAsync(st, h->d_stats, 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return TSIM_OK;
 }
 
@@ -188,10 +170,10 @@ extern "C" int tsim_rowtab_read(tsim_rowtab *h, uint8_t *keys_out, uint64_t *cou
                      (unsigned long long)st[3]);
   const size_t cap = (size_t)h->capacity, W = (size_t)h->W, kb = ((size_t)h->n_key + 7) / 8;
   std::vector<uint64_t> tags(cap), counts(cap), keys(h->exact ? 0 : cap * W);
-  ROWTAB_TRY(hipMemcpyAsync(tags.data(), h->d_tags, cap * 8, hipMemcpyDeviceToHost, s));
-  ROWTAB_TRY(hipMemcpyAsync(counts.data(), h->d_counts, cap * 8, hipMemcpyDeviceToHost, s));
-  if (!h->exact) ROWTAB_TRY(hipMemcpyAsync(keys.data(), h->d_keys, cap * W * 8, hipMemcpyDeviceToHost, s));
-  ROWTAB_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(tags.data(), h->d_tags, cap * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(counts.data(), h->d_counts, cap * 8, hipMemcpyDeviceToHost, s));
+  if (!h->exact) HIP_TRY(hipMemcpyAsync(keys.data(), h->d_keys, cap * W * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   int64_t found = 0;
   for (size_t i = 0; i < cap; ++i) {
     if (!tags[i]) continue;
@@ -209,11 +191,11 @@ extern "C" int tsim_rowtab_read(tsim_rowtab *h, uint8_t *keys_out, uint64_t *cou
 
 extern "C" int tsim_rowtab_reset(tsim_rowtab *h, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "row table is NULL");
-  ROWTAB_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
-  ROWTAB_TRY(hipMemsetAsync(h->d_tags, 0, (size_t)h->capacity * 8, s));
-  ROWTAB_TRY(hipMemsetAsync(h->d_counts, 0, (size_t)h->capacity * 8, s));
-  ROWTAB_TRY(hipMemsetAsync(h->d_stats, 0, 32, s));
+  HIP_TRY(hipMemsetAsync(h->d_tags, 0, (size_t)h->capacity * 8, s));
+  HIP_TRY(hipMemsetAsync(h->d_counts, 0, (size_t)h->capacity * 8, s));
+  HIP_TRY(hipMemsetAsync(h->d_stats, 0, 32, s));
   h->rows_added = 0;
   h->loaded = false;
   return TSIM_OK;
@@ -221,8 +203,8 @@ extern "C" int tsim_rowtab_reset(tsim_rowtab *h, void *stream) {
 
 extern "C" int tsim_rowtab_info(tsim_rowtab *h, int64_t out[8]) {
   if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
-  ROWTAB_TRY(hipSetDevice(h->device));
-  ROWTAB_TRY(hipDeviceSynchronize());  // (the counters live on the device: every add so far is waited for)
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());  // (the counters live on the device: every add so far is waited for)
   uint64_t st[4];
   if (int rc = rowtab_stats(h, st, nullptr)) return rc;
   out[0] = h->capacity;
@@ -264,19 +246,19 @@ extern "C" int tsim_rowtab_load(tsim_rowtab *h, const uint8_t *keys, const uint6
     vals[i] = values[r];
     if (!h->exact) std::copy(key.begin(), key.end(), image.begin() + i * W);
   }
-  ROWTAB_TRY(hipSetDevice(h->device));
-  ROWTAB_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
   if (!h->d_values) {
     hipError_t e = hipMalloc(&h->d_values, cap * 8);
     if (e != hipSuccess) return tsim_fail(e == hipErrorOutOfMemory ? TSIM_ENOMEM : TSIM_EHIP, "values of %lld slots: %s", (long long)cap, hipGetErrorString(e));
     h->bytes += (int64_t)cap * 8;
   }
-  ROWTAB_TRY(hipMemcpy(h->d_tags, tags.data(), cap * 8, hipMemcpyHostToDevice));
-  ROWTAB_TRY(hipMemcpy(h->d_values, vals.data(), cap * 8, hipMemcpyHostToDevice));
-  if (!h->exact) ROWTAB_TRY(hipMemcpy(h->d_keys, image.data(), cap * W * 8, hipMemcpyHostToDevice));
-  ROWTAB_TRY(hipMemset(h->d_counts, 0, cap * 8));
+  HIP_TRY(hipMemcpy(h->d_tags, tags.data(), cap * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_values, vals.data(), cap * 8, hipMemcpyHostToDevice));
+  if (!h->exact) HIP_TRY(hipMemcpy(h->d_keys, image.data(), cap * W * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(h->d_counts, 0, cap * 8));
   uint64_t st[4] = {0, (uint64_t)n, 0, 0};
-  ROWTAB_TRY(hipMemcpy(h->d_stats, st, 32, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_stats, st, 32, hipMemcpyHostToDevice));
   h->rows_added = 0;
   h->loaded = true;
   return TSIM_OK;
@@ -291,7 +273,7 @@ extern "C" int tsim_rowtab_decode_device(tsim_rowtab *h, const uint8_t *d_rows, 
   if (!d_counters || reinterpret_cast<uintptr_t>(d_counters) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_counters is NULL or not 8-byte aligned");
   if (!h->loaded) return tsim_fail(TSIM_ESTATE, "the table holds no values: tsim_rowtab_load comes first");
   if (n == 0) return TSIM_OK;
-  ROWTAB_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   a.obs_lo = obs_lo;
   a.obs_hi = obs_hi;
   a.dec = reinterpret_cast<unsigned long long *>(d_counters);
@@ -300,7 +282,7 @@ extern "C" int tsim_rowtab_decode_device(tsim_rowtab *h, const uint8_t *d_rows, 
     a.n = std::min(kRowsPerLaunch, n - r0);
     a.rows = d_rows + r0 * row_bytes;
     hipLaunchKernelGGL(rowtabk::k_decode, dim3(rowtab_blocks(h, a.n)), dim3(64 * rowtabk::kWaves), 16 + stage, (hipStream_t)stream, a);
-    ROWTAB_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     ++h->launches;
   }
   return TSIM_OK;

@@ -1,6 +1,7 @@
 // tsim_rowtab.hip.h - a table of the distinct patterns of bit-packed rows, each with an exact count (tsim_rowtab_*), and
-// the lookup decoder that probes such a table.  A row is kept iff (row ^ xor) & test == 0; its pattern (key) is row ^ xor
-// at the key columns, bit i of the key = key column i, W = ceil(n_key / 64) words of 64 bits.
+// the lookup decoder that probes such a table.  Rows, xor, test and the keep rule are the row contract of tsim_bitrows.hip.h,
+// whose reader these kernels use; a row's pattern (key) is row ^ xor at the key columns, bit i of the key = key column i,
+// W = ceil(n_key / 64) words of 64 bits.
 //
 // Table: open addressing, linear probing, capacity a power of two, slots never freed.  Per slot
 //   tags[s]    the word that is compared and swapped, 0 = empty.  n_key <= 63 ("exact"): the key itself | bit 63, so tag
@@ -24,15 +25,12 @@
 //             then per block in LDS, one atomic each per block.
 // Keys of a prefix selection (columns 0 .. n_key-1) are read from the staged bytes, in chunks of kChunk bytes for wide
 // rows; any other selection is gathered bit by bit from global memory, in key order.
-// Every address is formed in 64 bits.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "tsim_bitrows.hip.h"
 
 namespace rowtabk {
 
-constexpr int kChunk = 128;          // bytes of a row staged at a time in chunk mode (1024 columns)
-constexpr int kStage = kChunk + 4;   // LDS bytes per staged row in chunk mode (33 dwords: lanes fall on distinct banks)
+using namespace bitrows;  // kChunk, kStage, wsync, stage_rows, lds_word, mask_word, cut_pad, row_obs, readlane64
 constexpr int kWaves = 4;
 constexpr int kCache = 256;          // entries of a block's LDS cache
 constexpr uint64_t kUsed = 1ull << 63;
@@ -70,62 +68,6 @@ struct Args {
   unsigned long long *dec;    // k_decode: [0] kept [1] wrong [2] unknown
 };
 
-// keeps the compiler from moving LDS accesses of this wave across the point (the wave's LDS operations execute in order)
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// bytes b0 .. b0 + nb - 1 of `rows` rows -> LDS.  contig: the rows' whole span (b0 = 0, LDS stride = rb); else one LDS
-// row of kStage bytes per row.  w4: the row pointer and rb are multiples of 4 (b0 is a multiple of 8)
-__device__ __forceinline__ void stage_rows(uint8_t *stage, const uint8_t *src, int rows, int b0, int nb, long long rb, int contig,
-                                           int w4, int lane) {
-  if (contig) {
-    const int n = rows * (int)rb;
-    int done = 0;
-    if (w4) {
-      const int nd = n >> 2;
-      for (int i = lane; i < nd; i += 64) reinterpret_cast<uint32_t *>(stage)[i] = reinterpret_cast<const uint32_t *>(src)[i];
-      done = nd << 2;
-    }
-    for (int i = done + lane; i < n; i += 64) stage[i] = src[i];
-  } else if (w4) {  // (a dword that starts before nb ends inside the row: rb is a multiple of 4)
-    constexpr int kDw = kChunk / 4;
-    for (int i = lane; i < rows * kDw; i += 64) {
-      const int r = i / kDw, k = (i % kDw) * 4;
-      if (k < nb) *reinterpret_cast<uint32_t *>(stage + r * kStage + k) = *reinterpret_cast<const uint32_t *>(src + r * rb + b0 + k);
-    }
-  } else {
-    for (int r = 0; r < rows; ++r)
-      for (int k = lane; k < nb; k += 64) stage[r * kStage + k] = src[r * rb + b0 + k];
-  }
-}
-
-// 8 bytes of a staged row (p 4-aligned when a4)
-__device__ __forceinline__ uint64_t lds_word(const uint8_t *p, bool a4) {
-  if (a4) return (uint64_t)reinterpret_cast<const uint32_t *>(p)[0] | ((uint64_t)reinterpret_cast<const uint32_t *>(p)[1] << 32);
-  uint64_t w = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) w |= (uint64_t)p[q] << (8 * q);
-  return w;
-}
-
-// bytes b .. b + 7 of a mask row of `used` bytes (0 past its end, 0 for no mask); b is wave-uniform
-__device__ __forceinline__ uint64_t mask_word(const uint8_t *m, int b, int used) {
-  if (!m) return 0;
-  uint64_t w = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q)
-    if (b + q < used) w |= (uint64_t)m[b + q] << (8 * q);
-  return w;
-}
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
-  return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, l) |
-         ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), l) << 32);
-}
-
 // one wave's tile of rows
 struct Tile {
   const uint8_t *src;
@@ -154,8 +96,7 @@ __device__ __forceinline__ bool tile_kept(const Args &a, const Tile &t) {
       const int b = b0 + g * 8;
       uint64_t tw = mask_word(a.test, b, a.used);
       if (tw == 0) continue;
-      const int past = (b + 8) * 8 - a.n_cols;  // pad bits of the last byte are not columns
-      if (past > 0) tw &= past >= 64 ? 0ull : (~0ull >> past);
+      tw = cut_pad(tw, b, a.n_cols);
       fail |= (lds_word(p + g * 8, a4) ^ mask_word(a.xr, b, a.used)) & tw;
     }
   }
@@ -374,15 +315,7 @@ __global__ void __launch_bounds__(64 * kWaves) k_decode(Args a) {
     bool won = false;
     long long slot = kept ? probe<false>(a, tag, won) : -1;
     if (!a.exact && __builtin_amdgcn_ballot_w64(slot >= 0) && key_differs(a, tile, slot)) slot = -1;  // another syndrome's tag
-    uint64_t obs = 0;
-    if (kept) {
-      const uint8_t *row = tile.src + (long long)lane * a.rb;
-      for (int c = a.obs_lo; c < a.obs_hi; ++c) {
-        uint32_t byte = row[c >> 3];
-        if (a.xr) byte ^= a.xr[c >> 3];
-        obs |= (uint64_t)((byte >> (c & 7)) & 1u) << (c - a.obs_lo);
-      }
-    }
+    const uint64_t obs = kept ? row_obs(a, tile.src + (long long)lane * a.rb) : 0;
     const uint64_t pred = slot >= 0 ? a.values[slot] : 0ull;  // an unknown syndrome predicts no flip
     wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
     miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && slot < 0));

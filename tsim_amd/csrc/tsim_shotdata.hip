@@ -1,22 +1,13 @@
 // tsim_shotdata.hip - stim's shot-data formats on the device (tsim_shotdata_*): a small handle per device holding the
 // scan scratch, a result block and its pinned mirror, a stream and grow-only staging buffers; the kernels are
 // csrc/tsim_shotdata.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_shotdata.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
 
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int tsim_launch_compact(const uint64_t *d_in, int64_t B, int32_t WO, int32_t nbits, uint8_t *d_out, hipStream_t s);  // tsim_format.hip
-
-#define SD_TRY(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int kSlots = 16;
@@ -51,7 +42,7 @@ extern "C" int tsim_shotdata_create(int32_t device, tsim_shotdata **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
   *out = nullptr;
   int count = 0;
-  SD_TRY(hipGetDeviceCount(&count));
+  HIP_TRY(hipGetDeviceCount(&count));
   if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
   tsim_shotdata *h = new (std::nothrow) tsim_shotdata();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
@@ -79,10 +70,10 @@ extern "C" int tsim_shotdata_staging(tsim_shotdata *h, int32_t slot, int32_t pin
   if (!h || !ptr) return tsim_fail(TSIM_EINVAL, "NULL handle or ptr");
   if (slot < 0 || slot >= kSlots || nbytes < 0) return tsim_fail(TSIM_EINVAL, "slot %d (0 .. %d), nbytes %lld", slot, kSlots - 1, (long long)nbytes);
   const int kind = pinned ? 1 : 0;
-  SD_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   if (h->buf_cap[kind][slot] < nbytes || !h->buf[kind][slot]) {
-    SD_TRY(hipStreamSynchronize(h->stream));
-    if (h->buf[kind][slot]) SD_TRY(kind ? hipHostFree(h->buf[kind][slot]) : hipFree(h->buf[kind][slot]));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->buf[kind][slot]) HIP_TRY(kind ? hipHostFree(h->buf[kind][slot]) : hipFree(h->buf[kind][slot]));
     h->buf[kind][slot] = nullptr;
     h->buf_cap[kind][slot] = 0;
     const int64_t cap = std::max<int64_t>(nbytes, 64) + 16;  // (dword atomics may touch up to 3 bytes past a row buffer)
@@ -99,23 +90,23 @@ extern "C" int tsim_shotdata_copy(tsim_shotdata *h, void *dst, const void *src, 
   if (nbytes < 0) return tsim_fail(TSIM_EINVAL, "negative size");
   if (nbytes == 0) return TSIM_OK;
   if (!dst || !src) return tsim_fail(TSIM_EINVAL, "NULL buffer");
-  SD_TRY(hipSetDevice(h->device));
-  SD_TRY(hipMemcpyAsync(dst, src, (size_t)nbytes, hipMemcpyDefault, stream ? (hipStream_t)stream : h->stream));
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemcpyAsync(dst, src, (size_t)nbytes, hipMemcpyDefault, stream ? (hipStream_t)stream : h->stream));
   return TSIM_OK;
 }
 
 extern "C" int tsim_shotdata_synchronize(tsim_shotdata *h, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "NULL handle");
-  SD_TRY(hipSetDevice(h->device));
-  SD_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : h->stream));
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : h->stream));
   return TSIM_OK;
 }
 
 static int sd_scratch(tsim_shotdata *h, int64_t entries) {
   if (entries <= h->scratch_cap) return TSIM_OK;
-  SD_TRY(hipStreamSynchronize(h->stream));
-  SD_TRY(hipDeviceSynchronize());  // (callers' streams may still use the old scratch)
-  if (h->d_scratch) SD_TRY(hipFree(h->d_scratch));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipDeviceSynchronize());  // (callers' streams may still use the old scratch)
+  if (h->d_scratch) HIP_TRY(hipFree(h->d_scratch));
   h->d_scratch = nullptr;
   h->scratch_cap = 0;
   const int64_t cap = std::max<int64_t>(entries, 4096);
@@ -155,7 +146,7 @@ extern "C" int tsim_shotdata_encode(tsim_shotdata *h, int32_t format, const uint
   if (format == sdk::FPTB64 && n % 64 != 0) return tsim_fail(TSIM_EINVAL, "ptb64 needs a multiple of 64 rows, got %lld", (long long)n);
   if (n > 0 && used > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
   if (out_cap < 0) return tsim_fail(TSIM_EINVAL, "negative out_cap");
-  SD_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   sdk::EncArgs a{};
   a.rows = d_rows;
@@ -186,11 +177,11 @@ extern "C" int tsim_shotdata_encode(tsim_shotdata *h, int32_t format, const uint
     if (format == sdk::FR8) sd_launch_len<sdk::FR8>(a, (unsigned)nb, s);
     else if (format == sdk::FHITS) sd_launch_len<sdk::FHITS>(a, (unsigned)nb, s);
     else sd_launch_len<sdk::FDETS>(a, (unsigned)nb, s);
-    SD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sdk::k_scan_sums, dim3(1), dim3(sdk::kScanBlock), 0, s, a.sums, (long long)nb, &h->d_res->total);
-    SD_TRY(hipGetLastError());
-    SD_TRY(hipMemcpyAsync(&h->h_res->total, &h->d_res->total, sizeof(long long), hipMemcpyDeviceToHost, s));
-    SD_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h->h_res->total, &h->d_res->total, sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     total = h->h_res->total;
     *out_bytes = total;
     if (total > out_cap) return 1;
@@ -198,7 +189,7 @@ extern "C" int tsim_shotdata_encode(tsim_shotdata *h, int32_t format, const uint
     if (format == sdk::FR8) sd_launch_write<sdk::FR8>(a, (unsigned)nb, s);
     else if (format == sdk::FHITS) sd_launch_write<sdk::FHITS>(a, (unsigned)nb, s);
     else sd_launch_write<sdk::FDETS>(a, (unsigned)nb, s);
-    SD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return TSIM_OK;
   }
   *out_bytes = total;
@@ -231,7 +222,7 @@ extern "C" int tsim_shotdata_encode(tsim_shotdata *h, int32_t format, const uint
       p.out = d_out + r0 / 64 * 8 * (int64_t)n_bits;
       hipLaunchKernelGGL(sdk::k_enc_ptb64, dim3(sd_blocks(m / 64 * nw, sdk::kBlock / 64)), dim3(sdk::kBlock), 0, s, p);
     }
-    SD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   return TSIM_OK;
 }
@@ -240,14 +231,14 @@ template <int F>
 static int sd_decode_scan(tsim_shotdata *h, const sdk::DecArgs &a, hipStream_t s) {
   const int64_t nb = (a.n_in + sdk::kBlock - 1) / sdk::kBlock;
   hipLaunchKernelGGL(sdk::k_sum_bytes<F>, dim3((unsigned)nb), dim3(sdk::kBlock), 0, s, a);
-  SD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(sdk::k_scan_sums, dim3(1), dim3(sdk::kScanBlock), 0, s, a.sums, (long long)nb, &h->d_res->total);
-  SD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(sdk::k_dec_rows<F == sdk::FR8 ? sdk::FR8 : sdk::FHITS>, dim3(1), dim3(1), 0, s, a);
-  SD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   if (F == sdk::FR8) hipLaunchKernelGGL(sdk::k_dec_r8, dim3((unsigned)nb), dim3(sdk::kBlock), 0, s, a);
   else hipLaunchKernelGGL(sdk::k_dec_text<F>, dim3((unsigned)nb), dim3(sdk::kBlock), 0, s, a);
-  SD_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return TSIM_OK;
 }
 
@@ -264,7 +255,7 @@ extern "C" int tsim_shotdata_decode(tsim_shotdata *h, int32_t format, const uint
   if (format == sdk::FPTB64 && max_rows % 64 != 0) return tsim_fail(TSIM_EINVAL, "ptb64 needs max_rows a multiple of 64");
   if (n_in > 0 && !d_in) return tsim_fail(TSIM_EINVAL, "d_in is NULL");
   if (max_rows > 0 && used > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
-  SD_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   sdk::Res init{0, 0, 0, ~0ull};
   sdk::DecArgs a{};
@@ -300,7 +291,7 @@ extern "C" int tsim_shotdata_decode(tsim_shotdata *h, int32_t format, const uint
     }
     init.rows = rows;
     init.consumed = consumed;
-    SD_TRY(hipMemcpyAsync(h->d_res, &init, sizeof(init), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_res, &init, sizeof(init), hipMemcpyHostToDevice, s));
     a.n_rows = units + (partial ? 1 : 0);
     a.last_len = last_len;
     if (format == sdk::F01 && a.n_rows > 0) {
@@ -315,7 +306,7 @@ extern "C" int tsim_shotdata_decode(tsim_shotdata *h, int32_t format, const uint
       const int64_t waves = units * (((int64_t)n_bits + 63) / 64);
       hipLaunchKernelGGL(sdk::k_dec_ptb64, dim3(sd_blocks(waves, sdk::kBlock / 64)), dim3(sdk::kBlock), 0, s, a);
     }
-    SD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   } else {
     if (n_in == 0) {
       result[0] = result[1] = 0;
@@ -326,14 +317,14 @@ extern "C" int tsim_shotdata_decode(tsim_shotdata *h, int32_t format, const uint
     const int64_t nb = (n_in + sdk::kBlock - 1) / sdk::kBlock;
     if (int r = sd_scratch(h, nb)) return r;
     a.sums = h->d_scratch;
-    SD_TRY(hipMemcpyAsync(h->d_res, &init, sizeof(init), hipMemcpyHostToDevice, s));
-    if (max_rows > 0 && row_bytes > 0) SD_TRY(hipMemsetAsync(d_rows, 0, (size_t)(max_rows * row_bytes), s));
+    HIP_TRY(hipMemcpyAsync(h->d_res, &init, sizeof(init), hipMemcpyHostToDevice, s));
+    if (max_rows > 0 && row_bytes > 0) HIP_TRY(hipMemsetAsync(d_rows, 0, (size_t)(max_rows * row_bytes), s));
     int r = format == sdk::FR8 ? sd_decode_scan<sdk::FR8>(h, a, s)
                                : (format == sdk::FHITS ? sd_decode_scan<sdk::FHITS>(h, a, s) : sd_decode_scan<sdk::FDETS>(h, a, s));
     if (r) return r;
   }
-  SD_TRY(hipMemcpyAsync(h->h_res, h->d_res, sizeof(sdk::Res), hipMemcpyDeviceToHost, s));
-  SD_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(h->h_res, h->d_res, sizeof(sdk::Res), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   const sdk::Res &res = *h->h_res;
   result[0] = res.rows;
   result[1] = res.consumed;

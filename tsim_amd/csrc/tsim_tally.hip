@@ -1,19 +1,9 @@
 // tsim_tally.hip - counts over bit-packed device rows (tsim_tally_rows_device): kept rows, kept rows with an observable
 // set, per-column counts and a histogram, accumulated into caller-owned uint64 counters; the kernel is csrc/tsim_tally.hip.h.
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_tally.hip.h"
 
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define TALLY_TRY(expr)                                                                      \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int kWindow = 4096;              // columns per block's partials (16 KiB of LDS)
@@ -27,9 +17,8 @@ extern "C" int tsim_tally_rows_device(int32_t device, const uint8_t *d_rows, int
                                       const int32_t *hist_cols, int32_t n_hist, uint64_t *d_counts, void *stream) {
   if (n < 0) return tsim_fail(TSIM_EINVAL, "negative n");
   if (n_cols < 1 || n_cols > (1 << 30)) return tsim_fail(TSIM_EINVAL, "n_cols = %d (1 .. 2^30)", n_cols);
-  const int64_t used = ((int64_t)n_cols + 7) / 8;
-  if (row_bytes < used || row_bytes > 0x7FFFFFFF)
-    return tsim_fail(TSIM_EINVAL, "row_bytes = %lld for %lld bytes per row", (long long)row_bytes, (long long)used);
+  const int64_t used = tsimh::row_used(n_cols, row_bytes);
+  if (used < 0) return (int)used;
   if (obs_lo < 0 || obs_hi < obs_lo || obs_hi > n_cols)
     return tsim_fail(TSIM_EINVAL, "observable columns %d .. %d of %d", obs_lo, obs_hi, n_cols);
   if (n_hist < 0 || n_hist > tallyk::kMaxHist) return tsim_fail(TSIM_EINVAL, "n_hist = %d (0 .. %d)", n_hist, tallyk::kMaxHist);
@@ -43,7 +32,7 @@ extern "C" int tsim_tally_rows_device(int32_t device, const uint8_t *d_rows, int
   if (!d_counts || reinterpret_cast<uintptr_t>(d_counts) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_counts is NULL or not 8-byte aligned");
   if (n > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
   if (n == 0) return TSIM_OK;
-  TALLY_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
 
   tallyk::Args a{};
   a.rb = row_bytes;
@@ -59,10 +48,7 @@ extern "C" int tsim_tally_rows_device(int32_t device, const uint8_t *d_rows, int
   const int n_win = (int)(((int64_t)n_cols + kWindow - 1) / kWindow);
   a.win = n_win > 1 ? kWindow : (n_cols + 63) / 64 * 64;
   a.hist_lds = n_hist <= kLdsHistBits;
-  a.contig = n_win == 1 && row_bytes <= tallyk::kChunk;
-  const bool p4 = reinterpret_cast<uintptr_t>(d_rows) % 4 == 0;
-  a.w4 = p4 && (a.contig || row_bytes % 4 == 0);
-  a.stage_bytes = a.contig ? (int)(64 * row_bytes + 8 + 7) / 8 * 8 : 64 * tallyk::kStage;
+  tsimh::choose_staging(a, d_rows, row_bytes, n_win == 1);
   const int nw = tallyk::kMaxWaves;
   const size_t lds = (size_t)a.win * 4 + (a.hist_lds ? (size_t)(((1 << n_hist) + 1) & ~1) * 4 : 0) + 16 + (size_t)nw * a.stage_bytes;
   hipStream_t s = (hipStream_t)stream;
@@ -72,7 +58,7 @@ extern "C" int tsim_tally_rows_device(int32_t device, const uint8_t *d_rows, int
     const int64_t tiles = (a.n + 63) / 64;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + nw - 1) / nw, kBlocksPerWindow));
     hipLaunchKernelGGL(tallyk::k_tally, dim3((unsigned)blocks, (unsigned)n_win), dim3(64 * nw), lds, s, a);
-    TALLY_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   return TSIM_OK;
 }

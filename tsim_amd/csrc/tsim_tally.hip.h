@@ -1,6 +1,7 @@
 // tsim_tally.hip.h - counts over bit-packed rows (k_tally): kept rows, kept rows with an observable set, one count per
-// column over the kept rows, and a histogram over up to 16 columns of the kept rows.  A row is kept iff
-// (row ^ xor) & test == 0; every count is taken over row ^ xor.
+// column over the kept rows, and a histogram over up to 16 columns of the kept rows.  Rows, xor, test and the keep rule are
+// the row contract of tsim_bitrows.hip.h, whose reader this kernel uses; every count is taken over row ^ xor.  The test mask is
+// compared in whole bytes: its pad bits must be zero (the one consumer that does not cut them).
 //
 // One wave owns a tile of 64 rows (row r of the tile = lane r) and runs it in two passes over LDS-staged bytes:
 //   1. keep (only with a test mask, or for the observables): lane r ORs (row ^ xor) & test and (row ^ xor) & obs over
@@ -15,15 +16,12 @@
 // block adds every non-zero partial to its uint64 counter with one global atomic.  Integer adds commute: the counts do
 // not depend on the schedule.  Columns beyond `win` per block go through in windows (blockIdx.y): every window's blocks
 // compute the keep mask; window 0's also count kept rows, observables and the histogram.
-// Every address is formed in 64 bits (n x row bytes may exceed 2^31).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "tsim_bitrows.hip.h"
 
 namespace tallyk {
 
-constexpr int kChunk = 128;          // bytes of a row staged at a time in chunk mode (1024 columns)
-constexpr int kStage = kChunk + 4;   // LDS bytes per staged row in chunk mode (33 dwords: lanes fall on distinct banks)
+using namespace bitrows;  // kChunk, kStage, wsync, stage_rows, lds_word, mask_word
 constexpr int kMaxHist = 16;
 constexpr int kMaxWaves = 4;
 
@@ -41,57 +39,6 @@ struct Args {
   int contig, w4;           // stage a tile as one span; dword loads allowed
   int stage_bytes;          // LDS bytes of one wave's staging area
 };
-
-// keeps the compiler from moving LDS accesses of this wave across the point (the wave's LDS operations execute in order)
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// bytes b0 .. b0 + nb - 1 of `rows` rows -> LDS.  contig: the rows' whole span (b0 = 0, LDS stride = rb); else one LDS
-// row of kStage bytes per row.  w4: the row pointer and rb are multiples of 4 (b0 is a multiple of 8)
-__device__ __forceinline__ void stage_rows(uint8_t *stage, const uint8_t *src, int rows, int b0, int nb, long long rb, int contig,
-                                           int w4, int lane) {
-  if (contig) {
-    const int n = rows * (int)rb;
-    int done = 0;
-    if (w4) {
-      const int nd = n >> 2;
-      for (int i = lane; i < nd; i += 64) reinterpret_cast<uint32_t *>(stage)[i] = reinterpret_cast<const uint32_t *>(src)[i];
-      done = nd << 2;
-    }
-    for (int i = done + lane; i < n; i += 64) stage[i] = src[i];
-  } else if (w4) {  // (a dword that starts before nb ends inside the row: rb is a multiple of 4)
-    constexpr int kDw = kChunk / 4;
-    for (int i = lane; i < rows * kDw; i += 64) {
-      const int r = i / kDw, k = (i % kDw) * 4;
-      if (k < nb) *reinterpret_cast<uint32_t *>(stage + r * kStage + k) = *reinterpret_cast<const uint32_t *>(src + r * rb + b0 + k);
-    }
-  } else {
-    for (int r = 0; r < rows; ++r)
-      for (int k = lane; k < nb; k += 64) stage[r * kStage + k] = src[r * rb + b0 + k];
-  }
-}
-
-// 8 bytes of a staged row (p 4-aligned when a4)
-__device__ __forceinline__ uint64_t lds_word(const uint8_t *p, bool a4) {
-  if (a4) return (uint64_t)reinterpret_cast<const uint32_t *>(p)[0] | ((uint64_t)reinterpret_cast<const uint32_t *>(p)[1] << 32);
-  uint64_t w = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) w |= (uint64_t)p[q] << (8 * q);
-  return w;
-}
-
-// bytes b .. b + 7 of a mask row of `used` bytes (0 past its end, 0 for no mask); b is wave-uniform
-__device__ __forceinline__ uint64_t mask_word(const uint8_t *m, int b, int used) {
-  if (!m) return 0;
-  uint64_t w = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q)
-    if (b + q < used) w |= (uint64_t)m[b + q] << (8 * q);
-  return w;
-}
 
 // bits lo .. hi - 1 of the 64 columns starting at cb
 __device__ __forceinline__ uint64_t range_bits(int cb, int lo, int hi) {

@@ -81,7 +81,7 @@ extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, 
     adj[at[desc->edge_v[e]]++] = (uint16_t)e;
   }
   int cus = 0;
-  if (const int rc = ufh::open_device(device, &cus)) return rc;
+  if (const int rc = tsimh::open_device(device, &cus)) return rc;
   tsim_uf *h = new (std::nothrow) tsim_uf();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -123,10 +123,10 @@ extern "C" void tsim_uf_destroy(tsim_uf *h) {
 
 extern "C" int tsim_uf_info(tsim_uf *h, int64_t out[16]) {
   if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
-  UF_TRY(hipSetDevice(h->device));
-  UF_TRY(hipDeviceSynchronize());  // (the statistics live on the device: every decode so far is waited for)
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());  // (the statistics live on the device: every decode so far is waited for)
   uint64_t st[2];
-  UF_TRY(hipMemcpy(st, h->a.stats, 16, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(st, h->a.stats, 16, hipMemcpyDeviceToHost));
   std::fill(out, out + 16, 0);
   out[0] = h->a.n_nodes;
   out[1] = h->a.n_edges;
@@ -177,7 +177,7 @@ static int uf_decode(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_b
     a.hist = reinterpret_cast<unsigned long long *>(soft->d_hist);
   }
   if (n == 0) return TSIM_OK;
-  UF_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   ufh::fill_rows(a, d_rows, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters);
   return ufh::launch_rows(a, d_rows, n, d_pred, h->grid, &h->launches, [&](ufk::Args &a, int64_t r0, unsigned blocks, size_t lds) {
     if (soft) {

@@ -1,6 +1,6 @@
 // tsim_uf.hip.h - the union-find (cluster-growth) decoder over bit-packed device rows (tsim_uf_*); the rule is the module
-// docstring of tsim_amd/decode.py, which is also its numpy statement.  Rows, xor and test are those of k_decode
-// (tsim_rowtab.hip.h): a row is kept iff (row ^ xor) & test == 0, its syndrome is row ^ xor at columns 0 .. n_nodes - 2.
+// docstring of tsim_amd/decode.py, which is also its numpy statement.  Rows, xor, test and the keep rule are the row contract of
+// tsim_bitrows.hip.h, read straight from global memory (row_word); a row's syndrome is row ^ xor at columns 0 .. n_nodes - 2.
 //
 // One wave owns a tile of 64 rows (a persistent grid).  Pass 1, row r = lane r: the keep mask, "has a defect" and the
 // observables, read straight from the row; a row without defects is finished here and touches no per-shot state.  Pass 2:
@@ -40,10 +40,11 @@
 // registers and flushed once per wave; the others go to the histogram by global 64-bit adds, one per distinct bin of the tile.
 // Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "tsim_bitrows.hip.h"
 
 namespace ufk {
+
+using namespace bitrows;  // wsync, mask_word, below, row_word, row_obs
 
 constexpr int kMaxWaves = 4;             // shots (waves) per block at most
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // lp of a node no level has reached
@@ -98,38 +99,6 @@ __host__ inline long long layout(Args *a) {
   return at;
 }
 
-// keeps the compiler from moving LDS accesses of this wave across the point (the wave's LDS operations execute in order)
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// bytes b .. b + 7 of a mask row of `used` bytes (0 past its end, 0 for no mask)
-__device__ __forceinline__ uint64_t mask_word(const uint8_t *m, int b, int used) {
-  if (!m) return 0;
-  uint64_t w = 0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q)
-    if (b + q < used) w |= (uint64_t)m[b + q] << (8 * q);
-  return w;
-}
-
-// the bits of columns 8 b .. 8 b + 63 that are below column `end`
-__device__ __forceinline__ uint64_t below(int b, int end) {
-  const long long left = (long long)end - 8ll * b;
-  return left <= 0 ? 0ull : left >= 64 ? ~0ull : ~0ull >> (64 - left);
-}
-
-// bytes b .. b + 7 of a row (0 past its `used` bytes); `R` has used and w8 (Args here, the windowed decoder's in tsim_ufw.hip.h)
-template <class R>
-__device__ __forceinline__ uint64_t row_word(const R &a, const uint8_t *row, int b) {
-  if (a.w8) return *reinterpret_cast<const uint64_t *>(row + b);  // (rb is a multiple of 8: inside the row)
-  uint64_t w = 0;
-  for (int q = 0; q < 8 && b + q < a.used; ++q) w |= (uint64_t)row[b + q] << (8 * q);
-  return w;
-}
-
 // pass 1 of a lane's row: *fail = the test columns that are set, *defects = the detector columns that are set (after xor);
 // dmask: the detector columns as a mask row, NULL for the columns 0 .. nd - 1
 template <class R>
@@ -144,18 +113,6 @@ __device__ __forceinline__ void scan_row(const R &a, const uint8_t *row, bool va
     *fail |= w & tw;
     *defects |= w & dw;
   }
-}
-
-// the observable columns obs_lo .. obs_hi - 1 of a row, bit i = column obs_lo + i
-template <class R>
-__device__ __forceinline__ uint64_t row_obs(const R &a, const uint8_t *row) {
-  uint64_t obs = 0;
-  for (int c = a.obs_lo; c < a.obs_hi; ++c) {
-    uint32_t byte = row[c >> 3];
-    if (a.xr) byte ^= a.xr[c >> 3];
-    obs |= (uint64_t)((byte >> (c & 7)) & 1u) << (c - a.obs_lo);
-  }
-  return obs;
 }
 
 struct State {

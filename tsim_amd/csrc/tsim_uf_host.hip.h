@@ -1,23 +1,13 @@
 // tsim_uf_host.hip.h - the host side that the two union-find handles share (tsim_uf.hip, tsim_ufw.hip): the checks of a graph,
-// its caps and its heralds, the waves of a block, opening the device, the uploads a handle owns, and the row arguments and
-// launch loop of a decode call.  Host code only; every check comes before the first device call of its caller.
+// its caps and its heralds, the waves of a block, the uploads a handle owns, and the row arguments and launch loop of a decode
+// call, on the prelude of tsim_host.hip.h.  Host code only; every check comes before the first device call of its caller.
 #pragma once
 
-#include "../../include/tsim_hip.h"
+#include "tsim_host.hip.h"
 #include "tsim_uf.hip.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
-
-int tsim_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define UF_TRY(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) return tsim_fail(TSIM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace ufh {
 constexpr int kMaxIndex = 65535;               // nodes, and edges, of a graph a wave decodes: uint16 indices
@@ -97,16 +87,6 @@ inline void choose_waves(long long shot, int *waves, int *per_cu) {
   }
 }
 
-// makes `device` current; its compute units
-inline int open_device(int device, int *cus) {
-  int count = 0;
-  UF_TRY(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) return tsim_fail(TSIM_EINVAL, "device %d of %d", device, count);
-  UF_TRY(hipSetDevice(device));
-  UF_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device));
-  return TSIM_OK;
-}
-
 // the device tables of a handle: the first error is kept and ends the work, the bytes are added up
 struct Uploads {
   std::vector<void *> ptrs;
@@ -139,9 +119,7 @@ template <class Args>
 int check_rows(const Args &a, const uint8_t *d_rows, int64_t n, int64_t row_bytes, int32_t obs_lo, int32_t obs_hi, const uint64_t *d_counters,
                const uint64_t *d_pred) {
   if (n < 0) return tsim_fail(TSIM_EINVAL, "negative n");
-  const int64_t used = ((int64_t)a.n_cols + 7) / 8;
-  if (row_bytes < used || row_bytes > 0x7FFFFFFF)
-    return tsim_fail(TSIM_EINVAL, "row_bytes = %lld for %lld bytes per row", (long long)row_bytes, (long long)used);
+  if (const int64_t used = tsimh::row_used(a.n_cols, row_bytes); used < 0) return (int)used;
   if (n > 0 && !d_rows) return tsim_fail(TSIM_EINVAL, "d_rows is NULL");
   if (obs_lo < 0 || obs_hi < obs_lo || obs_hi > a.n_cols || obs_hi - obs_lo > 64)
     return tsim_fail(TSIM_EINVAL, "observable columns %d .. %d of %d (at most 64)", obs_lo, obs_hi, a.n_cols);
@@ -175,7 +153,7 @@ int launch_rows(Args &a, const uint8_t *d_rows, int64_t n, uint64_t *d_pred, int
     const int64_t tiles = (a.n + 63) / 64;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + a.waves - 1) / a.waves, grid));
     launch(a, r0, blocks, lds);
-    UF_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     ++*launches;
   }
   return TSIM_OK;

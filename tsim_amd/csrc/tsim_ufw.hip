@@ -235,7 +235,7 @@ extern "C" int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *desc,
   if (t.uv.empty()) t.uv.push_back(0), t.obs.push_back(0), t.cap.push_back(1);
   if (t.adj.empty()) t.adj.push_back(0);
   int cus = 0;
-  if (const int rc = ufh::open_device(device, &cus)) return rc;
+  if (const int rc = tsimh::open_device(device, &cus)) return rc;
   tsim_ufw *h = new (std::nothrow) tsim_ufw();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
   h->device = device;
@@ -284,10 +284,10 @@ extern "C" void tsim_ufw_destroy(tsim_ufw *h) {
 
 extern "C" int tsim_ufw_info(tsim_ufw *h, int64_t out[16]) {
   if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
-  UF_TRY(hipSetDevice(h->device));
-  UF_TRY(hipDeviceSynchronize());  // (the statistics live on the device: every decode so far is waited for)
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());  // (the statistics live on the device: every decode so far is waited for)
   uint64_t st[3];
-  UF_TRY(hipMemcpy(st, h->a.stats, sizeof st, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(st, h->a.stats, sizeof st, hipMemcpyDeviceToHost));
   std::fill(out, out + 16, 0);
   out[0] = h->n_nodes;
   out[1] = h->n_edges;
@@ -315,7 +315,7 @@ extern "C" int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_
   ufwk::Args a = h->a;
   if (const int rc = ufh::check_rows(a, d_rows, n, row_bytes, obs_lo, obs_hi, d_counters, d_pred)) return rc;
   if (n == 0) return TSIM_OK;
-  UF_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   ufh::fill_rows(a, d_rows, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters);
   return ufh::launch_rows(a, d_rows, n, d_pred, h->grid, &h->launches, [&](ufwk::Args &a, int64_t, unsigned blocks, size_t lds) {
     if (a.node_det) {

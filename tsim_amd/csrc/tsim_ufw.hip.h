@@ -1,7 +1,7 @@
 // tsim_ufw.hip.h - sliding-window union-find decoding over bit-packed device rows (tsim_ufw_*); the rule is "Sliding-window
 // decoding of long runs" in the module docstring of tsim_amd/decode.py, which is also its numpy statement.  Rows, xor and
-// test are those of k_uf (tsim_uf.hip.h), and so are the grid and the passes: one wave owns a tile of 64 rows; pass 1
-// finishes the rows without a defect straight from the row; pass 2 decodes each kept row with a defect by the whole wave in the
+// test are those of k_uf (the row contract of tsim_bitrows.hip.h), and so are the grid and the passes: one wave owns a tile
+// of 64 rows; pass 1 finishes the rows without a defect straight from the row; pass 2 decodes each kept row with a defect by the whole wave in the
 // wave's own state in LDS - here window after window, each by the steps of tsim_uf.hip.h (clear_edges, grow, forest, peel) on
 // that window's tables.
 //
@@ -102,7 +102,7 @@ __device__ __forceinline__ void pregrow_window(const Args &a, const WinDesc &d, 
       if (atomicOr(&st.full[fw], 1u << (e & 31)) == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)fw;  // (each word once)
     }
   }
-  ufk::wsync();
+  bitrows::wsync();
 }
 
 // one kept row with a defect, by the whole wave, window after window: the prediction (0 for a miss); *missed, *rounds (the most
@@ -110,7 +110,7 @@ __device__ __forceinline__ void pregrow_window(const Args &a, const WinDesc &d, 
 template <bool Weighted, bool Heralds>
 __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &st, uint32_t *carry, uint32_t *pred, const uint8_t *row,
                                                int lane, bool *missed, int *rounds, int *windows) {
-  using ufk::wsync;
+  using bitrows::wsync;
   for (int i = lane; i < a.carry_words; i += 64) carry[i] = 0;
   if (lane < 2) pred[lane] = 0;
   wsync();
@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
     uint64_t fail, defects;
     ufk::scan_row(a, row, valid, Heralds ? a.dmask : nullptr, a.nd, &fail, &defects);
     const bool kept = valid && fail == 0;
-    const uint64_t obs = kept ? ufk::row_obs(a, row) : 0;
+    const uint64_t obs = kept ? bitrows::row_obs(a, row) : 0;
     uint64_t pred = 0;
     bool missed = false;
     uint64_t work = __builtin_amdgcn_ballot_w64(kept && defects != 0);
