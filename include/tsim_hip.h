@@ -906,6 +906,11 @@ const char *tsim_version(void);
 /* The keys TSIM_AMD_TUNE="key=value,..." understands, comma separated (the launch planner's A/B switches; results never depend
  * on them - tests/test_gpu_knobs.py runs an oracle slice under every one).  No counterpart in the reference. */
 const char *tsim_tune_keys(void);
+/* The group schedule of tsim_sample_steps_device for the register first passes (host helper, no device): how many of the `left`
+ * batches of B shots that remain in a call the next fused group takes.  fused_max: the cap (TSIM_AMD_TUNE fused_max, default 16);
+ * long_shots: the fewest shots a group of more than 8 batches may hold (default 2^23, "fused_max=N:S" sets S).  Groups of more
+ * than 8 only while at least 32 batches are left; everything else in even groups of at most 8.  No counterpart in the reference. */
+int32_t tsim_steps_next_group(int32_t left, int64_t B, int32_t fused_max, int64_t long_shots);
 
 #ifdef __cplusplus
 }

@@ -230,6 +230,7 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_last_error": (C.c_char_p, []),
     "tsim_version": (C.c_char_p, []),
     "tsim_tune_keys": (C.c_char_p, []),
+    "tsim_steps_next_group": (_I32, [_I32, _I64, _I32, _I64]),
 }
 
 _lib = None

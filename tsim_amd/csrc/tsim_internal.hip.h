@@ -37,7 +37,7 @@
 #include <unordered_set>
 #include <vector>
 
-#define TSIMK_H_MAX_CTX 8   // launches served by one deferred hard-row batch (k_sample4h_multi)
+#define TSIMK_H_MAX_CTX 16  // launches served by one deferred hard-row batch (k_sample4h_multi)
 // Launch constants that were A/B switches until round 4 / 5 (the experiments are closed: HISTORY.md, profiles/r03 .. r05)
 constexpr int kListRows = 40;        // expected rows per hard-row sub-list
 constexpr int kMinLists = 4;
@@ -264,7 +264,7 @@ struct tsim_program {
                               // 0: after deep_after rows in that state, 1: at once, -1: never
     // TSIM_AMD_TUNE keys (A/B parameters of tests/ and scripts/)
     bool defer = true;        // defer_hard=0: every pipelined launch runs its own second pass
-    int defer_group = 4;      // defer_group: launches per deferred hard-row batch (<= TSIMK_H_MAX_CTX)
+    int defer_group = 4;      // defer_group: launches per deferred hard-row batch (<= 8)
     bool lw_fast = true;      // lw_fast=0: the generic fused pass (k_sample_lw_multi) also for one-component programs
     bool wide_fused = true;   // wide_fused=0: wide programs on the three-kernel path of round 2 (tables, k_sample4w, row kernel)
     bool hard_wave = true;    // hard_wave=0: hard-row batches on k_sample4h_multi (64 rows per block) instead of one block per row
@@ -273,7 +273,9 @@ struct tsim_program {
     bool hard_comp_par = true;  // hard_comp_par=0: the hard rows of multi-component programs one block per row (all components in turn)
     unsigned long long deep_after = 0;        // deep_after: rows in that state before the next depth is built; 0 = by the estimated build time
     int fused_lanes = 0;      // fused_lanes: first-pass lanes the fused groups rotate over (1-4; 0 = 2, 3 for small groups)
-    int fused_max = 8;        // fused_max: batches per fused first pass (<= TSIMK_LWM_MAX_STEPS = 16)
+    int fused_max = 16;       // fused_max: batches per fused first pass (<= TSIMK_LWM_MAX_STEPS = 16); more than 8 only in the interior of a
+                              // long call of large batches (tsim_steps_next_group); fused_max=8: every group as before the long ones existed
+    long long fused_long_shots = 1ll << 23;  // fused_max=N:S - the fewest shots a group of more than 8 batches may hold
     bool wide_tables = true;  // wide_tables=0: no pattern tables in front of the wide kernels
     bool hard_overflow = true; // hard_overflow=0: the latency kernels of a hard-row batch walk whole lists (no per-shot workers behind them)
     bool shallow = true;      // shallow=0: finalize builds the default table depth at once (round 4) instead of starting shallow

@@ -458,7 +458,7 @@ __device__ __forceinline__ void sample4_block(const SampleArgs &A, int comp4_off
 // When no list is longer than slot_begin - every launch but that one - a block reads the counts and exits.
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef TSIMK_H_MAX_CTX
-#define TSIMK_H_MAX_CTX 8
+#define TSIMK_H_MAX_CTX 16
 #endif
 struct Over4Multi {
   int n_ctx, comp4_off;

@@ -354,7 +354,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(3,
 
 // The hard rows of SEVERAL launches in one grid (deferred second pass, tsim_hip.hip): launch c owns
 // the blocks [c * blocks_per_ctx, (c + 1) * blocks_per_ctx), the last of them its check block.
-#define TSIMK_H_MAX_CTX 8
+#define TSIMK_H_MAX_CTX 16
 struct Hard4Multi {
   int n_ctx, blocks_per_ctx, group_tiles, loop_stride;
   int comp4_off, check_mask;

@@ -26,7 +26,7 @@
 
 namespace tsimk {
 
-#define TSIMK_HW_MAX_CTX 8
+#define TSIMK_HW_MAX_CTX 16  // = TSIMK_LWM_MAX_STEPS: the hard rows of a fused group are always ONE grid
 struct HwMulti {
   int n_ctx, waves_per_list, max_lists;
   int comp_par;                       // 1, or the program's component count: the lists carry component masks (LwMultiArgs.partial) and

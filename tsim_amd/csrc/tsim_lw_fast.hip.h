@@ -67,29 +67,17 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
   constexpr int L_BASES = L_RUNS + 4 * TSIMK_LWF_MAX_RUNS;  // [72]: bases[cnt], cnt <= 64; zeros above wmax
   constexpr int L_WORDS = L_BASES + 72;
   __shared__ uint32_t lds[L_WORDS];
-  const int nthr = blockDim.x;
-  cptr img = (cptr)(uintptr_t)M.img;
-  cptr rec = img + M.lw_off;     // the one component's LW record
-  cptr fr = img + M.lwf_off;     // its fast record
-  // ---- once per block: tables into LDS
-  {
-    const uint32_t *g = M.img;
-    const uint32_t rank_off = fr[LWF_RANK], lut_off = fr[LWF_LUT], runs_off = fr[LWF_RUNS], n_runs = fr[LWF_NRUNS];
-    for (int i = threadIdx.x; i < 8 * RSTR; i += nthr)
-      lds[L_RANK + i] = (i % RSTR) < NPOS ? g[rank_off + (uint32_t)(i / RSTR) * 128u + (uint32_t)(i % RSTR)] : 0u;
-    for (int i = threadIdx.x; i < (2 << NOUT); i += nthr) lds[L_LUT + i] = g[lut_off + i];
-    for (int i = threadIdx.x; i < 4 * TSIMK_LWF_MAX_RUNS; i += nthr) lds[L_RUNS + i] = (uint32_t)i < 4u * n_runs ? g[runs_off + i] : 0u;
-    if (threadIdx.x < 72) lds[L_BASES + threadIdx.x] = threadIdx.x < 8 ? g[M.lw_off + LW_BASES_INLINE + threadIdx.x] : 0u;
-    __syncthreads();
-  }
-  // ---- once per wave: scalars
-  const uint32_t n_runs = fr[LWF_NRUNS], flip0 = fr[LWF_FLIP0], flip1 = fr[LWF_FLIP1];
+  const int nthr = blockDim.x;  // 1024: every launcher's block size, and what the one-load-per-thread table fill below counts on
+  // ---- once per wave: scalars.  What the record headers hold comes with the kernel arguments (LwFastHeader): a block's
+  // way to its first draw is the kernel arguments, then the tables and the first f row side by side - not arguments, headers,
+  // tables, barrier, f row one after the other
+  const uint32_t n_runs = M.fh.n_runs, flip0 = M.fh.flip0, flip1 = M.fh.flip1;
   uint32_t sel[4];
 #pragma unroll
-  for (int w = 0; w < 4; ++w) sel[w] = w < WF32 ? rec[LW_SEL_INLINE + w] : 0u;
-  const uint32_t wmax = rec[LW_WMAX];
-  const uint32_t tab_byte = rec[LW_TAB] * 4u;
-  const uint32_t keybase = rec[LW_KEYBASE];
+  for (int w = 0; w < 4; ++w) sel[w] = w < WF32 ? M.fh.sel[w] : 0u;
+  const uint32_t wmax = M.fh.wmax;
+  const uint32_t tab_byte = M.fh.tab_byte;
+  const uint32_t keybase = M.fh.keybase;
   // the descriptor ends with the tables: a lane whose pattern index means nothing (hard rows) reads zeros, never beyond
   const __amdgpu_buffer_rsrc_t r_tab = __builtin_amdgcn_make_buffer_rsrc((void *)M.tab, 0, M.tab_bytes, 0x00020000);
   cstep steps = (cstep)((cbytes)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(LwMultiArgs, step));
@@ -118,6 +106,25 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
     }
   };
   load_f(step, rb);
+  // ---- once per block: tables into LDS.  8 x NPOS <= 1024 rank entries, at most 512 look-up words, 128 run words, 8 bases: one
+  // load per thread and table, every one requested (behind the f row's) before the first is waited for
+  {
+    const uint32_t *g = M.img;
+    const uint32_t t = threadIdx.x;
+    const bool in_rank = t < 8u * (uint32_t)NPOS, in_lut = t < (2u << NOUT), in_runs = t < 4u * n_runs, in_bases = t < 8u;
+    const uint32_t rk = t / (uint32_t)NPOS, rp = t % (uint32_t)NPOS;
+    uint32_t v_rank = 0u, v_lut = 0u, v_runs = 0u, v_bases = 0u;
+    if (in_rank) v_rank = g[M.fh.rank_off + rk * 128u + rp];
+    if (in_lut) v_lut = g[M.fh.lut_off + t];
+    if (in_runs) v_runs = g[M.fh.runs_off + t];
+    if (in_bases) v_bases = g[M.lw_off + LW_BASES_INLINE + t];
+    if (in_rank) lds[L_RANK + rk * (uint32_t)RSTR + rp] = v_rank;
+    if (t < 8u) lds[L_RANK + t * (uint32_t)RSTR + (uint32_t)NPOS] = 0u;  // what an exhausted lane reads
+    if (in_lut) lds[L_LUT + t] = v_lut;
+    if (t < 4u * TSIMK_LWF_MAX_RUNS) lds[L_RUNS + t] = v_runs;
+    if (t < 72u) lds[L_BASES + t] = v_bases;
+    __syncthreads();
+  }
   for (;;) {
     cstep S = steps + step;
     const uint32_t row = rb * (uint32_t)nthr + threadIdx.x;

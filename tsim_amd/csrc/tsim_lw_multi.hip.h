@@ -33,6 +33,16 @@ struct LwStep {
   uint32_t keys[2 * TSIMK_LWM_KEYS];  // per-output subkeys of this batch (sampler.py:74,147-148), host-computed
 };
 
+// What k_sample_lw_fast reads from the headers of the fast record and of the component's LW record, copied by the
+// host when the launch is built (lwf_fill_header, tsim_sample.hip; the host image mirrors the device's): the block
+// then knows where its tables are from the kernel arguments alone, one memory round trip earlier.
+struct LwFastHeader {
+  uint32_t rank_off, lut_off, runs_off, n_runs;  // LWF_RANK, LWF_LUT, LWF_RUNS, LWF_NRUNS
+  uint32_t flip0, flip1;                         // LWF_FLIP0, LWF_FLIP1
+  uint32_t wmax, tab_byte, keybase;              // LW_WMAX, 4 * LW_TAB, LW_KEYBASE
+  uint32_t sel[4];                               // LW_SEL_INLINE
+};
+
 struct LwMultiArgs {
   const uint32_t *img;
   const uint32_t *tab;    // integer thresholds, all components
@@ -46,6 +56,7 @@ struct LwMultiArgs {
   int partial;            // k_sample_lw_fastm: hard rows are stored too - direct outputs and the tabulated components' bits - and
                           // their list entries carry the mask of the components that are NOT tabulated in bits 28.. (k_sample_hw then
                           // evaluates exactly those, one block per (row, component), and ORs their bits in)
+  LwFastHeader fh;        // k_sample_lw_fast only (lwf_off != 0, one component)
   LwStep step[TSIMK_LWM_MAX_STEPS];
 };
 

@@ -282,7 +282,7 @@ extern "C" int tsim_program_finalize(tsim_program *p, int32_t device) {
     p->knobs.fused_steps = env_int("TSIM_AMD_FUSED_STEPS", 1) != 0;
     p->knobs.deep_tables = env_int("TSIM_AMD_DEEP_TABLES", 0);
     p->knobs.defer = tune_ll("defer_hard", 1) != 0;
-    p->knobs.defer_group = (int)std::max(0ll, std::min((long long)TSIMK_H_MAX_CTX, tune_ll("defer_group", 0)));  // 0: by table size, below
+    p->knobs.defer_group = (int)std::max(0ll, std::min(8ll, tune_ll("defer_group", 0)));  // 0: by table size, below
     p->knobs.lw_fast = tune_ll("lw_fast", 1) != 0;
     p->knobs.wide_fused = tune_ll("wide_fused", 1) != 0;
     p->knobs.hard_wave = tune_ll("hard_wave", 1) != 0;
@@ -291,7 +291,12 @@ extern "C" int tsim_program_finalize(tsim_program *p, int32_t device) {
     p->knobs.hard_comp_par = tune_ll("hard_comp_par", 1) != 0;
     p->knobs.deep_after = (unsigned long long)std::max(0ll, tune_ll("deep_after", 0));  // 0: by the estimated build time (tsim_tables_deep_after)
     p->knobs.fused_lanes = (int)std::max(0ll, std::min(4ll, tune_ll("fused_lanes", 0)));
-    p->knobs.fused_max = (int)std::max(1ll, std::min((long long)TSIMK_LWM_MAX_STEPS, tune_ll("fused_max", 8)));
+    p->knobs.fused_max = (int)std::max(1ll, std::min((long long)TSIMK_LWM_MAX_STEPS, tune_ll("fused_max", TSIMK_LWM_MAX_STEPS)));
+    {  // "fused_max=N:S": S = the fewest shots a group of more than 8 batches may hold (tsim_steps_next_group; default 2^23)
+      const size_t at = tune.find(",fused_max=");
+      const size_t colon = at == std::string::npos ? at : tune.find_first_of(":,", at + 1);
+      if (colon != std::string::npos && tune[colon] == ':') p->knobs.fused_long_shots = std::max(0ll, atoll(tune.c_str() + colon + 1));
+    }
     p->knobs.wide_tables = tune_ll("wide_tables", 1) != 0;
     p->knobs.wide_compact = tune_ll("wide_compact", 1) != 0;
     p->knobs.x3 = tune_ll("x3", 1) != 0;
@@ -1383,7 +1388,7 @@ retry_pack:
   if (img.size() >= (1ull << 30)) return tsim_fail(TSIM_ENOTSUP, "program image too large");  // (4 GB: the term-table gathers use 32-bit byte offsets)
 
   if (p->knobs.defer_group <= 0)  // (not told by TSIM_AMD_TUNE) launches per deferred batch: a batch lasts about as long as ONE hard-row
-    p->knobs.defer_group = p->stats[5] > (4ll << 20) ? TSIMK_H_MAX_CTX : 4;  // pass; 4 for small programs, 8 beyond 4 MB of chunk tables (C4)
+    p->knobs.defer_group = p->stats[5] > (4ll << 20) ? 8 : 4;  // pass; 4 for small programs, 8 beyond 4 MB of chunk tables (C4)
 
   fin_mark("pattern-table plan, first-pass records");
   // ---- upload ----

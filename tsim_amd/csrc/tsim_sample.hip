@@ -257,6 +257,24 @@ void hard_geometry(tsim_program *p, int WF, int WO) {
   p->h_lds = fixed_b + (size_t)std::max(1, p->h_group_tiles) * tile_b;
 }
 
+// k_sample_lw_fast takes the headers of its two records from the kernel arguments (LwFastHeader, tsim_lw_multi.hip.h).  The host
+// image is what the device's holds: the records change only in tsim_tables_extend_poll, with nothing of the handle in flight, and
+// M.tab - the table those records describe - is read from the handle at the same moment as this.
+static void lwf_fill_header(const tsim_program *p, LwMultiArgs &M) {
+  const uint32_t *fr = &p->img[(size_t)p->lwf_off], *rec = &p->img[(size_t)p->lw_off];
+  LwFastHeader &h = M.fh;
+  h.rank_off = fr[LWF_RANK];
+  h.lut_off = fr[LWF_LUT];
+  h.runs_off = fr[LWF_RUNS];
+  h.n_runs = fr[LWF_NRUNS];
+  h.flip0 = fr[LWF_FLIP0];
+  h.flip1 = fr[LWF_FLIP1];
+  h.wmax = rec[LW_WMAX];
+  h.tab_byte = rec[LW_TAB] * 4u;
+  h.keybase = rec[LW_KEYBASE];
+  for (int w = 0; w < 4; ++w) h.sel[w] = rec[LW_SEL_INLINE + w];
+}
+
 // One BLOCK per hard row (tsim_kernel_hw.hip.h) where the fast row layout exists and the rows are narrow: a batch then
 // takes the time of one row, and the approximate branch is no slower than the exact one ...
 // ... while the rows are FEW: a row costs this kernel ~10^4 wave instructions (one wave's worth of every level),
@@ -299,7 +317,7 @@ static int launch_over(tsim_program *p, const SampleArgs *ctx, int n_ctx, uint32
 #undef TSIM_LO
     case 32: {  // 81..128 parameters: two 32-KB tiles - more dynamic LDS than a kernel gets without asking
       auto kfn = k_sample4_over<4, 32>;
-      if (!(p->x4_attr_set & 1u)) { HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096)); p->x4_attr_set |= 1u; }
+      if (!(p->x4_attr_set & 1u)) { HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192)); p->x4_attr_set |= 1u; }
       hipLaunchKernelGGL(kfn, dim3(grid), dim3(blk), lds4, hs, M);
     } break;
     default: hipLaunchKernelGGL((k_sample4_over<4, 16>), dim3(grid), dim3(blk), lds4, hs, M); break;
@@ -359,7 +377,7 @@ static int launch_hw(tsim_program *p, const SampleArgs *ctx, int n_ctx, int max_
       TSIM_LHW(4, 0) TSIM_LHW(4, 20)
       case 32: {
         auto kfn = k_sample_hw<4, 32>;
-        if (!(p->x4_attr_set & 2u)) { HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096)); p->x4_attr_set |= 2u; }
+        if (!(p->x4_attr_set & 2u)) { HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192)); p->x4_attr_set |= 2u; }
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), ldsw, hs, H);
       } break;
       default: return tsim_fail(TSIM_ESTATE, "hard-row workers need chunk tables (%d chunks)", nch);
@@ -464,8 +482,8 @@ int flush_batch(tsim_program *p) {
 #define TSIM_LHM(N)                                                                                          \
   case N: {                                                                                                  \
     auto kfn = k_sample4h_multi<4, N, NW>;                                                                   \
-    if (!p->hm_attr_set) /* (the workers' list counts are 2 KB of static LDS) */                            \
-      HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024)); \
+    if (!p->hm_attr_set) /* (the workers' list counts are 4 KB of static LDS, and the kernel has a little more) */                            \
+      HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); \
     ++p->path_count[TP_SAMPLE4H_MULTI];                                                                      \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(NW * 64), lds_m, hs, M);                                        \
   } break;
@@ -827,6 +845,7 @@ static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_
       M.out_rb = (p->num_outputs + 7) / 8;
       M.lwf_off = p->lwf_off;
       M.tab_bytes = (uint32_t)p->lw_bytes;
+      lwf_fill_header(p, M);
       LwStep &st = M.step[0];
       st.f = a.f;
       st.out = a.out;
@@ -1113,6 +1132,22 @@ extern "C" int tsim_sample_batch_device_begin(tsim_program *p, int32_t slot, con
 // goes through tsim_sample_batch_device_begin batch by batch: same results either way.
 // ---------------------------------------------------------------------------
 
+// How many of the `left` batches of B shots that remain in a call the next fused group of the register first passes takes.
+// Up to 8: even groups, as few as possible (20 batches as 7+7+6).  More than 8 (fused_max, at most TSIMK_LWM_MAX_STEPS = the
+// contexts of one hard-row grid): one chip-wide ramp and one hard-row grid for twice the batches - but only while at least two
+// such groups' worth of batches are left, so that the call's last 16..31 batches go out in the small groups whose tail is short,
+// and only when the group holds at least `long_shots` shots: below that the hard-row grid, latency-bound, outlasts the first
+// pass and more batches per group only make its lists longer (C4 at 10^5 shots per batch).  Calls of fewer than 32 batches and
+// fused_max <= 8: the groups of before.
+extern "C" int32_t tsim_steps_next_group(int32_t left, int64_t B, int32_t fused_max, int64_t long_shots) {
+  if (left <= 0) return 0;
+  const int cap = std::max(1, std::min(TSIMK_LWM_MAX_STEPS, (int)fused_max));
+  if (cap > 8 && left >= 2 * TSIMK_LWM_MAX_STEPS && (long long)cap * (long long)B >= (long long)long_shots) return cap;
+  const int g = std::min(cap, 8);
+  const int groups = (left + g - 1) / g;
+  return (left + groups - 1) / groups;
+}
+
 static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f, int64_t B, int32_t num_f, uint32_t key[2],
                              int64_t shot_offset, void *const *d_out, float *const *d_dev, uint32_t flags, const LaunchPlan &plan) {
   const bool packed = (flags & TSIM_PIPE_OUT_BIT_PACKED) != 0;
@@ -1213,6 +1248,7 @@ static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f,
                     ((unsigned long long)shot_offset >> 32) == ((unsigned long long)(shot_offset + B - 1) >> 32);
   M.lwf_off = fast ? p->lwf_off : 0;
   M.tab_bytes = fast ? (uint32_t)p->lw_bytes : 0u;
+  if (fast) lwf_fill_header(p, M);
   // device noise in front of this group (tsim_sample_steps_noise_device): inside the first pass when that is the one-component
   // register pass and the sampler's tile is a whole number of row blocks, else k_noise_wave for every batch on this lane
   TsimNoiseRequest *nq = g_noise_req;
@@ -1446,7 +1482,7 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
     bool have_wide_plan = false;
     if (p->knobs.fused_steps && wide_applies(p, B, num_f, shot_offset) && p->series_left == 0) {
       const int left = n_steps - done;
-      const int gmax = std::min(TSIMK_LWM_MAX_STEPS, p->knobs.fused_max);
+      const int gmax = std::min(8, p->knobs.fused_max);  // (groups of more than 8 are the register first passes': tsim_steps_next_group)
       const int groups = (left + gmax - 1) / gmax;
       const int n = (left + groups - 1) / groups;
       bool okb = true;
@@ -1487,7 +1523,8 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
           if (int r = slot_prepare(p, k, 0)) return r;
         if (int r = slots_now_ready(p)) return r;
       }
-      plan = make_plan(p, false, true, (unsigned long long)std::min(n_steps - done, std::min(TSIMK_LWM_MAX_STEPS, p->knobs.fused_max)) * (unsigned long long)B);
+      const int n_long = (reg_fused && !gen_fused) ? (int)tsim_steps_next_group(n_steps - done, B, p->knobs.fused_max, p->knobs.fused_long_shots) : 0;
+      plan = make_plan(p, false, true, (unsigned long long)std::max(n_long, std::min(n_steps - done, std::min(8, p->knobs.fused_max))) * (unsigned long long)B);
       hard_geometry(p, WF, WO);
       TSIM_MARK("plan");
       have_plan = true;
@@ -1500,10 +1537,11 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
       // even groups of at most TSIMK_LWM_MAX_STEPS batches
       const int left = n_steps - done;
       // (k_sample_gen carries batches x compiled outputs subkey records per launch: 8 batches up to 40 outputs, fewer beyond)
-      const int gmax = std::min(gen_fused ? std::min(TSIMK_GEN_MAX_STEPS, std::max(1, TSIMK_GEN_KEYS / std::max(1, p->total_keys))) : TSIMK_LWM_MAX_STEPS, p->knobs.fused_max);
+      const int gmax = std::min(gen_fused ? std::min(TSIMK_GEN_MAX_STEPS, std::max(1, TSIMK_GEN_KEYS / std::max(1, p->total_keys))) : 8, p->knobs.fused_max);
       // (20 batches as 7+7+6; 5+5+5+5 - both lanes ending together - measured slower: a launch more)
       const int groups = (left + gmax - 1) / gmax;
-      const int n = (left + groups - 1) / groups;
+      // the register first passes: groups of up to fused_max = 16 batches in the interior of a long call of large batches
+      const int n = gen_fused ? (left + groups - 1) / groups : (int)tsim_steps_next_group(left, B, p->knobs.fused_max, p->knobs.fused_long_shots);
       // (group sizes that fill whole chip-fulls of first-pass blocks - 15 batches of 10^5 shots instead of 8 - make the first
       // pass cheaper per batch and the step slower: two hard-row grids per group, C4 at 10^5 shots 1.88 -> 1.53e10, C2 3.6 -> 2.9e10)
       {
