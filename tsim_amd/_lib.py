@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from pathlib import Path
 
 import numpy as np
@@ -308,6 +309,49 @@ def ptr(a: np.ndarray | None):
     if a is None:
         return None
     return a.ctypes.data_as(C.c_void_p)
+
+
+class DeviceHandle:
+    """A handle of ``libtsim_hip.so`` that its owner opens on first use: ``CREATE(*self._create_args(), &h)``, destroyed by
+    ``close()`` or with the owner through ``DESTROY``.  ``INFO``: the info call and the names of its ``int64`` slots."""
+
+    CREATE = DESTROY = ""
+    INFO: tuple = ("", ())
+    _h = _finalizer = None
+
+    def _create_args(self) -> tuple:
+        raise NotImplementedError
+
+    def _handle(self):
+        if self._h is None:
+            lib, h = load(), C.c_void_p()
+            check(getattr(lib, self.CREATE)(*self._create_args(), C.byref(h)), self.CREATE)
+            self._h = h
+            self._finalizer = weakref.finalize(self, getattr(lib, self.DESTROY), h)
+        return self._h
+
+    def close(self) -> None:
+        if self._finalizer is not None:
+            self._finalizer()
+        self._h = None
+        self._finalizer = None
+
+    def _read_info(self, call: str, names: tuple) -> dict:
+        out = (C.c_int64 * len(names))()
+        check(getattr(load(), call)(self._handle(), out), call)
+        return {k: int(v) for k, v in zip(names, out)}
+
+    def info(self) -> dict:
+        return self._read_info(*self.INFO)
+
+    def _request(self, call: str, head: tuple, B: int, d_out: int, *, key, first_shot, out_row_bytes, out_packed, col0, n_cols, stream) -> None:
+        """``call(handle, *head, B, first_shot, key, d_out, out_row_bytes, out_packed, col0, n_cols, stream)``: the tail every
+        sampling call of ``include/tsim_hip.h`` has (``n_cols`` None: the outputs from ``col0`` on)."""
+        n_cols = self.n_out - col0 if n_cols is None else n_cols
+        check(getattr(load(), call)(
+            self._handle(), *head, int(B), int(first_shot), int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF,
+            C.c_void_p(int(d_out)) if d_out else None, int(out_row_bytes), int(bool(out_packed)), int(col0), int(n_cols),
+            stream or None), call)
 
 
 def device_count() -> int:

@@ -20,7 +20,6 @@ the request is cut into launches, or on whether a GPU did the work.
 from __future__ import annotations
 
 import ctypes as C
-import weakref
 
 import numpy as np
 
@@ -108,7 +107,7 @@ def affine_rows_host(flip, row_ptr, cols, num_f: int, n_random: int, f_packed, B
     return out ^ flip[None, :]
 
 
-class AffineHandle:
+class AffineHandle(_lib.DeviceHandle):
     """``tsim_affine`` of one device: the CSR (``row_ptr``, ``cols`` over ``num_f`` f bits then ``n_random`` symbols) and
     the outputs' constant bits.  The device handle is created by the first launch."""
 
@@ -116,40 +115,21 @@ class AffineHandle:
         self.num_f, self.n_random, self._device = int(num_f), int(n_random), int(device)
         self.row_ptr, self.cols, self.flip = _check_csr(self.num_f, self.n_random, row_ptr, cols, flip)
         self.n_out = len(self.flip)
-        self._h = None
-        self._finalizer = None
 
-    def _handle(self):
-        if self._h is None:
-            lib = _lib.load()
-            h = C.c_void_p()
-            _lib.check(lib.tsim_affine_create(self._device, self.num_f, self.n_random, self.n_out, _lib.ptr(self.row_ptr),
-                                              _lib.ptr(self.cols), _lib.ptr(self.flip), C.byref(h)), "tsim_affine_create")
-            self._h = h
-            self._finalizer = weakref.finalize(self, lib.tsim_affine_destroy, h)
-        return self._h
+    CREATE, DESTROY = "tsim_affine_create", "tsim_affine_destroy"
+    INFO = ("tsim_affine_info", ("num_f", "n_random", "n_out", "nnz", "device", "window", "n_windows", "lds_bytes_per_wave"))
 
-    def close(self) -> None:
-        if self._finalizer is not None:
-            self._finalizer()
-        self._h = None
-        self._finalizer = None
-
-    def info(self) -> dict:
-        out = (C.c_int64 * 8)()
-        _lib.check(_lib.load().tsim_affine_info(self._handle(), out), "tsim_affine_info")
-        names = ("num_f", "n_random", "n_out", "nnz", "device", "window", "n_windows", "lds_bytes_per_wave")
-        return {k: int(v) for k, v in zip(names, out)}
+    def _create_args(self) -> tuple:
+        return (self._device, self.num_f, self.n_random, self.n_out, _lib.ptr(self.row_ptr), _lib.ptr(self.cols),
+                _lib.ptr(self.flip))
 
     def sample_device(self, d_f: int, B: int, d_out: int, *, key, first_shot: int = 0, f_row_bytes: int, out_row_bytes: int,
                       out_packed: bool, col0: int = 0, n_cols: int | None = None, stream: int = 0) -> None:
         """Caller-owned device buffers, asynchronous on ``stream`` (0: the handle's own stream); see
         ``tsim_affine_sample_device`` in ``include/tsim_hip.h``."""
-        n_cols = self.n_out - col0 if n_cols is None else n_cols
-        _lib.check(_lib.load().tsim_affine_sample_device(
-            self._handle(), C.c_void_p(int(d_f)) if d_f else None, int(f_row_bytes), int(B), int(first_shot),
-            int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF, C.c_void_p(int(d_out)) if d_out else None, int(out_row_bytes),
-            int(bool(out_packed)), int(col0), int(n_cols), stream or None), "tsim_affine_sample_device")
+        self._request("tsim_affine_sample_device", (C.c_void_p(int(d_f)) if d_f else None, int(f_row_bytes)), B, d_out, key=key,
+                      first_shot=first_shot, out_row_bytes=out_row_bytes, out_packed=out_packed, col0=col0, n_cols=n_cols,
+                      stream=stream)
 
 
 class CompiledAffineMeasurementSampler(CompiledMeasurementSampler):

@@ -2,17 +2,12 @@
 // compiled form of tsim_amd/faults.py (classes of noise sites, their tables, the error bit -> outputs CSR); the kernel is
 // csrc/tsim_faults.hip.h.  The same handle draws rows conditioned on exactly k fired sites (tsim_amd/fixed_weight.py) once
 // tsim_faults_set_split gave it the table of the class counts; that kernel is csrc/tsim_faults_weight.hip.h.
-#include "tsim_host.hip.h"
+#include "tsim_outputs_host.hip.h"
 #include "tsim_faults_weight.hip.h"
-
-#include <algorithm>
-#include <new>
-#include <vector>
 
 namespace {
 constexpr int64_t kLds = 160 * 1024;          // all the LDS a workgroup may take
 constexpr int32_t kMaxClassSites = 1 << 25;   // the draw index has 26 bits: a class needs at most n_c + n_c / kGapK + 2 draws
-constexpr int64_t kMaxShot = 1ll << 38;
 
 // The LDS of a block: the tables (tab_bytes, 0 when they stay in global memory), then per wave one row of S 32-bit words per
 // lane plus wave_extra bytes.  S is the outputs' words made odd when one wave's share fits, and the block then has as many
@@ -40,7 +35,7 @@ struct tsim_faults {
   int32_t n_out = 0, num_e = 0, n_sites = 0, n_classes = 0, n_gaps = 0, n_cols = 0, max_class = 0;
   int32_t tab_lds = 0, S = 1, win = 32, waves = 1;
   int64_t tab_bytes = 0;
-  std::vector<void *> bufs;
+  tsimh::Uploads up;  // the form's arrays
   fltk::Form form{};
   hipStream_t stream = nullptr;
   bool attr_set = false;
@@ -54,23 +49,11 @@ struct tsim_faults {
   bool w_attr_set = false;
 };
 
-static void faults_release(tsim_faults *h) {
-  if (h->device >= 0) (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void *p : h->bufs) (void)hipFree(p);
-  if (h->split) (void)hipFree(h->split);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-}
-
-template <typename T>
-static hipError_t upload(tsim_faults *h, const T *src, size_t n, const T **dst) {
-  void *p = nullptr;
-  hipError_t e = hipMalloc(&p, std::max<size_t>(1, n) * sizeof(T));
-  if (e != hipSuccess) return e;
-  h->bufs.push_back(p);
-  *dst = static_cast<const T *>(p);
-  return n ? hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-}
+// both kernels by 2 * (byte rows) + (tables in global memory)
+void (*const kFaults[4])(fltk::Args) = {fltk::k_faults<true, true>, fltk::k_faults<true, false>, fltk::k_faults<false, true>,
+                                        fltk::k_faults<false, false>};
+void (*const kFaultsWeight[4])(fltk::WeightArgs) = {fltk::k_faults_weight<true, true>, fltk::k_faults_weight<true, false>,
+                                                    fltk::k_faults_weight<false, true>, fltk::k_faults_weight<false, false>};
 
 extern "C" int tsim_faults_create(int32_t device, const tsim_faults_desc *d, tsim_faults **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
@@ -159,16 +142,16 @@ extern "C" int tsim_faults_create(int32_t device, const tsim_faults_desc *d, tsi
   f.n_classes = n_cls;
   f.n_gaps = d->n_gaps;
   f.n_outcomes = d->n_outcomes;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-#define UP(field, n) if (e == hipSuccess) e = upload(h, d->field, (size_t)(n), &f.field)
+  tsimh::Uploads &up = h->up;
+  up.err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+#define UP(field, n) f.field = up.put(d->field, (size_t)(n))
   UP(class_ptr, n_cls + 1); UP(site_e0, n_sites); UP(table_ptr, n_cls + 1); UP(table_gap, n_cls);
   UP(out_vals, d->n_outcomes); UP(out_thr, d->n_outcomes); UP(gap_thr, (size_t)fltk::kGapK * d->n_gaps);
   UP(col_ptr, num_e + 1); UP(cols, d->n_cols);
 #undef UP
-  if (e == hipSuccess) e = upload(h, cwords.data(), cwords.size(), &f.const_words);
-  if (e != hipSuccess) {
-    faults_release(h);
-    delete h;
+  f.const_words = up.put(cwords);
+  if (const hipError_t e = up.err; e != hipSuccess) {
+    tsim_faults_destroy(h);
     return tsim_fail(TSIM_EHIP, "fault sampler upload: %s", hipGetErrorString(e));
   }
   *out = h;
@@ -177,28 +160,9 @@ extern "C" int tsim_faults_create(int32_t device, const tsim_faults_desc *d, tsi
 
 extern "C" void tsim_faults_destroy(tsim_faults *h) {
   if (!h) return;
-  faults_release(h);
+  h->up.release(h->device, h->stream);
+  if (h->split) (void)hipFree(h->split);
   delete h;
-}
-
-// The checks every request shares, before any device call; *run = false: nothing to do.
-static int check_request(const tsim_faults *h, int64_t B, int64_t first_shot, const uint8_t *d_out, int64_t out_row_bytes, int32_t out_packed,
-                         int32_t col0, int32_t n_cols, bool *run) {
-  *run = false;
-  if (B < 0) return tsim_fail(TSIM_EINVAL, "negative B");
-  if (first_shot < 0 || first_shot % 64 != 0)
-    return tsim_fail(TSIM_EINVAL, "first_shot = %lld is not a non-negative multiple of 64", (long long)first_shot);
-  if (first_shot > kMaxShot || B > kMaxShot - first_shot)
-    return tsim_fail(TSIM_EINVAL, "first_shot + B = %lld + %lld exceeds 2^38", (long long)first_shot, (long long)B);
-  if (col0 < 0 || n_cols < 0 || (int64_t)col0 + n_cols > h->n_out)
-    return tsim_fail(TSIM_EINVAL, "outputs %d .. %d + %d of %d", col0, col0, n_cols, h->n_out);
-  const int64_t out_used = out_packed ? (n_cols + 7) / 8 : n_cols;
-  if (out_row_bytes < out_used || out_row_bytes > 0x7FFFFFFF)
-    return tsim_fail(TSIM_EINVAL, "out_row_bytes = %lld for %lld bytes per row", (long long)out_row_bytes, (long long)out_used);
-  if (B == 0 || n_cols == 0) return TSIM_OK;
-  if (!d_out) return tsim_fail(TSIM_EINVAL, "NULL buffer");
-  *run = true;
-  return TSIM_OK;
 }
 
 // The arguments both kernels take; the noise key is threefry2x32(key, (n0, n1)) of the counter given in A.n0, A.n1.
@@ -222,19 +186,11 @@ extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t firs
                                          int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "sampler is NULL");
   bool run = false;
-  const int rc = check_request(h, B, first_shot, d_out, out_row_bytes, out_packed, col0, n_cols, &run);
+  const int rc = outh::check_request(h->n_out, B, &first_shot, col0, n_cols, nullptr, out_row_bytes, out_packed, d_out != nullptr, &run);
   if (rc != TSIM_OK || !run) return rc;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  void (*k)(fltk::Args) = out_packed ? (h->tab_lds ? fltk::k_faults<true, true> : fltk::k_faults<true, false>)
-                                     : (h->tab_lds ? fltk::k_faults<false, true> : fltk::k_faults<false, false>);
-  if (!h->attr_set) {
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    h->attr_set = true;
-  }
+  if (const int ra = tsimh::allow_lds(kFaults, kLds, &h->attr_set)) return ra;
   fltk::Args A;
   A.n0 = 0x6E6F6973u;  // the request's noise key: threefry2x32(key, ("nois", "falt"))
   A.n1 = 0x66616C74u;
@@ -243,7 +199,7 @@ extern "C" int tsim_faults_sample_device(tsim_faults *h, int64_t B, int64_t firs
   const int nw = (int)std::min<int64_t>(h->waves, tiles);
   const size_t lds = (size_t)h->tab_bytes + (size_t)nw * 256 * (size_t)h->S;
   const int64_t blocks = std::min<int64_t>((tiles + nw - 1) / nw, 256 * 8);
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * nw), lds, s, A);
+  hipLaunchKernelGGL(kFaults[2 * !out_packed + !h->tab_lds], dim3((unsigned)blocks), dim3(64 * nw), lds, s, A);
   HIP_TRY(hipGetLastError());
   return TSIM_OK;
 }
@@ -302,19 +258,11 @@ extern "C" int tsim_faults_sample_weight_device(tsim_faults *h, int32_t k, int64
   if (k < 0 || k > h->kmax) return tsim_fail(TSIM_EINVAL, "k = %d: the split table serves 0 .. %d", k, h->kmax);
   if (k > h->n_sites) return tsim_fail(TSIM_EINVAL, "k = %d of %d noise sites", k, h->n_sites);
   bool run = false;
-  const int rc = check_request(h, B, first_shot, d_out, out_row_bytes, out_packed, col0, n_cols, &run);
+  const int rc = outh::check_request(h->n_out, B, &first_shot, col0, n_cols, nullptr, out_row_bytes, out_packed, d_out != nullptr, &run);
   if (rc != TSIM_OK || !run) return rc;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  void (*kern)(fltk::WeightArgs) = out_packed ? (h->w_tab_lds ? fltk::k_faults_weight<true, true> : fltk::k_faults_weight<true, false>)
-                                              : (h->w_tab_lds ? fltk::k_faults_weight<false, true> : fltk::k_faults_weight<false, false>);
-  if (!h->w_attr_set) {
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    HIP_TRY(hipFuncSetAttribute((const void *)fltk::k_faults_weight<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
-    h->w_attr_set = true;
-  }
+  if (const int ra = tsimh::allow_lds(kFaultsWeight, kLds, &h->w_attr_set)) return ra;
   fltk::WeightArgs W;
   W.a.n0 = 0x6E6F6973u;  // the request's noise key: threefry2x32(key, ("nois", "fixw")), a stream of its own
   W.a.n1 = 0x66697877u;
@@ -326,7 +274,7 @@ extern "C" int tsim_faults_sample_weight_device(tsim_faults *h, int32_t k, int64
   const int nw = (int)std::min<int64_t>(h->w_waves, tiles);
   const size_t lds = (size_t)h->w_tab_bytes + (size_t)nw * (256 * (size_t)h->w_S + 4 * fltk::kListWords);
   const int64_t blocks = std::min<int64_t>((tiles + nw - 1) / nw, 256 * 8);
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * nw), lds, s, W);
+  hipLaunchKernelGGL(kFaultsWeight[2 * !out_packed + !h->w_tab_lds], dim3((unsigned)blocks), dim3(64 * nw), lds, s, W);
   HIP_TRY(hipGetLastError());
   return TSIM_OK;
 }

@@ -1,57 +1,28 @@
 // tsim_frame.hip - the Pauli-frame sampler (tsim_frame_*): a handle of its own, bound to one device, holding the compiled
 // form of tsim_amd/frame.py (operation batches, noise sites and their tables, output lists) and the record-flip scratch; the
 // kernels are csrc/tsim_frame.hip.h.
-#include "tsim_host.hip.h"
+#include "tsim_outputs_host.hip.h"
 #include "tsim_frame.hip.h"
-
-#include <algorithm>
-#include <new>
-#include <vector>
 
 namespace {
 constexpr int64_t kFrameLds = 160 * 1024;         // the frames of a tile: all the LDS a workgroup may take
 constexpr int kMaxT = 32;                         // words per tile
 constexpr int64_t kScratchBudget = 256ll << 20;   // bytes of F: a request is cut into launches that fit
 constexpr int64_t kMaxLaunchWords = 1 << 14;      // 2^20 shots
-constexpr int kOutLds = 64 * 1024;                // dynamic LDS per block of the output stage
-constexpr int kWindow = 2048;                     // columns per window when one wave's LDS cannot hold every column's mask
-constexpr int64_t kMaxWindowedRowPtr = 1ll << 28;
-constexpr int64_t kMaxShot = 1ll << 38;
 }  // namespace
 
 struct tsim_frame {
   int device = -1;
-  int32_t nq = 0, n_rec = 0, n_hidden = 0, n_random = 0, n_out = 0, n_ops = 0, n_batches = 0, n_sites = 0;
+  int32_t nq = 0, n_rec = 0, n_hidden = 0, n_random = 0, n_ops = 0, n_batches = 0, n_sites = 0;
   int32_t log2T = 0, max_items = 0;
-  int32_t win = 0, n_win = 1;
   int64_t max_words = 0;  // words per launch = row stride of F
-  std::vector<void *> bufs;
   frmk::Form form{};
-  int32_t *d_row_ptr = nullptr, *d_cols = nullptr;
-  uint8_t *d_const = nullptr;
+  outh::Outputs o;     // the output stage, over the n_rec + n_random columns (csrc/tsim_outputs_host.hip.h)
+  tsimh::Uploads up;   // the form's arrays, the output stage's lists and constant bits, F
   uint64_t *d_F = nullptr;
   hipStream_t stream = nullptr;
   bool attr_set = false;
 };
-
-static void frame_release(tsim_frame *h) {
-  if (h->device >= 0) (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void *p : h->bufs) (void)hipFree(p);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-}
-
-static int64_t out_lds_per_wave(int64_t win) { return win * 8 + m2dk::kStageBytes; }
-
-template <typename T>
-static hipError_t upload(tsim_frame *h, const T *src, size_t n, const T **dst) {
-  void *p = nullptr;
-  hipError_t e = hipMalloc(&p, std::max<size_t>(1, n) * sizeof(T));
-  if (e != hipSuccess) return e;
-  h->bufs.push_back(p);
-  *dst = static_cast<const T *>(p);
-  return n ? hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-}
 
 extern "C" int tsim_frame_create(int32_t device, const tsim_frame_desc *d, tsim_frame **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
@@ -159,42 +130,13 @@ extern "C" int tsim_frame_create(int32_t device, const tsim_frame_desc *d, tsim_
   const int64_t T = 1ll << log2T;
   int64_t max_words = std::min<int64_t>(kMaxLaunchWords, kScratchBudget / (8 * std::max<int64_t>(1, n_rows)));
   max_words = std::max<int64_t>(T, max_words / T * T);
-  // ---- the output stage's windows (as tsim_affine_create builds them)
-  const int32_t *row_ptr = d->out_ptr, *cols = d->out_cols;
-  const int32_t nnz = d->n_cols;
-  int32_t win = 0, n_win = 1;
-  if (out_lds_per_wave(((int64_t)M + 63) / 64 * 64) <= kOutLds) {
-    win = std::max(64, (M + 63) / 64 * 64);
-  } else {
-    win = kWindow;
-    n_win = (int32_t)(((int64_t)M + kWindow - 1) / kWindow);
-  }
-  if ((int64_t)n_win * ((int64_t)n_out + 1) > kMaxWindowedRowPtr)
-    return tsim_fail(TSIM_ENOTSUP, "%d columns x %d outputs: %d windows of %d columns, more than %lld row pointers", M, n_out, n_win, kWindow,
-                     (long long)kMaxWindowedRowPtr);
-  std::vector<int32_t> wrp, wcols;
-  if (n_win > 1) try {  // bucket every output's columns by window; columns become window-local
-    wrp.assign((size_t)n_win * (n_out + 1), 0);
-    wcols.resize((size_t)nnz);
-    for (int32_t j = 0; j < n_out; ++j)
-      for (int32_t k = row_ptr[j]; k < row_ptr[j + 1]; ++k) ++wrp[(size_t)(cols[k] / win) * (n_out + 1) + j + 1];
-    int32_t run = 0;
-    for (int32_t w = 0; w < n_win; ++w) {
-      int32_t *r = wrp.data() + (size_t)w * (n_out + 1);
-      r[0] = run;
-      for (int32_t j = 0; j < n_out; ++j) r[j + 1] = (run += r[j + 1]);
-    }
-    std::vector<int32_t> fill(wrp);
-    for (int32_t j = 0; j < n_out; ++j)
-      for (int32_t k = row_ptr[j]; k < row_ptr[j + 1]; ++k) {
-        const int32_t w = cols[k] / win;
-        wcols[(size_t)fill[(size_t)w * (n_out + 1) + j]++] = cols[k] - w * win;
-      }
-    row_ptr = wrp.data();
-    cols = wcols.data();
-  } catch (const std::bad_alloc &) {
-    return tsim_fail(TSIM_ENOMEM, "out of host memory for the per-window CSR");
-  }
+  // ---- the output stage's windows; a form without a column still has one word of masks
+  outh::Outputs o;
+  if (o.plan(M, n_out, 64) > outh::kMaxWindowedRowPtr)
+    return tsim_fail(TSIM_ENOTSUP, "%d columns x %d outputs: %d windows of %d columns, more than %lld row pointers", M, n_out, o.n_win,
+                     outh::kWindow, (long long)outh::kMaxWindowedRowPtr);
+  outh::Lists lists;
+  if (const int rc = o.build(d->out_ptr, d->out_cols, &lists)) return rc;
   if (const int rc = tsimh::open_device(device, nullptr)) return rc;
   tsim_frame *h = new (std::nothrow) tsim_frame();
   if (!h) return tsim_fail(TSIM_ENOMEM, "out of host memory");
@@ -203,86 +145,57 @@ extern "C" int tsim_frame_create(int32_t device, const tsim_frame_desc *d, tsim_
   h->n_rec = n_rec;
   h->n_hidden = n_hid;
   h->n_random = d->n_random;
-  h->n_out = n_out;
   h->n_ops = d->n_ops;
   h->n_batches = d->n_batches;
   h->n_sites = d->n_sites;
   h->log2T = log2T;
   h->max_items = max_items;
-  h->win = win;
-  h->n_win = n_win;
   h->max_words = max_words;
   frmk::Form &f = h->form;
   f.n_batches = d->n_batches;
   f.nq = nq;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  tsimh::Uploads &up = h->up;
+  up.err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   const size_t no = (size_t)d->n_ops, ns = (size_t)d->n_sites;
-#define UP(field, n) if (e == hipSuccess) e = upload(h, d->field, (size_t)(n), &f.field)
+#define UP(field, n) f.field = up.put(d->field, (size_t)(n))
   UP(op_kind, no); UP(op_a, no); UP(op_b, no); UP(op_c, no); UP(batch_ptr, d->n_batches + 1);
   UP(site_chan, ns); UP(site_table, ns); UP(site_bit, ns + 1); UP(bit_ptr, d->n_bits + 1); UP(targets, d->n_targets);
   UP(table_ptr, d->n_tables + 1); UP(table_gap, d->n_tables); UP(out_vals, d->n_outcomes); UP(out_thr, d->n_outcomes);
   UP(gap_thr, 64 * (size_t)d->n_gaps);
 #undef UP
-  const int32_t *drp = nullptr, *dc = nullptr;
-  const uint8_t *dk = nullptr;
-  if (e == hipSuccess) e = upload(h, row_ptr, (size_t)n_win * (n_out + 1), &drp);
-  if (e == hipSuccess) e = upload(h, cols, (size_t)nnz, &dc);
-  if (e == hipSuccess) e = upload(h, d->out_const, (size_t)n_out, &dk);
-  if (e == hipSuccess) {
-    void *p = nullptr;
-    e = hipMalloc(&p, (size_t)std::max<int64_t>(1, n_rows) * (size_t)max_words * 8);
-    if (e == hipSuccess) {
-      h->bufs.push_back(p);
-      h->d_F = static_cast<uint64_t *>(p);
-    }
-  }
-  if (e != hipSuccess) {
-    frame_release(h);
-    delete h;
+  o.upload(up, lists, d->n_cols, d->out_const);
+  h->o = o;
+  h->d_F = static_cast<uint64_t *>(up.room((size_t)std::max<int64_t>(1, n_rows) * (size_t)max_words * 8));
+  if (const hipError_t e = up.err; e != hipSuccess) {
+    tsim_frame_destroy(h);
     return tsim_fail(TSIM_EHIP, "frame sampler upload: %s", hipGetErrorString(e));
   }
-  h->d_row_ptr = const_cast<int32_t *>(drp);
-  h->d_cols = const_cast<int32_t *>(dc);
-  h->d_const = const_cast<uint8_t *>(dk);
   *out = h;
   return TSIM_OK;
 }
 
 extern "C" void tsim_frame_destroy(tsim_frame *h) {
   if (!h) return;
-  frame_release(h);
+  h->up.release(h->device, h->stream);
   delete h;
 }
 
 extern "C" int tsim_frame_sample_device(tsim_frame *h, int64_t B, int64_t first_shot, uint32_t key_hi, uint32_t key_lo, uint8_t *d_out,
                                         int64_t out_row_bytes, int32_t out_packed, int32_t col0, int32_t n_cols, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "sampler is NULL");
-  if (B < 0) return tsim_fail(TSIM_EINVAL, "negative B");
-  if (first_shot < 0 || first_shot % 64 != 0)
-    return tsim_fail(TSIM_EINVAL, "first_shot = %lld is not a non-negative multiple of 64", (long long)first_shot);
-  if (first_shot > kMaxShot || B > kMaxShot - first_shot)
-    return tsim_fail(TSIM_EINVAL, "first_shot + B = %lld + %lld exceeds 2^38", (long long)first_shot, (long long)B);
-  if (col0 < 0 || n_cols < 0 || (int64_t)col0 + n_cols > h->n_out)
-    return tsim_fail(TSIM_EINVAL, "outputs %d .. %d + %d of %d", col0, col0, n_cols, h->n_out);
-  const int64_t out_used = out_packed ? (n_cols + 7) / 8 : n_cols;
-  if (out_row_bytes < out_used || out_row_bytes > 0x7FFFFFFF)
-    return tsim_fail(TSIM_EINVAL, "out_row_bytes = %lld for %lld bytes per row", (long long)out_row_bytes, (long long)out_used);
-  if (B == 0 || n_cols == 0) return TSIM_OK;
-  if (!d_out) return tsim_fail(TSIM_EINVAL, "NULL buffer");
+  bool run = false;
+  const int rc = outh::check_request(h->o.n_out, B, &first_shot, col0, n_cols, nullptr, out_row_bytes, out_packed, d_out != nullptr, &run);
+  if (rc != TSIM_OK || !run) return rc;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
   const int T = 1 << h->log2T;
   const size_t frame_lds = 16 * (size_t)h->nq * T;
   // threads of a block: what the largest batch keeps busy, 4 .. 16 waves (a block is often alone on its CU: waves hide latency)
   const int threads = (int)std::min<int64_t>(frmk::kMaxThreads, std::max<int64_t>(256, ((int64_t)h->max_items * T + 63) / 64 * 64));
-  if (!h->attr_set) {
-    HIP_TRY(hipFuncSetAttribute((const void *)frmk::k_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFrameLds));
-    h->attr_set = true;
-  }
+  void (*const frame_kernels[])(frmk::Args) = {frmk::k_frame};
+  if (const int rc = tsimh::allow_lds(frame_kernels, kFrameLds, &h->attr_set)) return rc;
   uint32_t n0 = 0x6E6F6973u, n1 = 0x6672616Du;  // the request's noise key: threefry2x32(key, ("nois", "fram"))
   tsimk::threefry2x32(key_hi, key_lo, n0, n1);
-  const int per_wave = (int)out_lds_per_wave(h->win);
-  const int nw = std::max(1, std::min(m2dk::kMaxWaves, kOutLds / per_wave));
   for (int64_t done = 0; done < B; done += h->max_words * 64) {  // launches whose flip words fit the scratch, in stream order
     const int64_t rows = std::min<int64_t>(B - done, h->max_words * 64), words = (rows + 63) / 64;
     frmk::Args A;
@@ -296,38 +209,17 @@ extern "C" int tsim_frame_sample_device(tsim_frame *h, int64_t B, int64_t first_
     A.n1 = n1;
     hipLaunchKernelGGL(frmk::k_frame, dim3((unsigned)((words + T - 1) / T)), dim3(threads), frame_lds, s, A);
     HIP_TRY(hipGetLastError());
-    uint8_t *dst = d_out + done * out_row_bytes;
     frmk::OutArgs O;
-    m2dk::Args &a = O.m;
-    a.in = nullptr;
-    a.B = rows;
-    a.in_rb = 0;
-    a.M = h->n_rec + h->n_random;
-    a.in_used = 0;
-    a.in_contig = 0;
-    a.in_w4 = 0;
-    a.row_ptr = h->d_row_ptr;
-    a.cols = h->d_cols;
-    a.ref = h->d_const;
-    a.col0 = col0;
-    a.n_cols = n_cols;
-    a.out = dst;
-    a.out_rb = out_row_bytes;
-    a.out_used = (int)out_used;
-    a.out_contig = out_row_bytes == out_used && out_row_bytes <= 64;
-    a.out_w4 = (out_row_bytes % 4 == 0 || a.out_contig) && reinterpret_cast<uintptr_t>(dst) % 4 == 0;
-    a.n_out = h->n_out;
-    a.win = h->win;
-    a.n_win = h->n_win;
+    O.m = h->o.args(rows, d_out + done * out_row_bytes, out_row_bytes, out_packed, col0, n_cols);
     O.F = h->d_F;
     O.stride = h->max_words;
     O.n_rec = h->n_rec;
     O.k0 = key_hi;
     O.k1 = key_lo;
     O.tile0 = A.tile0;
-    const int64_t blocks = std::min<int64_t>((words + nw - 1) / nw, 256 * 8 * 4 / nw);
+    const outh::Outputs::Launch g = h->o.geometry(words);
     void (*k)(frmk::OutArgs) = out_packed ? frmk::k_frame_out<true> : frmk::k_frame_out<false>;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * nw), (size_t)nw * per_wave, s, O);
+    hipLaunchKernelGGL(k, dim3(g.blocks), dim3(64 * g.nw), g.lds, s, O);
     HIP_TRY(hipGetLastError());
   }
   return TSIM_OK;
@@ -339,7 +231,7 @@ extern "C" int tsim_frame_info(const tsim_frame *h, int64_t out[16]) {
   out[1] = h->n_rec;
   out[2] = h->n_hidden;
   out[3] = h->n_random;
-  out[4] = h->n_out;
+  out[4] = h->o.n_out;
   out[5] = h->n_ops;
   out[6] = h->n_batches;
   out[7] = h->n_sites;
@@ -347,8 +239,8 @@ extern "C" int tsim_frame_info(const tsim_frame *h, int64_t out[16]) {
   out[9] = 1ll << h->log2T;
   out[10] = 16ll * h->nq * (1ll << h->log2T);
   out[11] = kFrameLds / 16;
-  out[12] = h->win;
-  out[13] = h->n_win;
+  out[12] = h->o.win;
+  out[13] = h->o.n_win;
   out[14] = h->max_words;
   out[15] = h->max_items;
   return TSIM_OK;

@@ -11,7 +11,7 @@ struct tsim_uf {
   int64_t launches = 0;
   int max_cap = 0;  // 0: unweighted
   int n_heralds = 0;
-  ufh::Uploads up;  // the tables a points to
+  tsimh::Uploads up;  // the tables a points to
 };
 
 extern "C" int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf **out) {
@@ -88,7 +88,7 @@ extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, 
   h->grid = std::max(1, cus) * per_cu;
   h->max_cap = max_cap;
   h->n_heralds = H;
-  ufh::Uploads &up = h->up;
+  tsimh::Uploads &up = h->up;
   a.edge_uv = up.put(uv);
   a.edge_obs = reinterpret_cast<const unsigned long long *>(up.put(obs));
   a.adj_ptr = up.put(ptr);

@@ -1,5 +1,5 @@
 // tsim_uf_host.hip.h - the host side that the two union-find handles share (tsim_uf.hip, tsim_ufw.hip): the checks of a graph,
-// its caps and its heralds, the waves of a block, the uploads a handle owns, and the row arguments and launch loop of a decode
+// its caps and its heralds, the waves of a block, and the row arguments and launch loop of a decode
 // call, on the prelude of tsim_host.hip.h.  Host code only; every check comes before the first device call of its caller.
 #pragma once
 
@@ -86,33 +86,6 @@ inline void choose_waves(long long shot, int *waves, int *per_cu) {
     if (blocks * w >= best) best = blocks * w, *waves = w, *per_cu = blocks;
   }
 }
-
-// the device tables of a handle: the first error is kept and ends the work, the bytes are added up
-struct Uploads {
-  std::vector<void *> ptrs;
-  int64_t bytes = 0;
-  hipError_t err = hipSuccess;
-
-  // n elements of src in a buffer of their own; `slack`: bytes after them that src holds too, uploaded but not counted
-  template <class T>
-  T *put(const T *src, size_t n, size_t slack = 0) {
-    void *d = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&d, n * sizeof(T) + slack);
-    if (err != hipSuccess) return nullptr;
-    ptrs.push_back(d);
-    err = hipMemcpy(d, src, n * sizeof(T) + slack, hipMemcpyHostToDevice);
-    bytes += (int64_t)(n * sizeof(T));
-    return static_cast<T *>(d);
-  }
-  template <class T>
-  T *put(const std::vector<T> &v) { return put(v.data(), v.size()); }
-
-  void release(int device) {
-    if (device >= 0) (void)hipSetDevice(device);
-    for (void *p : ptrs) (void)hipFree(p);
-    ptrs.clear();
-  }
-};
 
 // The row arguments of a decode call, for a.n_cols columns.  0, or an error code after tsim_fail.
 template <class Args>

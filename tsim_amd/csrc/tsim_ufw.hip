@@ -39,7 +39,7 @@ struct tsim_ufw {
   int n_nodes = 0, n_edges = 0, max_nodes = 0, max_edges = 0, max_cap = 0;
   int64_t launches = 0;
   int n_heralds = 0;
-  ufh::Uploads up;  // the tables a points to
+  tsimh::Uploads up;  // the tables a points to
 };
 
 // The windows of the graph (checked by the caller: u < v inside the nodes, pairs strictly ascending) with `commit` = C and
@@ -241,7 +241,7 @@ extern "C" int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *desc,
   h->device = device;
   h->grid = std::max(1, cus) * per_cu;
   h->n_nodes = N, h->n_edges = E, h->max_nodes = t.max_nodes, h->max_edges = t.max_edges, h->max_cap = max_cap;
-  ufh::Uploads &up = h->up;
+  tsimh::Uploads &up = h->up;
   a.desc = up.put(t.desc);
   a.edge_uv = up.put(t.uv);
   a.edge_obs = reinterpret_cast<const unsigned long long *>(up.put(t.obs));

@@ -43,13 +43,13 @@ tests.  The kernel is ``csrc/tsim_faults.hip.h`` behind the ``tsim_faults_*`` ha
 from __future__ import annotations
 
 import ctypes as C
-import weakref
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib, prng
 from .affine import MAX_SHOT, threefry2x32_np
+from . import frame
 from .frame import MAX_SITE_BITS, _FrameSampler, outcome_thresholds
 from .sampler import CompiledDetectorSampler
 
@@ -65,10 +65,8 @@ CLASS_FOLD = 0x9E3779B9
 # ---- the tables of the draw ---------------------------------------------------------------------------------------------
 
 def gap_thresholds(p_fire: float) -> np.ndarray:
-    """``uint32[K_GAP]``: entry ``k - 1`` is ``floor((1 - p_fire)^k 2^32)``, at most ``2^32 - 1``."""
-    k = np.arange(1, K_GAP + 1, dtype=np.float64)
-    t = np.floor(np.power(np.float64(1.0) - np.float64(p_fire), k) * 4294967296.0)
-    return np.minimum(t, 4294967295.0).astype(np.uint32)
+    """``uint32[K_GAP]``: ``frame.gap_thresholds`` with the ``K_GAP`` entries of this sampler's gap rows."""
+    return frame.gap_thresholds(p_fire, K_GAP)
 
 
 def skip_of(gap_row: np.ndarray, x0) -> np.ndarray:
@@ -273,55 +271,35 @@ def _rows_host(form: FaultForm, first_shot: int, B: int, fire, return_e: bool):
 
 # ---- the device handle --------------------------------------------------------------------------------------------------
 
-class FaultHandle:
+class FaultHandle(_lib.DeviceHandle):
     """``tsim_faults`` of one device: the form's arrays (outputs padded to whole uint64 words with constant zeros that
     nothing flips when ``pad_outputs``).  The device handle is created by the first launch."""
 
-    INFO = ("n_out", "num_e", "n_sites", "n_classes", "device", "gap_k", "window", "n_windows", "row_words", "waves",
-            "lds_bytes", "tables_in_lds", "n_gaps", "n_cols", "max_class_sites", "max_window")
+    CREATE, DESTROY = "tsim_faults_create", "tsim_faults_destroy"
+    INFO = ("tsim_faults_info", ("n_out", "num_e", "n_sites", "n_classes", "device", "gap_k", "window", "n_windows", "row_words", "waves",
+                                 "lds_bytes", "tables_in_lds", "n_gaps", "n_cols", "max_class_sites", "max_window"))
 
     def __init__(self, form: FaultForm, *, device: int = 0, pad_outputs: bool = False):
         self.form, self._device = form, int(device)
         pad = -form.n_out % 64 if pad_outputs else 0
         self.out_const = np.ascontiguousarray(np.concatenate([form.out_const, np.zeros(pad, np.uint8)]))
         self.n_out = len(self.out_const)
-        self._h = None
-        self._finalizer = None
 
-    def _handle(self):
-        if self._h is None:
-            lib, f = _lib.load(), self.form
-            arrays = dict(f.arrays(), out_const=self.out_const)
-            self._keep = {n: np.ascontiguousarray(arrays[n]) for n in _lib.FaultsDesc.ARRAYS}
-            sizes = dict(n_out=self.n_out, num_e=f.num_e, n_sites=f.n_sites, n_classes=f.n_classes, n_outcomes=len(f.out_vals),
-                         n_gaps=len(f.gap_thr), gap_k=f.gap_thr.shape[1] if f.gap_thr.ndim == 2 else 0, n_cols=len(f.cols))
-            desc = _lib.FaultsDesc(**sizes, **{n: a.ctypes.data for n, a in self._keep.items()})
-            h = C.c_void_p()
-            _lib.check(lib.tsim_faults_create(self._device, C.byref(desc), C.byref(h)), "tsim_faults_create")
-            self._h = h
-            self._finalizer = weakref.finalize(self, lib.tsim_faults_destroy, h)
-        return self._h
-
-    def close(self) -> None:
-        if self._finalizer is not None:
-            self._finalizer()
-        self._h = None
-        self._finalizer = None
-
-    def info(self) -> dict:
-        out = (C.c_int64 * 16)()
-        _lib.check(_lib.load().tsim_faults_info(self._handle(), out), "tsim_faults_info")
-        return {k: int(v) for k, v in zip(self.INFO, out)}
+    def _create_args(self) -> tuple:
+        f = self.form
+        arrays = dict(f.arrays(), out_const=self.out_const)
+        self._keep = {n: np.ascontiguousarray(arrays[n]) for n in _lib.FaultsDesc.ARRAYS}
+        sizes = dict(n_out=self.n_out, num_e=f.num_e, n_sites=f.n_sites, n_classes=f.n_classes, n_outcomes=len(f.out_vals),
+                     n_gaps=len(f.gap_thr), gap_k=f.gap_thr.shape[1] if f.gap_thr.ndim == 2 else 0, n_cols=len(f.cols))
+        desc = _lib.FaultsDesc(**sizes, **{n: a.ctypes.data for n, a in self._keep.items()})
+        return self._device, C.byref(desc)
 
     def sample_device(self, B: int, d_out: int, *, key, first_shot: int = 0, out_row_bytes: int, out_packed: bool, col0: int = 0,
                       n_cols: int | None = None, stream: int = 0) -> None:
         """Caller-owned output buffer, asynchronous on ``stream`` (0: the handle's own); see ``tsim_faults_sample_device`` in
         ``include/tsim_hip.h``."""
-        n_cols = self.n_out - col0 if n_cols is None else n_cols
-        _lib.check(_lib.load().tsim_faults_sample_device(
-            self._handle(), int(B), int(first_shot), int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF,
-            C.c_void_p(int(d_out)) if d_out else None, int(out_row_bytes), int(bool(out_packed)), int(col0), int(n_cols),
-            stream or None), "tsim_faults_sample_device")
+        self._request("tsim_faults_sample_device", (), B, d_out, key=key, first_shot=first_shot, out_row_bytes=out_row_bytes,
+                      out_packed=out_packed, col0=col0, n_cols=n_cols, stream=stream)
 
 
 # ---- the sampler --------------------------------------------------------------------------------------------------------

@@ -255,18 +255,13 @@ class FixedWeightHandle(FaultHandle):
         return self._h
 
     def weight_info(self) -> dict:
-        out = (C.c_int64 * 8)()
-        _lib.check(_lib.load().tsim_faults_weight_info(self._handle(), out), "tsim_faults_weight_info")
-        return {k: int(v) for k, v in zip(self.WEIGHT_INFO, out)}
+        return self._read_info("tsim_faults_weight_info", self.WEIGHT_INFO)
 
     def sample_device(self, B: int, d_out: int, *, key, first_shot: int = 0, out_row_bytes: int, out_packed: bool, col0: int = 0,
                       n_cols: int | None = None, stream: int = 0) -> None:
         """As ``FaultHandle.sample_device``; see ``tsim_faults_sample_weight_device`` in ``include/tsim_hip.h``."""
-        n_cols = self.n_out - col0 if n_cols is None else n_cols
-        _lib.check(_lib.load().tsim_faults_sample_weight_device(
-            self._handle(), int(self.weight), int(B), int(first_shot), int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF,
-            C.c_void_p(int(d_out)) if d_out else None, int(out_row_bytes), int(bool(out_packed)), int(col0), int(n_cols),
-            stream or None), "tsim_faults_sample_weight_device")
+        self._request("tsim_faults_sample_weight_device", (int(self.weight),), B, d_out, key=key, first_shot=first_shot,
+                      out_row_bytes=out_row_bytes, out_packed=out_packed, col0=col0, n_cols=n_cols, stream=stream)
 
 
 # ---- the sampler --------------------------------------------------------------------------------------------------------

@@ -48,7 +48,6 @@ from __future__ import annotations
 
 import bisect
 import ctypes as C
-import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -187,9 +186,9 @@ class _FrameRecorder(_Sim):
 
 # ---- the tables of the draw ---------------------------------------------------------------------------------------------
 
-def gap_thresholds(p_fire: float) -> np.ndarray:
-    """``uint32[64]``: entry ``k - 1`` is ``floor((1 - p_fire)^k 2^32)``, at most ``2^32 - 1``."""
-    k = np.arange(1, 65, dtype=np.float64)
+def gap_thresholds(p_fire: float, n: int = 64) -> np.ndarray:
+    """``uint32[n]``: entry ``k - 1`` is ``floor((1 - p_fire)^k 2^32)``, at most ``2^32 - 1``."""
+    k = np.arange(1, n + 1, dtype=np.float64)
     t = np.floor(np.power(np.float64(1.0) - np.float64(p_fire), k) * 4294967296.0)
     return np.minimum(t, 4294967295.0).astype(np.uint32)
 
@@ -507,12 +506,13 @@ def e_rows(e_words: np.ndarray, B: int) -> np.ndarray:
 
 # ---- the device handle --------------------------------------------------------------------------------------------------
 
-class FrameHandle:
+class FrameHandle(_lib.DeviceHandle):
     """``tsim_frame`` of one device: the form's arrays (outputs padded to whole uint64 words with constant zeros when
     ``pad_outputs``).  The device handle is created by the first launch."""
 
-    INFO = ("n_qubits", "n_records", "n_hidden", "n_random", "n_out", "n_ops", "n_batches", "n_sites", "device", "T",
-            "lds_bytes", "max_qubits", "window", "n_windows", "max_words", "max_batch_items")
+    CREATE, DESTROY = "tsim_frame_create", "tsim_frame_destroy"
+    INFO = ("tsim_frame_info", ("n_qubits", "n_records", "n_hidden", "n_random", "n_out", "n_ops", "n_batches", "n_sites", "device", "T",
+                                "lds_bytes", "max_qubits", "window", "n_windows", "max_words", "max_batch_items"))
 
     def __init__(self, form: FrameForm, *, device: int = 0, pad_outputs: bool = False):
         self.form, self._device = form, int(device)
@@ -520,45 +520,24 @@ class FrameHandle:
         self.out_ptr = np.ascontiguousarray(np.concatenate([form.out_ptr, np.full(pad, form.out_ptr[-1], np.int32)]))
         self.out_const = np.ascontiguousarray(np.concatenate([form.out_const, np.zeros(pad, np.uint8)]))
         self.n_out = len(self.out_const)
-        self._h = None
-        self._finalizer = None
 
-    def _handle(self):
-        if self._h is None:
-            lib, f = _lib.load(), self.form
-            arrays = dict(f.arrays(), out_const=self.out_const, out_ptr=self.out_ptr)
-            self._keep = {n: np.ascontiguousarray(arrays[n]) for n in _lib.FrameDesc.ARRAYS}
-            sizes = dict(n_qubits=f.n_qubits, n_records=f.n_records, n_hidden=f.n_hidden, n_random=f.n_random, n_out=self.n_out,
-                         n_ops=f.n_ops, n_batches=f.n_batches, n_sites=len(f.site_chan), n_bits=len(f.bit_ptr) - 1,
-                         n_targets=len(f.targets), n_tables=len(f.table_gap), n_outcomes=len(f.out_vals), n_gaps=len(f.gap_thr),
-                         n_cols=len(f.out_cols))
-            desc = _lib.FrameDesc(**sizes, **{n: a.ctypes.data for n, a in self._keep.items()})
-            h = C.c_void_p()
-            _lib.check(lib.tsim_frame_create(self._device, C.byref(desc), C.byref(h)), "tsim_frame_create")
-            self._h = h
-            self._finalizer = weakref.finalize(self, lib.tsim_frame_destroy, h)
-        return self._h
-
-    def close(self) -> None:
-        if self._finalizer is not None:
-            self._finalizer()
-        self._h = None
-        self._finalizer = None
-
-    def info(self) -> dict:
-        out = (C.c_int64 * 16)()
-        _lib.check(_lib.load().tsim_frame_info(self._handle(), out), "tsim_frame_info")
-        return {k: int(v) for k, v in zip(self.INFO, out)}
+    def _create_args(self) -> tuple:
+        f = self.form
+        arrays = dict(f.arrays(), out_const=self.out_const, out_ptr=self.out_ptr)
+        self._keep = {n: np.ascontiguousarray(arrays[n]) for n in _lib.FrameDesc.ARRAYS}
+        sizes = dict(n_qubits=f.n_qubits, n_records=f.n_records, n_hidden=f.n_hidden, n_random=f.n_random, n_out=self.n_out,
+                     n_ops=f.n_ops, n_batches=f.n_batches, n_sites=len(f.site_chan), n_bits=len(f.bit_ptr) - 1,
+                     n_targets=len(f.targets), n_tables=len(f.table_gap), n_outcomes=len(f.out_vals), n_gaps=len(f.gap_thr),
+                     n_cols=len(f.out_cols))
+        desc = _lib.FrameDesc(**sizes, **{n: a.ctypes.data for n, a in self._keep.items()})
+        return self._device, C.byref(desc)
 
     def sample_device(self, B: int, d_out: int, *, key, first_shot: int = 0, out_row_bytes: int, out_packed: bool, col0: int = 0,
                       n_cols: int | None = None, stream: int = 0) -> None:
         """Caller-owned output buffer, asynchronous on ``stream`` (0: the handle's own); see ``tsim_frame_sample_device`` in
         ``include/tsim_hip.h``.  The record-flip scratch belongs to the handle and grows to what ``B`` needs."""
-        n_cols = self.n_out - col0 if n_cols is None else n_cols
-        _lib.check(_lib.load().tsim_frame_sample_device(
-            self._handle(), int(B), int(first_shot), int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF,
-            C.c_void_p(int(d_out)) if d_out else None, int(out_row_bytes), int(bool(out_packed)), int(col0), int(n_cols),
-            stream or None), "tsim_frame_sample_device")
+        self._request("tsim_frame_sample_device", (), B, d_out, key=key, first_shot=first_shot, out_row_bytes=out_row_bytes,
+                      out_packed=out_packed, col0=col0, n_cols=n_cols, stream=stream)
 
 
 # ---- the samplers -------------------------------------------------------------------------------------------------------

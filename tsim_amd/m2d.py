@@ -10,7 +10,6 @@ created by the first conversion that has work to do.
 from __future__ import annotations
 
 import ctypes as C
-import weakref
 
 import numpy as np
 
@@ -21,7 +20,7 @@ __all__ = ["CompiledMeasurementsToDetectionEventsConverter"]
 _BOTH_FLAGS = "Can't specify separate_observables=True with append_observables=True or prepend_observables=True"
 
 
-class CompiledMeasurementsToDetectionEventsConverter:
+class CompiledMeasurementsToDetectionEventsConverter(_lib.DeviceHandle):
     """stim's converter surface over a CSR of record indices: ``records[j]`` lists the measurement records output ``j``
     XORs (outputs = ``num_detectors`` detectors, then the observables), ``ref[j]`` its constant bit."""
 
@@ -41,8 +40,6 @@ class CompiledMeasurementsToDetectionEventsConverter:
         if self._ref.shape != (self._n_out,):
             raise ValueError(f"ref must have {self._n_out} entries")
         self._device = int(device)
-        self._h = None
-        self._finalizer = None
 
     # -- stim's properties ---------------------------------------------------------------------------------------
     @property
@@ -62,21 +59,11 @@ class CompiledMeasurementsToDetectionEventsConverter:
         return self._row_ptr.copy(), self._cols.copy(), self._ref.copy()
 
     # -- the device handle ------------------------------------------------------------------------------------------
-    def _handle(self):
-        if self._h is None:
-            lib = _lib.load()
-            h = C.c_void_p()
-            _lib.check(lib.tsim_m2d_create(self._device, self._M, self._n_out, _lib.ptr(self._row_ptr),
-                                           _lib.ptr(self._cols), _lib.ptr(self._ref), C.byref(h)), "tsim_m2d_create")
-            self._h = h
-            self._finalizer = weakref.finalize(self, lib.tsim_m2d_destroy, h)
-        return self._h
+    CREATE, DESTROY = "tsim_m2d_create", "tsim_m2d_destroy"
+    INFO = ("tsim_m2d_info", ("num_measurements", "n_out", "nnz", "device"))
 
-    def close(self) -> None:
-        if self._finalizer is not None:
-            self._finalizer()
-        self._h = None
-        self._finalizer = None
+    def _create_args(self) -> tuple:
+        return self._device, self._M, self._n_out, _lib.ptr(self._row_ptr), _lib.ptr(self._cols), _lib.ptr(self._ref)
 
     # -- conversion -------------------------------------------------------------------------------------------------
     def _columns(self, separate_observables: bool, append_observables: bool) -> list[tuple[int, int]]:
