@@ -241,14 +241,22 @@ static LaunchPlan make_plan(tsim_program *p, bool has_row_index, bool pipelined,
 // Every pipeline slot has its stream.  (Streams are created HERE, in one go, and nowhere earlier: HIP deals streams to its
 // few hardware queues in creation order, and one more stream in front of the lanes - created at finalize for the table
 // build of an earlier version - moved two lanes onto one queue: C4 at 10^5 shots per step 1.73 -> 1.07e10.)
-static int slots_now_ready(tsim_program *p) {
+// The first pipelined launch of a handle: the four lanes, in one go; the other slots' streams and buffers on first use.
+static int lanes_ready(tsim_program *p) {
+  if (p->slots_ready) return 0;
+  for (int k = 1; k <= 4; ++k)
+    if (int r = slot_prepare(p, k, 0)) return r;
   p->slots_ready = true;
   return 0;
+}
+// the hard-row lists of a slot: TSIMK_LW_LISTS lists that each hold every row of the 256-row blocks that feed them
+static size_t hard_list_bytes(int64_t B) {
+  return (size_t)(((B + 255) / 256 + TSIMK_LW_LISTS - 1) / TSIMK_LW_LISTS * 1024) * TSIMK_LW_LISTS * 4;
 }
 static thread_local const LaunchPlan *g_carry_plan = nullptr;  // a plan drawn by the caller of tsim_sample_batch_device_begin
 
 // k_sample4h geometry (LDS budget -> tiles per group), 0 tiles = the kernel cannot run this program
-void hard_geometry(tsim_program *p, int WF, int WO) {
+static void hard_geometry(tsim_program *p, int WF, int WO) {
   constexpr int NW = TSIM_HARD_NW;
   const size_t tile_b = (size_t)p->v4_max_nch * 16 * p->v4_gt * 16;
   const size_t fixed_b = (size_t)(2 * WF + 2 * WO) * 64 * 4 + (size_t)NW * 8 * 64 * 4;
@@ -529,7 +537,7 @@ int flush_batch(tsim_program *p) {
 
 // p->deferred in batches of at most TSIMK_H_MAX_CTX launches (a hard-row grid carries that many contexts in its kernel
 // arguments; fused groups may be larger), all on the stream the caller chose
-int flush_chunks(tsim_program *p) {
+static int flush_chunks(tsim_program *p) {
   if ((int)p->deferred.size() <= TSIMK_H_MAX_CTX) return flush_batch(p);
   std::vector<int> all;
   all.swap(p->deferred);
@@ -624,6 +632,60 @@ int fill_sample_args(tsim_program *p, tsim_program::Slot &sl, SampleArgs &a, con
   if (num_f == 0) a.WF = 0;
   return 0;
 }
+// `a` now describes the row lists a first pass has filled (the check row was forced into one of them): what the hard-row
+// kernels need of that launch
+void describe_lists(SampleArgs &a, const uint32_t *hard_index, const uint32_t *ctl, int n_lists, int list_cap, bool has_check) {
+  a.row_index = hard_index;
+  a.row_count = ctl;
+  a.row_lists = n_lists;
+  a.row_list_cap = list_cap;
+  a.check_row = has_check ? ctl + 32 * TSIMK_LW_LISTS : nullptr;
+  a.no_check = has_check ? 0 : 1;
+  a.row_slot_begin = 0;
+  a.row_slot_end = 0;
+}
+// The specialised first passes (tsim_lw_fast.hip.h, tsim_lw_fastm.hip.h) use 32-bit byte offsets everywhere: batches below
+// 2^28 rows, tables below 4 GB, a power of two of lists, and a shot range that does not cross a multiple of 2^32
+static bool lw32_ok(const tsim_program *p, int64_t B, int64_t shot_offset, int n_lists) {
+  return B < (1ll << 28) && p->lw_bytes < (1ll << 32) && (n_lists & (n_lists - 1)) == 0 &&
+         ((unsigned long long)shot_offset >> 32) == ((unsigned long long)(shot_offset + B - 1) >> 32);
+}
+// what every launch of the register first passes' group kernels carries, whatever the kernel (lwf_off, tab_bytes, the
+// header and the steps are the caller's)
+static void lwm_common_args(const tsim_program *p, LwMultiArgs &M, int64_t B, int64_t shot_offset, int n, long long bps, bool has_check,
+                            long long list_cap, int n_lists) {
+  M.img = p->d_img;
+  M.tab = p->d_lw_tab;
+  M.B = B;
+  M.shot_offset = shot_offset;
+  M.n_steps = n;
+  M.blocks_per_step = (int)bps;
+  M.n_comp = (int)p->comps.size();
+  M.lw_off = p->lw_off;
+  M.direct_rot = p->lw_direct_rot;
+  M.binom_off = p->lw_binom_off;
+  M.has_check = has_check ? 1 : 0;
+  M.list_cap = (int)list_cap;
+  M.n_lists = n_lists;
+  M.out_rb = (p->num_outputs + 7) / 8;
+}
+// (Kernel instances come out in the library in the order this file first names them.  launch_sample names its sparse-column
+// pass before its first k_sample_lw_fast: named here, it keeps its place in front of the sixteen instances below.)
+[[maybe_unused]] static constexpr auto k_named_first = k_sample4w<1, 10>;
+// k_sample_lw_fast by f words and the component's outputs: a group of the steps call, or one batch of the serial API
+static int launch_lw_fast(int WF, int n_out, long long grid, hipStream_t s, const LwMultiArgs &M) {
+#define TSIM_LF(N)                                                                                      \
+  case N:                                                                                               \
+    if (WF == 1) hipLaunchKernelGGL((k_sample_lw_fast<2, N>), dim3((unsigned)grid), dim3(1024), 0, s, M); \
+    else hipLaunchKernelGGL((k_sample_lw_fast<4, N>), dim3((unsigned)grid), dim3(1024), 0, s, M);        \
+    break;
+  switch (n_out) {
+    TSIM_LF(1) TSIM_LF(2) TSIM_LF(3) TSIM_LF(4) TSIM_LF(5) TSIM_LF(6) TSIM_LF(7) TSIM_LF(8)
+    default: return tsim_fail(TSIM_ESTATE, "fast record with %d outputs", n_out);
+  }
+#undef TSIM_LF
+  return 0;
+}
 static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_t num_f, uint32_t key_hi,
                          uint32_t key_lo, int64_t shot_offset, uint64_t *d_out, float *d_dev, hipStream_t s,
                          const uint32_t *d_row_index = nullptr, const uint32_t *d_row_count = nullptr,
@@ -642,14 +704,7 @@ static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_
   // per-output subkeys: key, subkey = split(key) once per output, threaded through the
   // components in processing order (sampler.py:74,147-148)
   tsim_program::Slot &sl = p->slots[slot];
-  {
-    size_t hard_bytes = 0;
-    if (p->lw || p->v4w) {
-      const long long g1 = (B + 255) / 256;  // the pattern pass uses 256-thread blocks unless overridden
-      hard_bytes = (size_t)((g1 + TSIMK_LW_LISTS - 1) / TSIMK_LW_LISTS * 1024) * TSIMK_LW_LISTS * 4;
-    }
-    if (int r = slot_prepare(p, slot, hard_bytes)) return r;
-  }
+  if (int r = slot_prepare(p, slot, (p->lw || p->v4w) ? hard_list_bytes(B) : 0)) return r;
   SampleArgs a{};
   if (int r = fill_sample_args(p, sl, a, d_f, B, num_f, key_hi, key_lo, shot_offset, d_out, d_dev, s, slot, out_bit_packed)) return r;
   a.row_index = d_row_index;
@@ -762,12 +817,7 @@ static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_
     hipLaunchKernelGGL((k_sample4w<1, kWideK>), dim3((unsigned)grid1), dim3(kWideBlock), ldsw, s, w);
     HIP_TRY(hipGetLastError());
     if (prof && !(from_lists && p->prof_light)) { int r = prof_event(p, s, from_lists ? PROF_HARD : PROF_PASS1); if (r) return r; }
-    a.row_index = w.hard_index;
-    a.row_count = ctl;
-    a.row_lists = kWideLists;
-    a.row_list_cap = (int)list_cap;
-    a.check_row = has_check ? ctl + 32 * TSIMK_LW_LISTS : nullptr;
-    a.no_check = has_check ? 0 : 1;
+    describe_lists(a, w.hard_index, ctl, kWideLists, (int)list_cap, has_check);
     B2 = list_cap;
     return 0;
   };
@@ -818,8 +868,7 @@ static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_
     // one component of at most 8 outputs: the specialised pass of the fused groups (tsim_lw_fast.hip.h), as a group of ONE
     // batch - 14.5 instead of 19.6 us per 10^6 shots for the serial API too (same conditions as in steps_group_fused)
     const bool fast1 = reg_form && p->lwf_off != 0 && p->knobs.lw_fast && blk1 == 1024 && a.n_inline_keys > 0 && p->total_keys <= TSIMK_LWM_KEYS &&
-                       B < (1ll << 28) && p->lw_bytes < (1ll << 32) && (n_lists & (n_lists - 1)) == 0 && a.WO == 1 &&
-                       ((unsigned long long)shot_offset >> 32) == ((unsigned long long)(shot_offset + B - 1) >> 32);
+                       a.WO == 1 && lw32_ok(p, B, shot_offset, n_lists);
     if (gen1) {
       long long cap1 = 0;
       if (int r = gen_one(p, sl, a, B, num_f, key_hi, key_lo, shot_offset, l.hard_index, l.ctl, l.ctl_next, n_lists, has_check, &cap1, s)) return r;
@@ -829,20 +878,7 @@ static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_
       const long long cap1 = (blocks + n_lists - 1) / n_lists * blk1;  // the fused kernels' list geometry: row block rb -> list rb % n_lists
       if ((size_t)cap1 * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
       LwMultiArgs M{};
-      M.img = p->d_img;
-      M.tab = p->d_lw_tab;
-      M.B = B;
-      M.shot_offset = shot_offset;
-      M.n_steps = 1;
-      M.blocks_per_step = (int)blocks;
-      M.n_comp = (int)p->comps.size();
-      M.lw_off = p->lw_off;
-      M.direct_rot = p->lw_direct_rot;
-      M.binom_off = p->lw_binom_off;
-      M.has_check = has_check ? 1 : 0;
-      M.list_cap = (int)cap1;
-      M.n_lists = n_lists;
-      M.out_rb = (p->num_outputs + 7) / 8;
+      lwm_common_args(p, M, B, shot_offset, 1, blocks, has_check, cap1, n_lists);
       M.lwf_off = p->lwf_off;
       M.tab_bytes = (uint32_t)p->lw_bytes;
       lwf_fill_header(p, M);
@@ -857,18 +893,8 @@ static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_
       const long long chip = (long long)p->n_cu * (2048 / blk1);
       const long long it1 = (blocks + chip - 1) / chip;
       const long long gridf = (blocks + it1 - 1) / it1;
-      const int n_out = p->comps[0].n_out;
-#define TSIM_LF1(N)                                                                                        \
-  case N:                                                                                                  \
-    if (a.WF == 1) hipLaunchKernelGGL((k_sample_lw_fast<2, N>), dim3((unsigned)gridf), dim3(blk1), 0, s, M); \
-    else hipLaunchKernelGGL((k_sample_lw_fast<4, N>), dim3((unsigned)gridf), dim3(blk1), 0, s, M);          \
-    break;
       ++p->path_count[TP_LW_FAST1];
-      switch (n_out) {
-        TSIM_LF1(1) TSIM_LF1(2) TSIM_LF1(3) TSIM_LF1(4) TSIM_LF1(5) TSIM_LF1(6) TSIM_LF1(7) TSIM_LF1(8)
-        default: return tsim_fail(TSIM_ESTATE, "fast record with %d outputs", n_out);
-      }
-#undef TSIM_LF1
+      if (int r = launch_lw_fast(a.WF, p->comps[0].n_out, gridf, s, M)) return r;
       l.list_cap = (int)cap1;
     } else if (reg_form) {
       // narrow rows: everything in registers, no LDS
@@ -884,12 +910,7 @@ static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_
     HIP_TRY(hipGetLastError());
     if (prof) { int r = prof_event(p, s, PROF_PASS1); if (r) return r; }
     // pass 2 below runs on the hard lists; the check row was forced into one of them
-    a.row_index = l.hard_index;
-    a.row_count = ctl;
-    a.row_lists = n_lists;
-    a.row_list_cap = l.list_cap;
-    a.check_row = has_check ? ctl + 32 * TSIMK_LW_LISTS : nullptr;
-    a.no_check = has_check ? 0 : 1;
+    describe_lists(a, l.hard_index, ctl, n_lists, l.list_cap, has_check);
     B2 = l.list_cap;
     // wide components: the listed rows go through the sparse-column pass first, its overflow to the row kernel
     // (ctl2 alternates on its own: launches that skip the tables - dense batches - do not touch it, and its reset
@@ -1051,6 +1072,125 @@ int slot_order_after_previous(tsim_program *p, tsim_program::Slot &sl, hipStream
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// The group protocol (tsim_sample_internal.hip.h): what the four group launchers of
+// tsim_sample_steps_device do around their kernels.
+// ---------------------------------------------------------------------------
+
+// Groups that leave hard-row lists: two first-pass lanes; three for small groups, whose hard-row grids (latency-bound, on
+// the group's lane) take longer than their first passes (C4 at 8 x 10^5 shots per group: 1.16 -> 1.53e10 shots/s; the large
+// groups of C2: no change)
+int list_group_lanes(const tsim_program *p, int n, int64_t B) {
+  return p->knobs.fused_lanes > 0 ? p->knobs.fused_lanes : ((long long)n * B <= (1ll << 21) ? 3 : 2);
+}
+// The group's lane - `lanes` of them in turn - behind what is queued on the handle's stream, unless the caller vouches for
+// its inputs
+int group_lane(tsim_program *p, int lanes, uint32_t flags, hipStream_t *lane) {
+  hipStream_t s = p->slots[1 + (int)(p->steps_groups++ % (unsigned long long)lanes)].side;
+  if (!(flags & TSIM_PIPE_INPUTS_READY) && p->stream != s) {
+    if (!p->sync_ev) HIP_TRY(hipEventCreateWithFlags(&p->sync_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(p->sync_ev, p->stream));
+    HIP_TRY(hipStreamWaitEvent(s, p->sync_ev, 0));
+  }
+  *lane = s;
+  return 0;
+}
+// a slot this group takes still waits for its hard rows (many lanes, few slots): those first
+int flush_if_group_parked(tsim_program *p, int n) {
+  for (int j = 0; j < n; ++j)
+    if (p->slots[steps_slot_at(p, j)].deferred) return tsim_flush_hard(p);
+  return 0;
+}
+// behind the slot's previous launch; key, subkey = split(key)  (sampler.py:399)
+static int order_and_split(tsim_program *p, TakenSlot &t, hipStream_t s, uint32_t key[2]) {
+  if (int r = slot_order_after_previous(p, *t.sl, s)) return r;
+  uint32_t o[4];
+  tsim_key_split(key[0], key[1], o);
+  key[0] = o[0];
+  key[1] = o[1];
+  t.sub[0] = o[2];
+  t.sub[1] = o[3];
+  return 0;
+}
+// The next slot for a batch whose first pass leaves hard-row lists (the caller has prepared it: slot_prepare with
+// hard_list_bytes).  sl.ctx holds the batch's SampleArgs and describes the lists already - what the hard-row grid needs of
+// this launch; the counter sets alternate (pass 1 of a launch resets the set of the slot's next one).
+int take_list_slot(tsim_program *p, hipStream_t s, uint32_t key[2], const uint64_t *d_f, int64_t B, int32_t num_f, int64_t shot_offset, void *d_out,
+                   float *d_dev, bool packed, int n_lists, long long list_cap, bool has_check, TakenSlot &t) {
+  t.sidx = steps_slot_at(p, 0);
+  ++p->steps_slot;
+  tsim_program::Slot &sl = p->slots[t.sidx];
+  t.sl = &sl;
+  if (sl.deferred) return tsim_fail(TSIM_ESTATE, "pipeline slot %d still holds a parked launch", t.sidx - 1);
+  if ((size_t)list_cap * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
+  if (int r = order_and_split(p, t, s, key)) return r;
+  sl.ctx = SampleArgs{};
+  if (int r = fill_sample_args(p, sl, sl.ctx, d_f, B, num_f, t.sub[0], t.sub[1], shot_offset, (uint64_t *)d_out, d_dev, s, t.sidx, packed)) return r;
+  t.hard_index = (uint32_t *)sl.hard;
+  t.ctl = sl.ctl + sl.parity * (TSIMK_LW_LISTS + 1) * 32;
+  t.ctl_next = sl.ctl + (sl.parity ^ 1) * (TSIMK_LW_LISTS + 1) * 32;
+  sl.parity ^= 1;
+  describe_lists(sl.ctx, t.hard_index, t.ctl, n_lists, (int)list_cap, has_check);
+  return 0;
+}
+// The next slot for a batch of a group that leaves nothing behind: counters, keys and events only
+int take_plain_slot(tsim_program *p, hipStream_t s, uint32_t key[2], TakenSlot &t) {
+  t.sidx = steps_slot_at(p, 0);
+  ++p->steps_slot;
+  if (int r = slot_prepare(p, t.sidx, 0)) return r;
+  t.sl = &p->slots[t.sidx];
+  if (t.sl->deferred) return tsim_fail(TSIM_ESTATE, "pipeline slot %d still holds a parked launch", t.sidx - 1);
+  return order_and_split(p, t, s, key);
+}
+// the profiling bracket of a group's first pass
+int group_prof_begin(tsim_program *p, hipStream_t s, bool *prof) {
+  *prof = p->profiling && (p->prof_counter++ % p->prof_every == 0);
+  return *prof ? prof_event(p, s, PROF_BEGIN) : 0;
+}
+int group_prof_pass1(tsim_program *p, hipStream_t s, bool prof, int n) {
+  if (!prof) return 0;
+  if (int r = prof_event(p, s, PROF_PASS1)) return r;
+  p->prof_steps += n;
+  return 0;
+}
+// Behind a first pass that left lists: the group's slots wait for their hard rows, which go out at once - on the group's own
+// lane when the group is small (letting them wait for the lane's NEXT first pass was tried -
+// profiles/r03/hard_lag_experiment.txt: slower).  `partial`: the pass stored partial rows and component masks.
+int park_group(tsim_program *p, int n, const int *slots, hipStream_t s, int64_t B, int WF, bool has_check, bool partial) {
+  hard_geometry(p, WF, (p->num_outputs + 63) / 64);
+  for (int j = 0; j < n; ++j) {
+    tsim_program::Slot &sl = p->slots[slots[j]];
+    sl.ctx_check = has_check;
+    sl.deferred = true;
+    sl.pending = true;
+    sl.p1_stream = s;
+    sl.partial = partial;
+    p->deferred.push_back(slots[j]);
+  }
+  p->stat_begins += (unsigned long long)n;
+  p->stat_deferred += (unsigned long long)n;
+  ++p->stat_fused;
+  if ((long long)n * B <= p->knobs.hard_inline_rows) p->flush_inline = s;
+  const int rf = flush_chunks(p);
+  TSIM_MARK("hard");
+  return rf;
+}
+// Behind a grid that left nothing: the group's `n` slots, from `first` on round the ring, are done when it is
+int finish_group(tsim_program *p, int n, int first, hipStream_t s) {
+  hipEvent_t ev = p->slots[first].ev2;
+  HIP_TRY(hipEventRecord(ev, s));
+  for (int j = 0; j < n; ++j) {
+    tsim_program::Slot &sl = p->slots[1 + (first - 1 + j) % TSIM_PIPELINE_SLOTS];
+    sl.pending = true;
+    sl.last_done = s;
+    sl.done_ev = ev;
+    sl.batch_seq = 0;
+  }
+  p->stat_begins += (unsigned long long)n;
+  ++p->stat_fused;
+  return 0;
+}
+
 extern "C" int tsim_sample_batch_device_begin(tsim_program *p, int32_t slot, const uint64_t *d_f, int64_t B,
                                               int32_t num_f, uint32_t key_hi, uint32_t key_lo, int64_t shot_offset,
                                               uint64_t *d_out, float *d_max_norm_dev, void *stream, uint32_t flags) {
@@ -1062,14 +1202,7 @@ extern "C" int tsim_sample_batch_device_begin(tsim_program *p, int32_t slot, con
   if (slot < 0 || slot >= TSIM_PIPELINE_SLOTS) return tsim_fail(TSIM_EINVAL, "slot %d out of range", slot);
   hipStream_t s_user = stream ? (hipStream_t)stream : p->stream;
   tsim_program::Slot &sl = p->slots[1 + slot];
-  if (!p->slots_ready) {  // first pipelined launch: create every slot's stream/buffers now, not mid-run
-    size_t hard_bytes = 0;
-    if (p->lw || p->v4w) hard_bytes = (size_t)(((B + 255) / 256 + TSIMK_LW_LISTS - 1) / TSIMK_LW_LISTS * 1024) * TSIMK_LW_LISTS * 4;
-    (void)hard_bytes;  // (each launch sizes its own slot's lists: launch_sample)
-    for (int k = 1; k <= 4; ++k)  // the lanes, in one go (hardware queues follow the creation order); other slots' buffers on first use
-      if (int r = slot_prepare(p, k, 0)) return r;
-    if (int r = slots_now_ready(p)) return r;
-  }
+  if (int r = lanes_ready(p)) return r;  // (each launch sizes its own slot's lists: launch_sample)
   if (int r = slot_prepare(p, 1 + slot, 0)) return r;
   // The whole launch runs on the slot's own stream (a "lane"): launches of one slot are ordered by the
   // stream itself, launches of different slots overlap.  Unless the caller vouches for its inputs the
@@ -1132,6 +1265,12 @@ extern "C" int tsim_sample_batch_device_begin(tsim_program *p, int32_t slot, con
 // goes through tsim_sample_batch_device_begin batch by batch: same results either way.
 // ---------------------------------------------------------------------------
 
+// even groups of at most `cap` batches, as few as possible (20 batches under a cap of 8: 7+7+6; 5+5+5+5 - both lanes ending
+// together - measured slower: a launch more): the next one's size
+static int even_group(int left, int cap) {
+  const int groups = (left + cap - 1) / cap;
+  return (left + groups - 1) / groups;
+}
 // How many of the `left` batches of B shots that remain in a call the next fused group of the register first passes takes.
 // Up to 8: even groups, as few as possible (20 batches as 7+7+6).  More than 8 (fused_max, at most TSIMK_LWM_MAX_STEPS = the
 // contexts of one hard-row grid): one chip-wide ramp and one hard-row grid for twice the batches - but only while at least two
@@ -1143,9 +1282,7 @@ extern "C" int32_t tsim_steps_next_group(int32_t left, int64_t B, int32_t fused_
   if (left <= 0) return 0;
   const int cap = std::max(1, std::min(TSIMK_LWM_MAX_STEPS, (int)fused_max));
   if (cap > 8 && left >= 2 * TSIMK_LWM_MAX_STEPS && (long long)cap * (long long)B >= (long long)long_shots) return cap;
-  const int g = std::min(cap, 8);
-  const int groups = (left + g - 1) / g;
-  return (left + groups - 1) / groups;
+  return even_group(left, std::min(cap, 8));
 }
 
 static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f, int64_t B, int32_t num_f, uint32_t key[2],
@@ -1153,15 +1290,8 @@ static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f,
   const bool packed = (flags & TSIM_PIPE_OUT_BIT_PACKED) != 0;
   if (!p->deferred.empty())
     if (int r = flush_batch(p)) return r;  // rows parked by batch-by-batch launches: their own batch first
-  // two first-pass lanes; three for small groups, whose hard-row grids (latency-bound, on the group's lane) take longer
-  // than their first passes (C4 at 8 x 10^5 shots per group: 1.16 -> 1.53e10 shots/s; the large groups of C2: no change)
-  const int lanes = p->knobs.fused_lanes > 0 ? p->knobs.fused_lanes : ((long long)n * B <= (1ll << 21) ? 3 : 2);
-  hipStream_t s = p->slots[1 + (int)(p->steps_groups++ % (unsigned long long)lanes)].side;
-  if (!(flags & TSIM_PIPE_INPUTS_READY) && p->stream != s) {
-    if (!p->sync_ev) HIP_TRY(hipEventCreateWithFlags(&p->sync_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(p->sync_ev, p->stream));
-    HIP_TRY(hipStreamWaitEvent(s, p->sync_ev, 0));
-  }
+  hipStream_t s;
+  if (int r = group_lane(p, list_group_lanes(p, n, B), flags, &s)) return r;
   const int WF = std::max(1, (num_f + 63) / 64);
   const int blk1 = 1024;
   const long long bps = (B + blk1 - 1) / blk1;
@@ -1175,62 +1305,24 @@ static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f,
   if (list_cap > 0x7FFFFFFFll || bps * n > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row lists");
   const bool has_check = shot_offset == 0;
   LwMultiArgs M{};
-  M.img = p->d_img;
-  M.tab = p->d_lw_tab;
-  M.B = B;
-  M.shot_offset = shot_offset;
-  M.n_steps = n;
-  M.blocks_per_step = (int)bps;
-  M.n_comp = (int)p->comps.size();
-  M.lw_off = p->lw_off;
-  M.direct_rot = p->lw_direct_rot;
-  M.binom_off = p->lw_binom_off;
-  M.has_check = has_check ? 1 : 0;
-  M.list_cap = (int)list_cap;
-  M.n_lists = n_lists;
-  M.out_rb = (p->num_outputs + 7) / 8;
+  lwm_common_args(p, M, B, shot_offset, n, bps, has_check, list_cap, n_lists);
   p->last_lists = n_lists;
   int slots[TSIMK_LWM_MAX_STEPS];
-  for (int j = 0; j < n; ++j)  // a slot this group takes still waits for its hard rows (many lanes, few slots): those first
-    if (p->slots[1 + (int)((p->steps_slot + (unsigned long long)j) % (unsigned long long)TSIM_PIPELINE_SLOTS)].deferred) {
-      if (int r = tsim_flush_hard(p)) return r;
-      break;
-    }
+  if (int r = flush_if_group_parked(p, n)) return r;
   for (int j = 0; j < n; ++j) {
-    const int sidx = 1 + (int)(p->steps_slot++ % (unsigned long long)TSIM_PIPELINE_SLOTS);
-    slots[j] = sidx;
-    tsim_program::Slot &sl = p->slots[sidx];
-    if (sl.deferred) return tsim_fail(TSIM_ESTATE, "pipeline slot %d still holds a parked launch", sidx - 1);
-    if ((size_t)list_cap * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
-    if (int r = slot_order_after_previous(p, sl, s)) return r;
-    uint32_t o[4];
-    tsim_key_split(key[0], key[1], o);  // key, subkey = split(key)  (sampler.py:399)
-    key[0] = o[0];
-    key[1] = o[1];
-    SampleArgs &a = sl.ctx;
-    a = SampleArgs{};
-    if (int r = fill_sample_args(p, sl, a, d_f[j], B, num_f, o[2], o[3], shot_offset, (uint64_t *)d_out[j], d_dev ? d_dev[j] : nullptr, s,
-                                 sidx, packed))
+    TakenSlot t;
+    if (int r = take_list_slot(p, s, key, d_f[j], B, num_f, shot_offset, d_out[j], d_dev ? d_dev[j] : nullptr, packed, n_lists, list_cap, has_check, t))
       return r;
+    slots[j] = t.sidx;
+    const SampleArgs &a = t.sl->ctx;
     LwStep &st = M.step[j];
     st.f = d_f[j];
     st.out = a.out;
     st.out_compact = a.out_compact;
-    st.hard_index = (uint32_t *)sl.hard;
-    uint32_t *ctl = sl.ctl + sl.parity * (TSIMK_LW_LISTS + 1) * 32;
-    st.ctl = ctl;
-    st.ctl_next = sl.ctl + (sl.parity ^ 1) * (TSIMK_LW_LISTS + 1) * 32;
-    sl.parity ^= 1;
+    st.hard_index = t.hard_index;
+    st.ctl = t.ctl;
+    st.ctl_next = t.ctl_next;
     memcpy(st.keys, a.inline_keys, sizeof(uint32_t) * 2 * (size_t)p->total_keys);
-    // what the hard-row batch needs of this launch (launch_sample fills the same fields behind its first pass)
-    a.row_index = st.hard_index;
-    a.row_count = ctl;
-    a.row_lists = n_lists;
-    a.row_list_cap = (int)list_cap;
-    a.check_row = has_check ? ctl + 32 * TSIMK_LW_LISTS : nullptr;
-    a.no_check = has_check ? 0 : 1;
-    a.row_slot_begin = 0;
-    a.row_slot_end = 0;
   }
   // one chip-full of blocks (2048 threads per CU), every block the same number of (batch, row block) pairs
   const long long total = bps * n;
@@ -1239,13 +1331,11 @@ static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f,
   const long long grid = (total + iters - 1) / iters;
   TSIM_MARK("args");
   if (int r = tsim_tables_slice(p, s)) return r;  // (a table build in the background: its next slice goes first)
-  const bool prof = p->profiling && (p->prof_counter++ % p->prof_every == 0);
-  if (prof) { if (int r = prof_event(p, s, PROF_BEGIN)) return r; }
-  // one component of at most 8 outputs: the specialised pass (tsim_lw_fast.hip.h) - 32-bit byte offsets everywhere, so
-  // batches below 2^28 rows, tables below 4 GB, and a shot range that does not cross a multiple of 2^32
+  bool prof;
+  if (int r = group_prof_begin(p, s, &prof)) return r;
+  // one component of at most 8 outputs: the specialised pass (tsim_lw_fast.hip.h), where its 32-bit offsets reach (lw32_ok)
   bool part = false;
-  const bool fast = p->lwf_off != 0 && p->knobs.lw_fast && B < (1ll << 28) && p->lw_bytes < (1ll << 32) && (n_lists & (n_lists - 1)) == 0 &&
-                    ((unsigned long long)shot_offset >> 32) == ((unsigned long long)(shot_offset + B - 1) >> 32);
+  const bool fast = p->lwf_off != 0 && p->knobs.lw_fast && lw32_ok(p, B, shot_offset, n_lists);
   M.lwf_off = fast ? p->lwf_off : 0;
   M.tab_bytes = fast ? (uint32_t)p->lw_bytes : 0u;
   if (fast) lwf_fill_header(p, M);
@@ -1281,21 +1371,10 @@ static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f,
 #undef TSIM_LNF
     ++p->stat_fast;
   } else if (fast) {
-    const int n_out = p->comps[0].n_out;
-#define TSIM_LF(N)                                                                                     \
-  case N:                                                                                              \
-    if (WF == 1) hipLaunchKernelGGL((k_sample_lw_fast<2, N>), dim3((unsigned)grid), dim3(blk1), 0, s, M); \
-    else hipLaunchKernelGGL((k_sample_lw_fast<4, N>), dim3((unsigned)grid), dim3(blk1), 0, s, M);        \
-    break;
     ++p->path_count[TP_LW_FAST];
-    switch (n_out) {
-      TSIM_LF(1) TSIM_LF(2) TSIM_LF(3) TSIM_LF(4) TSIM_LF(5) TSIM_LF(6) TSIM_LF(7) TSIM_LF(8)
-      default: return tsim_fail(TSIM_ESTATE, "fast record with %d outputs", n_out);
-    }
-#undef TSIM_LF
+    if (int r = launch_lw_fast(WF, p->comps[0].n_out, grid, s, M)) return r;
     ++p->stat_fast;
-  } else if (p->lwfm_off != 0 && p->knobs.lw_fast && B < (1ll << 28) && p->lw_bytes < (1ll << 32) &&
-             (n_lists & (n_lists - 1)) == 0 && ((unsigned long long)shot_offset >> 32) == ((unsigned long long)(shot_offset + B - 1) >> 32)) {
+  } else if (p->lwfm_off != 0 && p->knobs.lw_fast && lw32_ok(p, B, shot_offset, n_lists)) {
     // 2..4 components of at most 8 outputs each: the specialised pass with per-component tables (tsim_lw_fastm.hip.h)
     M.lwf_off = p->lwfm_off;
     M.tab_bytes = (uint32_t)p->lw_bytes;
@@ -1332,30 +1411,8 @@ static int steps_group_fused(tsim_program *p, int n, const uint64_t *const *d_f,
   }
   HIP_TRY(hipGetLastError());
   TSIM_MARK("launch");
-  if (prof) {
-    if (int r = prof_event(p, s, PROF_PASS1)) return r;
-    p->prof_steps += n;
-  }
-  hard_geometry(p, WF, (p->num_outputs + 63) / 64);
-  for (int j = 0; j < n; ++j) {
-    tsim_program::Slot &sl = p->slots[slots[j]];
-    sl.ctx_check = has_check;
-    sl.deferred = true;
-    sl.pending = true;
-    sl.p1_stream = s;
-    sl.partial = part;
-    p->deferred.push_back(slots[j]);
-  }
-  p->stat_begins += (unsigned long long)n;
-  p->stat_deferred += (unsigned long long)n;
-  ++p->stat_fused;
-  if ((long long)n * B <= p->knobs.hard_inline_rows) {
-    // (letting the hard rows wait for the lane's NEXT first pass was tried - profiles/r03/hard_lag_experiment.txt: slower)
-    p->flush_inline = s;
-  }
-  const int rf = flush_chunks(p);
-  TSIM_MARK("hard");
-  return rf;
+  if (int r = group_prof_pass1(p, s, prof, n)) return r;
+  return park_group(p, n, slots, s, B, WF, has_check, part);
 }
 
 // Programs without components (Clifford-only circuits): up to TSIMK_DIRECT_MAX_STEPS batches as one streaming grid
@@ -1366,12 +1423,8 @@ static int steps_group_direct(tsim_program *p, int n, const uint64_t *const *d_f
   const bool packed = (flags & TSIM_PIPE_OUT_BIT_PACKED) != 0;
   if (!p->deferred.empty())
     if (int r = tsim_flush_hard(p)) return r;
-  hipStream_t s = p->slots[1 + (int)(p->steps_groups++ & 1ull)].side;
-  if (!(flags & TSIM_PIPE_INPUTS_READY) && p->stream != s) {
-    if (!p->sync_ev) HIP_TRY(hipEventCreateWithFlags(&p->sync_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(p->sync_ev, p->stream));
-    HIP_TRY(hipStreamWaitEvent(s, p->sync_ev, 0));
-  }
+  hipStream_t s;
+  if (int r = group_lane(p, 2, flags, &s)) return r;
   const int WF = std::max(1, (num_f + 63) / 64);
   const long long bps = (B + 256 * TSIMK_DIRECT_RPT - 1) / (256 * TSIMK_DIRECT_RPT);
   if (bps * n > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large");
@@ -1386,16 +1439,10 @@ static int steps_group_direct(tsim_program *p, int n, const uint64_t *const *d_f
   M.out_rb = (p->num_outputs + 7) / 8;
   int first = 0;
   for (int j = 0; j < n; ++j) {
-    const int sidx = 1 + (int)(p->steps_slot++ % (unsigned long long)TSIM_PIPELINE_SLOTS);
-    if (j == 0) first = sidx;
-    if (int r = slot_prepare(p, sidx, 0)) return r;
-    tsim_program::Slot &sl = p->slots[sidx];
-    if (sl.deferred) return tsim_fail(TSIM_ESTATE, "pipeline slot %d still holds a parked launch", sidx - 1);
-    if (int r = slot_order_after_previous(p, sl, s)) return r;
-    uint32_t o[4];
-    tsim_key_split(key[0], key[1], o);
-    key[0] = o[0];
-    key[1] = o[1];
+    TakenSlot t;
+    if (int r = take_plain_slot(p, s, key, t)) return r;
+    if (j == 0) first = t.sidx;
+    tsim_program::Slot &sl = *t.sl;
     M.step[j].f = reinterpret_cast<const uint32_t *>(d_f[j]);
     uint8_t *series = sl.compact_out;  // (tsim_pipeline_set_compact_output: the slot's next launch also writes bit_packed rows there)
     M.step[j].out = packed ? nullptr : (uint64_t *)d_out[j];
@@ -1406,18 +1453,7 @@ static int steps_group_direct(tsim_program *p, int n, const uint64_t *const *d_f
   if (WF == 1) hipLaunchKernelGGL(k_direct_multi<2>, dim3((unsigned)(bps * n)), dim3(256), 0, s, M);
   else hipLaunchKernelGGL(k_direct_multi<4>, dim3((unsigned)(bps * n)), dim3(256), 0, s, M);
   HIP_TRY(hipGetLastError());
-  hipEvent_t ev = p->slots[first].ev2;
-  HIP_TRY(hipEventRecord(ev, s));
-  for (int j = 0; j < n; ++j) {
-    tsim_program::Slot &sl = p->slots[1 + (int)((p->steps_slot - (unsigned long long)n + (unsigned long long)j) % (unsigned long long)TSIM_PIPELINE_SLOTS)];
-    sl.pending = true;
-    sl.last_done = s;
-    sl.done_ev = ev;
-    sl.batch_seq = 0;
-  }
-  p->stat_begins += (unsigned long long)n;
-  ++p->stat_fused;
-  return 0;
+  return finish_group(p, n, first, s);
 }
 extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const uint64_t *const *d_f, int64_t B, int32_t num_f,
                                         uint32_t key[2], int64_t shot_offset, void *const *d_out, float *const *d_max_norm_dev,
@@ -1444,7 +1480,7 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
       // (the f buffer of a batch is its pipeline slot's as far as this call can tell: the handle's stream first gets behind the
       // launches those slots carried last - their hard rows may still read the rows the noise is about to overwrite)
       for (int j = 0; j < n; ++j) {
-        tsim_program::Slot &sl = p->slots[1 + (int)((p->steps_slot + (unsigned long long)j) % (unsigned long long)TSIM_PIPELINE_SLOTS)];
+        tsim_program::Slot &sl = p->slots[steps_slot_at(p, j)];
         if (sl.deferred)
           if (int r = tsim_flush_hard(p)) return r;
         if (int r = slot_order_after_previous(p, sl, p->stream)) return r;
@@ -1464,65 +1500,39 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
     // no components at all: the streaming kernel for direct outputs (rows of at most 128 f bits and 128 outputs)
     if (p->comps.empty() && p->knobs.fused_steps && p->num_outputs > 0 && p->num_outputs <= 128 && WF <= 2 && p->lw_direct_chunks > 0 &&
         B > 0 && B <= 0x7FFFFFFFll) {
-      if (!p->slots_ready) {
-        for (int k = 1; k <= 4; ++k)
-          if (int r = slot_prepare(p, k, 0)) return r;
-        if (int r = slots_now_ready(p)) return r;
-      }
-      const int left = n_steps - done;
-      const int groups = (left + TSIMK_DIRECT_MAX_STEPS - 1) / TSIMK_DIRECT_MAX_STEPS;
-      const int n = (left + groups - 1) / groups;
+      if (int r = lanes_ready(p)) return r;
+      const int n = even_group(n_steps - done, TSIMK_DIRECT_MAX_STEPS);
       if (int r = noise_first(n)) return r;
       if (int r = steps_group_direct(p, n, d_f + done, B, num_f, key, d_out + done, flags)) return r;
       done += n;
       continue;
     }
     // wide components: groups of batches through k_sample_wide, one pass per component
-    LaunchPlan wide_plan;
-    bool have_wide_plan = false;
+    LaunchPlan plan;  // the plan drawn for this batch or group, if one was (a launch counts once: _begin takes it over)
+    bool have_plan = false;
     if (p->knobs.fused_steps && wide_applies(p, B, num_f, shot_offset) && p->series_left == 0) {
-      const int left = n_steps - done;
-      const int gmax = std::min(8, p->knobs.fused_max);  // (groups of more than 8 are the register first passes': tsim_steps_next_group)
-      const int groups = (left + gmax - 1) / gmax;
-      const int n = (left + groups - 1) / groups;
+      // (groups of more than 8 are the register first passes': tsim_steps_next_group)
+      const int n = even_group(n_steps - done, std::min(8, p->knobs.fused_max));
+      // padded rows: not next to a slot's bit_packed copy (bit_packed rows alone: any size and alignment, tsim_wide.hip.h oc_put)
       bool okb = true;
-      if (flags & TSIM_PIPE_OUT_BIT_PACKED) {
-        okb = true;  // (rows of any size and alignment since round 5: tsim_wide.hip.h oc_put)
-      } else {
-        for (int j = 0; j < n; ++j) okb = okb && !p->slots[1 + (int)((p->steps_slot + (unsigned long long)j) % (unsigned long long)TSIM_PIPELINE_SLOTS)].compact_out;
-      }
+      for (int j = 0; j < n && !(flags & TSIM_PIPE_OUT_BIT_PACKED); ++j) okb = okb && !p->slots[steps_slot_at(p, j)].compact_out;
       if (okb) {
-        if (!p->slots_ready) {
-          for (int k = 1; k <= 4; ++k)
-            if (int r = slot_prepare(p, k, 0)) return r;
-          if (int r = slots_now_ready(p)) return r;
-        }
-        const LaunchPlan wplan = make_plan(p, false, true, (unsigned long long)n * (unsigned long long)B);
+        if (int r = lanes_ready(p)) return r;
+        plan = make_plan(p, false, true, (unsigned long long)n * (unsigned long long)B);
+        have_plan = true;
         TSIM_MARK("plan");
         // (make_plan may have swapped deeper tables in: the 32-bit offsets of k_sample_wide are checked against THOSE - ADVICE r04)
-        if (wplan.use_tables && wide_applies(p, B, num_f, shot_offset)) {
+        if (plan.use_tables && wide_applies(p, B, num_f, shot_offset)) {
           if (int r = noise_first(n)) return r;
           if (int r = steps_group_wide(p, n, d_f + done, B, num_f, key, shot_offset, d_out + done, d_max_norm_dev ? d_max_norm_dev + done : nullptr, flags))
             return r;
           done += n;
           continue;
         }
-        wide_plan = wplan;
-        have_wide_plan = true;
       }
-    }
-    LaunchPlan plan;
-    bool have_plan = false;
-    if (have_wide_plan) {
-      plan = wide_plan;
-      have_plan = true;
     }
     if (fused) {
-      if (!p->slots_ready) {  // as in _begin: every slot's stream / buffers now, not mid-run
-        for (int k = 1; k <= 4; ++k)
-          if (int r = slot_prepare(p, k, 0)) return r;
-        if (int r = slots_now_ready(p)) return r;
-      }
+      if (int r = lanes_ready(p)) return r;
       const int n_long = (reg_fused && !gen_fused) ? (int)tsim_steps_next_group(n_steps - done, B, p->knobs.fused_max, p->knobs.fused_long_shots) : 0;
       plan = make_plan(p, false, true, (unsigned long long)std::max(n_long, std::min(n_steps - done, std::min(8, p->knobs.fused_max))) * (unsigned long long)B);
       hard_geometry(p, WF, WO);
@@ -1534,21 +1544,15 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
       fused = (plan.defer || p->narrow_big || p->lw_trie) && plan.use_tables && p->h_group_tiles >= 1;
     }
     if (fused) {
-      // even groups of at most TSIMK_LWM_MAX_STEPS batches
       const int left = n_steps - done;
       // (k_sample_gen carries batches x compiled outputs subkey records per launch: 8 batches up to 40 outputs, fewer beyond)
-      const int gmax = std::min(gen_fused ? std::min(TSIMK_GEN_MAX_STEPS, std::max(1, TSIMK_GEN_KEYS / std::max(1, p->total_keys))) : 8, p->knobs.fused_max);
-      // (20 batches as 7+7+6; 5+5+5+5 - both lanes ending together - measured slower: a launch more)
-      const int groups = (left + gmax - 1) / gmax;
+      const int gen_max = std::min(std::min(TSIMK_GEN_MAX_STEPS, std::max(1, TSIMK_GEN_KEYS / std::max(1, p->total_keys))), p->knobs.fused_max);
       // the register first passes: groups of up to fused_max = 16 batches in the interior of a long call of large batches
-      const int n = gen_fused ? (left + groups - 1) / groups : (int)tsim_steps_next_group(left, B, p->knobs.fused_max, p->knobs.fused_long_shots);
+      const int n = gen_fused ? even_group(left, gen_max) : (int)tsim_steps_next_group(left, B, p->knobs.fused_max, p->knobs.fused_long_shots);
       // (group sizes that fill whole chip-fulls of first-pass blocks - 15 batches of 10^5 shots instead of 8 - make the first
       // pass cheaper per batch and the step slower: two hard-row grids per group, C4 at 10^5 shots 1.88 -> 1.53e10, C2 3.6 -> 2.9e10)
-      {
-        const size_t hard_bytes = (size_t)(((B + 255) / 256 + TSIMK_LW_LISTS - 1) / TSIMK_LW_LISTS * 1024) * TSIMK_LW_LISTS * 4;
-        for (int j = 0; j < n; ++j)
-          if (int r = slot_prepare(p, 1 + (int)((p->steps_slot + (unsigned long long)j) % TSIM_PIPELINE_SLOTS), hard_bytes)) return r;
-      }
+      for (int j = 0; j < n; ++j)
+        if (int r = slot_prepare(p, steps_slot_at(p, j), hard_list_bytes(B))) return r;
       if (gen_fused) {
         if (int r = noise_first(n)) return r;
         if (int r = steps_group_gen(p, n, d_f + done, B, num_f, key, shot_offset, d_out + done, d_max_norm_dev ? d_max_norm_dev + done : nullptr,
@@ -1562,7 +1566,8 @@ extern "C" int tsim_sample_steps_device(tsim_program *p, int32_t n_steps, const 
       // (the noise first: noise_first orders it behind the previous launches of slot steps_slot - the slot this batch takes.
       // Behind the increment it waited for the next slot's instead, and the noise could rewrite rows this slot's hard rows read)
       if (int r = noise_first(1)) return r;
-      const int slot = (int)(p->steps_slot++ % (unsigned long long)TSIM_PIPELINE_SLOTS);
+      const int slot = steps_slot_at(p, 0) - 1;
+      ++p->steps_slot;
       uint32_t o[4];
       tsim_key_split(key[0], key[1], o);
       key[0] = o[0];
@@ -1601,9 +1606,7 @@ extern "C" int tsim_pipeline_wait_stream(tsim_program *p, void *stream) {
     // launches with TSIM_PIPE_INPUTS_READY, as sampler.py does: the first group of a fresh handle raced with the noise kernel that
     // fills its f buffers (hidden while creating the 32 slot streams took 80 ms; seen once the streams came from the pool:
     // tests/test_gpu_sampler.py::test_device_postselection[rows] behind test_gpu_noise.py).  Create the lanes and order them.
-    for (int k = 1; k <= 4; ++k)
-      if (int r = slot_prepare(p, k, 0)) return r;
-    if (int r = slots_now_ready(p)) return r;
+    if (int r = lanes_ready(p)) return r;
   }
   if (!p->sync_ev) HIP_TRY(hipEventCreateWithFlags(&p->sync_ev, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(p->sync_ev, s_user));

@@ -8,19 +8,18 @@ using namespace tsimhost;
 
 
 // Any narrow program (k_sample_gen, tsim_gen.hip.h): up to TSIMK_GEN_MAX_STEPS batches as one grid of chip-resident blocks, the
-// rows staged in LDS wave by wave; hard rows to each batch's lists, the group's hard-row grid behind it - the protocol of
-// steps_group_fused, whose bookkeeping this shares.
+// rows staged in LDS wave by wave; hard rows to each batch's lists, the group's hard-row grid behind it - a group that leaves
+// lists, as steps_group_fused (the group protocol, tsim_sample_internal.hip.h).
 struct GenLayout {
   int block = 0, nbuf = 1;
   size_t lds = 0;
   int l_wave = 0, wave_bytes = 0;
 };
-GenLayout gen_layout(const tsim_program *p, int WF32, int n_steps) {
+GenLayout gen_layout(const tsim_program *p, int WF32) {
   GenLayout L;
   if (!p->gr_off) return L;
   const uint32_t *h = &p->img[p->gr_off];
   auto up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
-  (void)n_steps;
   size_t off = ((size_t)h[GR_LDS_WORDS] + 8 * (size_t)h[GR_NCOMP]) * 4;  // rank tables, pattern bases
   off = up(off, 16);
   const size_t buf = (size_t)64 * WF32 * 4;
@@ -49,7 +48,7 @@ bool gen_applies(const tsim_program *p, int64_t B, int32_t num_f, int64_t shot_o
   if (((unsigned long long)shot_offset >> 32) != ((unsigned long long)(shot_offset + B - 1) >> 32)) return false;
   const int WF32 = 2 * std::max(1, (num_f + 63) / 64);
   if (WF32 < (int)p->img[p->gr_off + GR_WF32_MIN] || WF32 > 64) return false;
-  return gen_layout(p, WF32, 1).block != 0;
+  return gen_layout(p, WF32).block != 0;
 }
 
 static int gen_launch(tsim_program *p, const GenArgs &G, const GenLayout &L, long long grid, hipStream_t s) {
@@ -121,7 +120,7 @@ static long long gen_grid(const tsim_program *p, const GenLayout &L, long long c
 int gen_one(tsim_program *p, const tsim_program::Slot &sl, const SampleArgs &a, int64_t B, int32_t num_f, uint32_t key_hi, uint32_t key_lo, int64_t shot_offset,
             uint32_t *hard_index, uint32_t *ctl, uint32_t *ctl_next, int n_lists, bool has_check, long long *list_cap_out, hipStream_t s) {
   const int WF = std::max(1, (num_f + 63) / 64);
-  const GenLayout L = gen_layout(p, 2 * WF, 1);
+  const GenLayout L = gen_layout(p, 2 * WF);
   if (!L.block) return tsim_fail(TSIM_ESTATE, "k_sample_gen does not fit");
   if (p->total_keys > TSIMK_GEN_KEYS) return tsim_fail(TSIM_ESTATE, "k_sample_gen: %d compiled outputs", p->total_keys);
   const long long bps = (B + 1023) / 1024;
@@ -149,15 +148,10 @@ int steps_group_gen(tsim_program *p, int n, const uint64_t *const *d_f, int64_t 
   const bool packed = (flags & TSIM_PIPE_OUT_BIT_PACKED) != 0;
   if (!p->deferred.empty())
     if (int r = flush_batch(p)) return r;
-  const int lanes = p->knobs.fused_lanes > 0 ? p->knobs.fused_lanes : ((long long)n * B <= (1ll << 21) ? 3 : 2);
-  hipStream_t s = p->slots[1 + (int)(p->steps_groups++ % (unsigned long long)lanes)].side;
-  if (!(flags & TSIM_PIPE_INPUTS_READY) && p->stream != s) {
-    if (!p->sync_ev) HIP_TRY(hipEventCreateWithFlags(&p->sync_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(p->sync_ev, p->stream));
-    HIP_TRY(hipStreamWaitEvent(s, p->sync_ev, 0));
-  }
+  hipStream_t s;
+  if (int r = group_lane(p, list_group_lanes(p, n, B), flags, &s)) return r;
   const int WF = std::max(1, (num_f + 63) / 64);
-  const GenLayout L = gen_layout(p, 2 * WF, n);
+  const GenLayout L = gen_layout(p, 2 * WF);
   if (!L.block) return tsim_fail(TSIM_ESTATE, "k_sample_gen does not fit");
   const long long bps = (B + 1023) / 1024;  // hard-row lists by row blocks of 1024 rows, whatever the kernel's block
   const int n_lists = plan.lists;
@@ -169,75 +163,32 @@ int steps_group_gen(tsim_program *p, int n, const uint64_t *const *d_f, int64_t 
   gen_common_args(p, G, L, B, shot_offset, n, WF, has_check, list_cap, n_lists);
   p->last_lists = n_lists;
   int slots[TSIMK_GEN_MAX_STEPS];
-  for (int j = 0; j < n; ++j)
-    if (p->slots[1 + (int)((p->steps_slot + (unsigned long long)j) % (unsigned long long)TSIM_PIPELINE_SLOTS)].deferred) {
-      if (int r = tsim_flush_hard(p)) return r;
-      break;
-    }
+  if (int r = flush_if_group_parked(p, n)) return r;
   for (int j = 0; j < n; ++j) {
-    const int sidx = 1 + (int)(p->steps_slot++ % (unsigned long long)TSIM_PIPELINE_SLOTS);
-    slots[j] = sidx;
-    tsim_program::Slot &sl = p->slots[sidx];
-    if (sl.deferred) return tsim_fail(TSIM_ESTATE, "pipeline slot %d still holds a parked launch", sidx - 1);
-    if ((size_t)list_cap * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
-    if (int r = slot_order_after_previous(p, sl, s)) return r;
-    uint32_t o[4];
-    tsim_key_split(key[0], key[1], o);  // key, subkey = split(key)  (sampler.py:399)
-    key[0] = o[0];
-    key[1] = o[1];
-    SampleArgs &a = sl.ctx;
-    a = SampleArgs{};
-    if (int r = fill_sample_args(p, sl, a, d_f[j], B, num_f, o[2], o[3], shot_offset, (uint64_t *)d_out[j], d_dev ? d_dev[j] : nullptr, s,
-                                 sidx, packed))
+    TakenSlot t;
+    if (int r = take_list_slot(p, s, key, d_f[j], B, num_f, shot_offset, d_out[j], d_dev ? d_dev[j] : nullptr, packed, n_lists, list_cap, has_check, t))
       return r;
+    slots[j] = t.sidx;
+    const SampleArgs &a = t.sl->ctx;
     GenStep &st = G.step[j];
     st.f = d_f[j];
     st.out = a.out;
     st.out_compact = a.out_compact;
-    st.hard_index = (uint32_t *)sl.hard;
-    uint32_t *ctl = sl.ctl + sl.parity * (TSIMK_LW_LISTS + 1) * 32;
-    st.ctl = ctl;
-    st.ctl_next = sl.ctl + (sl.parity ^ 1) * (TSIMK_LW_LISTS + 1) * 32;
-    sl.parity ^= 1;
-    gen_step_keys(p, sl, a, o[2], o[3], G.keys + 2 * (size_t)j * (size_t)p->total_keys);
-    a.row_index = st.hard_index;
-    a.row_count = ctl;
-    a.row_lists = n_lists;
-    a.row_list_cap = (int)list_cap;
-    a.check_row = has_check ? ctl + 32 * TSIMK_LW_LISTS : nullptr;
-    a.no_check = has_check ? 0 : 1;
-    a.row_slot_begin = 0;
-    a.row_slot_end = 0;
+    st.hard_index = t.hard_index;
+    st.ctl = t.ctl;
+    st.ctl_next = t.ctl_next;
+    gen_step_keys(p, *t.sl, a, t.sub[0], t.sub[1], G.keys + 2 * (size_t)j * (size_t)p->total_keys);
   }
   const long long chunks = (long long)G.chunks_per_step * n;
   const long long grid = gen_grid(p, L, chunks);
   TSIM_MARK("args");
   if (int r = tsim_tables_slice(p, s)) return r;  // (a table build in the background: its next slice goes first)
-  const bool prof = p->profiling && (p->prof_counter++ % p->prof_every == 0);
-  if (prof) { if (int r = prof_event(p, s, PROF_BEGIN)) return r; }
+  bool prof;
+  if (int r = group_prof_begin(p, s, &prof)) return r;
   ++p->path_count[TP_GEN];
   if (int r = gen_launch(p, G, L, grid, s)) return r;
   HIP_TRY(hipGetLastError());
   TSIM_MARK("launch");
-  if (prof) {
-    if (int r = prof_event(p, s, PROF_PASS1)) return r;
-    p->prof_steps += n;
-  }
-  hard_geometry(p, WF, (p->num_outputs + 63) / 64);
-  for (int j = 0; j < n; ++j) {
-    tsim_program::Slot &sl = p->slots[slots[j]];
-    sl.ctx_check = has_check;
-    sl.deferred = true;
-    sl.pending = true;
-    sl.p1_stream = s;
-    sl.partial = false;
-    p->deferred.push_back(slots[j]);
-  }
-  p->stat_begins += (unsigned long long)n;
-  p->stat_deferred += (unsigned long long)n;
-  ++p->stat_fused;
-  if ((long long)n * B <= p->knobs.hard_inline_rows) p->flush_inline = s;
-  const int rf = flush_chunks(p);
-  TSIM_MARK("hard");
-  return rf;
+  if (int r = group_prof_pass1(p, s, prof, n)) return r;
+  return park_group(p, n, slots, s, B, WF, has_check, false);
 }

@@ -1,9 +1,11 @@
 // tsim_sample_internal.hip.h - what the translation units of the sampling launchers share (tsim_sample.hip
 // had grown to 2200 lines of three launch families):
-//   tsim_sample.hip       the launch plan, the pipeline slots, the hard-row stages, the one-batch launcher, the register first
-//                         passes' fused groups, the C entry points
-//   tsim_sample_wide.hip  k_sample_wide: layout, eligibility, one pass per component, its fused groups
-//   tsim_sample_gen.hip   k_sample_gen: layout, eligibility, its fused groups
+//   tsim_sample.hip       the launch plan, the pipeline slots, the hard-row stages, the one-batch launcher, the group protocol
+//                         (below), the groups of the register first passes and of k_direct_multi, the C entry points
+//   tsim_sample_wide.hip  k_sample_wide: layout, eligibility, one pass per component, its groups
+//   tsim_sample_gen.hip   k_sample_gen: layout, eligibility, its groups
+// A group launcher is its kernel's arguments and launch between the protocol's calls: group_lane, take_list_slot or
+// take_plain_slot per batch, group_prof_begin / _pass1, park_group or finish_group.
 #pragma once
 #include "tsim_internal.hip.h"
 #include <chrono>
@@ -52,8 +54,32 @@ int fill_sample_args(tsim_program *p, tsim_program::Slot &sl, tsimk::SampleArgs 
                      uint32_t key_hi, uint32_t key_lo, int64_t shot_offset, uint64_t *d_out, float *d_dev, hipStream_t s,
                      int slot, bool out_bit_packed);
 int flush_batch(tsim_program *p);
-int flush_chunks(tsim_program *p);
-void hard_geometry(tsim_program *p, int WF, int WO);
+
+// ---- the group protocol of tsim_sample_steps_device (tsim_sample.hip).  Two kinds of group: those whose first
+// pass leaves hard-row lists (the register first passes, k_sample_gen: take_list_slot ... park_group) and those that leave
+// nothing (k_sample_wide, k_direct_multi: take_plain_slot ... finish_group).
+// the pipeline slot (index into p->slots) of the j-th batch from here on
+inline int steps_slot_at(const tsim_program *p, int j) {
+  return 1 + (int)((p->steps_slot + (unsigned long long)j) % (unsigned long long)TSIM_PIPELINE_SLOTS);
+}
+// a slot as the launcher of a group gets it
+struct TakenSlot {
+  int sidx = 0;
+  tsim_program::Slot *sl = nullptr;
+  uint32_t sub[2] = {0u, 0u};  // the batch's subkey
+  uint32_t *hard_index = nullptr, *ctl = nullptr, *ctl_next = nullptr;  // (take_list_slot) the lists, this launch's counter set, the next one's
+};
+int list_group_lanes(const tsim_program *p, int n, int64_t B);
+int group_lane(tsim_program *p, int lanes, uint32_t flags, hipStream_t *s);
+int flush_if_group_parked(tsim_program *p, int n);
+int take_list_slot(tsim_program *p, hipStream_t s, uint32_t key[2], const uint64_t *d_f, int64_t B, int32_t num_f, int64_t shot_offset, void *d_out,
+                   float *d_dev, bool packed, int n_lists, long long list_cap, bool has_check, TakenSlot &t);
+int take_plain_slot(tsim_program *p, hipStream_t s, uint32_t key[2], TakenSlot &t);
+void describe_lists(tsimk::SampleArgs &a, const uint32_t *hard_index, const uint32_t *ctl, int n_lists, int list_cap, bool has_check);
+int group_prof_begin(tsim_program *p, hipStream_t s, bool *prof);
+int group_prof_pass1(tsim_program *p, hipStream_t s, bool prof, int n);
+int park_group(tsim_program *p, int n, const int *slots, hipStream_t s, int64_t B, int WF, bool has_check, bool partial);
+int finish_group(tsim_program *p, int n, int first, hipStream_t s);
 
 // ---- device noise in front of the steps (tsim_sample_steps_noise_device, tsim_noise.hip): the request travels thread-locally
 // through tsim_sample_steps_device.  A fused group of the one-component register pass runs k_noise_sample_fast (noise + first

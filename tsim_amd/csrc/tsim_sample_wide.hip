@@ -179,53 +179,27 @@ int steps_group_wide(tsim_program *p, int n, const uint64_t *const *d_f, int64_t
   const bool packed = (flags & TSIM_PIPE_OUT_BIT_PACKED) != 0;
   if (!p->deferred.empty())
     if (int r = tsim_flush_hard(p)) return r;
-  hipStream_t s = p->slots[1 + (int)(p->steps_groups++ & 1ull)].side;
-  if (!(flags & TSIM_PIPE_INPUTS_READY) && p->stream != s) {
-    if (!p->sync_ev) HIP_TRY(hipEventCreateWithFlags(&p->sync_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(p->sync_ev, p->stream));
-    HIP_TRY(hipStreamWaitEvent(s, p->sync_ev, 0));
-  }
+  hipStream_t s;
+  if (int r = group_lane(p, 2, flags, &s)) return r;
   const SampleArgs *args[TSIMK_LWM_MAX_STEPS];
   int first = 0;
   for (int j = 0; j < n; ++j) {
-    const int sidx = 1 + (int)(p->steps_slot++ % (unsigned long long)TSIM_PIPELINE_SLOTS);
-    if (j == 0) first = sidx;
-    if (int r = slot_prepare(p, sidx, 0)) return r;  // (k_sample_wide leaves no row lists: counters, keys and events only)
-    tsim_program::Slot &sl = p->slots[sidx];
-    if (sl.deferred) return tsim_fail(TSIM_ESTATE, "pipeline slot %d still holds a parked launch", sidx - 1);
-    if (int r = slot_order_after_previous(p, sl, s)) return r;
-    uint32_t o[4];
-    tsim_key_split(key[0], key[1], o);  // key, subkey = split(key)  (sampler.py:399)
-    key[0] = o[0];
-    key[1] = o[1];
-    SampleArgs &a = sl.ctx;
+    TakenSlot t;
+    if (int r = take_plain_slot(p, s, key, t)) return r;  // (k_sample_wide leaves no row lists)
+    if (j == 0) first = t.sidx;
+    SampleArgs &a = t.sl->ctx;
     a = SampleArgs{};
-    if (int r = fill_sample_args(p, sl, a, d_f[j], B, num_f, o[2], o[3], shot_offset, (uint64_t *)d_out[j], d_dev ? d_dev[j] : nullptr, s, sidx, packed))
+    if (int r = fill_sample_args(p, *t.sl, a, d_f[j], B, num_f, t.sub[0], t.sub[1], shot_offset, (uint64_t *)d_out[j], d_dev ? d_dev[j] : nullptr, s, t.sidx, packed))
       return r;
     if (!wide_buffers_ok(p, a)) return tsim_fail(TSIM_ESTATE, "bit_packed rows wider than the wide record's output words");
     args[j] = &a;
   }
   TSIM_MARK("args");
-  const bool prof = p->profiling && (p->prof_counter++ % p->prof_every == 0);
-  if (prof) { if (int r = prof_event(p, s, PROF_BEGIN)) return r; }
+  bool prof;
+  if (int r = group_prof_begin(p, s, &prof)) return r;
   if (int r = tsim_tables_slice(p, s)) return r;  // (a table build in the background: its next slice goes first)
   if (int r = launch_wide(p, n, args, B, num_f, shot_offset, s)) return r;
   TSIM_MARK("launch");
-  if (prof) {
-    if (int r = prof_event(p, s, PROF_PASS1)) return r;
-    p->prof_steps += n;
-  }
-  hipEvent_t ev = p->slots[first].ev2;
-  HIP_TRY(hipEventRecord(ev, s));
-  for (int j = 0; j < n; ++j) {
-    tsim_program::Slot &sl = p->slots[1 + (int)((p->steps_slot - (unsigned long long)n + (unsigned long long)j) % (unsigned long long)TSIM_PIPELINE_SLOTS)];
-    sl.pending = true;
-    sl.last_done = s;
-    sl.done_ev = ev;
-    sl.batch_seq = 0;
-  }
-  p->stat_begins += (unsigned long long)n;
-  ++p->stat_fused;
-  return 0;
+  if (int r = group_prof_pass1(p, s, prof, n)) return r;
+  return finish_group(p, n, first, s);
 }
-
