@@ -161,7 +161,7 @@ int tsim_launch_trie_nodes4(const LwBuildArgs &a, unsigned grid, hipStream_t s) 
   const size_t lds = 2 * (size_t)a.nch * Tile4<GT>::kChunkBytes;
   switch (a.nch) {
 #define TSIM_T4(N) case N: hipLaunchKernelGGL((k_trie_nodes4<GT, N>), dim3(grid), dim3(256), lds, s, a); break;
-    TSIM_T4(2) TSIM_T4(4) TSIM_T4(6) TSIM_T4(8) TSIM_T4(10) TSIM_T4(12) TSIM_T4(14) TSIM_T4(16) TSIM_T4(20) TSIM_T4(32)
+    TSIM_NCH_LIST(TSIM_T4)
 #undef TSIM_T4
     default: return tsim_fail(TSIM_ESTATE, "bad chunk count %d", a.nch);
   }
@@ -186,7 +186,7 @@ int tsim_launch_lw_build4(tsim_program *p, int ci, const LwBuildArgs &a, int n_o
     auto kfn = k_lw_nodes4<GT, N>;                                                                                     \
     hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, s, a, comp4);                                      \
   } break;
-    TSIM_B4(2) TSIM_B4(4) TSIM_B4(6) TSIM_B4(8) TSIM_B4(10) TSIM_B4(12) TSIM_B4(14) TSIM_B4(16) TSIM_B4(20) TSIM_B4(32)
+    TSIM_NCH_LIST(TSIM_B4)
 #undef TSIM_B4
     default: return tsim_fail(TSIM_ESTATE, "bad chunk count %d", nch);
   }

@@ -38,6 +38,21 @@
 #include <vector>
 
 #define TSIMK_H_MAX_CTX 16  // launches served by one deferred hard-row batch (k_sample4h_multi)
+// The chunk counts of a program's chunk tables (tsim_program::v4_max_nch: the least of them with 4 * nch >= the parameters of
+// the widest level, tsim_program.hip; 0: no chunk tables), stated once: every kernel with an NCH template argument is
+// instantiated for these and dispatched by a switch made of this list (DESIGN.md 4.3 has the table).  In parts, because
+// k_sample4_over and k_sample4 serve 16 from their `default:` and k_sample_hw has its instances by parameter words.
+#define TSIM_NCH_TO_14(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14)
+#define TSIM_NCH_TO_16(X) TSIM_NCH_TO_14(X) X(16)
+#define TSIM_NCH_FROM_20(X) X(20) X(32)
+#define TSIM_NCH_LIST(X) TSIM_NCH_TO_16(X) TSIM_NCH_FROM_20(X)
+// the chunk count of a program whose widest level has max_params parameters (a chunk is four of them; beyond 128: 32)
+inline int tsim_choose_nch(int max_params) {
+#define TSIM_NCH_FITS(N) if (4 * N >= max_params) return N;
+  TSIM_NCH_LIST(TSIM_NCH_FITS)
+#undef TSIM_NCH_FITS
+  return 32;
+}
 // Launch constants that were A/B switches until round 4 / 5 (the experiments are closed: HISTORY.md, profiles/r03 .. r05)
 constexpr int kListRows = 40;        // expected rows per hard-row sub-list
 constexpr int kMinLists = 4;
@@ -288,10 +303,11 @@ struct tsim_program {
     int wide_passes = 8;      // wide_passes=N: programs of up to N wide-path components run as N k_sample_wide passes (1: round-4 behaviour)
     bool wide_compact = true; // wide_compact=0: k_sample_wide keeps one 16-byte column table per graph even when all graphs fit one entry
   } knobs;
-  bool h_attr_set = false;    // k_sample4h: large dynamic LDS enabled
-  bool hm_attr_set = false;   // k_sample4h_multi: the same
+  // the dynamic-LDS limit of the ONE instance this program's chunk count selects was raised (allow_lds_one)
+  bool h_attr_set = false;    // k_sample4h
+  bool hm_attr_set = false;   // k_sample4h_multi
+  bool over_attr_set = false, hw_attr_set = false, s4_attr_set = false;  // NCH = 32 (81..128 parameters): k_sample4_over, k_sample_hw, k_sample4
   unsigned gen_attr_set = 0;  // k_sample_gen<WO32>: bit WO32
-  unsigned x4_attr_set = 0;   // NCH = 32 instantiations (81..128 parameters) whose dynamic-LDS limit was raised: 1 over, 2 hw, 4 k_sample4
   unsigned wide_attr_set = 0; // k_sample_wide<WO32, K>: bit WO32
   int lw_off = 0;             // image offset of the LW component records
   int lw_direct_prog = 0;     // image offset of the direct-output gather program

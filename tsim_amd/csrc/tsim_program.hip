@@ -599,10 +599,7 @@ retry_pack:
       int maxp = 1;
       for (auto &c : p->comps)
         for (auto &lv : c.levels) maxp = std::max(maxp, lv.P);
-      static const int kNch[] = {2, 4, 6, 8, 10, 12, 14, 16, 20, 32};
-      p->v4_max_nch = 32;
-      for (int v : kNch)
-        if (4 * v >= maxp) { p->v4_max_nch = v; break; }
+      p->v4_max_nch = tsim_choose_nch(maxp);
       if (wide) {  // no chunk tables at all, one graph per tile (column tables only)
         p->v4_max_nch = 0;
         p->v4_gt = 1;

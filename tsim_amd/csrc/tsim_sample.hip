@@ -289,11 +289,27 @@ static void lwf_fill_header(const tsim_program *p, LwMultiArgs &M) {
 // the per-shot kernel ~1.5 * 10^3 - beyond ~10^3 rows per batch of launches the block-per-row kernel would take the
 // vector ALUs from the first passes (C3: 340 rows per launch, p_bit 0.05: 5000), so those go the per-shot way
 static bool hw_eligible(tsim_program *p, const SampleArgs &a, int n_ctx) {
-  int wmax = 1;
-  for (int w : p->comp_w) wmax = std::max(wmax, w);
+  const int wmax = max_param_words(p);
   const uint32_t fb_rows = p->h_feedback ? p->h_feedback[0] : 0u;
   return p->fast && p->knobs.hard_wave && wmax <= 4 && a.WF <= 32 && a.WO <= 2 && p->hw_max_rows < 60000 &&
          (unsigned long long)fb_rows * (unsigned)n_ctx <= (unsigned long long)p->knobs.hard_wave_rows;
+}
+// The dynamic-LDS limit of ONE kernel instance, raised on its first use (*done: one flag per kernel family - a program has
+// one chunk count, so one instance of a family)
+template <class K>
+static int allow_lds_one(K *kernel, int64_t bytes, bool *done) {
+  K *const one[1] = {kernel};
+  return tsimh::allow_lds(one, bytes, done);
+}
+// The contexts of a grid that serves several launches: each a copy of its launch's arguments that knows where in the kernel
+// arguments it lies.  whole_lists: the grid has its own slot range (slot_begin), not the launch's.
+template <class Multi, class At>
+static void fill_contexts(Multi &M, int n_ctx, At ctx_at, bool whole_lists = false) {
+  for (int i = 0; i < n_ctx; ++i) {
+    M.ctx[i] = ctx_at(i);
+    M.ctx[i].kernarg_off = (int)(offsetof(Multi, ctx) + (size_t)i * sizeof(SampleArgs));
+    if (whole_lists) M.ctx[i].row_slot_begin = M.ctx[i].row_slot_end = 0;
+  }
 }
 // Behind the latency kernels of a hard-row batch: the list slots they left (k_sample4_over, tsim_kernel4.hip.h).  A fixed
 // grid of chip-resident blocks; when every list ends before `slot_begin` - all launches but the first after a jump of
@@ -304,31 +320,22 @@ static int launch_over(tsim_program *p, const SampleArgs *ctx, int n_ctx, uint32
   M.comp4_off = p->comp4_off;
   M.slot_begin = slot_begin;
   M.masked = masked ? 1 : 0;
-  for (int i = 0; i < n_ctx; ++i) {
-    M.ctx[i] = ctx[i];
-    M.ctx[i].kernarg_off = (int)(offsetof(Over4Multi, ctx) + (size_t)i * sizeof(SampleArgs));
-    M.ctx[i].row_slot_begin = 0;
-    M.ctx[i].row_slot_end = 0;
-  }
+  fill_contexts(M, n_ctx, [&](int i) -> const SampleArgs & { return ctx[i]; }, true);
   // (a small footprint: in all launches but one the blocks only read the counts - 256 threads and ~25 KB of LDS start beside
   // a first pass that holds the chip, 512 threads with 60 KB wait for it and then delay the next one: 6-12 % of C2 / C3)
   const int blk = 256;
-  const size_t tile_bytes = std::max((size_t)p->v4_max_nch * 16, (size_t)p->v4_max_sent) * p->v4_gt * 16;
-  const size_t lds4 = (size_t)(2 * ctx[0].WF + 2 * ctx[0].WO) * blk * 4 + 2 * tile_bytes;
-  if (lds4 > (p->v4_max_nch == 32 ? 160 : 64) * 1024) return tsim_fail(TSIM_ENOTSUP, "v4 kernel needs %zu B of LDS", lds4);
+  const size_t lds4 = v4_block_lds(p, ctx[0].WF, ctx[0].WO, blk);
+  if (int r = v4_lds_check(p, lds4)) return r;
   // fill_chip: the lists are known to be long (throughput work) - as many blocks as the chip holds at once
   const unsigned grid = (unsigned)p->n_cu * (fill_chip ? (unsigned)std::max<size_t>(1, std::min<size_t>(2048 / blk, (160 * 1024) / (lds4 + 256))) : 1u);
   ++p->path_count[TP_OVER];
   switch (p->v4_max_nch) {
-#define TSIM_LO(N) case N: hipLaunchKernelGGL((k_sample4_over<4, N>), dim3(grid), dim3(blk), lds4, hs, M); break;
-    TSIM_LO(2) TSIM_LO(4) TSIM_LO(6) TSIM_LO(8) TSIM_LO(10) TSIM_LO(12) TSIM_LO(14) TSIM_LO(20)
+    // (NCH = 32, 81..128 parameters: two 32-KB tiles - more dynamic LDS than a kernel gets without asking)
+#define TSIM_LO(N) case N: { auto kfn = k_sample4_over<4, N>; if (N == 32) if (int r = allow_lds_one(kfn, 160 * 1024 - 8192, &p->over_attr_set)) return r; \
+                             hipLaunchKernelGGL(kfn, dim3(grid), dim3(blk), lds4, hs, M); } break;
+    TSIM_NCH_TO_14(TSIM_LO) TSIM_NCH_FROM_20(TSIM_LO)
 #undef TSIM_LO
-    case 32: {  // 81..128 parameters: two 32-KB tiles - more dynamic LDS than a kernel gets without asking
-      auto kfn = k_sample4_over<4, 32>;
-      if (!(p->x4_attr_set & 1u)) { HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192)); p->x4_attr_set |= 1u; }
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(blk), lds4, hs, M);
-    } break;
-    default: hipLaunchKernelGGL((k_sample4_over<4, 16>), dim3(grid), dim3(blk), lds4, hs, M); break;
+    default: hipLaunchKernelGGL((k_sample4_over<4, 16>), dim3(grid), dim3(blk), lds4, hs, M); break;  // 16
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -337,8 +344,7 @@ static int launch_over(tsim_program *p, const SampleArgs *ctx, int n_ctx, uint32
 static bool over_available(const tsim_program *p) { return p->v4 && p->knobs.hard_overflow; }
 
 static int launch_hw(tsim_program *p, const SampleArgs *ctx, int n_ctx, int max_lists, hipStream_t hs, bool partial, bool with_feedback = true) {
-  int wmax = 1;
-  for (int w : p->comp_w) wmax = std::max(wmax, w);
+  const int wmax = max_param_words(p);
   const uint32_t fb_max = p->h_feedback ? p->h_feedback[1] : 192u;
   HwMulti H{};
   H.n_ctx = n_ctx;
@@ -347,10 +353,7 @@ static int launch_hw(tsim_program *p, const SampleArgs *ctx, int n_ctx, int max_
   // row; longer lists are walked in turns (blocks of four waves: one row at a time each, see k_sample_hw)
   H.waves_per_list = (int)std::max(8u, std::min(128u, std::min(fb_max, 4096u) * 2u + 8u));
   H.feedback = with_feedback ? p->d_feedback : nullptr;
-  for (int i = 0; i < n_ctx; ++i) {
-    H.ctx[i] = ctx[i];
-    H.ctx[i].kernarg_off = (int)(offsetof(HwMulti, ctx) + (size_t)i * sizeof(SampleArgs));
-  }
+  fill_contexts(H, n_ctx, [&](int i) -> const SampleArgs & { return ctx[i]; });
   H.comp_par = partial ? (int)p->comps.size() : 1;  // the lists carry component masks: one block per (row, component)
   // each block takes at most four turns; per-shot worker blocks appended to the grid serve what lies behind them (lists
   // sized by STALE counts: the first group after a jump of the noise level) and exit at once otherwise
@@ -363,18 +366,23 @@ static int launch_hw(tsim_program *p, const SampleArgs *ctx, int n_ctx, int max_
   size_t ldsw = (size_t)H.par_words * 8 * 4 + 16;  // two buffers of four bit arrays (previous bit x trial bit) + the sampled bit.s word
   unsigned grid = gridw;
   if (workers) {
-    const size_t tile_bytes = std::max((size_t)p->v4_max_nch * 16, (size_t)p->v4_max_sent) * p->v4_gt * 16;
-    ldsw = std::max(ldsw, (size_t)(2 * ctx[0].WF + 2 * ctx[0].WO) * 256 * 4 + 2 * tile_bytes);
-    if (ldsw > (p->v4_max_nch == 32 ? 160 : 64) * 1024) return tsim_fail(TSIM_ENOTSUP, "v4 kernel needs %zu B of LDS", ldsw);
+    ldsw = std::max(ldsw, v4_block_lds(p, ctx[0].WF, ctx[0].WO, 256));
+    if (int r = v4_lds_check(p, ldsw)) return r;
     grid += (unsigned)(2 * p->n_cu);
   }
   // (blocks of 512 / 1024 threads - more helper waves per row - were tried: no faster alone, the row pass is not the chain;
   // next to a first pass slower, 8.8 -> 8.3 / 5.9e10 at --steps 200)
   const int nch = workers ? p->v4_max_nch : 0;
   ++p->path_count[TP_HW];
-#define TSIM_LHW(WV, N) case N: hipLaunchKernelGGL((k_sample_hw<WV, N>), dim3(grid), dim3(256), ldsw, hs, H); break;
+  // Instances by parameter words: one or two words with no workers or chunk counts up to 16 (at most 64 parameters), four
+  // words with none, 20 or 32 (65..128), eight words without workers.  (NCH = 32: more dynamic LDS, as in launch_over.)
+#define TSIM_LHW(WV, N) case N: { auto kfn = k_sample_hw<WV, N>; if (N == 32) if (int r = allow_lds_one(kfn, 160 * 1024 - 8192, &p->hw_attr_set)) return r; \
+                                  hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), ldsw, hs, H); } break;
+#define TSIM_LHW1(N) TSIM_LHW(1, N)
+#define TSIM_LHW2(N) TSIM_LHW(2, N)
+#define TSIM_LHW4(N) TSIM_LHW(4, N)
   if (wmax == 1) switch (nch) {
-    TSIM_LHW(1, 0) TSIM_LHW(1, 2) TSIM_LHW(1, 4) TSIM_LHW(1, 6) TSIM_LHW(1, 8) TSIM_LHW(1, 10) TSIM_LHW(1, 12) TSIM_LHW(1, 14) TSIM_LHW(1, 16)
+    TSIM_LHW1(0) TSIM_NCH_TO_16(TSIM_LHW1)
     default: return tsim_fail(TSIM_ESTATE, "bad chunk count %d", nch);
   } else if (wmax > 4) {  // parameter rows of 129..256 bits: the check / overflow rows of wide components with many graphs (class F140:
     // one lane of the row kernel took 413 us per batch for the check row of 140 graphs)
@@ -382,18 +390,16 @@ static int launch_hw(tsim_program *p, const SampleArgs *ctx, int n_ctx, int max_
     hipLaunchKernelGGL((k_sample_hw<8, 0>), dim3(grid), dim3(256), ldsw, hs, H);
   } else if (wmax > 2) {  // parameter rows of 65..128 bits (chunk tables, and so workers, only for 65..80 parameters: NCH = 20)
     switch (nch) {
-      TSIM_LHW(4, 0) TSIM_LHW(4, 20)
-      case 32: {
-        auto kfn = k_sample_hw<4, 32>;
-        if (!(p->x4_attr_set & 2u)) { HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192)); p->x4_attr_set |= 2u; }
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), ldsw, hs, H);
-      } break;
+      TSIM_LHW4(0) TSIM_NCH_FROM_20(TSIM_LHW4)
       default: return tsim_fail(TSIM_ESTATE, "hard-row workers need chunk tables (%d chunks)", nch);
     }
   } else switch (nch) {
-    TSIM_LHW(2, 0) TSIM_LHW(2, 2) TSIM_LHW(2, 4) TSIM_LHW(2, 6) TSIM_LHW(2, 8) TSIM_LHW(2, 10) TSIM_LHW(2, 12) TSIM_LHW(2, 14) TSIM_LHW(2, 16)
+    TSIM_LHW2(0) TSIM_NCH_TO_16(TSIM_LHW2)
     default: return tsim_fail(TSIM_ESTATE, "bad chunk count %d", nch);
   }
+#undef TSIM_LHW4
+#undef TSIM_LHW2
+#undef TSIM_LHW1
 #undef TSIM_LHW
   HIP_TRY(hipGetLastError());
   return 0;
@@ -429,9 +435,8 @@ int flush_batch(tsim_program *p) {
   const uint32_t fb_max = p->h_feedback ? p->h_feedback[1] : 192u;
   // (so many hard rows that they are throughput work - below: the 8-waves-per-64-rows blocks take ONE block's worth of every list,
   // the per-shot workers everything behind it)
-  const uint32_t fb_sum0 = p->h_feedback ? p->h_feedback[0] : 0xFFFFFFFFu;
-  const bool many0 = over_available(p) && fb_sum0 != 0xFFFFFFFFu && (unsigned long long)fb_sum0 * (unsigned)p->deferred.size() > 16384ull;
-  const int hb = many0 ? 1 : (int)std::max(1u, std::min(4u, (std::min(fb_max, 192u) + 32u + 63u) / 64u));
+  const bool many = many_hard_rows(p, M.n_ctx);
+  const int hb = over_available(p) && many ? 1 : (int)std::max(1u, std::min(4u, (std::min(fb_max, 192u) + 32u + 63u) / 64u));
   int max_lists = 1;
   for (int sidx : p->deferred) max_lists = std::max(max_lists, p->slots[sidx].ctx.row_lists);
   M.blocks_per_ctx = hb * max_lists + 1;
@@ -445,10 +450,9 @@ int flush_batch(tsim_program *p) {
     tsim_program::Slot &d = p->slots[p->deferred[i]];
     for (int k = 0; k < 2; ++k)
       if (d.p1_stream == p->slots[1 + k].side) lane_used[k] = true;
-    M.ctx[i] = d.ctx;
-    M.ctx[i].kernarg_off = (int)(offsetof(Hard4Multi, ctx) + (size_t)i * sizeof(SampleArgs));
     if (d.ctx_check) M.check_mask |= 1 << i;
   }
+  fill_contexts(M, M.n_ctx, [&](int i) -> const SampleArgs & { return p->slots[p->deferred[i]].ctx; });
   for (int k = 0; k < 2; ++k)
     if (lane_used[k] && p->slots[1 + k].side != hs) {
       if (!p->lane_ev[k]) HIP_TRY(hipEventCreateWithFlags(&p->lane_ev[k], hipEventDisableTiming));
@@ -465,8 +469,6 @@ int flush_batch(tsim_program *p) {
   // ... or ONE stride when the last launches left so many hard rows that they are throughput work (more than 16384 per group -
   // programs whose tables stop at weight 4, class F70: 1.4 % of the rows, 112 000 per group, took 450 us on the 8-waves-per-64-rows
   // form; the per-shot workers take them at the full kernel's rate)
-  const uint32_t fb_sum = p->h_feedback ? p->h_feedback[0] : 0xFFFFFFFFu;
-  const bool many = fb_sum != 0xFFFFFFFFu && (unsigned long long)fb_sum * (unsigned)M.n_ctx > 16384ull;
   const uint32_t cap4h = over_available(p) ? (uint32_t)M.loop_stride * (many ? 1u : 16u) : 0u;
   for (int i = 0; i < M.n_ctx; ++i) M.ctx[i].row_slot_end = (int)cap4h;
   unsigned grid = (unsigned)(M.n_ctx * M.blocks_per_ctx);
@@ -477,8 +479,8 @@ int flush_batch(tsim_program *p) {
   // resident tiles: one block of eight waves per CU)
   const bool over_apart = many && cap4h != 0;
   if (cap4h && !over_apart) {  // the workers ride in the same grid (a kernel of their own behind this one cost C3 4 %)
-    const size_t tile_bytes = std::max((size_t)p->v4_max_nch * 16, (size_t)p->v4_max_sent) * p->v4_gt * 16;
-    lds_m = std::max(lds_m, (size_t)(2 * M.ctx[0].WF + 2 * M.ctx[0].WO) * (NW * 64) * 4 + 2 * tile_bytes);
+    // (no limit check here: DESIGN.md 4.3 says what bounds it, and where it does not)
+    lds_m = std::max(lds_m, v4_block_lds(p, M.ctx[0].WF, M.ctx[0].WO, NW * 64));
     grid += (unsigned)p->n_cu * (many ? 2u : 1u);
   }
   if (over_apart) {
@@ -490,17 +492,16 @@ int flush_batch(tsim_program *p) {
 #define TSIM_LHM(N)                                                                                          \
   case N: {                                                                                                  \
     auto kfn = k_sample4h_multi<4, N, NW>;                                                                   \
-    if (!p->hm_attr_set) /* (the workers' list counts are 4 KB of static LDS, and the kernel has a little more) */                            \
-      HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); \
+    /* (152 KB: the workers' list counts are 4 KB of static LDS, and the kernel has a little more) */        \
+    if (int r = allow_lds_one(kfn, 152 * 1024, &p->hm_attr_set)) return r;                                   \
     ++p->path_count[TP_SAMPLE4H_MULTI];                                                                      \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(NW * 64), lds_m, hs, M);                                        \
   } break;
-    TSIM_LHM(2) TSIM_LHM(4) TSIM_LHM(6) TSIM_LHM(8) TSIM_LHM(10) TSIM_LHM(12) TSIM_LHM(14) TSIM_LHM(16) TSIM_LHM(20) TSIM_LHM(32)
+    TSIM_NCH_LIST(TSIM_LHM)
 #undef TSIM_LHM
     default: return tsim_fail(TSIM_ESTATE, "bad chunk count %d", p->v4_max_nch);
   }
   HIP_TRY(hipGetLastError());
-  p->hm_attr_set = true;
   if (over_apart) {
     // ... and on a lane of its own: the latency kernel above is ONE pass's latency on a few CUs, the workers are throughput work
     // that need not wait for it (n16: 363 + 707 us per group one behind the other; 10^6 shots: n13 77 -> 66 us, n16 152 -> 124)
@@ -686,363 +687,440 @@ static int launch_lw_fast(int WF, int n_out, long long grid, hipStream_t s, cons
 #undef TSIM_LF
   return 0;
 }
-static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_t num_f, uint32_t key_hi,
-                         uint32_t key_lo, int64_t shot_offset, uint64_t *d_out, float *d_dev, hipStream_t s,
-                         const uint32_t *d_row_index = nullptr, const uint32_t *d_row_count = nullptr,
-                         int slot = 0, const LaunchPlan *plan_in = nullptr, bool out_bit_packed = false) {
+// ---------------------------------------------------------------------------
+// The one-batch launcher: every batch that does not ride a fused group.  launch_sample routes; the stages
+// below it share one OneBatch.
+// ---------------------------------------------------------------------------
+struct OneBatch {
+  tsim_program *p;
+  int slot;
+  tsim_program::Slot &sl;
+  hipStream_t s;
+  int64_t B;
+  int32_t num_f;
+  uint32_t key_hi, key_lo;
+  int64_t shot_offset;
+  bool by_row_index;        // sample_rows_device: `a` carries the caller's row list
+  SampleArgs a{};           // the launch's arguments; behind a first pass they describe the row lists it left
+  LaunchPlan plan;
+  bool foreign = false;     // `s` is a stream of the caller's
+  bool prof = false;
+  bool has_check = false;   // the normalisation check applies to in-batch shot 0 (sampler.py:66-72) or the first listed row
+  bool use_tables = false, gen1 = false;
+  long long B2 = 0;         // slots per row list of the full kernel's launch
+  bool pipelined() const { return slot > 0; }  // lane launch: the caller passed the slot's own stream as `s`
+};
+// the profiling event that closes a stage: always, or unless the profile is light, or unless it is light and tables are in use
+enum ProfWhen { PROF_ALWAYS, PROF_UNLESS_LIGHT, PROF_UNLESS_LIGHT_TABLES };
+static int ob_prof(const OneBatch &o, int tag, ProfWhen when = PROF_ALWAYS) {
+  if (!o.prof) return 0;
+  if (when == PROF_UNLESS_LIGHT && o.p->prof_light) return 0;
+  if (when == PROF_UNLESS_LIGHT_TABLES && o.p->prof_light && o.use_tables) return 0;
+  return prof_event(o.p, o.s, tag);
+}
+// one wide component: everything in one kernel (tsim_wide.hip.h), here as a group of one batch
+static bool ob_wide_one_applies(const OneBatch &o) {
+  return o.use_tables && !o.by_row_index && wide_applies(o.p, o.B, o.num_f, o.shot_offset) && wide_buffers_ok(o.p, o.a);
+}
+// The argument checks, the slot, the arguments, the plan and what follows from it for the tables.  1: nothing to sample.
+static int ob_begin(OneBatch &o, const uint64_t *d_f, uint64_t *d_out, float *d_dev, const uint32_t *d_row_index, const uint32_t *d_row_count,
+                    const LaunchPlan *plan_in, bool out_bit_packed) {
+  tsim_program *p = o.p;
+  const int64_t B = o.B;
+  const int32_t num_f = o.num_f;
+  const hipStream_t s = o.s;
   if (!p->sampleable) return tsim_fail(TSIM_ESTATE, "program has joint-mode components (evaluate-only)");
-  if (B < 0 || num_f < 0 || shot_offset < 0) return tsim_fail(TSIM_EINVAL, "negative B/num_f/shot_offset");
+  if (B < 0 || num_f < 0 || o.shot_offset < 0) return tsim_fail(TSIM_EINVAL, "negative B/num_f/shot_offset");
   // a stream that is not the handle's own: the caller's - a table swap has to wait for what it carries too (tsim_tables_extend_poll):
-  // an event of the handle's is recorded behind this launch's last kernel (finish)
+  // an event of the handle's is recorded behind this launch's last kernel (ob_finish)
   bool foreign = !(s == p->stream || s == p->ext_stream);
   for (int k = 1; k <= TSIM_PIPELINE_SLOTS && foreign; ++k) foreign = !(p->slots[k].side_ready && p->slots[k].side == s);
+  o.foreign = foreign;
   if (p->max_f_index >= num_f)
     return tsim_fail(TSIM_EINVAL, "program references f index %d but num_f=%d", p->max_f_index, num_f);
-  if (B == 0 || p->num_outputs == 0) return 0;
+  if (B == 0 || p->num_outputs == 0) return 1;
   if (!d_f && num_f > 0) return tsim_fail(TSIM_EINVAL, "f buffer is NULL");
   if (!d_out) return tsim_fail(TSIM_EINVAL, "out buffer is NULL");
   // per-output subkeys: key, subkey = split(key) once per output, threaded through the
   // components in processing order (sampler.py:74,147-148)
-  tsim_program::Slot &sl = p->slots[slot];
-  if (int r = slot_prepare(p, slot, (p->lw || p->v4w) ? hard_list_bytes(B) : 0)) return r;
-  SampleArgs a{};
-  if (int r = fill_sample_args(p, sl, a, d_f, B, num_f, key_hi, key_lo, shot_offset, d_out, d_dev, s, slot, out_bit_packed)) return r;
+  if (int r = slot_prepare(p, o.slot, (p->lw || p->v4w) ? hard_list_bytes(B) : 0)) return r;
+  SampleArgs &a = o.a;
+  if (int r = fill_sample_args(p, o.sl, a, d_f, B, num_f, o.key_hi, o.key_lo, o.shot_offset, d_out, d_dev, s, o.slot, out_bit_packed)) return r;
   a.row_index = d_row_index;
   a.row_count = d_row_index ? d_row_count : nullptr;
   if (B > 0x7FFFFFFFll * 64) return tsim_fail(TSIM_ENOTSUP, "batch too large");
-  const bool prof = p->profiling && (p->prof_counter++ % p->prof_every == 0);
-  if (prof) { int r = prof_event(p, s, PROF_BEGIN); if (r) return r; }
-  // the normalisation check applies to in-batch shot 0 (sampler.py:66-72) or the first listed row
-  bool has_check = (shot_offset == 0 || d_row_index);
-  long long B2 = B;  // slots per row list of the full kernel's launch
-  const bool pipelined = slot > 0;  // lane launch: the caller passed the slot's own stream as `s`
-  auto finish = [&]() -> int {
-    if (!pipelined) p->first_call_out.store(true, std::memory_order_release);
-    if (foreign) {  // (looked up HERE: the launch plan drawn above may have swapped tables and dropped the events noted so far)
-      hipEvent_t ev = nullptr;
-      for (auto &cs : p->caller_streams)
-        if (cs.s == s) ev = cs.ev;
-      if (!ev && p->caller_streams.size() < 16) {
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        p->caller_streams.push_back({s, ev});
-      }
-      if (ev) HIP_TRY(hipEventRecord(ev, s));
-      else p->caller_streams_overflow = true;
-    }
-    if (pipelined) {
-      HIP_TRY(hipEventRecord(sl.ev2, s));
-      sl.pending = true;
-      sl.last_done = s;
-      sl.done_ev = sl.ev2;
-      sl.batch_seq = 0;
-    }
-    return 0;
-  };
-  const LaunchPlan plan = plan_in ? *plan_in : make_plan(p, d_row_index != nullptr, false, (unsigned long long)B);
-  bool use_tables = plan.use_tables;
-  const bool need_overflow = plan.need_overflow;
+  o.prof = p->profiling && (p->prof_counter++ % p->prof_every == 0);
+  if (int r = ob_prof(o, PROF_BEGIN)) return r;
+  o.has_check = (o.shot_offset == 0 || d_row_index);
+  o.B2 = B;
+  o.plan = plan_in ? *plan_in : make_plan(p, d_row_index != nullptr, false, (unsigned long long)B);
+  o.use_tables = o.plan.use_tables;
   // f rows wider than the round-2 wide kernels read (p->wide_big): k_sample_wide, or every row on the row kernel
-  const bool big_out = p->wide_big && !(use_tables && !d_row_index && wide_applies(p, B, num_f, shot_offset) && wide_buffers_ok(p, a));
-  if (big_out) use_tables = false;
+  if (p->wide_big && !ob_wide_one_applies(o)) o.use_tables = false;
   // a narrow program with more than 64 selected bits in a component: the one-batch first passes (k_sample_lw / _lw_reg / _lw_fast as a
   // group of one) hold f_sel in 64 bits - every row on the chunk-table kernel here; the fused groups ride k_sample_gen
   // ... and prefix-tree tables (components of more than 12 outputs, tsim_trie.hip.h) are walked by k_sample_gen only
   // - unless k_sample_gen takes the batch as a group of one (gen_one)
-  const bool gen1 = (p->narrow_big || p->lw_trie) && use_tables && !d_row_index && gen_applies(p, B, num_f, shot_offset) &&
-                    p->total_keys <= TSIMK_GEN_KEYS;
-  if ((p->narrow_big || p->lw_trie) && !gen1) use_tables = false;
-  if (int r = tsim_tables_slice(p, s)) return r;  // (a table build in the background: its next slice goes first)
-  // The sparse-column pass (k_sample4w) over every row, or - behind a pattern-table first pass - over that pass's
-  // hard-row lists (from_lists; `a` then describes them).  Its own overflow (more than K set bits, the check row)
-  // goes to row lists of its own, which `a` describes afterwards: the row kernel below serves them.
-  const bool wide_fits = p->v4w && !p->wide_big &&
-                         (size_t)(2 * a.WF + 2 * a.WO) * 256 * 4 + 2 * (size_t)p->v4_max_sent * p->v4_gt * 16 <= 64 * 1024;
-  auto wide_pass = [&](bool from_lists, int par) -> int {
-    if (B > 0xFFFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row list");
-    constexpr int kWideBlock = 256, kWideK = 10, kWideLists = 16;
-    // (streamed tables: two buffers of up to 24 KB - groups of graphs, eval_level4_groups - never less than one graph's table)
-    const size_t stage_b = (size_t)(2 * a.WF + 2 * a.WO) * kWideBlock * 4, one_tile = (size_t)p->v4_max_sent * p->v4_gt * 16;
-    const size_t stream_buf = std::max(one_tile, std::min<size_t>(24 * 1024, (64 * 1024 - stage_b) / 2) / 16 * 16), stream_b = 2 * stream_buf;
-    // all levels of a component resident in LDS when that still leaves room for two blocks per CU
-    const bool resident = stage_b + p->v4w_resident_bytes <= 64 * 1024;
-    const size_t ldsw = stage_b + (resident ? std::max(p->v4w_resident_bytes, (size_t)16) : stream_b);
-    if (p->v4w_occ_lds != ldsw) {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sample4w<1, kWideK>, kWideBlock, ldsw) != hipSuccess || nb < 1) {
-        (void)hipGetLastError();
-        nb = 1;
-      }
-      p->v4w_occ_blocks = nb;
-      p->v4w_occ_lds = ldsw;
+  o.gen1 = (p->narrow_big || p->lw_trie) && o.use_tables && !d_row_index && gen_applies(p, B, num_f, o.shot_offset) &&
+           p->total_keys <= TSIMK_GEN_KEYS;
+  if ((p->narrow_big || p->lw_trie) && !o.gen1) o.use_tables = false;
+  return tsim_tables_slice(p, s);  // (a table build in the background: its next slice goes first)
+}
+// behind the launch's last kernel
+static int ob_finish(OneBatch &o) {
+  tsim_program *p = o.p;
+  const hipStream_t s = o.s;
+  if (!o.pipelined()) p->first_call_out.store(true, std::memory_order_release);
+  if (o.foreign) {  // (looked up HERE: the launch plan drawn above may have swapped tables and dropped the events noted so far)
+    hipEvent_t ev = nullptr;
+    for (auto &cs : p->caller_streams)
+      if (cs.s == s) ev = cs.ev;
+    if (!ev && p->caller_streams.size() < 16) {
+      HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      p->caller_streams.push_back({s, ev});
     }
-    const long long chip = (long long)p->n_cu * p->v4w_occ_blocks * 1;
-    long long grid1, list_cap;
-    if (from_lists) {
-      // every input list gets the same number of blocks, which stride over it
-      const long long chip_l = chip;
-      const long long per_list = std::max(1ll, std::min(chip_l / a.row_lists, ((long long)a.row_list_cap + kWideBlock - 1) / kWideBlock));
-      grid1 = per_list * a.row_lists;
-      const long long rows_per_block = ((long long)a.row_list_cap + per_list * kWideBlock - 1) / (per_list * kWideBlock) * kWideBlock;
-      // an output list takes the overflow of the blocks with its residue - never more than the launch has rows
-      list_cap = std::min((grid1 + kWideLists - 1) / kWideLists * rows_per_block, (long long)(B + kWideBlock - 1) / kWideBlock * kWideBlock);
-    } else {
-      const long long blocks = (B + kWideBlock - 1) / kWideBlock;
-      // One component with resident tables: the kernel copies the tables once per block and strides over the rows, so
-      // the grid is what the chip holds at once (occupancy of this kernel with this much LDS), not one block per 256 rows
-      grid1 = blocks;
-      if (resident && p->comps.size() == 1) grid1 = std::min(blocks, chip);
-      const long long iters = (blocks + grid1 - 1) / grid1;
-      list_cap = (grid1 + kWideLists - 1) / kWideLists * iters * kWideBlock;
-    }
-    void *lists = from_lists ? sl.hard2 : sl.hard;
-    uint32_t *ctl_base = from_lists ? sl.ctl2 : sl.ctl;
-    const size_t lists_sz = from_lists ? sl.hard2_sz : sl.hard_sz;
-    if (list_cap > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row lists");
-    if (!lists || !ctl_base || (size_t)list_cap * kWideLists * 4 > lists_sz) return tsim_fail(TSIM_ESTATE, "row list too small");
-    Wide4Args w;
-    w.s = a;
-    w.comp4_off = p->comp4_off;
-    w.has_check = has_check ? 1 : 0;
-    w.check_row_in = (from_lists && has_check) ? a.check_row : nullptr;
-    w.feedback = from_lists ? p->d_feedback : nullptr;
-    w.hard_index = (uint32_t *)lists;
-    uint32_t *ctl = ctl_base + par * (TSIMK_LW_LISTS + 1) * 32;
-    w.ctl = ctl;
-    w.ctl_next = ctl_base + (par ^ 1) * (TSIMK_LW_LISTS + 1) * 32;
-    w.list_cap = (int)list_cap;
-    w.n_lists = kWideLists;
-    w.resident = resident ? 1 : 0;
-    w.stream_buf = (int)stream_buf;
-    ++p->path_count[TP_SAMPLE4W];
-    hipLaunchKernelGGL((k_sample4w<1, kWideK>), dim3((unsigned)grid1), dim3(kWideBlock), ldsw, s, w);
-    HIP_TRY(hipGetLastError());
-    if (prof && !(from_lists && p->prof_light)) { int r = prof_event(p, s, from_lists ? PROF_HARD : PROF_PASS1); if (r) return r; }
-    describe_lists(a, w.hard_index, ctl, kWideLists, (int)list_cap, has_check);
-    B2 = list_cap;
-    return 0;
-  };
-  if (use_tables && !d_row_index && wide_applies(p, B, num_f, shot_offset) && wide_buffers_ok(p, a)) {
-    // one wide component: everything in one kernel (tsim_wide.hip.h), here as a group of one batch
-    const SampleArgs *one = &a;
-    if (int r = launch_wide(p, 1, &one, B, num_f, shot_offset, s)) return r;
-    if (prof) { int r = prof_event(p, s, PROF_PASS1); if (r) return r; }
-    return finish();
+    if (ev) HIP_TRY(hipEventRecord(ev, s));
+    else p->caller_streams_overflow = true;
   }
-  if (use_tables) {
-    // pass 1: shots whose f_sel patterns are tabulated finish here, the others go to the hard list
-    if (B > 0xFFFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row list");
-    // few large blocks: 1024 threads finish a batch of 10^6 rows in 977 blocks - measurably better than
-    // 3906 blocks of 256 when the blocks of several launches and of the hard-row kernel share the CUs
-    const int blk1 = ((size_t)(2 * a.WF + 2 * a.WO) * 1024 * 4 <= 32 * 1024 ? 1024 : 256);
-    const bool reg_form = p->lw_reg && (a.WF == 1 || a.WF == 2) && a.WO == 1;
-    const long long blocks = (B + blk1 - 1) / blk1;
-    // the register form strides over the rows: no more blocks than the chip holds at once (2048 threads per CU)
-    long long grid1 = blocks;
-    if (reg_form)
-      grid1 = std::min(blocks, (long long)p->n_cu * (2048 / blk1));
-    const long long iters = (blocks + grid1 - 1) / grid1;
-    // n_lists sub-lists share the buffer sized for TSIMK_LW_LISTS of them: a list can hold every row of
-    // the blocks that feed it
-    const int n_lists = plan.lists;
-    const long long list_cap = (grid1 + n_lists - 1) / n_lists * iters * blk1;
-    if (list_cap > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row lists");
-    if ((size_t)list_cap * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
-    p->last_lists = n_lists;
-    LwArgs l;
-    l.s = a;
-    l.tab = p->d_lw_tab;
-    l.lw_off = p->lw_off;
-    l.direct_prog = p->lw_direct_prog;
-    l.direct_chunks = p->lw_direct_chunks;
-    l.direct_rot = p->lw_direct_rot;
-    l.has_check = has_check ? 1 : 0;
-    l.hard_index = (uint32_t *)sl.hard;
-    uint32_t *ctl = sl.ctl + sl.parity * (TSIMK_LW_LISTS + 1) * 32;
-    l.ctl = ctl;
-    l.ctl_next = sl.ctl + (sl.parity ^ 1) * (TSIMK_LW_LISTS + 1) * 32;
-    sl.parity ^= 1;
-    l.list_cap = (int)list_cap;
-    l.n_lists = n_lists;
-    l.binom_off = p->lw_binom_off;
-    const size_t lds1 = (size_t)(2 * a.WF + 2 * a.WO) * blk1 * 4 + (p->lw_wide ? 4096 : 0);
-    // one component of at most 8 outputs: the specialised pass of the fused groups (tsim_lw_fast.hip.h), as a group of ONE
-    // batch - 14.5 instead of 19.6 us per 10^6 shots for the serial API too (same conditions as in steps_group_fused)
-    const bool fast1 = reg_form && p->lwf_off != 0 && p->knobs.lw_fast && blk1 == 1024 && a.n_inline_keys > 0 && p->total_keys <= TSIMK_LWM_KEYS &&
-                       a.WO == 1 && lw32_ok(p, B, shot_offset, n_lists);
-    if (gen1) {
-      long long cap1 = 0;
-      if (int r = gen_one(p, sl, a, B, num_f, key_hi, key_lo, shot_offset, l.hard_index, l.ctl, l.ctl_next, n_lists, has_check, &cap1, s)) return r;
-      if ((size_t)cap1 * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
-      l.list_cap = (int)cap1;
-    } else if (fast1) {
-      const long long cap1 = (blocks + n_lists - 1) / n_lists * blk1;  // the fused kernels' list geometry: row block rb -> list rb % n_lists
-      if ((size_t)cap1 * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
-      LwMultiArgs M{};
-      lwm_common_args(p, M, B, shot_offset, 1, blocks, has_check, cap1, n_lists);
-      M.lwf_off = p->lwf_off;
-      M.tab_bytes = (uint32_t)p->lw_bytes;
-      lwf_fill_header(p, M);
-      LwStep &st = M.step[0];
-      st.f = a.f;
-      st.out = a.out;
-      st.out_compact = a.out_compact;
-      st.hard_index = l.hard_index;
-      st.ctl = l.ctl;
-      st.ctl_next = l.ctl_next;
-      memcpy(st.keys, a.inline_keys, sizeof(uint32_t) * 2 * (size_t)p->total_keys);
-      const long long chip = (long long)p->n_cu * (2048 / blk1);
-      const long long it1 = (blocks + chip - 1) / chip;
-      const long long gridf = (blocks + it1 - 1) / it1;
-      ++p->path_count[TP_LW_FAST1];
-      if (int r = launch_lw_fast(a.WF, p->comps[0].n_out, gridf, s, M)) return r;
-      l.list_cap = (int)cap1;
-    } else if (reg_form) {
-      // narrow rows: everything in registers, no LDS
-      ++p->path_count[TP_LW_REG];
-      if (a.WF == 1) hipLaunchKernelGGL(k_sample_lw_reg<2>, dim3((unsigned)grid1), dim3(blk1), 0, s, l);
-      else hipLaunchKernelGGL(k_sample_lw_reg<4>, dim3((unsigned)grid1), dim3(blk1), 0, s, l);
-    } else {
-      if (lds1 > 64 * 1024) return tsim_fail(TSIM_ENOTSUP, "num_f + num_outputs too large for LDS staging (%zu B)", lds1);
-      ++p->path_count[p->lw_wide ? TP_LW_LDS_WIDE : TP_LW_LDS];
-      if (p->lw_wide) hipLaunchKernelGGL(k_sample_lw<true>, dim3((unsigned)grid1), dim3(blk1), lds1, s, l);
-      else hipLaunchKernelGGL(k_sample_lw<false>, dim3((unsigned)grid1), dim3(blk1), lds1, s, l);
-    }
-    HIP_TRY(hipGetLastError());
-    if (prof) { int r = prof_event(p, s, PROF_PASS1); if (r) return r; }
-    // pass 2 below runs on the hard lists; the check row was forced into one of them
-    describe_lists(a, l.hard_index, ctl, n_lists, l.list_cap, has_check);
-    B2 = l.list_cap;
-    // wide components: the listed rows go through the sparse-column pass first, its overflow to the row kernel
-    // (ctl2 alternates on its own: launches that skip the tables - dense batches - do not touch it, and its reset
-    // is done by the launch that used it last)
-    if (p->lw_wide && wide_fits) {
-      if (int r = wide_pass(true, sl.parity2)) return r;
-      sl.parity2 ^= 1;
-    }
-  } else if (wide_fits) {
-    // wide components: sparse-column pass on every row (k_sample4w); rows with more than K set f bits and the
-    // normalisation-check row go to the row lists, which the row kernel below serves
-    if (int r = wide_pass(false, sl.parity)) return r;
-    sl.parity ^= 1;
-  } else if (!has_check) {
-    a.no_check = 1;
+  if (o.pipelined()) {
+    HIP_TRY(hipEventRecord(o.sl.ev2, s));
+    o.sl.pending = true;
+    o.sl.last_done = s;
+    o.sl.done_ev = o.sl.ev2;
+    o.sl.batch_seq = 0;
   }
-  int block = 256;
-  size_t lds = (size_t)(2 * a.WF + 2 * a.WO) * block * 4;
-  if (lds > 60 * 1024) { block = 64; lds = (size_t)(2 * a.WF + 2 * a.WO) * block * 4; }
-  if (lds > 60 * 1024) return tsim_fail(TSIM_ENOTSUP, "num_f + num_outputs too large for LDS staging (%zu B)", lds);
-  const long long nlists = a.row_lists > 1 ? a.row_lists : 1;
-  const long long grid = (B2 + block - 1) / block * nlists;
-  if (grid > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large");
-  if (p->v4) {
-    // chunk-table kernel: LDS = f/out staging + two tile buffers; one extra block replays shot 0
-    Sample4Args a4;
-    a4.s = a;
-    a4.comp4_off = p->comp4_off;
-    a4.has_check = has_check ? 1 : 0;
-    a4.feedback = (a.row_lists > 1 && !plan.hard_kernel) ? p->d_feedback : nullptr;
-    const int blk = kV4Block;
-    const size_t tile_bytes = std::max((size_t)p->v4_max_nch * 16, (size_t)p->v4_max_sent) * p->v4_gt * 16;
-    const size_t lds4 = (size_t)(2 * a.WF + 2 * a.WO) * blk * 4 + 2 * tile_bytes;
-    if (lds4 > (p->v4_max_nch == 32 ? 160 : 64) * 1024) return tsim_fail(TSIM_ENOTSUP, "v4 kernel needs %zu B of LDS", lds4);
-    if (a.row_lists > 1 && plan.hard_kernel) {
-      // short row lists (second pass of a two-pass launch): NW waves per 64 rows, tsim_kernel4h.hip.h
-      constexpr int NW = TSIM_HARD_NW;
-      hard_geometry(p, a.WF, a.WO);
-      const int group_tiles = p->h_group_tiles;
-      if (group_tiles >= 1 && plan.defer && pipelined) {
-        // leave the hard rows to the next batch: this lane goes on with the next launch's first pass
-        if (!p->deferred.empty() && (p->slots[p->deferred[0]].ctx.WF != a.WF || p->slots[p->deferred[0]].ctx.WO != a.WO))
-          if (int r = tsim_flush_hard(p)) return r;  // one LDS layout per batch
-        sl.ctx = a;
-        sl.ctx.row_slot_begin = 0;
-        sl.ctx.row_slot_end = 0;
-        sl.ctx_check = has_check;
-        sl.deferred = true;
-        sl.pending = true;
-        sl.p1_stream = s;
-        sl.partial = false;
-        p->deferred.push_back(slot);
-        if ((int)p->deferred.size() >= p->knobs.defer_group) return tsim_flush_hard(p);
-        return 0;
-      }
-      if (group_tiles >= 1 && hw_eligible(p, a, 1)) {
-        // few hard rows, fast row layout: one block per row (tsim_kernel_hw.hip.h), whole lists - nothing left for k_sample4
-        if (int r = launch_hw(p, &a, 1, a.row_lists, s, false)) return r;
-        if (prof && !p->prof_light) { int r = prof_event(p, s, PROF_HARD); if (r) return r; }
-        if (prof && !(p->prof_light && use_tables)) { int r = prof_event(p, s, PROF_FULL); if (r) return r; }
-        return finish();
-      }
-      if (group_tiles >= 1) {
-        // the first kHardBlocks * 64 slots of every list go to the NW-wave kernel; k_sample4 below
-        // serves the rest (its blocks exit at once when the lists are short - the usual case)
-        constexpr int kHardBlocks = 4;
-        const size_t ldsh = p->h_lds;
-        const long long gridh = (long long)kHardBlocks * nlists + a4.has_check;
-        Sample4Args ah = a4;
-        const int cap1 = over_available(p) ? kHardBlocks * 64 * 16 : 0;  // without an overflow launch: 16 strides, then k_sample4_over
-        ah.s.row_slot_end = need_overflow ? kHardBlocks * 64 : cap1;
-        const int loop_stride = need_overflow ? 0 : kHardBlocks * 64;
-        switch (p->v4_max_nch) {
+  return 0;
+}
+static int ob_wide_one(OneBatch &o) {  // (ob_wide_one_applies, above ob_begin)
+  const SampleArgs *one = &o.a;
+  if (int r = launch_wide(o.p, 1, &one, o.B, o.num_f, o.shot_offset, o.s)) return r;
+  if (int r = ob_prof(o, PROF_PASS1)) return r;
+  return ob_finish(o);
+}
+// The sparse-column pass (k_sample4w) over every row, or - behind a pattern-table first pass - over that pass's
+// hard-row lists (from_lists; `a` then describes them).  Its own overflow (more than K set bits, the check row)
+// goes to row lists of its own, which `a` describes afterwards: the row kernel serves them.
+// (Its staging and tiles are NOT v4_block_lds: one tile per graph and no chunk tables, so v4_max_sent alone.)
+static bool sparse_pass_fits(const tsim_program *p, const SampleArgs &a) {
+  return p->v4w && !p->wide_big && (size_t)(2 * a.WF + 2 * a.WO) * 256 * 4 + 2 * (size_t)p->v4_max_sent * p->v4_gt * 16 <= 64 * 1024;
+}
+static int ob_sparse_pass(OneBatch &o, bool from_lists, int par) {
+  tsim_program *p = o.p;
+  tsim_program::Slot &sl = o.sl;
+  SampleArgs &a = o.a;
+  const int64_t B = o.B;
+  if (B > 0xFFFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row list");
+  constexpr int kWideBlock = 256, kWideK = 10, kWideLists = 16;
+  // (streamed tables: two buffers of up to 24 KB - groups of graphs, eval_level4_groups - never less than one graph's table)
+  const size_t stage_b = (size_t)(2 * a.WF + 2 * a.WO) * kWideBlock * 4, one_tile = (size_t)p->v4_max_sent * p->v4_gt * 16;
+  const size_t stream_buf = std::max(one_tile, std::min<size_t>(24 * 1024, (64 * 1024 - stage_b) / 2) / 16 * 16), stream_b = 2 * stream_buf;
+  // all levels of a component resident in LDS when that still leaves room for two blocks per CU
+  const bool resident = stage_b + p->v4w_resident_bytes <= 64 * 1024;
+  const size_t ldsw = stage_b + (resident ? std::max(p->v4w_resident_bytes, (size_t)16) : stream_b);
+  if (p->v4w_occ_lds != ldsw) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sample4w<1, kWideK>, kWideBlock, ldsw) != hipSuccess || nb < 1) {
+      (void)hipGetLastError();
+      nb = 1;
+    }
+    p->v4w_occ_blocks = nb;
+    p->v4w_occ_lds = ldsw;
+  }
+  const long long chip = (long long)p->n_cu * p->v4w_occ_blocks * 1;
+  long long grid1, list_cap;
+  if (from_lists) {
+    // every input list gets the same number of blocks, which stride over it
+    const long long per_list = std::max(1ll, std::min(chip / a.row_lists, ((long long)a.row_list_cap + kWideBlock - 1) / kWideBlock));
+    grid1 = per_list * a.row_lists;
+    const long long rows_per_block = ((long long)a.row_list_cap + per_list * kWideBlock - 1) / (per_list * kWideBlock) * kWideBlock;
+    // an output list takes the overflow of the blocks with its residue - never more than the launch has rows
+    list_cap = std::min((grid1 + kWideLists - 1) / kWideLists * rows_per_block, (long long)(B + kWideBlock - 1) / kWideBlock * kWideBlock);
+  } else {
+    const long long blocks = (B + kWideBlock - 1) / kWideBlock;
+    // One component with resident tables: the kernel copies the tables once per block and strides over the rows, so
+    // the grid is what the chip holds at once (occupancy of this kernel with this much LDS), not one block per 256 rows
+    grid1 = blocks;
+    if (resident && p->comps.size() == 1) grid1 = std::min(blocks, chip);
+    list_cap = list_geometry(blocks, grid1, kWideLists, kWideBlock);
+  }
+  void *lists = from_lists ? sl.hard2 : sl.hard;
+  uint32_t *ctl_base = from_lists ? sl.ctl2 : sl.ctl;
+  const size_t lists_sz = from_lists ? sl.hard2_sz : sl.hard_sz;
+  if (list_cap > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row lists");
+  if (!lists || !ctl_base || (size_t)list_cap * kWideLists * 4 > lists_sz) return tsim_fail(TSIM_ESTATE, "row list too small");
+  Wide4Args w;
+  w.s = a;
+  w.comp4_off = p->comp4_off;
+  w.has_check = o.has_check ? 1 : 0;
+  w.check_row_in = (from_lists && o.has_check) ? a.check_row : nullptr;
+  w.feedback = from_lists ? p->d_feedback : nullptr;
+  w.hard_index = (uint32_t *)lists;
+  const CtlPair ctl = ctl_pair(ctl_base, par);
+  w.ctl = ctl.now;
+  w.ctl_next = ctl.next;
+  w.list_cap = (int)list_cap;
+  w.n_lists = kWideLists;
+  w.resident = resident ? 1 : 0;
+  w.stream_buf = (int)stream_buf;
+  ++p->path_count[TP_SAMPLE4W];
+  hipLaunchKernelGGL((k_sample4w<1, kWideK>), dim3((unsigned)grid1), dim3(kWideBlock), ldsw, o.s, w);
+  HIP_TRY(hipGetLastError());
+  if (int r = from_lists ? ob_prof(o, PROF_HARD, PROF_UNLESS_LIGHT) : ob_prof(o, PROF_PASS1)) return r;
+  describe_lists(a, w.hard_index, ctl.now, kWideLists, (int)list_cap, o.has_check);
+  o.B2 = list_cap;
+  return 0;
+}
+// one component of at most 8 outputs: the specialised pass of the fused groups (tsim_lw_fast.hip.h), as a group of ONE
+// batch - 14.5 instead of 19.6 us per 10^6 shots for the serial API too (same conditions as in steps_group_fused)
+static int ob_lw_fast1(OneBatch &o, LwArgs &l, long long blocks, int blk1, int n_lists) {
+  tsim_program *p = o.p;
+  const SampleArgs &a = o.a;
+  const long long cap1 = (blocks + n_lists - 1) / n_lists * blk1;  // the fused kernels' list geometry: row block rb -> list rb % n_lists
+  if ((size_t)cap1 * n_lists * 4 > o.sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
+  LwMultiArgs M{};
+  lwm_common_args(p, M, o.B, o.shot_offset, 1, blocks, o.has_check, cap1, n_lists);
+  M.lwf_off = p->lwf_off;
+  M.tab_bytes = (uint32_t)p->lw_bytes;
+  lwf_fill_header(p, M);
+  LwStep &st = M.step[0];
+  st.f = a.f;
+  st.out = a.out;
+  st.out_compact = a.out_compact;
+  st.hard_index = l.hard_index;
+  st.ctl = l.ctl;
+  st.ctl_next = l.ctl_next;
+  memcpy(st.keys, a.inline_keys, sizeof(uint32_t) * 2 * (size_t)p->total_keys);
+  const long long chip = (long long)p->n_cu * (2048 / blk1);
+  const long long it1 = (blocks + chip - 1) / chip;
+  const long long gridf = (blocks + it1 - 1) / it1;
+  ++p->path_count[TP_LW_FAST1];
+  if (int r = launch_lw_fast(a.WF, p->comps[0].n_out, gridf, o.s, M)) return r;
+  l.list_cap = (int)cap1;
+  return 0;
+}
+// pass 1: shots whose f_sel patterns are tabulated finish here, the others go to the hard list - by k_sample_gen as a group of
+// one, k_sample_lw_fast as a group of one, k_sample_lw_reg or k_sample_lw; wide components then send the listed rows through
+// the sparse-column pass
+static int ob_table_pass(OneBatch &o) {
+  tsim_program *p = o.p;
+  tsim_program::Slot &sl = o.sl;
+  SampleArgs &a = o.a;
+  const int64_t B = o.B;
+  const hipStream_t s = o.s;
+  if (B > 0xFFFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row list");
+  // few large blocks: 1024 threads finish a batch of 10^6 rows in 977 blocks - measurably better than
+  // 3906 blocks of 256 when the blocks of several launches and of the hard-row kernel share the CUs
+  const int blk1 = ((size_t)(2 * a.WF + 2 * a.WO) * 1024 * 4 <= 32 * 1024 ? 1024 : 256);
+  const bool reg_form = p->lw_reg && (a.WF == 1 || a.WF == 2) && a.WO == 1;
+  const long long blocks = (B + blk1 - 1) / blk1;
+  // the register form strides over the rows: no more blocks than the chip holds at once (2048 threads per CU)
+  long long grid1 = blocks;
+  if (reg_form)
+    grid1 = std::min(blocks, (long long)p->n_cu * (2048 / blk1));
+  // n_lists sub-lists share the buffer sized for TSIMK_LW_LISTS of them
+  const int n_lists = o.plan.lists;
+  const long long list_cap = list_geometry(blocks, grid1, n_lists, blk1);
+  if (list_cap > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large for the row lists");
+  if ((size_t)list_cap * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
+  p->last_lists = n_lists;
+  LwArgs l;
+  l.s = a;
+  l.tab = p->d_lw_tab;
+  l.lw_off = p->lw_off;
+  l.direct_prog = p->lw_direct_prog;
+  l.direct_chunks = p->lw_direct_chunks;
+  l.direct_rot = p->lw_direct_rot;
+  l.has_check = o.has_check ? 1 : 0;
+  l.hard_index = (uint32_t *)sl.hard;
+  const CtlPair ctl = ctl_pair(sl.ctl, sl.parity);
+  l.ctl = ctl.now;
+  l.ctl_next = ctl.next;
+  sl.parity ^= 1;
+  l.list_cap = (int)list_cap;
+  l.n_lists = n_lists;
+  l.binom_off = p->lw_binom_off;
+  const size_t lds1 = (size_t)(2 * a.WF + 2 * a.WO) * blk1 * 4 + (p->lw_wide ? 4096 : 0);
+  const bool fast1 = reg_form && p->lwf_off != 0 && p->knobs.lw_fast && blk1 == 1024 && a.n_inline_keys > 0 && p->total_keys <= TSIMK_LWM_KEYS &&
+                     a.WO == 1 && lw32_ok(p, B, o.shot_offset, n_lists);
+  if (o.gen1) {
+    long long cap1 = 0;
+    if (int r = gen_one(p, sl, a, B, o.num_f, o.key_hi, o.key_lo, o.shot_offset, l.hard_index, l.ctl, l.ctl_next, n_lists, o.has_check, &cap1, s)) return r;
+    if ((size_t)cap1 * n_lists * 4 > sl.hard_sz) return tsim_fail(TSIM_ESTATE, "hard-row list too small");
+    l.list_cap = (int)cap1;
+  } else if (fast1) {
+    if (int r = ob_lw_fast1(o, l, blocks, blk1, n_lists)) return r;
+  } else if (reg_form) {
+    // narrow rows: everything in registers, no LDS
+    ++p->path_count[TP_LW_REG];
+    if (a.WF == 1) hipLaunchKernelGGL(k_sample_lw_reg<2>, dim3((unsigned)grid1), dim3(blk1), 0, s, l);
+    else hipLaunchKernelGGL(k_sample_lw_reg<4>, dim3((unsigned)grid1), dim3(blk1), 0, s, l);
+  } else {
+    if (lds1 > 64 * 1024) return tsim_fail(TSIM_ENOTSUP, "num_f + num_outputs too large for LDS staging (%zu B)", lds1);
+    ++p->path_count[p->lw_wide ? TP_LW_LDS_WIDE : TP_LW_LDS];
+    if (p->lw_wide) hipLaunchKernelGGL(k_sample_lw<true>, dim3((unsigned)grid1), dim3(blk1), lds1, s, l);
+    else hipLaunchKernelGGL(k_sample_lw<false>, dim3((unsigned)grid1), dim3(blk1), lds1, s, l);
+  }
+  HIP_TRY(hipGetLastError());
+  if (int r = ob_prof(o, PROF_PASS1)) return r;
+  // pass 2 runs on the hard lists; the check row was forced into one of them
+  describe_lists(a, l.hard_index, ctl.now, n_lists, l.list_cap, o.has_check);
+  o.B2 = l.list_cap;
+  // wide components: the listed rows go through the sparse-column pass first, its overflow to the row kernel
+  // (ctl2 alternates on its own: launches that skip the tables - dense batches - do not touch it, and its reset
+  // is done by the launch that used it last)
+  if (p->lw_wide && sparse_pass_fits(p, a)) {
+    if (int r = ob_sparse_pass(o, true, sl.parity2)) return r;
+    sl.parity2 ^= 1;
+  }
+  return 0;
+}
+// The head of short row lists (second pass of a two-pass launch) on the chunk-table program's latency kernels: parked for
+// the slot's batch (flush_batch), or one block per row (launch_hw), or k_sample4h for the first kHardBlocks * 64 slots of
+// every list with k_sample4_over behind it.  1: the launch is complete; 0: k_sample4 serves what `a4` and o.B2 now say.
+static int ob_hard_lists(OneBatch &o, Sample4Args &a4, long long nlists) {
+  tsim_program *p = o.p;
+  tsim_program::Slot &sl = o.sl;
+  const SampleArgs &a = o.a;
+  const hipStream_t s = o.s;
+  // short row lists: NW waves per 64 rows, tsim_kernel4h.hip.h
+  constexpr int NW = TSIM_HARD_NW;
+  hard_geometry(p, a.WF, a.WO);
+  const int group_tiles = p->h_group_tiles;
+  if (group_tiles < 1) return 0;
+  if (o.plan.defer && o.pipelined()) {
+    // leave the hard rows to the next batch: this lane goes on with the next launch's first pass
+    if (!p->deferred.empty() && (p->slots[p->deferred[0]].ctx.WF != a.WF || p->slots[p->deferred[0]].ctx.WO != a.WO))
+      if (int r = tsim_flush_hard(p)) return r;  // one LDS layout per batch
+    sl.ctx = a;
+    sl.ctx.row_slot_begin = 0;
+    sl.ctx.row_slot_end = 0;
+    sl.ctx_check = o.has_check;
+    sl.deferred = true;
+    sl.pending = true;
+    sl.p1_stream = s;
+    sl.partial = false;
+    p->deferred.push_back(o.slot);
+    if ((int)p->deferred.size() >= p->knobs.defer_group)
+      if (int r = tsim_flush_hard(p)) return r;
+    return 1;
+  }
+  if (hw_eligible(p, a, 1)) {
+    // few hard rows, fast row layout: one block per row (tsim_kernel_hw.hip.h), whole lists - nothing left for k_sample4
+    if (int r = launch_hw(p, &a, 1, a.row_lists, s, false)) return r;
+    if (int r = ob_prof(o, PROF_HARD, PROF_UNLESS_LIGHT)) return r;
+    if (int r = ob_prof(o, PROF_FULL, PROF_UNLESS_LIGHT_TABLES)) return r;
+    if (int r = ob_finish(o)) return r;
+    return 1;
+  }
+  // the first kHardBlocks * 64 slots of every list go to the NW-wave kernel; k_sample4 below
+  // serves the rest (its blocks exit at once when the lists are short - the usual case)
+  constexpr int kHardBlocks = 4;
+  const bool need_overflow = o.plan.need_overflow;
+  const size_t ldsh = p->h_lds;
+  const long long gridh = (long long)kHardBlocks * nlists + a4.has_check;
+  Sample4Args ah = a4;
+  const int cap1 = over_available(p) ? kHardBlocks * 64 * 16 : 0;  // without an overflow launch: 16 strides, then k_sample4_over
+  ah.s.row_slot_end = need_overflow ? kHardBlocks * 64 : cap1;
+  const int loop_stride = need_overflow ? 0 : kHardBlocks * 64;
+  switch (p->v4_max_nch) {
 #define TSIM_LH(N)                                                                                          \
   case N: {                                                                                                 \
     auto kfn = k_sample4h<4, N, NW>;                                                                        \
-    if (!p->h_attr_set)                                                                                     \
-      HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+    if (int r = allow_lds_one(kfn, 160 * 1024, &p->h_attr_set)) return r;                                   \
     ++p->path_count[TP_SAMPLE4H];                                                                           \
     hipLaunchKernelGGL(kfn, dim3((unsigned)gridh), dim3(NW * 64), ldsh, s, ah, group_tiles, loop_stride,    \
                        p->d_feedback);                                                                      \
   } break;
-          TSIM_LH(2) TSIM_LH(4) TSIM_LH(6) TSIM_LH(8) TSIM_LH(10) TSIM_LH(12) TSIM_LH(14) TSIM_LH(16) TSIM_LH(20) TSIM_LH(32)
+    TSIM_NCH_LIST(TSIM_LH)
 #undef TSIM_LH
-          default: return tsim_fail(TSIM_ESTATE, "bad chunk count %d", p->v4_max_nch);
-        }
-        HIP_TRY(hipGetLastError());
-        if (prof && !p->prof_light) { int r = prof_event(p, s, PROF_HARD); if (r) return r; }
-        p->h_attr_set = true;
-        a4.has_check = 0;  // done by the kernel above
-        a4.s.no_check = 1;
-        a4.s.row_slot_begin = kHardBlocks * 64;
-        B2 = need_overflow ? std::max<long long>(0, B2 - kHardBlocks * 64) : 0;
-        if (!need_overflow && cap1)
-          if (int r = launch_over(p, &a, 1, (uint32_t)cap1, false, s)) return r;
-      }
-    }
-    const long long grid4 = (B2 + blk - 1) / blk * nlists + a4.has_check;
-    if (grid4 > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large");
-    if (grid4 > 0) ++p->path_count[TP_SAMPLE4];
-    if (grid4 > 0) switch (p->v4_max_nch) {
-#define TSIM_L4(N) case N: hipLaunchKernelGGL((k_sample4<4, N>), dim3((unsigned)grid4), dim3(blk), lds4, s, a4); break;
-      TSIM_L4(2) TSIM_L4(4) TSIM_L4(6) TSIM_L4(8) TSIM_L4(10) TSIM_L4(12) TSIM_L4(14) TSIM_L4(20)
-#undef TSIM_L4
-      case 32: {
-        auto kfn = k_sample4<4, 32>;
-        if (!(p->x4_attr_set & 4u)) { HIP_TRY(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096)); p->x4_attr_set |= 4u; }
-        hipLaunchKernelGGL(kfn, dim3((unsigned)grid4), dim3(blk), lds4, s, a4);
-      } break;
-      default: hipLaunchKernelGGL((k_sample4<4, 16>), dim3((unsigned)grid4), dim3(blk), lds4, s, a4); break;
-    }
-    HIP_TRY(hipGetLastError());
-    if (prof && !(p->prof_light && use_tables)) { int r = prof_event(p, s, PROF_FULL); if (r) return r; }
-    return finish();
+    default: return tsim_fail(TSIM_ESTATE, "bad chunk count %d", p->v4_max_nch);
   }
-  int wmax = 1;
-  for (int w : p->comp_w) wmax = std::max(wmax, w);
+  HIP_TRY(hipGetLastError());
+  if (int r = ob_prof(o, PROF_HARD, PROF_UNLESS_LIGHT)) return r;
+  a4.has_check = 0;  // done by the kernel above
+  a4.s.no_check = 1;
+  a4.s.row_slot_begin = kHardBlocks * 64;
+  o.B2 = need_overflow ? std::max<long long>(0, o.B2 - kHardBlocks * 64) : 0;
+  if (!need_overflow && cap1)
+    if (int r = launch_over(p, &a, 1, (uint32_t)cap1, false, s)) return r;
+  return 0;
+}
+// The chunk-table program's rows: every row, or the lists a first pass left (their head on the latency kernels above)
+static int ob_chunk_tables(OneBatch &o, long long nlists) {
+  tsim_program *p = o.p;
+  const SampleArgs &a = o.a;
+  // chunk-table kernel: LDS = f/out staging + two tile buffers; one extra block replays shot 0
+  Sample4Args a4;
+  a4.s = a;
+  a4.comp4_off = p->comp4_off;
+  a4.has_check = o.has_check ? 1 : 0;
+  a4.feedback = (a.row_lists > 1 && !o.plan.hard_kernel) ? p->d_feedback : nullptr;
+  const int blk = kV4Block;
+  const size_t lds4 = v4_block_lds(p, a.WF, a.WO, blk);
+  if (int r = v4_lds_check(p, lds4)) return r;
+  if (a.row_lists > 1 && o.plan.hard_kernel)
+    if (int r = ob_hard_lists(o, a4, nlists)) return r < 0 ? r : 0;
+  const long long grid4 = (o.B2 + blk - 1) / blk * nlists + a4.has_check;
+  if (grid4 > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large");
+  if (grid4 > 0) ++p->path_count[TP_SAMPLE4];
+  if (grid4 > 0) switch (p->v4_max_nch) {
+#define TSIM_L4(N) case N: { auto kfn = k_sample4<4, N>; if (N == 32) if (int r = allow_lds_one(kfn, 160 * 1024 - 4096, &p->s4_attr_set)) return r; \
+                             hipLaunchKernelGGL(kfn, dim3((unsigned)grid4), dim3(blk), lds4, o.s, a4); } break;
+    TSIM_NCH_TO_14(TSIM_L4) TSIM_NCH_FROM_20(TSIM_L4)
+#undef TSIM_L4
+    default: hipLaunchKernelGGL((k_sample4<4, 16>), dim3((unsigned)grid4), dim3(blk), lds4, o.s, a4); break;  // 16
+  }
+  HIP_TRY(hipGetLastError());
+  if (int r = ob_prof(o, PROF_FULL, PROF_UNLESS_LIGHT_TABLES)) return r;
+  return ob_finish(o);
+}
+// Programs without chunk tables: the row kernel on every row or on the lists, or the block-per-row kernel on the lists
+static int ob_row_tail(OneBatch &o, long long grid, int block, size_t lds) {
+  tsim_program *p = o.p;
+  const SampleArgs &a = o.a;
+  const int wmax = max_param_words(p);
   // The rows left in lists behind the sparse-column pass (more than K set bits, the normalisation-check row): ONE lane of the row
   // kernel walks all levels and graphs of such a row by itself - 280 us per batch for the check row of a 148-term program with
   // 65 parameters (class F60, profiles/r05/shape_map.txt) - the block-per-row kernel takes ~25.  (Programs of a few graphs - the C5 family - are
   // quicker on the one lane: 2wide 111 -> 127 us per step with the block-per-row kernel, measured.)
   // (no feedback from this grid: the plan's counts are the sparse-column pass's - the rows that miss the tables - not its overflow)
-  if (a.row_lists > 1 && !p->v4 && use_tables &&
-      ((gen1 && p->lw_trie) || (p->fast && p->knobs.hard_wave && wmax <= 8 && p->total_graphs >= 64 && a.WF <= 32 && a.WO <= 2 && p->hw_max_rows < 60000))) {  // (gen1: as flush_batch does)
-    if (int r = launch_hw(p, &a, 1, a.row_lists, s, false, false)) return r;
-    if (prof && !(p->prof_light && use_tables)) { int r = prof_event(p, s, PROF_FULL); if (r) return r; }
-    return finish();
+  if (a.row_lists > 1 && !p->v4 && o.use_tables &&
+      ((o.gen1 && p->lw_trie) || (p->fast && p->knobs.hard_wave && wmax <= 8 && p->total_graphs >= 64 && a.WF <= 32 && a.WO <= 2 && p->hw_max_rows < 60000))) {  // (gen1: as flush_batch does)
+    if (int r = launch_hw(p, &a, 1, a.row_lists, o.s, false, false)) return r;
+  } else {
+    ++p->path_count[TP_ROWS];
+    if (int r = tsim_launch_rows(p, wmax, a, grid, block, lds, o.s)) return r;
   }
-  ++p->path_count[TP_ROWS];
-  if (int r = tsim_launch_rows(p, wmax, a, grid, block, lds, s)) return r;
-  if (prof && !(p->prof_light && use_tables)) { int r = prof_event(p, s, PROF_FULL); if (r) return r; }
-  return finish();
+  if (int r = ob_prof(o, PROF_FULL, PROF_UNLESS_LIGHT_TABLES)) return r;
+  return ob_finish(o);
+}
+static int launch_sample(tsim_program *p, const uint64_t *d_f, int64_t B, int32_t num_f, uint32_t key_hi,
+                         uint32_t key_lo, int64_t shot_offset, uint64_t *d_out, float *d_dev, hipStream_t s,
+                         const uint32_t *d_row_index = nullptr, const uint32_t *d_row_count = nullptr,
+                         int slot = 0, const LaunchPlan *plan_in = nullptr, bool out_bit_packed = false) {
+  OneBatch o{p, slot, p->slots[slot], s, B, num_f, key_hi, key_lo, shot_offset, d_row_index != nullptr};
+  if (int r = ob_begin(o, d_f, d_out, d_dev, d_row_index, d_row_count, plan_in, out_bit_packed)) return r < 0 ? r : 0;
+  if (ob_wide_one_applies(o)) return ob_wide_one(o);
+  if (o.use_tables) {
+    if (int r = ob_table_pass(o)) return r;
+  } else if (sparse_pass_fits(p, o.a)) {
+    // wide components: sparse-column pass on every row (k_sample4w); rows with more than K set f bits and the
+    // normalisation-check row go to the row lists, which the row kernel below serves
+    if (int r = ob_sparse_pass(o, false, o.sl.parity)) return r;
+    o.sl.parity ^= 1;
+  } else if (!o.has_check) {
+    o.a.no_check = 1;
+  }
+  // the row kernel's geometry (refused here for a chunk-table program too)
+  const SampleArgs &a = o.a;
+  int block = 256;
+  size_t lds = (size_t)(2 * a.WF + 2 * a.WO) * block * 4;
+  if (lds > 60 * 1024) { block = 64; lds = (size_t)(2 * a.WF + 2 * a.WO) * block * 4; }
+  if (lds > 60 * 1024) return tsim_fail(TSIM_ENOTSUP, "num_f + num_outputs too large for LDS staging (%zu B)", lds);
+  const long long nlists = a.row_lists > 1 ? a.row_lists : 1;
+  const long long grid = (o.B2 + block - 1) / block * nlists;
+  if (grid > 0x7FFFFFFFll) return tsim_fail(TSIM_ENOTSUP, "batch too large");
+  return p->v4 ? ob_chunk_tables(o, nlists) : ob_row_tail(o, grid, block, lds);
 }
 // A slot's previous launch (its lists, counters and output rows are reused) may have finished on another stream than
 // `s`: order this launch after it.  Batches complete in order (one stream) and a lane is in order too: once a lane
@@ -1127,8 +1205,9 @@ int take_list_slot(tsim_program *p, hipStream_t s, uint32_t key[2], const uint64
   sl.ctx = SampleArgs{};
   if (int r = fill_sample_args(p, sl, sl.ctx, d_f, B, num_f, t.sub[0], t.sub[1], shot_offset, (uint64_t *)d_out, d_dev, s, t.sidx, packed)) return r;
   t.hard_index = (uint32_t *)sl.hard;
-  t.ctl = sl.ctl + sl.parity * (TSIMK_LW_LISTS + 1) * 32;
-  t.ctl_next = sl.ctl + (sl.parity ^ 1) * (TSIMK_LW_LISTS + 1) * 32;
+  const CtlPair ctl = ctl_pair(sl.ctl, sl.parity);
+  t.ctl = ctl.now;
+  t.ctl_next = ctl.next;
   sl.parity ^= 1;
   describe_lists(sl.ctx, t.hard_index, t.ctl, n_lists, (int)list_cap, has_check);
   return 0;

@@ -1,7 +1,9 @@
 // tsim_sample_internal.hip.h - what the translation units of the sampling launchers share (tsim_sample.hip
 // had grown to 2200 lines of three launch families):
-//   tsim_sample.hip       the launch plan, the pipeline slots, the hard-row stages, the one-batch launcher, the group protocol
-//                         (below), the groups of the register first passes and of k_direct_multi, the C entry points
+//   tsim_sample.hip       the launch plan, the pipeline slots, the hard-row stages (launch_over, launch_hw, flush_batch), the
+//                         one-batch launcher (launch_sample over its stages ob_*; its pure rules below), the group
+//                         protocol (below), the groups of the register first passes and of k_direct_multi, the C
+//                         entry points
 //   tsim_sample_wide.hip  k_sample_wide: layout, eligibility, one pass per component, its groups
 //   tsim_sample_gen.hip   k_sample_gen: layout, eligibility, its groups
 // A group launcher is its kernel's arguments and launch between the protocol's calls: group_lane, take_list_slot or
@@ -23,6 +25,46 @@ struct LaunchPlan {
   uint32_t fb_max = 0xFFFFFFFFu;
   int lists = TSIMK_LW_LISTS;  // hard-row sub-lists of this launch: about 40 expected rows each
 };
+
+// ---- the pure rules under the one-batch launcher and the hard-row stages (tsim_sample.hip).  No HIP call in any
+// of them: scripts/host_checks/launch_geometry.cpp runs them without a device.
+// one tile buffer of a chunk-table block: the chunk tables of one group of v4_gt graphs, or the largest sentinel table
+inline size_t v4_tile_bytes(const tsim_program *p) {
+  return std::max((size_t)p->v4_max_nch * 16, (size_t)p->v4_max_sent) * p->v4_gt * 16;
+}
+// dynamic LDS of a block of `threads` threads of a chunk-table kernel (k_sample4, k_sample4_over, the per-shot workers in the
+// grids of k_sample_hw and k_sample4h_multi): f / out staging + two tile buffers
+inline size_t v4_block_lds(const tsim_program *p, int WF, int WO, int threads) {
+  return (size_t)(2 * WF + 2 * WO) * threads * 4 + 2 * v4_tile_bytes(p);
+}
+// ... which a CU must hold: 64 KB as any kernel gets it, 160 KB for the NCH = 32 instances (allow_lds_one)
+inline int v4_lds_check(const tsim_program *p, size_t lds) {
+  if (lds > (p->v4_max_nch == 32 ? 160 : 64) * 1024) return tsim_fail(TSIM_ENOTSUP, "v4 kernel needs %zu B of LDS", lds);
+  return 0;
+}
+// 64-bit words of the widest component's parameter rows
+inline int max_param_words(const tsim_program *p) {
+  int wmax = 1;
+  for (int w : p->comp_w) wmax = std::max(wmax, w);
+  return wmax;
+}
+// the last launch left so many hard rows that a batch of n_ctx launches is throughput work (more than 16384 rows), not
+// latency work; the count is read ONCE per batch (the device writes it)
+inline bool many_hard_rows(const tsim_program *p, int n_ctx) {
+  const uint32_t fb_sum = p->h_feedback ? p->h_feedback[0] : 0xFFFFFFFFu;
+  return fb_sum != 0xFFFFFFFFu && (unsigned long long)fb_sum * (unsigned)n_ctx > 16384ull;
+}
+// slots per hard-row list of a first pass of `grid` blocks that strides over `blocks` row blocks of `block` rows: a list
+// can hold every row of the blocks that feed it
+inline long long list_geometry(long long blocks, long long grid, int n_lists, int block) {
+  const long long iters = (blocks + grid - 1) / grid;
+  return (grid + n_lists - 1) / n_lists * iters * block;
+}
+// the two counter sets of a slot, used alternately: this launch's, and the next one's, which this launch's first pass resets
+struct CtlPair { uint32_t *now, *next; };
+inline CtlPair ctl_pair(uint32_t *base, int parity) {
+  return {base + parity * (TSIMK_LW_LISTS + 1) * 32, base + (parity ^ 1) * (TSIMK_LW_LISTS + 1) * 32};
+}
 
 // TSIM_HOST_TIMING=1: where the host time of a several-batches call goes (stderr, one line per call)
 struct HostMarks {
