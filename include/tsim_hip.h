@@ -622,6 +622,28 @@ int tsim_rowtab_info(tsim_rowtab *h, int64_t out[8]);
 int tsim_rowtab_load(tsim_rowtab *h, const uint8_t *keys, const uint64_t *values, int64_t n);
 int tsim_rowtab_decode_device(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
                               const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, void *stream);
+/* tsim_rowtab_decode_device with an outlet for the predictions: every argument means the same and accumulates the same, and
+ * d_pred (uint64[n], 8-byte aligned) receives every row's value under the contract of tsim_uf_decode_device's d_pred: 0 for a
+ * row that is not kept and for a key that is not in the table.  d_pred == NULL is tsim_rowtab_decode_device itself. */
+int tsim_rowtab_decode_pred_device(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                   const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                   void *stream);
+
+/* ---- predictions into bit-packed device rows (count(decoder=..., corrected=True): corrected observables; decode_file) -----
+ * d_pred[r] (uint64[n], 8-byte aligned: the d_pred of a decode call below or above) is the prediction of row r, bit k =
+ * column col0 + k, for n_obs columns (1 .. 64; the bits at and above n_obs are ignored); rows as for tsim_tally_rows_device
+ * (any base address, any row_bytes >= 1), col0 >= 0 and col0 + n_obs <= 8 * row_bytes.
+ *   mode 0 (XOR):   the columns col0 .. col0 + n_obs - 1 of row r become ^= bit k of d_pred[r].  No other bit of the buffer
+ *                   changes, pad bits and padding bytes included, and a row whose prediction is 0 is not written at all: the
+ *                   rows of a decode call become rows with CORRECTED observables, which every reader above takes unchanged.
+ *   mode 1 (WRITE): the columns are SET to those bits and the other bits of the bytes col0 / 8 .. (col0 + n_obs - 1) / 8 are
+ *                   cleared; bytes outside those are not touched.  With col0 = 0 and row_bytes = ceil(n_obs / 8) the buffer
+ *                   becomes the rows of predictions the shot-data encoders take (tsim_shotdata_encode).
+ * One lane per row, 8-byte accesses when d_rows and row_bytes are multiples of 8, bytes otherwise.  Asynchronous on `stream`
+ * (NULL: the null stream) of HIP device `device`: behind the decode call that writes d_pred on the same stream it needs no
+ * other ordering.  Arguments are checked before any device call (TSIM_EINVAL); n == 0 returns 0 without a launch. */
+int tsim_pred_rows_device(int32_t device, const uint64_t *d_pred, int64_t n, int32_t n_obs, uint8_t *d_rows, int64_t row_bytes,
+                          int32_t col0, int32_t mode, void *stream);
 
 /* ---- the union-find (cluster-growth) decoder over bit-packed device rows (count(decoder=UnionFindDecoder)) ----------
  * The decoding graph: node 0 is the boundary, node i + 1 is detector (column) i; edge e joins edge_u[e] < edge_v[e], the

@@ -167,6 +167,8 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_rowtab_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_rowtab_load": (C.c_int, [_P, _P, _P, _I64]),
     "tsim_rowtab_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P]),
+    "tsim_rowtab_decode_pred_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _P]),
+    "tsim_pred_rows_device": (C.c_int, [_I32, _P, _I64, _I32, _P, _I64, _I32, _I32, _P]),
     "tsim_uf_create": (C.c_int, [_I32, C.POINTER(UfDesc), C.POINTER(_P)]),
     "tsim_uf_create_weighted": (C.c_int, [_I32, C.POINTER(UfDesc), _P, C.POINTER(_P)]),
     "tsim_uf_create_heralds": (C.c_int, [_I32, C.POINTER(UfDesc), _P, C.POINTER(UfHeralds), C.POINTER(_P)]),

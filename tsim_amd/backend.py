@@ -444,14 +444,31 @@ class HipProgram:
         _lib.check(self._lib.tsim_rowtab_load(C.c_void_p(handle), _lib.ptr(keys) if keys.size else None,
                                               _lib.ptr(values) if values.size else None, int(values.size)), "tsim_rowtab_load")
 
-    def rowtab_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_xor: int = 0,
-                             d_test: int = 0, stream: int = 0) -> None:
+    def rowtab_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,
+                             d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
         """Look the rows' keys up in a loaded table and count kept / wrong / unknown into ``d_counters``
-        (``tsim_rowtab_decode_device``); asynchronous on ``stream`` (0: the handle's stream)."""
+        (``tsim_rowtab_decode_device``); asynchronous on ``stream`` (0: the handle's stream).  ``d_pred``: ``uint64[n]`` for the
+        predictions, 0 for a row that is not kept and for an unknown syndrome (``tsim_rowtab_decode_pred_device``)."""
+        if d_pred:
+            self._uf_decode("tsim_rowtab_decode_pred_device", handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test,
+                            stream)
+            return
         _lib.check(self._lib.tsim_rowtab_decode_device(C.c_void_p(handle), C.c_void_p(int(d_rows)), int(n), int(row_bytes),
                                                        C.c_void_p(int(d_xor)) if d_xor else None, C.c_void_p(int(d_test)) if d_test else None,
                                                        int(observables[0]), int(observables[1]), C.c_void_p(int(d_counters)),
                                                        C.c_void_p(stream or self.stream_ptr())), "tsim_rowtab_decode_device")
+
+    PRED_ROWS_MODES = ("xor", "write")
+
+    def pred_rows_device(self, d_pred: int, n: int, n_obs: int, d_rows: int, row_bytes: int, col0: int, mode, *, stream: int = 0) -> None:
+        """The predictions ``uint64[n]`` at ``d_pred`` (what a decode call wrote there) into the columns ``col0 .. col0 + n_obs - 1``
+        of ``n`` bit-packed device rows (``tsim_pred_rows_device``, include/tsim_hip.h).  ``mode``: ``"xor"`` (0) XORs them into the
+        rows, which then hold corrected observables; ``"write"`` (1) sets the columns and clears the rest of their bytes: rows of
+        predictions.  Asynchronous on ``stream`` (0: the handle's stream)."""
+        m = self.PRED_ROWS_MODES.index(mode) if isinstance(mode, str) else int(mode)
+        _lib.check(self._lib.tsim_pred_rows_device(self.device, C.c_void_p(int(d_pred)) if d_pred else None, int(n), int(n_obs),
+                                                   C.c_void_p(int(d_rows)) if d_rows else None, int(row_bytes), int(col0), m,
+                                                   C.c_void_p(stream or self.stream_ptr())), "tsim_pred_rows_device")
 
     def rowtab_destroy(self, handle: int) -> None:
         self._lib.tsim_rowtab_destroy(C.c_void_p(handle))

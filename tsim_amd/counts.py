@@ -19,7 +19,10 @@ without the rows crossing PCIe.  ``decoder`` (:class:`tsim_amd.decode.LookupDeco
 :class:`tsim_amd.decode.UnionFindDecoder`, cluster growth on the circuit's decoding graph, ``tsim_uf_*``, or
 :class:`tsim_amd.decode.WindowedUnionFindDecoder`, the same window after window for long runs, ``tsim_ufw_*``, with heralded
 erasures too when the decoder has ``heralds=True``) is applied to every kept shot where it lies, and the wrong predictions are
-counted.
+counted.  ``corrected=True`` goes one step further: the predictions are XORed into the observable columns of the rows in HBM
+(``tsim_pred_rows_device``, ``csrc/tsim_predrows.hip.h``) before anything is counted, so the column counts, the histogram, the
+pair counts and the patterns are those of the corrected rows - per-observable logical error rates and the joint law of the
+residual flips.
 """
 
 from __future__ import annotations
@@ -57,7 +60,11 @@ class ShotCounts:
     ``soft_output`` (``None`` unless the decoder is a ``UnionFindDecoder.with_soft_output(metric, bins)``): the metric's name;
     then ``soft_kept[b]`` (int64 ``[bins]``) are the kept shots whose metric falls into bin ``b = min(value, bins - 1)`` and
     ``soft_errors[b]`` those of them that count in ``decoded_errors`` (``soft_kept.sum() == kept``,
-    ``soft_errors.sum() == decoded_errors``); :meth:`rejection_curve` sums them up."""
+    ``soft_errors.sum() == decoded_errors``); :meth:`rejection_curve` sums them up.  ``corrected`` (``count(decoder=...,
+    corrected=True)``): every kept shot's prediction was XORed into its observables before anything was counted, so
+    ``observable_counts[k]`` are the kept shots in which observable ``k`` is still flipped after decoding, ``histogram``,
+    ``pair_counts`` and ``patterns`` are over the corrected rows and ``kept_with_observable_flip == decoded_errors``; ``kept``,
+    ``detector_counts`` and the decoder's own counts are what they are without it."""
 
     shots: int
     kept: int
@@ -77,6 +84,7 @@ class ShotCounts:
     soft_output: str | None = None
     soft_kept: np.ndarray | None = None
     soft_errors: np.ndarray | None = None
+    corrected: bool = False
 
     @property
     def detector_counts(self) -> np.ndarray:
@@ -106,11 +114,14 @@ class ShotCounts:
                                                and np.array_equal(self.pattern_counts, other.pattern_counts)))
                 and self.pattern_overflow == other.pattern_overflow
                 and self.decoded_errors == other.decoded_errors and self.decoder_misses == other.decoder_misses
-                and self.soft_output == other.soft_output
+                # ("no soft output" is any false value: callers that build counts from the fields in front of the soft ones,
+                # positionally, hand the last field's False to soft_output since `corrected` was appended)
+                and (self.soft_output or None) == (other.soft_output or None)
                 and (self.soft_kept is None) == (other.soft_kept is None)
                 and (self.soft_kept is None or np.array_equal(self.soft_kept, other.soft_kept))
                 and (self.soft_errors is None) == (other.soft_errors is None)
-                and (self.soft_errors is None or np.array_equal(self.soft_errors, other.soft_errors)))
+                and (self.soft_errors is None or np.array_equal(self.soft_errors, other.soft_errors))
+                and bool(self.corrected) == bool(other.corrected))
 
     def pair_correlations(self) -> np.ndarray:
         """The float64 ``[k, k]`` matrix of the p_ij estimator over ``pair_columns`` (diagonal NaN):
@@ -262,8 +273,9 @@ class _HostTally:
     """The numpy statement of the tally, accumulated batch by batch (memory O(columns + bins))."""
 
     def __init__(self, n_cols: int, num_detectors: int, postselection_mask, histogram_columns, pair_columns=(), pattern_columns=(),
-                 pattern_capacity=None, decoder=None):
+                 pattern_capacity=None, decoder=None, corrected: bool = False):
         self.n_cols, self.nd = int(n_cols), int(num_detectors)
+        self.corrected = check_corrected(corrected, decoder)
         self.tc, self.tcap = tuple(pattern_columns), pattern_capacity
         self.table = {}          # packed pattern bytes -> rows, in the order of first appearance
         self.overflow = 0
@@ -285,6 +297,18 @@ class _HostTally:
         if self.mask is not None:
             rows = rows[~(rows[:, : self.nd] & self.mask).any(axis=1)]
         self.kept += len(rows)
+        if self.decoder is not None and len(rows):
+            dets, obs = rows[:, : self.nd], rows[:, self.nd:]
+            pred = self.decoder.decode(dets)
+            wrong = (pred != obs).any(axis=1)
+            self.errors += int(wrong.sum())
+            self.misses += int(self.decoder.missed(dets).sum())
+            if self.soft:
+                kept, errors = self.decoder.soft_bin_counts(dets, wrong)
+                self.soft_hist[0] += kept
+                self.soft_hist[1] += errors
+            if self.corrected:  # everything below counts the corrected rows (a copy: the caller's rows stay)
+                rows = np.concatenate([dets, obs ^ pred], axis=1)
         self.kept_obs += int(rows[:, self.nd:].any(axis=1).sum())
         self.cols += rows.sum(axis=0, dtype=np.int64)
         idx = np.zeros(len(rows), dtype=np.int64)
@@ -305,15 +329,6 @@ class _HostTally:
                     self.table[key] = int(cnt[i])
                 else:
                     self.overflow += int(cnt[i])
-        if self.decoder is not None and len(rows):
-            dets, obs = rows[:, : self.nd], rows[:, self.nd:]
-            wrong = (self.decoder.decode(dets) != obs).any(axis=1)
-            self.errors += int(wrong.sum())
-            self.misses += int(self.decoder.missed(dets).sum())
-            if self.soft:
-                kept, errors = self.decoder.soft_bin_counts(dets, wrong)
-                self.soft_hist[0] += kept
-                self.soft_hist[1] += errors
 
     def result(self) -> ShotCounts:
         patterns = pattern_counts = None
@@ -324,11 +339,12 @@ class _HostTally:
         return ShotCounts(self.shots, self.kept, self.kept_obs, self.cols.copy(), self.nd, self.hc, self.hist.copy(), self.pc,
                           None if self.pairs is None else self.pairs.copy(), self.tc, patterns, pattern_counts, self.overflow,
                           None if self.decoder is None else self.errors, None if self.decoder is None else self.misses,
-                          *((self.soft[0], self.soft_hist[0].copy(), self.soft_hist[1].copy()) if self.soft else ()))
+                          *((self.soft[0], self.soft_hist[0].copy(), self.soft_hist[1].copy()) if self.soft else ()),
+                          corrected=self.corrected)
 
 
 def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_columns=(), pair_columns=(), pattern_columns=(),
-               pattern_capacity=None, decoder=None) -> ShotCounts:
+               pattern_capacity=None, decoder=None, corrected: bool = False) -> ShotCounts:
     """The tally of boolean rows (detectors, then observables) in numpy: a row is kept iff no masked detector is set; the
     column counts, ``kept_with_observable_flip`` (a set observable), the histogram and the pair counts over
     ``pair_columns`` (:func:`check_pair_columns`) are taken over the kept rows.  ``pattern_columns``
@@ -336,7 +352,9 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
     of :class:`ShotCounts`; ``pattern_capacity`` (default: no limit) admits that many patterns in the order of first
     appearance and counts the rows of the others in ``pattern_overflow``.  ``decoder``: a
     :class:`tsim_amd.decode.LookupDecoder` or :class:`tsim_amd.decode.UnionFindDecoder` applied to the kept rows; one with a
-    soft output (``with_soft_output``) also fills ``soft_kept`` / ``soft_errors``, from its ``soft_outputs()``."""
+    soft output (``with_soft_output``) also fills ``soft_kept`` / ``soft_errors``, from its ``soft_outputs()``.  ``corrected``
+    (needs a decoder): every kept row gets ``obs ^= decoder.decode(dets)`` before anything but the decoder's own counts is
+    taken (:class:`ShotCounts`); ``rows`` itself is not changed."""
     rows = np.asarray(rows, dtype=np.bool_)
     if rows.ndim != 2:
         raise ValueError(f"rows must be 2-D, got shape {rows.shape}")
@@ -348,7 +366,7 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
     t = _HostTally(n_cols, num_detectors, postselection_mask, check_histogram_columns(histogram_columns, n_cols),
                    check_pair_columns(pair_columns, n_cols, num_detectors),
                    check_pattern_columns(pattern_columns, n_cols, num_detectors), check_pattern_capacity(pattern_capacity),
-                   check_decoder(decoder, n_cols, num_detectors))
+                   check_decoder(decoder, n_cols, num_detectors), corrected)
     t.add(rows)
     return t.result()
 
@@ -372,6 +390,13 @@ def check_decoder(decoder, n_cols: int, num_detectors: int):
     if decoder.num_detectors < 1:
         raise ValueError("a decoder needs at least one detector")
     return decoder
+
+
+def check_corrected(corrected, decoder) -> bool:
+    """``corrected`` as a bool; ``ValueError`` when it is asked for without a decoder."""
+    if corrected and decoder is None:
+        raise ValueError("corrected=True needs a decoder: the predictions are what is XORed into the observables")
+    return bool(corrected)
 
 
 def tally_rows_device(d_rows: int, n: int, *, row_bytes: int, n_cols: int, d_counts: int, d_xor: int = 0, d_test: int = 0,
@@ -478,8 +503,11 @@ class _DeviceTally:
     ``[lo, hi)`` of the rows handed to it that belong to the request (a reference row riding in front, padding behind)."""
 
     def __init__(self, hp, n_cols: int, num_detectors: int, *, xor_bits=None, test_bits=None, histogram_columns=(), lo: int = 0,
-                 hi: int = 0, pair_columns=(), pattern_columns=(), pattern_capacity=None, decoder=None):
+                 hi: int = 0, pair_columns=(), pattern_columns=(), pattern_capacity=None, decoder=None, corrected: bool = False):
         self.hp, self.n_cols, self.nd, self.hc = hp, int(n_cols), int(num_detectors), tuple(histogram_columns)
+        self.corrected = check_corrected(corrected, decoder)
+        self._d_pred = None      # corrected: the predictions of one call's rows, uint64[_d_pred_rows], grown on demand
+        self._d_pred_rows = 0
         self.lo, self.hi = int(lo), int(hi)
         self.pc = tuple(pair_columns)
         self.tc = tuple(pattern_columns)
@@ -499,14 +527,7 @@ class _DeviceTally:
             if self.tc:
                 self._table = hp.rowtab_create(self.n_cols, self.tc, pattern_capacity or DEFAULT_PATTERN_CAPACITY)
             if decoder is not None:
-                from .decode import UnionFindDecoder, WindowedUnionFindDecoder
-
-                if isinstance(decoder, (UnionFindDecoder, WindowedUnionFindDecoder)):
-                    self._dec = decoder._handle(hp, self.n_cols)
-                else:
-                    keys, values = decoder.table()
-                    self._dec = hp.rowtab_create(self.n_cols, range(self.nd), max(64, 4 * len(values))), hp.rowtab_decode_device, hp.rowtab_destroy
-                    hp.rowtab_load(self._dec[0], keys, values)
+                self._dec = decoder._handle(hp, self.n_cols)
                 self.d_decoded = self._upload(np.zeros(3, dtype=np.uint64))
                 if self.soft:
                     self.d_soft_hist = self._upload(np.zeros(2 * self.soft[1], dtype=np.uint64))
@@ -535,6 +556,15 @@ class _DeviceTally:
         a, b = max(r0, self.lo), min(r1, self.hi)
         if b <= a:
             return
+        if self.corrected:
+            # decode first, then XOR every prediction into its row's raw observables: the readers below, on the same stream, see
+            # corrected rows and apply the xor mask themselves (the rows are the sampler's output and are not read again)
+            d_pred = self._pred_room(b - a)
+            self._pairs_stream = stream
+            self._decode(d_first + (a - r0) * row_bytes, b - a, row_bytes, stream, d_pred=d_pred)
+            if self.n_cols > self.nd:
+                self.hp.pred_rows_device(self._d_pred.ptr, b - a, self.n_cols - self.nd, d_first + (a - r0) * row_bytes, row_bytes, self.nd,
+                                         "xor", stream=stream)
         self.hp.tally_rows_device(d_first + (a - r0) * row_bytes, b - a, row_bytes, self.n_cols, self.d_counts.ptr,
                                   d_xor=self.d_xor.ptr if self.d_xor is not None else 0,
                                   d_test=self.d_test.ptr if self.d_test is not None else 0,
@@ -550,8 +580,25 @@ class _DeviceTally:
                          stream=stream)
             if self._table is not None:
                 self.hp.rowtab_add_device(self._table, d_first + (a - r0) * row_bytes, b - a, row_bytes, **masks)
-            if self._dec is not None:
+            if self._dec is not None and not self.corrected:
                 self._dec[1](self._dec[0], d_first + (a - r0) * row_bytes, b - a, row_bytes, (self.nd, self.n_cols), self.d_decoded.ptr, **masks)
+
+    def _decode(self, d_rows: int, n: int, row_bytes: int, stream: int, d_pred: int) -> None:
+        """``corrected``: the decoder's call with an outlet for the predictions (it writes every row's, 0 for a row that is not kept)."""
+        self._dec[1](self._dec[0], d_rows, n, row_bytes, (self.nd, self.n_cols), self.d_decoded.ptr, d_pred=d_pred,
+                     d_xor=self.d_xor.ptr if self.d_xor is not None else 0, d_test=self.d_test.ptr if self.d_test is not None else 0,
+                     stream=stream)
+
+    def _pred_room(self, n: int) -> int:
+        """The scratch buffer of the predictions, for ``n`` rows at least."""
+        if self._d_pred_rows < n:
+            if self._d_pred is not None:  # (the launches of the call before may still use it)
+                self.hp.stream_synchronize(self._pairs_stream)
+                self._d_pred.free()
+                self._d_pred, self._d_pred_rows = None, 0
+            self._d_pred = self.hp.malloc(8 * n + 16)
+            self._d_pred_rows = n
+        return self._d_pred.ptr
 
     def result(self, shots: int) -> ShotCounts:
         """The counters, once every tally launch has completed (the caller has synchronised their streams)."""
@@ -580,9 +627,12 @@ class _DeviceTally:
             soft = (self.soft[0], hist[:self.soft[1]].copy(), hist[self.soft[1]:].copy())
         return ShotCounts(out.shots, out.kept, out.kept_with_observable_flip, out.column_counts, out.num_detectors,
                           out.histogram_columns, out.histogram, self.pc, pairs, self.tc, patterns, pattern_counts, overflow,
-                          errors, misses, *soft)
+                          errors, misses, *soft, corrected=self.corrected)
 
     def release(self) -> None:
+        if self._d_pred is not None:
+            self._d_pred.free()
+            self._d_pred, self._d_pred_rows = None, 0
         if self._table is not None:
             self.hp.rowtab_destroy(self._table)
             self._table = None

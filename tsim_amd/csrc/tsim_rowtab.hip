@@ -287,3 +287,31 @@ extern "C" int tsim_rowtab_decode_device(tsim_rowtab *h, const uint8_t *d_rows, 
   }
   return TSIM_OK;
 }
+
+extern "C" int tsim_rowtab_decode_pred_device(tsim_rowtab *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                              const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                              void *stream) {
+  if (!d_pred) return tsim_rowtab_decode_device(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, stream);
+  rowtabk::Args a{};
+  if (int rc = rowtab_args(h, d_rows, n, row_bytes, d_xor, d_test, &a)) return rc;
+  if (obs_lo < 0 || obs_hi < obs_lo || obs_hi > h->n_cols || obs_hi - obs_lo > 64)
+    return tsim_fail(TSIM_EINVAL, "observable columns %d .. %d of %d (at most 64)", obs_lo, obs_hi, h->n_cols);
+  if (!d_counters || reinterpret_cast<uintptr_t>(d_counters) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_counters is NULL or not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_pred) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_pred is not 8-byte aligned");
+  if (!h->loaded) return tsim_fail(TSIM_ESTATE, "the table holds no values: tsim_rowtab_load comes first");
+  if (n == 0) return TSIM_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  a.obs_lo = obs_lo;
+  a.obs_hi = obs_hi;
+  a.dec = reinterpret_cast<unsigned long long *>(d_counters);
+  const size_t stage = (size_t)rowtabk::kWaves * a.stage_bytes;
+  for (int64_t r0 = 0; r0 < n; r0 += kRowsPerLaunch) {
+    a.n = std::min(kRowsPerLaunch, n - r0);
+    a.rows = d_rows + r0 * row_bytes;
+    a.pred = reinterpret_cast<unsigned long long *>(d_pred) + r0;
+    hipLaunchKernelGGL(rowtabk::k_decode_pred, dim3(rowtab_blocks(h, a.n)), dim3(64 * rowtabk::kWaves), 16 + stage, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    ++h->launches;
+  }
+  return TSIM_OK;
+}

@@ -23,6 +23,7 @@
 //   k_decode  the read-only probe on the key columns (the detectors), the full key compared (wide keys), the slot's
 //             value XORed with the row's observable columns: kept / kept and wrong / kept and unknown, merged per wave,
 //             then per block in LDS, one atomic each per block.
+//   k_decode_pred  k_decode that also stores every row's value (0: not kept, unknown) to pred[r], one plain store per lane.
 // Keys of a prefix selection (columns 0 .. n_key-1) are read from the staged bytes, in chunks of kChunk bytes for wide
 // rows; any other selection is gathered bit by bit from global memory, in key order.
 #pragma once
@@ -66,6 +67,7 @@ struct Args {
   unsigned long long *stats;  // [0] kept [1] entries [2] overflow rows [3] collisions
   int obs_lo, obs_hi;         // k_decode: the observable columns
   unsigned long long *dec;    // k_decode: [0] kept [1] wrong [2] unknown
+  unsigned long long *pred;   // k_decode_pred: [n] every row's prediction
 };
 
 // one wave's tile of rows
@@ -317,6 +319,47 @@ __global__ void __launch_bounds__(64 * kWaves) k_decode(Args a) {
     if (!a.exact && __builtin_amdgcn_ballot_w64(slot >= 0) && key_differs(a, tile, slot)) slot = -1;  // another syndrome's tag
     const uint64_t obs = kept ? row_obs(a, tile.src + (long long)lane * a.rb) : 0;
     const uint64_t pred = slot >= 0 ? a.values[slot] : 0ull;  // an unknown syndrome predicts no flip
+    wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
+    miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && slot < 0));
+  }
+  if (lane == 0) {
+    if (kept_acc) atomicAdd(&stat[0], kept_acc);
+    if (wrong_acc) atomicAdd(&stat[1], wrong_acc);
+    if (miss_acc) atomicAdd(&stat[2], miss_acc);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && stat[threadIdx.x]) atomicAdd(&a.dec[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
+}
+
+// k_decode with an outlet: the same lookups and counters, and pred[r] = row r's value, 0 for a row that is not kept and for an
+// unknown syndrome (the contract of tsim_uf_decode_device's d_pred: every row of the call is written)
+__global__ void __launch_bounds__(64 * kWaves) k_decode_pred(Args a) {
+  extern __shared__ uint64_t lds_raw[];
+  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, unknown
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint8_t *stage = reinterpret_cast<uint8_t *>(stat + 4) + (size_t)wave * a.stage_bytes;
+  if (threadIdx.x < 4) stat[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0;
+  const long long tiles = (a.n + 63) >> 6;
+  for (long long t = (long long)blockIdx.x * kWaves + wave; t < tiles; t += (long long)gridDim.x * kWaves) {
+    const Tile tile = tile_of(a, t, stage, lane);
+    const bool valid = lane < tile.rows;
+    const long long r = (t << 6) + lane;
+    const bool kept = tile_kept(a, tile);
+    const uint64_t keep = __builtin_amdgcn_ballot_w64(kept);
+    if (!keep) {
+      if (valid) a.pred[r] = 0ull;
+      continue;
+    }
+    kept_acc += (uint32_t)__popcll(keep);
+    const uint64_t tag = tile_tag(a, tile);
+    bool won = false;
+    long long slot = kept ? probe<false>(a, tag, won) : -1;
+    if (!a.exact && __builtin_amdgcn_ballot_w64(slot >= 0) && key_differs(a, tile, slot)) slot = -1;  // another syndrome's tag
+    const uint64_t obs = kept ? row_obs(a, tile.src + (long long)lane * a.rb) : 0;
+    const uint64_t pred = slot >= 0 ? a.values[slot] : 0ull;  // an unknown syndrome predicts no flip
+    if (valid) a.pred[r] = pred;                              // (a row that is not kept has no slot: 0)
     wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
     miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && slot < 0));
   }

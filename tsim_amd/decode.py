@@ -160,6 +160,14 @@ after the xor mask.  A row with ``r == 0`` predicts 0 and is not decoded, whatev
 Growth, forest, peeling, the committed flips, the carry into ``r`` and a miss are as written above.  With ``W >= nd`` there is
 one window and every number - prediction, miss, flipped edges, growth rounds - equals that of :class:`UnionFindDecoder` over
 ``g``.  The rule is the one above plus a fixed set of edges that start full, so it stays independent of any parallel order.
+
+What becomes of a prediction (``tsim_pred_rows_device``, ``csrc/tsim_predrows.hip.h``)
+---------------------------------------------------------------------------------------------------------
+Every device decode call can write its predictions (``d_pred``: a uint64 per row, bit ``k`` = observable ``k``, 0 for a row that
+is not kept, an unknown syndrome and a miss).  ``count(..., decoder=dec, corrected=True)`` XORs them into the observable
+columns of the rows where they lie, so every count is taken over corrected rows (``ShotCounts.corrected``);
+:func:`decode_file` (``dec.decode_file(...)`` of all three decoders) decodes the detection events of a shot-data file and
+writes the predictions as another.
 """
 
 from __future__ import annotations
@@ -168,7 +176,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-__all__ = ["LookupDecoder", "DecodingGraph", "UnionFindDecoder", "UnionFindWindow", "WindowedUnionFindDecoder"]
+__all__ = ["LookupDecoder", "DecodingGraph", "UnionFindDecoder", "UnionFindWindow", "WindowedUnionFindDecoder", "DecodeFileResult",
+           "decode_file"]
 
 MAX_GRAPH = 65535  # nodes, and edges: uint16 indices on the device
 MAX_CAP = 14       # of an edge: the device counts grown[e] in 4 bits and may pass the cap by one
@@ -195,6 +204,94 @@ def _as_uint64(bits: np.ndarray) -> np.ndarray:
     p = _pack(bits)
     out[:, : p.shape[1]] = p
     return out.view("<u8").reshape(len(bits))
+
+
+class DecodeFileResult(NamedTuple):
+    """What :func:`decode_file` counted: the rows of the file, those that were kept (all of them: there is no post-selection),
+    the rows whose prediction differs from the observables the file carries (``None`` when it carries none) and the rows for
+    which the decoder has no prediction (an unknown syndrome, a miss) and predicts no flip."""
+
+    shots: int
+    kept: int
+    decoded_errors: int | None
+    decoder_misses: int
+
+
+def decode_file(decoder, *, detection_events_filepath, detection_events_format: str, predictions_filepath, predictions_format: str,
+                observables_appended: bool = False, hp=None) -> DecodeFileResult:
+    """Recorded shots to predictions, on the GPU: the method ``decode_file`` of the three decoder classes.
+
+    The file at ``detection_events_filepath`` (any format of :mod:`tsim_amd.shotdata`; in ``dets`` the detectors are ``D``, the
+    observables ``L``) holds ``num_detectors`` bits per shot, or ``num_detectors + num_observables`` with
+    ``observables_appended=True``.  It is read piece by piece (``shotdata.iter_device_rows``); every piece is decoded where it
+    lies by one handle of the decoder, the predictions (``d_pred``) become rows of ``num_observables`` columns
+    (``tsim_pred_rows_device``, mode 1) and those go to a ``shotdata.ShotWriter`` of ``predictions_format`` (``dets``: the
+    observables section, ``L``): rows never cross PCIe except as file bytes.  ``hp``: the :class:`tsim_amd.backend.HipProgram`
+    whose device and stream do the work (default: a small one built here and closed again).  The handle, the buffers and the
+    reader's staging are released on every path; on an error the writer is aborted and the predictions file is not valid.
+
+    Out of scope: ``sample()`` / ``sample_write()`` / ``convert_file()`` with a decoder, post-selection (every row is kept) and
+    the soft outputs of a ``UnionFindDecoder.with_soft_output`` (only predictions are written)."""
+    from . import shotdata
+
+    nd, n_obs = int(decoder.num_detectors), int(decoder.num_observables)
+    shotdata.check_format(detection_events_format)
+    shotdata.check_format(predictions_format)
+    if nd < 1 or n_obs < 1:
+        raise ValueError(f"decode_file needs at least one detector and one observable, the decoder has {nd} and {n_obs}")
+    n_cols = nd + (n_obs if observables_appended else 0)
+    in_rb = ((n_cols + 7) // 8 + 7) // 8 * 8   # whole uint64 words per row: the kernels read them 8 bytes at a time
+    out_rb = (n_obs + 7) // 8                   # packed, as ptb64 wants its rows
+    own = hp is None
+    if own:
+        from . import synth
+        from .backend import HipProgram
+
+        hp = HipProgram(synth.kat_h_m())
+    writer = handle = pieces = None
+    bufs = []
+    try:
+        writer = shotdata.ShotWriter(predictions_filepath, predictions_format, n_obs, (0, 0, n_obs), device=hp.device)
+        handle = decoder._handle(hp, n_cols)
+        cnt = np.zeros(3, np.uint64)
+        d_cnt = hp.malloc(cnt.nbytes + 16)
+        bufs.append(d_cnt)
+        hp.h2d(d_cnt, cnt)
+        stream, room, shots = hp.stream_ptr(), 0, 0
+        pieces = shotdata.iter_device_rows(detection_events_filepath, detection_events_format, n_cols, (0, nd, n_cols - nd),
+                                           device=hp.device, row_bytes=in_rb)
+        for d_rows, n, rb in pieces:
+            if n > room:  # (nothing is in flight: every piece ends with the stream drained)
+                for b in bufs[1:]:
+                    b.free()
+                del bufs[1:]
+                room = 0
+                bufs.append(hp.malloc(8 * n + 16))
+                bufs.append(hp.malloc(n * out_rb + 16))
+                room = n
+            d_pred, d_out = bufs[1].ptr, bufs[2].ptr
+            handle[1](handle[0], d_rows, n, rb, (nd, n_cols), d_cnt.ptr, d_pred=d_pred, stream=stream)
+            hp.pred_rows_device(d_pred, n, n_obs, d_out, out_rb, 0, "write", stream=stream)
+            writer.write_device(d_out, n, out_rb, stream)
+            hp.stream_synchronize(stream)  # the reader's next piece overwrites the rows, the next predictions d_out
+            shots += n
+        hp.d2h(cnt, d_cnt)
+    except BaseException:
+        if writer is not None:
+            writer.abort()
+        raise
+    else:
+        writer.close()
+    finally:
+        if pieces is not None:
+            pieces.close()  # (gives the reader's staging slots back when the loop was left early)
+        if handle is not None:
+            handle[2](handle[0])
+        for b in bufs:
+            b.free()
+        if own:
+            hp.close()
+    return DecodeFileResult(shots, int(cnt[0]), int(cnt[1]) if observables_appended else None, int(cnt[2]))
 
 
 class LookupDecoder:
@@ -272,6 +369,19 @@ class LookupDecoder:
     def missed(self, dets) -> np.ndarray:
         """bool ``[n]``: the rows whose syndrome is not in the table."""
         return self._lookup(dets) < 0
+
+    def _handle(self, hp, n_cols: int):
+        """``(handle, what decodes rows by it, what destroys it)``: a row table over the detectors, loaded with :meth:`table`."""
+        keys, values = self.table()
+        h = hp.rowtab_create(n_cols, range(self.num_detectors), max(64, 4 * len(values)))
+        try:
+            hp.rowtab_load(h, keys, values)
+        except BaseException:
+            hp.rowtab_destroy(h)
+            raise
+        return h, hp.rowtab_decode_device, hp.rowtab_destroy
+
+    decode_file = decode_file
 
 
 class DecodingGraph:
@@ -601,6 +711,8 @@ class _RowDecoder:
             destroy(h)
             for b in bufs:
                 b.free()
+
+    decode_file = decode_file
 
 
 class UnionFindDecoder(_RowDecoder):

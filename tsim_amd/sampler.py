@@ -1029,7 +1029,8 @@ class _CompiledSamplerBase:
     # -- counts instead of rows (counts.py) ----------------------------------------------------------------------------
     def _count(self, shots: int, batch_size: int | None, *, mask: np.ndarray | None = None, xor_det: bool = False,
                xor_obs: bool = False, histogram_columns=None, pair_columns=None, pattern_columns=None,
-               pattern_capacity=counts_mod.DEFAULT_PATTERN_CAPACITY, decoder=None, sample_kw: dict | None = None) -> ShotCounts:
+               pattern_capacity=counts_mod.DEFAULT_PATTERN_CAPACITY, decoder=None, corrected: bool = False,
+               sample_kw: dict | None = None) -> ShotCounts:
         """The tally of what ``sample()`` with the same arguments returns (rows: detectors, then observables), computed
         where the rows are.  Every batch, key and noise key ``sample()`` would use is used in the same order; only the
         download is replaced.  ``mask``: the caller's post-selection mask (validated).  Warns (``RuntimeWarning``) when
@@ -1038,6 +1039,8 @@ class _CompiledSamplerBase:
         patterns = counts_mod.check_pattern_columns(pattern_columns, n_out, nd)
         capacity = counts_mod.check_pattern_capacity(pattern_capacity) or counts_mod.DEFAULT_PATTERN_CAPACITY
         extra = dict(pattern_columns=patterns, pattern_capacity=capacity, decoder=counts_mod.check_decoder(decoder, n_out, nd))
+        if counts_mod.check_corrected(corrected, decoder):  # (absent otherwise: the default builds what it built before)
+            extra["corrected"] = True
         out = self._count_rows(shots, batch_size, mask, xor_det, xor_obs, histogram_columns, pair_columns, extra, sample_kw)
         return counts_mod.warn_pattern_overflow(out, capacity)
 
@@ -1233,7 +1236,7 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
     def count(self, shots: int, *, batch_size: int | None = None, postselection_mask: np.ndarray | None = None,
               use_detector_reference_sample: bool = False, use_observable_reference_sample: bool = False,
               histogram_columns=None, pair_columns=None, pattern_columns=None,
-              pattern_capacity: int = counts_mod.DEFAULT_PATTERN_CAPACITY, decoder=None) -> ShotCounts:
+              pattern_capacity: int = counts_mod.DEFAULT_PATTERN_CAPACITY, decoder=None, corrected: bool = False) -> ShotCounts:
         """Counts over the rows ``sample()`` returns for the same arguments, reduced on the GPU - only the counters cross
         PCIe (:mod:`tsim_amd.counts`).  A shot is kept iff none of its detectors in ``postselection_mask`` is set (the
         reference's advice: sample, then drop the rows with a masked detector); ``column_counts`` (detectors, then
@@ -1257,7 +1260,11 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
         ``decoder_misses``: kept shots for which it has no prediction (an unknown syndrome; a cluster that cannot reach the
         boundary) and predicts no flip.  A ``UnionFindDecoder.with_soft_output(metric, bins)`` also fills ``soft_kept`` /
         ``soft_errors``: the kept shots and the decoded errors per bin of the decoder's confidence in the shot
-        (``ShotCounts.rejection_curve()``).  For a fresh sampler with the same seed and arguments this
+        (``ShotCounts.rejection_curve()``).  ``corrected=True`` (needs a decoder) XORs every kept shot's prediction into its
+        observable columns where the row lies (``tsim_pred_rows_device``) before anything else reads it: ``observable_counts``
+        are then the per-observable logical errors after decoding, ``histogram`` / ``pair_counts`` / ``patterns`` the joint law of
+        the residual flips, ``kept_with_observable_flip == decoded_errors``, and the decoder's own counts are unchanged.
+        For a fresh sampler with the same seed and arguments this
         equals ``counts.tally_rows(sample(..., append_observables=True), ...)``, and the sampler's keys stand where that
         ``sample()`` would leave them."""
         nd = self._num_detectors
@@ -1270,7 +1277,8 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
                   use_observable_reference_sample=use_observable_reference_sample)
         return self._count(shots, batch_size, mask=mask, xor_det=use_detector_reference_sample,
                            xor_obs=use_observable_reference_sample, histogram_columns=histogram_columns, pair_columns=pair_columns,
-                           pattern_columns=pattern_columns, pattern_capacity=pattern_capacity, decoder=decoder, sample_kw=kw)
+                           pattern_columns=pattern_columns, pattern_capacity=pattern_capacity, decoder=decoder, corrected=corrected,
+                           sample_kw=kw)
 
     def _sample_rows_for_count(self, shots: int, batch_size: int | None, sample_kw: dict) -> np.ndarray:
         return self.sample(shots, batch_size=batch_size, append_observables=True, **sample_kw)
