@@ -6,10 +6,14 @@ in ``image_hashes.json``; ``tests/test_packer_image.py`` compares.  A change of 
 a rewrite of the packer's algebra (round 6: GF(2) forms at word level, term-table power tables, chunk values by increments) is not:
 the hashes must not move.
 
-    python tests/golden/gen_image_hashes.py            # rewrite the golden file
+The same run prints one ``finalize: plan`` line per program - the routing flags, table depths and offsets the host stages decide
+beside the image - recorded in ``finalize_plans.json`` and compared by the same test file.
+
+    python tests/golden/gen_image_hashes.py            # rewrite the golden files
 """
 from __future__ import annotations
 
+import functools
 import json
 import os
 import re
@@ -18,6 +22,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "image_hashes.json")
+OUT_PLANS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "finalize_plans.json")
 
 CHILD = r"""
 import os, sys
@@ -47,17 +52,29 @@ for name, prog in progs:
 """
 
 
-def collect() -> dict:
+# every variable tsim_program_finalize reads (TSIM_AMD_DEBUG is set below)
+FINALIZE_ENV = ("TSIM_AMD_TUNE", "TSIM_AMD_MODE", "TSIM_AMD_KERNEL", "TSIM_AMD_PATTERN_TABLES", "TSIM_AMD_PATTERN_TABLE_MB",
+                "TSIM_AMD_DEEP_TABLES", "TSIM_AMD_ADAPTIVE", "TSIM_AMD_FUSED_STEPS")
+
+
+@functools.lru_cache(maxsize=None)
+def collect_all() -> tuple:
+    """(image hashes, plan lines) of one child run: {"<program> <mode>": ...} each."""
     env = dict(os.environ, TSIM_AMD_DEBUG="finalize,imghash")
-    env.pop("TSIM_AMD_TUNE", None)
-    env.pop("TSIM_AMD_MODE", None)
+    for k in FINALIZE_ENV:
+        env.pop(k, None)
     r = subprocess.run([sys.executable, "-c", CHILD % (ROOT, ROOT)], env=env, capture_output=True, text=True, timeout=1200)
     res: dict = {}
+    plans: dict = {}
     cur = None
     for line in r.stderr.splitlines():
         if line.startswith("## "):
             cur = line[3:].strip()
             res[cur] = {}
+            continue
+        if line.startswith("[tsim] finalize: plan ") and cur is not None:
+            # every scalar the host stages decide (routing flags, depths, offsets): host arithmetic only, nothing asked of a device
+            plans[cur] = line[len("[tsim] finalize: plan "):].strip()
             continue
         m = re.match(r"\[tsim\] finalize: (\S.*?) [0-9.]+ ms \(image (\d+) words, hash ([0-9a-f]+)\)", line)
         if m and cur is not None and not m.group(1).startswith(" "):
@@ -65,7 +82,15 @@ def collect() -> dict:
             # (the third host phase, the pattern-table plan, may follow the device's free memory: not pinned)
             if m.group(1) in ("rows / fast formulation packed", "chunk / column tables"):
                 res[cur].setdefault(m.group(1), [int(m.group(2)), m.group(3)])
-    return res
+    return res, plans
+
+
+def collect() -> dict:
+    return collect_all()[0]
+
+
+def collect_plans() -> dict:
+    return collect_all()[1]
 
 
 if __name__ == "__main__":
@@ -73,3 +98,6 @@ if __name__ == "__main__":
     with open(OUT, "w") as f:
         json.dump(h, f, indent=0, sort_keys=True)
     print(f"{len(h)} programs x phases -> {OUT}")
+    with open(OUT_PLANS, "w") as f:
+        json.dump(collect_plans(), f, indent=0, sort_keys=True)
+    print(f"{len(collect_plans())} plan lines -> {OUT_PLANS}")

@@ -1,6 +1,7 @@
 // tsim_internal.hip.h - host-side state shared by the translation units of libtsim_hip.so.
 //
-//   tsim_program.hip   handle life cycle: description -> packed image -> upload; memory/stream plumbing
+//   tsim_program.hip   handle life cycle: create, add, info, destroy; memory/stream plumbing
+//   tsim_finalize.hip  tsim_program_finalize as stages: description -> packed image -> upload (host only)
 //   tsim_pack.hip      the packer: reference-layout rows -> bit-packed rows, pack-time GF(2) algebra,
 //                      chunk tables (host only)
 //   tsim_sample.hip    launch planner + pipeline scheduler + the sampling kernels (k_sample_lw, k_sample4,
