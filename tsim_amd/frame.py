@@ -564,8 +564,7 @@ class _FrameSampler:
         self._num_detectors = int(form.num_detectors)
         self._direct = None
         self._direct_detector_mask = np.zeros(self._num_detectors, dtype=np.bool_)
-        self._device_noise = self._f_slots = self._f_ring = self._stage = None
-        self._bufs = {}
+        self._init_route_state()
         self._frame = None
         self._carrier = None
 

@@ -16,9 +16,13 @@ The orchestration is organised differently: a sampler is built from an already c
 noise model (``channel_probs``, ``error_transform``; e.g. ``from_npz``), and there are two *routes*:
 
 * the **device route** (the product): error rows are generated packed, every batch runs through the
-  pipelined C-ABI launches into ONE device-resident result buffer, post-selection is the direct-detector
-  filter kernel plus row gather/scatter by survivor index, and the request is downloaded once, in the layout
-  the caller asked for (bools, or bit-packed bytes compacted on the GPU);
+  pipelined C-ABI launches into ONE device-resident result buffer, and every finished batch (host noise) or
+  group of batches (device noise) leaves on a copy stream while the next ones are sampled - to the host in the
+  layout the caller asked for (bools, bit-packed bytes written by the kernels or compacted on the GPU, column
+  blocks arranged there), or into a sink that reads the rows where they are (``count()``, ``sample_write()``):
+  :class:`_RowDelivery`.  Post-selection under host noise is the direct-detector filter kernel plus row
+  gather/scatter by survivor index, with one download at the end; under device noise every row is sampled and
+  the discarded ones are blanked on their way out;
 * the **seam route**: when ``tsim_amd.sampler.sample_program`` - a module attribute resolved at call time,
   like the reference's - has been replaced (tests spying on or substituting the backend, exactly as the
   reference's own tests do), batches go through that callable on host arrays in the reference layout.
@@ -219,7 +223,6 @@ class _DevicePostselect:
         self.wf, self.wo = max(1, (self.num_f + 63) // 64), (self.n_out + 63) // 64
         self.shots, self.size = shots, size
         self.n_comp = max(1, len(prog.components))
-        self.devs = []
         # the store, the rows, the flags and the unpack scratch are O(shots) on the device: refuse what cannot fit instead
         # of failing half way
         need = shots * (self.wf * 8 + self.wo * 8 + 1 + 4 + self.n_out) + size * (self.wf * 8 + self.wo * 8 + 8)
@@ -241,8 +244,8 @@ class _DevicePostselect:
 
         self.d_store, self.d_rows = m(shots * self.wf * 8), m(shots * self.wo * 8)
         self.d_flags, self.d_list, self.d_count = m(shots), m(size * 4), m(4)
-        self.d_fb, self.d_ob, self.d_idx = m(size * self.wf * 8), m(size * self.wo * 8), m(size * 4)
-        self.d_dev, self.d_mask, self.d_ref = m(4 * self.n_comp), m(self.wo * 8), m(self.wo * 8)
+        self.d_fb, self.d_ob = m(size * self.wf * 8), m(size * self.wo * 8)
+        self.d_mask, self.d_ref = m(self.wo * 8), m(self.wo * 8)
         # the survivor queue (shot ids in shot order, appended chunk by chunk on the device), its tail, scan scratch, and one
         # normalisation-deviation record per dispatched batch (read once, at the end)
         self.max_dispatch = shots // max(1, size) + 2
@@ -261,27 +264,6 @@ class _DevicePostselect:
         full = np.zeros(self.wo * 64, dtype=np.uint8)
         full[: self.nd] = np.asarray(det_bits, dtype=np.uint8)
         return np.packbits(full, bitorder="little").view(np.uint64)
-
-    def admit(self, start: int, n: int) -> np.ndarray:
-        hp = self.hp
-        rows = self.owner._channel_sampler.sample_packed(n)
-        hp.h2d(self.d_store.ptr + start * self.wf * 8, rows)
-        hp.postselect_device(self.d_store.ptr + start * self.wf * 8, n, self.num_f, self.d_mask.ptr,
-                             self.d_ref.ptr if self.has_ref else 0, self.d_rows.ptr + start * self.wo * 8,
-                             self.d_list.ptr, self.d_count.ptr, self.d_flags.ptr + start)
-        gone = np.empty(n, dtype=np.uint8)
-        hp.d2h(gone, self.d_flags.ptr + start)
-        return np.flatnonzero(gone == 0)
-
-    def dispatch(self, shot_ids: np.ndarray, size: int, key) -> None:
-        hp, n = self.hp, len(shot_ids)
-        hp.h2d(self.d_idx, shot_ids.astype(np.uint32))
-        hp.gather_rows_device(self.d_store.ptr, self.wf, self.d_idx.ptr, n, size, self.d_fb.ptr)
-        hp.sample_batch_device(self.d_fb.ptr, size, self.num_f, key, self.d_ob.ptr, d_norm_dev=self.d_dev.ptr)
-        hp.scatter_rows_device(self.d_ob.ptr, self.wo, self.d_idx.ptr, n, self.d_rows.ptr)
-        dev = np.zeros(self.n_comp, dtype=np.float32)
-        hp.d2h(dev, self.d_dev)
-        self.devs.append(dev)
 
     def admit_device(self, start: int, rows: np.ndarray) -> int:
         """A chunk's packed f rows -> store, direct bits + discard flags, survivors appended (in shot order) to the device
@@ -319,13 +301,7 @@ class _DevicePostselect:
         no fancy indexing over an 80 MB bool array, no host packbits."""
         hp, owner = self.hp, self.owner
         row_bytes = self.wo * 8
-
-        def as_row(cols) -> np.ndarray:
-            full = np.zeros(row_bytes * 8, dtype=np.uint8)
-            full[: self.n_out] = np.asarray(cols, dtype=np.uint8)[: self.n_out]
-            return np.packbits(full, bitorder="little")
-
-        masks = np.concatenate([as_row(post[k]) for k in ("test", "test_ref", "keep", "xor_kept", "xor_discarded")])
+        masks = _postselect_mask_rows(post, self.n_out, row_bytes)
         d_masks = hp.malloc(masks.nbytes + 16)
         self._bufs.append(d_masks)
         hp.h2d(d_masks, masks)
@@ -341,35 +317,145 @@ class _DevicePostselect:
             hp.d2h(rows, d_c)
         else:
             rows = owner._download_bools(hp, self.d_rows, self.shots)
-        if self.n_dispatch:
-            devs = np.zeros(self.n_dispatch * self.n_comp, dtype=np.float32)
-            hp.d2h(devs, self.d_devs.ptr)
-            self.devs += [devs[k * self.n_comp:(k + 1) * self.n_comp] for k in range(self.n_dispatch)]
+        self._check_dispatched()
         self.release()
-        for dev in self.devs:
-            owner._check_devs(dev)
         return rows, gone.view(np.bool_)
 
     def tally_device(self, tally) -> None:
         """``count()``: the finished rows go to the tally where they are (its masks drop the discarded rows: their masked
         direct detector fires), then the batches' normalisation deviations are checked as :meth:`collect_device` does."""
         tally(self.d_rows.ptr, self.wo * 8, 0, self.shots)  # (the handle's stream, behind the scatters)
+        self._check_dispatched()
+
+    def _check_dispatched(self) -> None:
+        """The dispatched batches' normalisation deviations: one download (the handle's stream, behind the batches)."""
         if self.n_dispatch:
             devs = np.zeros(self.n_dispatch * self.n_comp, dtype=np.float32)
             self.hp.d2h(devs, self.d_devs.ptr)
-            self.devs += [devs[k * self.n_comp:(k + 1) * self.n_comp] for k in range(self.n_dispatch)]
-        for dev in self.devs:
-            self.owner._check_devs(dev)
+            for k in range(self.n_dispatch):
+                self.owner._check_devs(devs[k * self.n_comp:(k + 1) * self.n_comp])
 
-    def collect(self):
-        rows, gone = self.owner._download_bools(self.hp, self.d_rows, self.shots), np.empty(self.shots, dtype=np.uint8)
-        self.hp.d2h(gone, self.d_flags)
-        self.release()
-        for dev in self.devs:
-            self.owner._check_devs(dev)
-        gone = gone.astype(np.bool_)
-        rows[gone, self.nd:] = False  # a discarded shot keeps its direct DETECTOR columns only
-        return rows, gone
+
+def _postselect_mask_rows(post: dict, n_out: int, row_bytes: int) -> np.ndarray:
+    """The five column masks of ``tsim_postselect_rows_device`` (:meth:`_CompiledSamplerBase._postselect_masks`), packed in the
+    layout of device rows of ``row_bytes`` bytes, one after the other."""
+    def as_row(cols) -> np.ndarray:
+        full = np.zeros(row_bytes * 8, dtype=np.uint8)
+        full[:n_out] = np.asarray(cols, dtype=np.uint8)[:n_out]
+        return np.packbits(full, bitorder="little")
+
+    return np.concatenate([as_row(post[k]) for k in ("test", "test_ref", "keep", "xor_kept", "xor_discarded")])
+
+
+def _reference_flip_columns(nd: int, n_out: int, ref, xor_det: bool, xor_obs: bool):
+    """The detector and the observable column tables of ``tsim_arrange_rows_device`` and the file sink: the column index,
+    bit 31 set where the reference sample's bit is to be XORed in."""
+    det, obs = np.arange(nd, dtype=np.uint32), np.arange(nd, n_out, dtype=np.uint32)
+    if ref is not None and xor_det:
+        det = det | (ref[:nd].astype(np.uint32) << np.uint32(31))
+    if ref is not None and xor_obs:
+        obs = obs | (ref[nd:].astype(np.uint32) << np.uint32(31))
+    return det, obs
+
+
+# ---------------------------------------------------------------------------------------------------------
+# where a finished block of device rows goes
+# ---------------------------------------------------------------------------------------------------------
+
+
+class _RowDelivery:
+    """The way of the two pipelines' rows (:meth:`_device_plain`, :meth:`_device_noise_plain`) out of the device row buffer:
+    into ``sink`` where they are (``count()``, ``sample_write()``), as the column blocks of ``layout`` (``[(columns,
+    packed)]``, arranged on the device), as ``bit_packed`` rows of the ``packed_columns`` leading columns (written by the
+    kernels themselves when those are all columns: ``direct_packed``; compacted on the device otherwise), or as bools.
+    At most one of the three is given.  Results land in recycled pinned memory (``backend.PinnedPool``): truly asynchronous
+    copies, no first-touch page faults.  The pipelines size their row buffer by ``row_bytes`` and hand ``direct_packed`` to
+    the kernels before :meth:`allocate` takes the result and the scratch of ``total`` rows."""
+
+    def __init__(self, hp: HipProgram, sampler, n_out: int, total: int, *, sink=None, layout: list | None = None,
+                 packed_columns: int | None = None):
+        self.hp, self.sampler, self.n_out, self.total = hp, sampler, n_out, total
+        self.sink, self.layout, self.packed_columns = sink, layout, packed_columns
+        self.wo = (n_out + 63) // 64
+        # all columns wanted bit-packed: the kernels write that layout themselves (no padded rows, no compaction pass)
+        self.direct_packed = layout is None and packed_columns is not None and packed_columns == n_out
+        self.row_bytes = (n_out + 7) // 8 if self.direct_packed else self.wo * 8
+        self.blocks = self.out = self.d_stage = None
+
+    def allocate(self) -> None:
+        hp, total = self.hp, self.total
+        if self.sink is not None:
+            return
+        if self.layout is not None:  # column selection / order / flips / packing per output block, on the device
+            self.blocks = [self._block(k, np.ascontiguousarray(cols, dtype=np.uint32), bool(packed))
+                           for k, (cols, packed) in enumerate(self.layout)]
+            return
+        packed = self.packed_columns is not None
+        self.width = (self.packed_columns + 7) // 8 if packed else self.n_out  # bytes per delivered row
+        self.out = result_pool().take((total, self.width))
+        if not self.direct_packed:
+            self.d_stage = (self.sampler._scratch(hp, "compact", total * self.width + 16) if packed
+                            else self.sampler._scratch(hp, "unpacked", total * self.width))
+
+    def _block(self, k: int, cols: np.ndarray, packed: bool) -> dict:
+        """One wanted output block: device column table, device staging and a pinned host array."""
+        n_cols = len(cols)
+        nbytes = (n_cols + 7) // 8 if packed else n_cols
+        blk = {"n_cols": n_cols, "packed": packed, "nbytes": nbytes,
+               "out": result_pool().take((self.total, nbytes)) if nbytes else np.empty((self.total, 0), np.uint8)}
+        if nbytes:
+            blk["d_cols"] = self.sampler._scratch(self.hp, f"cols{k}", n_cols * 4 + 16)
+            self.hp.h2d(blk["d_cols"], cols)
+            blk["d_arr"] = self.sampler._scratch(self.hp, f"arranged{k}", self.total * nbytes + 16)
+        return blk
+
+    def send(self, d_first: int, r0: int, r1: int, stream: int) -> None:
+        """Rows ``r0 .. r1`` of the request, finished and lying at ``d_first``, leave on ``stream`` (which the caller has put
+        behind the batches that wrote them)."""
+        hp, n = self.hp, r1 - r0
+        if self.sink is not None:
+            self.sink(d_first, self.row_bytes, r0, r1, stream)
+        elif self.blocks is not None:
+            for blk in self.blocks:
+                if blk["nbytes"]:
+                    dst = blk["d_arr"].ptr + r0 * blk["nbytes"]
+                    hp.arrange_rows_device(d_first, n, self.wo, blk["d_cols"].ptr, blk["n_cols"], blk["packed"], dst, stream=stream)
+                    hp.d2h_async(blk["out"][r0:r1], dst, stream)
+        elif self.direct_packed:
+            hp.d2h_async(self.out[r0:r1], d_first, stream)
+        else:
+            dst = self.d_stage.ptr + r0 * self.width
+            if self.packed_columns is not None:
+                hp.compact_rows_device(d_first, n, self.packed_columns, dst, in_words=self.wo, stream=stream)
+            else:
+                hp.unpack_bits_device(d_first, n, self.n_out, dst, stream=stream)
+            hp.d2h_async(self.out[r0:r1], dst, stream)
+
+    def result(self, skip: int, shots: int):
+        """Rows ``skip .. skip + shots`` as the caller gets them, once the stream of :meth:`send` has drained: bytes where
+        they are bit-packed, bools elsewhere; a list of blocks for a ``layout``; ``None`` for a sink."""
+        if self.sink is not None:
+            return None
+        if self.blocks is not None:
+            return [(b["out"][skip:skip + shots] if b["packed"] else b["out"][skip:skip + shots].view(np.bool_)) for b in self.blocks]
+        res = self.out[skip:skip + shots]
+        return res if self.packed_columns is not None else res.view(np.bool_)
+
+    def first_row_bools(self, d_first: int):
+        """Row 0 (the riding reference row, lying at ``d_first``) as booleans whatever the layout of the rows.  ``None``
+        where nobody reads it: a sink, and arranged blocks (their caller computed the row beforehand, see ``sample()``)."""
+        if self.sink is not None or self.blocks is not None:
+            return None
+        if self.packed_columns is None:
+            return self.out[0].view(np.bool_).copy()
+        hp, n_out = self.hp, self.n_out
+        one = np.zeros((1, n_out), dtype=np.uint8)  # one more tiny download
+        d_one = self.sampler._scratch(hp, "ref_row", n_out)
+        if self.direct_packed:  # the kernels wrote bit_packed rows: unpack row 0 on the host
+            return np.unpackbits(self.out[0], bitorder="little")[:n_out].astype(np.bool_)
+        hp.unpack_bits_device(d_first, 1, n_out, d_one.ptr)
+        hp.d2h(one, d_one.ptr)
+        return one[0].view(np.bool_).copy()
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -401,11 +487,12 @@ class _CompiledSamplerBase:
         self._num_detectors = int(self._program.num_detectors)
         self._direct = _DirectOutputs(self._program)
         self._direct_detector_mask = self._direct.detector_mask
+        self._init_route_state()
+
+    def _init_route_state(self) -> None:
         self._device_noise = None
-        self._f_slots = None
-        self._f_ring = None
-        self._stage = None      # host staging array of one batch of packed f rows
-        self._bufs: dict = {}  # name -> (HipProgram, DeviceBuffer): grow-only scratch of the device route
+        self._stage = None      # host staging arrays of one batch of packed f rows each
+        self._bufs: dict = {}  # name -> (HipProgram, [DeviceBuffer]): grow-only device buffers of the device route
 
     @classmethod
     def from_npz(cls, path, *, seed: int | None = None, device: int = 0, **kw):
@@ -460,6 +547,19 @@ class _CompiledSamplerBase:
         quiet = np.zeros((1, self._channel_sampler.num_f), dtype=np.uint8)
         rows = self._seam(quiet, self._next_key()) if self._program.components else self._direct.fill(quiet)
         return np.asarray(rows[0], dtype=np.bool_)
+
+    def _reference_row(self, want_ref: bool, direct_mask: bool = False):
+        """``(reference bits or None, rides)`` for a request on the device route.  Host noise over compiled components: the
+        quiet row rides as row 0 of the first batch (sampler.py:395-404) - its bits are computed here first, same row, same
+        subkey (peeked: the batch itself draws it), same in-batch index, so that they are known before the rows are
+        arranged.  Device noise, no components, or direct post-selection (``direct_mask``: the survivors' batches have no
+        row to spare): a sample of its own, which draws a key iff something is compiled."""
+        if not want_ref:
+            return None, False
+        if not self._program.components or self._noise == "device" or direct_mask:
+            return self._compute_reference_sample(), False
+        quiet = np.zeros((1, self._channel_sampler.num_f), dtype=np.uint8)
+        return np.asarray(self._seam(quiet, prng.split(self._key)[1])[0], dtype=np.bool_), True
 
     def _compute_direct_outputs(self, f_params_np: np.ndarray) -> np.ndarray:
         return self._direct.fill(np.asarray(f_params_np))
@@ -570,39 +670,26 @@ class _CompiledSamplerBase:
             self._device_noise = DeviceNoiseSampler(hp, self._channel_sampler)
         return self._device_noise
 
-    def _lane_buffers(self, hp: HipProgram, nbytes: int) -> list:
-        have = self._f_slots
-        if have is None or have[0] is not hp or have[1] < nbytes:
-            if have is not None and have[0] is hp:
-                hp.synchronize()
-                for buf in have[2]:
-                    buf.free()
-            self._f_slots = have = (hp, nbytes, [hp.malloc(nbytes) for _ in range(_LANES)])
-        return have[2]
-
-    def _scratch(self, hp: HipProgram, name: str, nbytes: int):
+    def _scratch(self, hp: HipProgram, name: str, nbytes: int, count: int = 0):
         """A device buffer of at least ``nbytes`` kept between calls (allocation and free cost more than the
-        kernels of a small request); grown when too small, dropped by :meth:`release`."""
+        kernels of a small request); grown when too small, dropped by :meth:`release`.  ``count``: a ring of that many
+        buffers, as a list - launches in flight may still read a ring, so the device is drained before one is freed."""
         have = self._bufs.get(name)
-        if have is None or have[0] is not hp or have[1].nbytes < nbytes:
+        if have is None or have[0] is not hp or have[1][0].nbytes < nbytes:
             if have is not None and have[0] is hp:
-                have[1].free()
-            have = self._bufs[name] = (hp, hp.malloc(max(1, nbytes)))
-        return have[1]
+                if count:
+                    hp.synchronize()
+                for buf in have[1]:
+                    buf.free()
+            have = self._bufs[name] = (hp, [hp.malloc(max(1, nbytes)) for _ in range(count or 1)])
+        return have[1] if count else have[1][0]
 
     def release(self) -> None:
         """Give the cached device buffers back (they are otherwise freed with the program's handle)."""
-        for _hp, buf in self._bufs.values():
-            buf.free()
+        for _hp, bufs in self._bufs.values():
+            for buf in bufs:
+                buf.free()
         self._bufs.clear()
-        if self._f_ring is not None:
-            for buf in self._f_ring[2]:
-                buf.free()
-            self._f_ring = None
-        if self._f_slots is not None:
-            for buf in self._f_slots[2]:
-                buf.free()
-            self._f_slots = None
 
     def _download_bools(self, hp: HipProgram, d_rows, n: int) -> np.ndarray:
         """Packed device rows -> ``bool[n, num_outputs]`` on the host (unpack kernel + one D2H into a pageable
@@ -613,35 +700,6 @@ class _CompiledSamplerBase:
         host = np.empty((n, n_out), dtype=np.uint8)
         hp.d2h(host, d_u8.ptr)
         return host.view(np.bool_)
-
-    # -- output arrangement on the device (sample()'s epilogue, sampler.py:850-868) -------------------------------------
-    def _layout_blocks(self, hp: HipProgram, layout: list, total: int) -> list:
-        """Per wanted output block: device column table, device staging and a pinned host array."""
-        pool = result_pool()
-        blocks = []
-        for k, (cols, packed) in enumerate(layout):
-            cols = np.ascontiguousarray(cols, dtype=np.uint32)
-            n_cols = len(cols)
-            nbytes = (n_cols + 7) // 8 if packed else n_cols
-            blk = {"n_cols": n_cols, "packed": bool(packed), "nbytes": nbytes, "out": pool.take((total, nbytes)) if nbytes else np.empty((total, 0), np.uint8)}
-            if nbytes:
-                blk["d_cols"] = self._scratch(hp, f"cols{k}", n_cols * 4 + 16)
-                hp.h2d(blk["d_cols"], cols)
-                blk["d_arr"] = self._scratch(hp, f"arranged{k}", total * nbytes + 16)
-            blocks.append(blk)
-        return blocks
-
-    def _layout_download(self, hp: HipProgram, blocks: list, d_rows_ptr: int, wo: int, r0: int, r1: int, stream: int) -> None:
-        for blk in blocks:
-            if not blk["nbytes"]:
-                continue
-            dst = blk["d_arr"].ptr + r0 * blk["nbytes"]
-            hp.arrange_rows_device(d_rows_ptr, r1 - r0, wo, blk["d_cols"].ptr, blk["n_cols"], blk["packed"], dst, stream=stream)
-            hp.d2h_async(blk["out"][r0:r1], dst, stream)
-
-    @staticmethod
-    def _layout_result(blocks: list, lo: int, hi: int) -> list:
-        return [(b["out"][lo:hi] if b["packed"] else b["out"][lo:hi].view(np.bool_)) for b in blocks]
 
     def _device_noise_plain(self, shots: int, batch_size: int | None, want_ref: bool, packed_columns: int | None = None,
                             post: dict | None = None, layout: list | None = None, sink=None):
@@ -664,49 +722,20 @@ class _CompiledSamplerBase:
         ref = self._compute_reference_sample() if want_ref else None
         cs = self._channel_sampler
         num_f, n_out = cs.num_f, int(self._program.num_outputs)
-        wf, wo = max(1, (num_f + 63) // 64), (n_out + 63) // 64
+        wf = max(1, (num_f + 63) // 64)
         n_comp = max(1, len(self._program.components))
         total, size = plan.size * plan.count, plan.size
         nslot = HipProgram.PIPELINE_SLOTS
-        ring = self._f_ring
-        if ring is None or ring[0] is not hp or ring[1] < size * wf * 8:
-            if ring is not None and ring[0] is hp:
-                hp.synchronize()
-                for buf in ring[2]:
-                    buf.free()
-            self._f_ring = ring = (hp, size * wf * 8, [hp.malloc(size * wf * 8) for _ in range(nslot)])
-        f_ring = ring[2]
-        direct_packed = layout is None and packed_columns is not None and packed_columns == n_out
-        row_bytes = (n_out + 7) // 8 if direct_packed else wo * 8
+        f_ring = self._scratch(hp, "f_ring", size * wf * 8, count=nslot)
+        dl = _RowDelivery(hp, self, n_out, total, sink=sink, layout=layout, packed_columns=packed_columns)
+        row_bytes = dl.row_bytes
         d_rows, d_devs = self._scratch(hp, "rows", total * row_bytes + 16), self._scratch(hp, "devs", plan.count * n_comp * 4)
         noise = self._device_noise_sampler(hp)
         s_copy = hp.aux_stream(1)
-        # results land in recycled pinned memory (backend.PinnedPool): truly asynchronous copies, no first-touch page faults
-        pool = result_pool()
-        blocks = None
-        if sink is not None:
-            out = None
-        elif layout is not None:  # column selection / order / flips / packing per output block, on the device
-            blocks = self._layout_blocks(hp, layout, total)
-            out = None
-        elif direct_packed:
-            out = pool.take((total, row_bytes))
-        elif packed_columns is not None:
-            rb = (packed_columns + 7) // 8
-            out = pool.take((total, rb))
-            d_c = self._scratch(hp, "compact", total * rb + 16)
-        else:
-            out = pool.take((total, n_out))
-            d_u8 = self._scratch(hp, "unpacked", total * n_out)
+        dl.allocate()
         d_masks = d_gone = None
-        if post is not None:
-            # post-selection after sampling (tsim_postselect_rows_device): five column masks in the layout of the device rows
-            def as_row(cols) -> np.ndarray:
-                full = np.zeros(row_bytes * 8, dtype=np.uint8)
-                full[:n_out] = np.asarray(cols, dtype=np.uint8)[:n_out]
-                return np.packbits(full, bitorder="little")
-
-            masks = np.concatenate([as_row(post[k]) for k in ("test", "test_ref", "keep", "xor_kept", "xor_discarded")])
+        if post is not None:  # post-selection after sampling (tsim_postselect_rows_device)
+            masks = _postselect_mask_rows(post, n_out, row_bytes)
             d_masks, d_gone = self._scratch(hp, "ps_masks", masks.nbytes + 16), self._scratch(hp, "ps_gone", total + 16)
             hp.h2d(d_masks, masks)
         key_state = (C.c_uint32 * 2)(self._key[0] & 0xFFFFFFFF, self._key[1] & 0xFFFFFFFF)
@@ -726,18 +755,7 @@ class _CompiledSamplerBase:
             r0, r1 = lo * size, (lo + n) * size
             if post is not None:  # blank the discarded rows where they are, before any layout conversion
                 hp.postselect_rows_device(d_rows.ptr + r0 * row_bytes, r1 - r0, row_bytes, d_masks.ptr, d_gone.ptr + r0, stream=s_copy)
-            if sink is not None:
-                sink(d_rows.ptr + r0 * row_bytes, row_bytes, r0, r1, s_copy)
-            elif blocks is not None:
-                self._layout_download(hp, blocks, d_rows.ptr + r0 * row_bytes, wo, r0, r1, s_copy)
-            elif direct_packed:
-                hp.d2h_async(out[r0:r1], d_rows.ptr + r0 * row_bytes, s_copy)
-            elif packed_columns is not None:
-                hp.compact_rows_device(d_rows.ptr + r0 * row_bytes, r1 - r0, packed_columns, d_c.ptr + r0 * rb, in_words=wo, stream=s_copy)
-                hp.d2h_async(out[r0:r1], d_c.ptr + r0 * rb, s_copy)
-            else:
-                hp.unpack_bits_device(d_rows.ptr + r0 * row_bytes, r1 - r0, n_out, d_u8.ptr + r0 * n_out, stream=s_copy)
-                hp.d2h_async(out[r0:r1], d_u8.ptr + r0 * n_out, s_copy)
+            dl.send(d_rows.ptr + r0 * row_bytes, r0, r1, s_copy)
 
         noise_key_state = (C.c_uint32 * 2)(self._noise_key[0] & 0xFFFFFFFF, self._noise_key[1] & 0xFFFFFFFF)
         for n in sizes:
@@ -749,7 +767,7 @@ class _CompiledSamplerBase:
             # rows (the distillation shapes) draw the noise inside their first pass: one kernel per group instead of n + 1.
             hp.sample_steps_noise_device(noise, [f_ring[sl].ptr for sl in slots], size, num_f, key_state, noise_key_state,
                                          [d_rows.ptr + (b0 + i) * size * row_bytes for i in range(n)],
-                                         out_bit_packed=direct_packed, d_norm_dev=[d_devs.ptr + (b0 + i) * n_comp * 4 for i in range(n)])
+                                         out_bit_packed=dl.direct_packed, d_norm_dev=[d_devs.ptr + (b0 + i) * n_comp * 4 for i in range(n)])
             groups.append((b0, n, slots))
             b0 += n
             if len(groups) >= 2:  # the previous group's rows leave while this group is sampled (pinned target: the call returns at once)
@@ -767,13 +785,7 @@ class _CompiledSamplerBase:
         hp.d2h(devs, d_devs.ptr)
         for b in range(plan.count):
             self._check_devs(devs[b * n_comp:(b + 1) * n_comp])
-        if sink is not None:
-            return None, ref
-        if blocks is not None:
-            res = self._layout_result(blocks, 0, shots)
-        else:
-            res = out[:shots]
-            res = res if (direct_packed or packed_columns is not None) else res.view(np.bool_)
+        res = dl.result(0, shots)
         if post is not None:
             gone = np.empty(total, dtype=np.uint8)
             hp.d2h(gone, d_gone.ptr)
@@ -800,34 +812,17 @@ class _CompiledSamplerBase:
         hp = self._hip()
         rides = want_ref
         plan = plan_batches(shots, batch_size, self._estimate_batch_size(), reserve_row=rides)
-        ref = None
         cs = self._channel_sampler
         num_f, n_out = cs.num_f, int(self._program.num_outputs)
-        wf, wo = max(1, (num_f + 63) // 64), (n_out + 63) // 64
+        wf = max(1, (num_f + 63) // 64)
         n_comp = max(1, len(self._program.components))
         total, size = plan.size * plan.count, plan.size
-        lanes = self._lane_buffers(hp, size * wf * 8)
-        # all columns wanted bit-packed: the kernels write that layout themselves (no padded rows, no compaction pass)
-        direct_packed = layout is None and packed_columns is not None and packed_columns == n_out
-        row_bytes = (n_out + 7) // 8 if direct_packed else wo * 8
+        lanes = self._scratch(hp, "f_lanes", size * wf * 8, count=_LANES)
+        dl = _RowDelivery(hp, self, n_out, total, sink=sink, layout=layout, packed_columns=packed_columns)
+        row_bytes = dl.row_bytes
         d_rows, d_devs = self._scratch(hp, "rows", total * row_bytes + 16), self._scratch(hp, "devs", plan.count * n_comp * 4)
         s_up, s_copy = hp.aux_stream(0), hp.aux_stream(1)
-        pool = result_pool()
-        blocks = None
-        if sink is not None:
-            out = None
-        elif layout is not None:
-            blocks = self._layout_blocks(hp, layout, total)
-            out = None
-        elif direct_packed:
-            out = pool.take((total, row_bytes))
-        elif packed_columns is not None:
-            rb = (packed_columns + 7) // 8
-            out = pool.take((total, rb))
-            d_c = self._scratch(hp, "compact", total * rb + 16)
-        else:
-            out = pool.take((total, n_out))
-            d_u8 = self._scratch(hp, "unpacked", total * n_out)
+        dl.allocate()
         # staging ring: three pinned buffers (one being filled, one being uploaded, one spare)
         n_stage = min(3, plan.count)
         if self._stage is None or self._stage[0].shape != (size, wf) or len(self._stage) < n_stage:
@@ -854,18 +849,7 @@ class _CompiledSamplerBase:
         def download(b: int) -> None:
             hp.sample_batch_device_end(b % _LANES, s_copy)  # the copy stream waits for exactly this batch
             r0, r1 = b * size, (b + 1) * size
-            if sink is not None:
-                sink(d_rows.ptr + r0 * row_bytes, row_bytes, r0, r1, s_copy)
-            elif blocks is not None:
-                self._layout_download(hp, blocks, d_rows.ptr + r0 * row_bytes, wo, r0, r1, s_copy)
-            elif direct_packed:
-                hp.d2h_async(out[r0:r1], d_rows.ptr + r0 * row_bytes, s_copy)
-            elif packed_columns is not None:
-                hp.compact_rows_device(d_rows.ptr + r0 * row_bytes, size, packed_columns, d_c.ptr + r0 * rb, in_words=wo, stream=s_copy)
-                hp.d2h_async(out[r0:r1], d_c.ptr + r0 * rb, s_copy)
-            else:
-                hp.unpack_bits_device(d_rows.ptr + r0 * row_bytes, size, n_out, d_u8.ptr + r0 * n_out, stream=s_copy)
-                hp.d2h_async(out[r0:r1], d_u8.ptr + r0 * n_out, s_copy)
+            dl.send(d_rows.ptr + r0 * row_bytes, r0, r1, s_copy)
 
         try:
             for b in range(plan.count):
@@ -883,7 +867,7 @@ class _CompiledSamplerBase:
                 hp.pipeline_wait_stream(s_up)  # every lane is behind the upload
                 hp.sample_batch_device_begin(lane, lanes[lane].ptr, size, num_f, self._next_key(),
                                              d_rows.ptr + b * size * row_bytes, d_norm_dev=d_devs.ptr + b * n_comp * 4,
-                                             inputs_ready=True, out_bit_packed=direct_packed)
+                                             inputs_ready=True, out_bit_packed=dl.direct_packed)
                 if b > 0:
                     download(b - 1)
                 hp.stream_synchronize(s_up)  # (0.15 ms per 8 MB) the staging buffer may be refilled
@@ -903,31 +887,11 @@ class _CompiledSamplerBase:
         hp.stream_synchronize(s_copy)  # behind every batch: the devs below are final
         devs = np.zeros(plan.count * n_comp, dtype=np.float32)
         hp.d2h(devs, d_devs.ptr)
-        if sink is not None:
-            for b in range(plan.count):
-                self._check_devs(devs[b * n_comp:(b + 1) * n_comp])
-            return None, None
-        skip = 1 if rides else 0
-        if rides:
-            if blocks is not None:  # (arranged output: the caller computed the reference row beforehand, see sample())
-                ref = None
-            elif packed_columns is None:
-                ref = out[0].view(np.bool_).copy()
-            else:  # the reference row is wanted as booleans whatever the layout of the rows: one more tiny download
-                one = np.zeros((1, n_out), dtype=np.uint8)
-                d_one = self._scratch(hp, "ref_row", n_out)
-                if direct_packed:  # the kernels wrote bit_packed rows: unpack row 0 on the host
-                    ref = np.unpackbits(out[0], bitorder="little")[:n_out].astype(np.bool_)
-                else:
-                    hp.unpack_bits_device(d_rows.ptr, 1, n_out, d_one.ptr)
-                    hp.d2h(one, d_one.ptr)
-                    ref = one[0].view(np.bool_).copy()
+        # the reference row is wanted as booleans whatever the layout of the rows
+        ref = dl.first_row_bools(d_rows.ptr) if rides else None
         for b in range(plan.count):
             self._check_devs(devs[b * n_comp:(b + 1) * n_comp])
-        if blocks is not None:
-            return self._layout_result(blocks, skip, skip + shots), ref
-        res = out[skip:skip + shots]
-        return (res if packed_columns is not None else res.view(np.bool_)), ref
+        return dl.result(1 if rides else 0, shots), ref
 
     # -- post-selection -----------------------------------------------------------------------------------------
     def _sample_batches_with_postselection(self, shots: int, batch_size: int | None, *, postselection_mask: np.ndarray,
@@ -954,29 +918,22 @@ class _CompiledSamplerBase:
         size = plan_batches(shots, batch_size, self._estimate_batch_size()).size
         ref = self._compute_reference_sample() if compute_reference else None
         ref_det = ref[:nd] if (ref is not None and xor_detector_ref) else None
-        work = (_SeamPostselect(self, shots, test_mask, ref_det) if self._seam_replaced()
-                else _DevicePostselect(self, shots, size, test_mask, ref_det))
-        on_device = isinstance(work, _DevicePostselect)
-        try:
-            if on_device:
-                _run_postselected_device(shots, size, work, self._next_key, self._channel_sampler.sample_packed)
-            else:
-                _run_postselected(shots, size, work, self._next_key)
-            if on_device:
-                direct = self._direct_detector_mask
-                post = self._postselect_masks(test_mask, ref, ref_det, xor_observable_ref)
-                rows, gone = work.collect_device(post, packed_columns)
-            else:
-                rows, gone = work.collect()
-        finally:
-            if hasattr(work, "release"):
-                work.release()
-        if not on_device:
+        if self._seam_replaced():
+            work = _SeamPostselect(self, shots, test_mask, ref_det)
+            _run_postselected(shots, size, work, self._next_key)
+            rows, gone = work.collect()
             self._apply_detector_reference(rows, gone, ref_det)
             if xor_observable_ref and ref is not None:
                 rows[~gone, nd:] ^= ref[nd:]
             if packed_columns is not None:
                 rows = np.packbits(rows[:, :packed_columns], axis=1, bitorder="little")
+            return rows, ref, gone
+        work = _DevicePostselect(self, shots, size, test_mask, ref_det)
+        try:
+            _run_postselected_device(shots, size, work, self._next_key, self._channel_sampler.sample_packed)
+            rows, gone = work.collect_device(self._postselect_masks(test_mask, ref, ref_det, xor_observable_ref), packed_columns)
+        finally:
+            work.release()
         return rows, ref, gone
 
     def _postselect_masks(self, test_mask, ref, ref_det, xor_observable_ref: bool) -> dict:
@@ -1061,20 +1018,13 @@ class _CompiledSamplerBase:
         hp = self._hip()
         comps = bool(self._program.components)
         direct_mask = mask is not None and comps and bool((mask & self._direct_detector_mask).any())
-        ref = None
-        if want_ref:
-            if not comps or self._noise == "device" or direct_mask:
-                ref = self._compute_reference_sample()  # (draws a key iff something is compiled, as sample() does first)
-            else:  # host noise: the reference row rides as row 0 of the first batch - its bits, computed first (as sample())
-                quiet = np.zeros((1, self._channel_sampler.num_f), dtype=np.uint8)
-                ref = np.asarray(self._seam(quiet, prng.split(self._key)[1])[0], dtype=np.bool_)
+        ref, rides = self._reference_row(want_ref, direct_mask)
         xor = np.zeros(n_out, dtype=np.bool_)
         if ref is not None:
             if xor_det:
                 xor[:nd] = ref[:nd]
             if xor_obs:
                 xor[nd:] = ref[nd:]
-        rides = want_ref and comps and self._noise == "host" and not direct_mask
         skip = 1 if rides else 0
         tally = counts_mod._DeviceTally(hp, n_out, nd, xor_bits=xor, test_bits=mask, histogram_columns=hist, lo=skip, hi=skip + shots,
                                         pair_columns=pairs, **extra)
@@ -1116,19 +1066,8 @@ class _CompiledSamplerBase:
         want_ref = xor_det or xor_obs
         comps = bool(self._program.components)
         on_host = shots == 0 or self._seam_replaced() or n_out == 0
-        ref = None
-        if not on_host and want_ref:
-            if not comps or self._noise == "device":
-                ref = self._compute_reference_sample()
-            else:  # host noise: the reference row rides as row 0 of the first batch - its bits, computed first (as sample())
-                quiet = np.zeros((1, self._channel_sampler.num_f), dtype=np.uint8)
-                ref = np.asarray(self._seam(quiet, prng.split(self._key)[1])[0], dtype=np.bool_)
-        det = np.arange(nd, dtype=np.uint32)
-        obs = np.arange(nd, n_out, dtype=np.uint32)
-        if ref is not None and xor_det:
-            det = det | (ref[:nd].astype(np.uint32) << np.uint32(31))
-        if ref is not None and xor_obs:
-            obs = obs | (ref[nd:].astype(np.uint32) << np.uint32(31))
+        ref, rides = self._reference_row(want_ref and not on_host)
+        det, obs = _reference_flip_columns(nd, n_out, ref, xor_det, xor_obs)
         writers = []
         try:
             for path, fmt, blocks, sec in files:
@@ -1142,7 +1081,6 @@ class _CompiledSamplerBase:
                                    else np.zeros((0, (w.n_bits + 7) // 8), np.uint8))
             else:
                 hp = self._hip()
-                rides = want_ref and comps and self._noise == "host"
                 skip = 1 if rides else 0
                 cols = [np.concatenate([det if b == "det" else obs for b in blocks]) if blocks else np.zeros(0, np.uint32)
                         for _p, _f, blocks, _s in files]
@@ -1359,28 +1297,14 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
             # everything sample() does to the rows - column blocks, their order, the reference-sample flips, bit-packing -
             # happens on the device (tsim_arrange_rows_device); the host receives the arrays it hands out
             _check_request(shots, batch_size)
-            ref = None
-            if want_ref:
-                if self._noise == "device":
-                    ref = self._compute_reference_sample()  # (its own key, then the batches: as _device_noise_plain does it)
-                else:
-                    # host noise: the reference row rides as row 0 of the first batch (sampler.py:395-404) - the same row, same
-                    # subkey, same in-batch index computed here first, so that its bits are known before the rows are arranged
-                    quiet = np.zeros((1, self._channel_sampler.num_f), dtype=np.uint8)
-                    ref = np.asarray(self._seam(quiet, prng.split(self._key)[1])[0], dtype=np.bool_)
-            det = np.arange(nd, dtype=np.uint32)
-            obs = np.arange(nd, n_out, dtype=np.uint32)
-            if ref is not None and use_detector_reference_sample:
-                det = det | (ref[:nd].astype(np.uint32) << np.uint32(31))
-            if ref is not None and use_observable_reference_sample:
-                obs = obs | (ref[nd:].astype(np.uint32) << np.uint32(31))
+            ref, rides = self._reference_row(want_ref)
+            det, obs = _reference_flip_columns(nd, n_out, ref, use_detector_reference_sample, use_observable_reference_sample)
             if separate_observables:
                 cols = [det, obs]
             elif prepend_observables:
                 cols = [np.concatenate([obs, det] + ([obs] if append_observables else []))]
             else:
                 cols = [np.concatenate([det, obs]) if append_observables else det]
-            rides = want_ref and self._noise != "device"
             res = self._device_plain(shots, batch_size, rides, layout=[(c, bit_packed) for c in cols])[0]
             return tuple(res) if separate_observables else res[0]
         elif want_ref:
