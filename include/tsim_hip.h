@@ -682,11 +682,28 @@ typedef struct tsim_uf_heralds {
 } tsim_uf_heralds;
 int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
                            tsim_uf **out);
+/* Cluster matching ("Cluster matching" in the module docstring of tsim_amd/decode.py): growth as the other handles (edge_cap
+ * as tsim_uf_create_weighted, NULL: cap 2 everywhere), then every cluster of 1 .. max_defects defects is corrected by the
+ * minimum-weight matching of its defects, the boundary allowed, under the match weights match_w[e] in 1 .. 65535
+ * (uint16[n_edges], required), by a dynamic program over the subsets of its defects with the tie rule of the docstring; a
+ * larger cluster is peeled as before.  The distances and the observables of the paths come from the match table
+ * (uint32 + uint64 per pair of nodes), which this call builds on the device.  max_defects is 1 .. 12.  No heralds: the
+ * table is static.  Every argument - the graph as tsim_uf_create, the caps, a NULL match_w, a weight of 0, max_defects - is
+ * checked before any device call (TSIM_EINVAL).  TSIM_ENOTSUP for more than 2048 nodes and when a shot's state plus the
+ * dynamic program's (5 bytes per subset: 2^max_defects subsets; 4 bytes per pair of a cluster's defects) does not fit a
+ * block's 64 KiB of LDS.  tsim_uf_decode_device on the handle runs the matching kernel and means what it means on the
+ * others; tsim_uf_decode_soft_device is TSIM_EINVAL. */
+int tsim_uf_create_matching(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const uint16_t *match_w,
+                            int32_t max_defects, tsim_uf **out);
+/* The match table of a handle of tsim_uf_create_matching, to the host: dist (uint32[n_nodes * n_nodes], 0x7FFFFFFF: no path)
+ * and mask (uint64[n_nodes * n_nodes]), row a = source a.  TSIM_EINVAL for another handle or a NULL.  Synchronous. */
+int tsim_uf_match_table(tsim_uf *h, uint32_t *dist, uint64_t *mask);
 void tsim_uf_destroy(tsim_uf *h);
 /* out[0] nodes, [1] edges, [2] LDS bytes per shot, [3] shots (waves) per block, [4] kernel launches so far, [5] the most
  * growth rounds a row took, [6] bytes of device memory, [7] rows decoded in LDS (kept rows with a defect), [8] n_cols,
  * [9] blocks of a full grid, [10] the largest cap (0: an unweighted handle), [11] heralds, [12] detector columns of a row
- * (n_nodes - 1 without heralds); the rest 0.  Synchronises the device. */
+ * (n_nodes - 1 without heralds), [13] max_defects (0: not a handle of tsim_uf_create_matching), [14] clusters matched and
+ * [15] clusters peeled, over the rows decoded in LDS that are no miss.  Synchronises the device. */
 int tsim_uf_info(tsim_uf *h, int64_t out[16]);
 /* Rows, d_xor, d_test, obs_lo, obs_hi and d_counters are those of tsim_rowtab_decode_device and mean the same (masks of
  * ceil(n_cols / 8) bytes): a row is KEPT iff (row ^ xor) & test == 0, its syndrome is row ^ xor at columns

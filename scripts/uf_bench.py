@@ -4,6 +4,7 @@
     python scripts/uf_bench.py --circuits d15 --shots 1000000
     python scripts/uf_bench.py --resolution 4        # weighted against unweighted growth: d = 5, 9, 15
     python scripts/uf_bench.py --soft largest_cluster  # the price of a soft output: d = 5, 9
+    python scripts/uf_bench.py --match 10 --resolution 4  # the price of cluster matching: d = 5, 9
 
 Per distance the ``method="faults"`` sampler counts ``--shots`` shots per call in batches of 10^6, once without a decoder and
 once with ``decoder=UnionFindDecoder.from_circuit(circuit)``, alternating, each warmed up first; the time is a host clock
@@ -22,6 +23,11 @@ handle of its own.
 ``UnionFindDecoder.from_circuit(circuit)`` and with its ``with_soft_output(METRIC, --bins)``, alternating over the same seeded
 rows (with ``--resolution R`` both are the weighted decoder): both rates, their ratio, the two histograms and the rejection
 curve.  The leg stops when the two calls disagree on a counter or the histograms do not add up to them.
+
+``--match K`` is a leg of its own (``--circuits`` then defaults to d5,d9): the same ``count()`` call with the decoder
+(weighted with ``--resolution R``) and with its ``with_cluster_matching(K)``, alternating over the same seeded rows: both rates,
+their ratio, both decoded error counts, and what ``tsim_uf_info`` says after ``--info-rows`` rows (LDS per shot, shots per block,
+clusters matched and peeled).  The leg stops when the two calls disagree on kept rows, raw flips or misses.
 """
 
 from __future__ import annotations
@@ -138,6 +144,57 @@ def soft_leg(args) -> None:
             flush=True)
 
 
+def match_leg(args) -> None:
+    for name in (args.circuits or "d5,d9").split(","):
+        d = int(name[1:])
+        c = memory(d, args.p)
+        plain = (UnionFindDecoder.from_circuit(c) if args.resolution is None
+                 else UnionFindDecoder.from_circuit(c, weights="probability", resolution=args.resolution))
+        decoders = {"plain": plain, "matching": plain.with_cluster_matching(args.match)}
+        def sampler():  # a fresh one per call: every call counts the same seeded rows
+            return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+        times, last = {m: [] for m in decoders}, {}
+        for m, uf in decoders.items():
+            sampler().count(args.shots, batch_size=10**6, decoder=uf)  # warm-up at the timed size
+        for _ in range(args.reps):
+            for m, uf in decoders.items():
+                s = sampler()
+                t0 = time.perf_counter()
+                last[m] = s.count(args.shots, batch_size=10**6, decoder=uf)
+                times[m].append(time.perf_counter() - t0)
+        a, b = last["plain"], last["matching"]
+        if (a.kept, a.kept_with_observable_flip, a.decoder_misses) != (b.kept, b.kept_with_observable_flip, b.decoder_misses):
+            sys.exit("uf_bench: the matching decoder did not see the rows, or the misses, of the plain one")
+        hp = s._hip()
+        um = decoders["matching"]
+        rows = c.compile_detector_sampler(seed=3, noise="device", method="faults").sample(args.info_rows, append_observables=True)
+        import numpy as np
+
+        packed = np.ascontiguousarray(np.packbits(rows, axis=1, bitorder="little"))
+        nd, n_cols = um.num_detectors, um.num_detectors + um.num_observables
+        h, decode, destroy = um._handle(hp, n_cols)
+        d_rows, d_cnt = hp.malloc(packed.nbytes + 16), hp.malloc(64)
+        try:
+            hp.h2d(d_rows, packed)
+            hp.h2d(d_cnt, np.zeros(3, np.uint64))
+            decode(h, d_rows.ptr, len(packed), packed.shape[1], (nd, n_cols), d_cnt.ptr)
+            info = hp.uf_info(h)
+        finally:
+            destroy(h)
+            d_rows.free()
+            d_cnt.free()
+        rate = {m: args.shots / statistics.median(t) for m, t in times.items()}
+        print(json.dumps(dict(
+            case=name, leg="match", max_defects=args.match, resolution=args.resolution, p=args.p, shots=args.shots, reps=args.reps,
+            graph=plain.info(), median_s={m: statistics.median(t) for m, t in times.items()}, min_s={m: min(t) for m, t in times.items()},
+            max_s={m: max(t) for m, t in times.items()}, shots_per_s=rate, matching_over_plain=rate["matching"] / rate["plain"], kept=b.kept,
+            raw_flips=b.kept_with_observable_flip, decoded_errors={m: last[m].decoded_errors for m in decoders}, misses=b.decoder_misses,
+            info_rows=args.info_rows, lds_bytes_per_shot=info["lds_bytes_per_shot"], shots_per_block=info["shots_per_block"],
+            clusters_matched=info["clusters_matched"], clusters_peeled=info["clusters_peeled"], rows_decoded=info["rows_decoded"],
+            device_bytes=info["device_bytes"])), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shots", type=int, default=10**7)
@@ -150,10 +207,14 @@ def main() -> None:
     ap.add_argument("--soft", default=None, metavar="METRIC",
                     help="the leg that runs a decoder with this soft output against the same decoder without (weighted with --resolution)")
     ap.add_argument("--bins", type=int, default=64, help="the bins of --soft")
+    ap.add_argument("--match", type=int, default=None, metavar="K",
+                    help="the leg that runs a decoder with cluster matching of at most K defects against the same decoder without")
     args = ap.parse_args()
     _lib.load()
     if _lib.device_count() < 1:
         sys.exit("uf_bench: no HIP device - nothing is measured without one")
+    if args.match is not None:
+        return match_leg(args)
     if args.soft is not None:
         return soft_leg(args)
     if args.resolution is not None:

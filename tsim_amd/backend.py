@@ -474,7 +474,31 @@ class HipProgram:
         self._lib.tsim_rowtab_destroy(C.c_void_p(handle))
 
     UF_INFO = ("n_nodes", "n_edges", "lds_bytes_per_shot", "shots_per_block", "launches", "max_rounds", "device_bytes", "rows_decoded",
-               "n_cols", "grid_blocks", "max_cap", "n_heralds", "n_det_cols")
+               "n_cols", "grid_blocks", "max_cap", "n_heralds", "n_det_cols", "max_defects", "clusters_matched", "clusters_peeled")
+
+    def uf_create_matching(self, graph, n_cols: int, match_weights, max_defects: int, caps=None) -> int:
+        """A cluster-matching union-find decoder over ``graph`` (``tsim_uf_create_matching``; "Cluster matching" in the module
+        docstring of :mod:`tsim_amd.decode`): ``match_weights``, an integer per edge in 1 .. 65535, ``max_defects`` in 1 .. 12,
+        ``caps`` as :meth:`uf_create`.  The handle decodes by :meth:`uf_decode_device` and is given back to :meth:`uf_destroy`."""
+        desc, d_caps, her, _keep = self._uf_graph_args(graph, n_cols, caps)
+        if her is not None:
+            raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
+        w = np.ascontiguousarray(match_weights)
+        if w.shape != (graph.n_edges,) or not np.issubdtype(w.dtype, np.integer) or (w.size and (w.min() < 0 or w.max() > 65535)):
+            raise ValueError(f"match_weights: {graph.n_edges} integers in 1 .. 65535 expected")
+        w = np.concatenate([w.astype(np.uint16), np.zeros(1, np.uint16)])  # (never an empty buffer)
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_uf_create_matching(self.device, C.byref(desc), d_caps, C.c_void_p(w.ctypes.data),
+                                                     int(min(max(max_defects, -1), 0x7FFFFFFF)), C.byref(h)), "tsim_uf_create_matching")
+        return h.value
+
+    def uf_match_table(self, handle: int):
+        """``(dist uint32[n_nodes, n_nodes], mask uint64[n_nodes, n_nodes])``: the match table the handle of
+        :meth:`uf_create_matching` built on the device (``tsim_uf_match_table``)."""
+        n_nodes = self.uf_info(handle)["n_nodes"]
+        dist, mask = np.zeros((n_nodes, n_nodes), np.uint32), np.zeros((n_nodes, n_nodes), np.uint64)
+        _lib.check(self._lib.tsim_uf_match_table(C.c_void_p(handle), _lib.ptr(dist), _lib.ptr(mask)), "tsim_uf_match_table")
+        return dist, mask
 
     def uf_create(self, graph, n_cols: int, caps=None) -> int:
         """A union-find decoder over ``graph`` (:class:`tsim_amd.decode.DecodingGraph`) for rows of ``n_cols`` columns on this

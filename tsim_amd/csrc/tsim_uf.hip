@@ -1,6 +1,7 @@
 // tsim_uf.hip - the union-find decoder over bit-packed device rows (tsim_uf_*): a handle of its own, bound to one device,
 // holding the decoding graph's tables; the kernel is csrc/tsim_uf.hip.h, the rule tsim_amd/decode.py.
 #include "tsim_uf_host.hip.h"
+#include "tsim_uf_match.hip.h"
 
 #include <new>
 
@@ -11,6 +12,7 @@ struct tsim_uf {
   int64_t launches = 0;
   int max_cap = 0;  // 0: unweighted
   int n_heralds = 0;
+  ufk::TableArgs table{};  // cluster matching: the match table (a.match_k != 0)
   tsimh::Uploads up;  // the tables a points to
 };
 
@@ -22,8 +24,27 @@ extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc,
   return tsim_uf_create_heralds(device, desc, edge_cap, nullptr, out);
 }
 
+// every create call; match_w != NULL: tsim_uf_create_matching, with max_defects
+static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her, const uint16_t *match_w,
+                     int32_t max_defects, tsim_uf **out);
+
 extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
                                       tsim_uf **out) {
+  return uf_create(device, desc, edge_cap, her, nullptr, 0, out);
+}
+
+extern "C" int tsim_uf_create_matching(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const uint16_t *match_w,
+                                       int32_t max_defects, tsim_uf **out) {
+  if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!match_w) return tsim_fail(TSIM_EINVAL, "match_w is NULL");
+  if (max_defects < 1 || max_defects > ufk::kMaxMatchDefects)
+    return tsim_fail(TSIM_EINVAL, "max_defects = %d (1 .. %d)", max_defects, ufk::kMaxMatchDefects);
+  return uf_create(device, desc, edge_cap, nullptr, match_w, max_defects, out);
+}
+
+static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her, const uint16_t *match_w,
+                     int32_t max_defects, tsim_uf **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
   *out = nullptr;
   if (!desc) return tsim_fail(TSIM_EINVAL, "desc is NULL");
@@ -35,6 +56,12 @@ extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, 
   long long n_det = 0;
   int max_cap = 0;
   if (const int rc = ufh::check_graph(desc, edge_cap, her, &n_det, &max_cap)) return rc;
+  if (match_w) {
+    for (int e = 0; e < E; ++e)
+      if (match_w[e] < 1) return tsim_fail(TSIM_EINVAL, "edge %d has match weight 0 (1 .. 65535)", e);
+    if (N > ufk::kMaxMatchNodes)
+      return tsim_fail(TSIM_ENOTSUP, "%d nodes (a match table has at most %d: 12 bytes per pair of nodes)", N, ufk::kMaxMatchNodes);
+  }
   const int H = her ? her->n_heralds : 0, mask_bytes = (desc->n_cols + 7) / 8;
   std::vector<int32_t> her_tab;  // node_det [N - 1], col_herald [n_det], herald_ptr [H + 1], herald_edges [n_listed], a spare entry
   std::vector<uint8_t> masks;    // dmask, hmask: mask_bytes each, and 8 bytes of zeros
@@ -55,9 +82,11 @@ extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, 
   a.n_det_cols = (int)n_det;
   a.w32 = std::max(1, (E + 31) / 32);
   a.w_cnt = edge_cap ? std::max(1, (E + 7) / 8) : 0;
+  a.match_k = match_w ? max_defects : 0;
   const long long shot = ufk::layout(&a);
   if (16 + shot > ufk::kLdsBlock)
-    return tsim_fail(TSIM_ENOTSUP, "one shot's state takes %lld bytes of LDS (%d nodes, %d edges), a block has %d", shot, N, E, ufk::kLdsBlock - 16);
+    return tsim_fail(TSIM_ENOTSUP, "one shot's state takes %lld bytes of LDS (%d nodes, %d edges%s), a block has %d", shot, N, E,
+                     match_w ? ", the dynamic program of max_defects" : "", ufk::kLdsBlock - 16);
   a.shot_bytes = (int)shot;
   int per_cu = 1;
   ufh::choose_waves(shot, &a.waves, &per_cu);
@@ -94,8 +123,23 @@ extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, 
   a.adj_ptr = up.put(ptr);
   a.adj_edge = up.put(adj);
   if (edge_cap) a.cap = up.put(cap);
-  const uint64_t zero[2] = {0, 0};
-  a.stats = reinterpret_cast<unsigned long long *>(up.put(zero, 2));
+  const uint64_t zero[4] = {0, 0, 0, 0};
+  a.stats = reinterpret_cast<unsigned long long *>(up.put(zero, match_w ? 4 : 2));
+  if (match_w) {  // the match table, built here once
+    const std::vector<uint16_t> w(match_w, match_w + E);
+    const size_t pairs = (size_t)N * (size_t)N;
+    ufk::TableArgs &t = h->table;
+    t.n_nodes = N, t.edge_uv = a.edge_uv, t.edge_obs = a.edge_obs, t.adj_ptr = a.adj_ptr, t.adj_edge = a.adj_edge;
+    t.w = up.put(w);
+    t.dist = static_cast<uint32_t *>(up.room(pairs * sizeof(uint32_t)));
+    t.mask = static_cast<unsigned long long *>(up.room(pairs * sizeof(uint64_t)));
+    up.bytes += (int64_t)(pairs * 12);
+    if (up.err == hipSuccess) {
+      hipLaunchKernelGGL(ufk::k_match_table, dim3(N), dim3(ufk::kTableThreads), ufk::table_lds(N), nullptr, t);
+      up.err = hipGetLastError();
+    }
+    a.mdist = t.dist, a.mmask = t.mask;
+  }
   if (her) {
     a.node_det = up.put(her_tab);
     a.col_herald = a.node_det + (N - 1);
@@ -141,6 +185,12 @@ extern "C" int tsim_uf_info(tsim_uf *h, int64_t out[16]) {
   out[10] = h->max_cap;
   out[11] = h->n_heralds;
   out[12] = h->a.n_det_cols;
+  if (h->a.match_k) {
+    HIP_TRY(hipMemcpy(st, h->a.stats + 2, 16, hipMemcpyDeviceToHost));
+    out[13] = h->a.match_k;
+    out[14] = (int64_t)st[0];
+    out[15] = (int64_t)st[1];
+  }
   return TSIM_OK;
 }
 
@@ -153,6 +203,12 @@ struct SoftOut {  // what tsim_uf_decode_soft_device adds to tsim_uf_decode_devi
 
 template <bool Soft>
 void uf_launch(const ufk::Args &a, unsigned blocks, size_t lds, hipStream_t stream) {
+  if constexpr (!Soft)
+    if (a.match_k) {  // (a handle of tsim_uf_create_matching: no heralds, no soft outputs)
+      if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, false, false, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+      else hipLaunchKernelGGL((ufk::k_uf<false, false, false, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+      return;
+    }
   if (a.node_det) {
     if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, true, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
     else hipLaunchKernelGGL((ufk::k_uf<false, true, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
@@ -168,6 +224,7 @@ static int uf_decode(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_b
   ufk::Args a = h->a;
   if (const int rc = ufh::check_rows(a, d_rows, n, row_bytes, obs_lo, obs_hi, d_counters, d_pred)) return rc;
   if (soft) {
+    if (a.match_k) return tsim_fail(TSIM_EINVAL, "a cluster-matching handle has no soft outputs");
     if (soft->metric < 0 || soft->metric > 3) return tsim_fail(TSIM_EINVAL, "metric = %d (0 rounds, 1 full_edges, 2 largest_cluster, 3 correction_weight)", soft->metric);
     if (soft->n_bins < 2 || soft->n_bins > 1024) return tsim_fail(TSIM_EINVAL, "n_bins = %d (2 .. 1024)", soft->n_bins);
     if (!soft->d_hist || reinterpret_cast<uintptr_t>(soft->d_hist) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_hist is NULL or not 8-byte aligned");
@@ -200,4 +257,14 @@ extern "C" int tsim_uf_decode_soft_device(tsim_uf *h, const uint8_t *d_rows, int
                                           int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream) {
   const SoftOut soft{metric, n_bins, d_hist, d_soft};
   return uf_decode(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, d_pred, &soft, stream);
+}
+
+extern "C" int tsim_uf_match_table(tsim_uf *h, uint32_t *dist, uint64_t *mask) {
+  if (!h || !dist || !mask) return tsim_fail(TSIM_EINVAL, "NULL argument");
+  if (!h->a.match_k) return tsim_fail(TSIM_EINVAL, "the handle has no match table (tsim_uf_create_matching makes one)");
+  const size_t pairs = (size_t)h->a.n_nodes * (size_t)h->a.n_nodes;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemcpy(dist, h->table.dist, pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(mask, h->table.mask, pairs * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return TSIM_OK;
 }

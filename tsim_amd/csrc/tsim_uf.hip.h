@@ -38,6 +38,15 @@
 // by the lane that flips an edge, in the function handed to peel().  The three per-lane numbers are reduced over the wave in
 // registers.  Of a tile's rows those of bin 0 (every kept row without a defect among them) are counted by ballot into
 // registers and flushed once per wave; the others go to the histogram by global 64-bit adds, one per distinct bin of the tile.
+// Cluster matching (k_uf<Weighted, false, false, true>, tsim_uf_create_matching; "Decoding a row" of the cluster-matching section
+// of the docstring): growth is the one above.  Then lp[], dead until forest(), counts the defects of every cluster at its root,
+// par[], dead after growth, marks the roots (1: matched, 1 .. K defects; 2: peeled, more), and a sweep of the nodes compacted by
+// ballot lists the defects of the matched clusters in ascending node order in lp[].  Each matched cluster in turn, by the whole
+// wave: its defects are compacted out of that list the same way, its K (K + 1) / 2 + K distances are read from the match table
+// (global memory; tsim_uf_match.hip.h builds it) into LDS, the dynamic program runs by layers of popcount(S), lanes over the
+// subsets, keeping per subset the cost (uint32: at most 12 finite terms below 2^27 each, so the 64-bit sum of the rule fits) and
+// the candidate that won, and one lane walks the winners back from the full set, XORing the table's masks.  forest() and peel()
+// run only when a peeled cluster exists, and a flip counts only when its child node lies in one.
 // Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
 #pragma once
 #include "tsim_bitrows.hip.h"
@@ -51,6 +60,11 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;  // lp of a node no level has reached
 constexpr int kLdsBlock = 64 * 1024;     // LDS a block may ask for
 constexpr int kLdsCU = 160 * 1024;
 constexpr int kMaxCap = 14;              // of an edge: its 4-bit counter may pass the cap by one
+constexpr int kMaxMatchNodes = 2048;     // of a graph with a match table (uint32 + uint64 per pair of nodes)
+constexpr int kMaxMatchDefects = 12;     // K at most: 2^K subsets of a cluster's defects in LDS
+constexpr uint32_t kMatchInf = 0x7FFFFFFFu;  // a distance of the match table: no path
+constexpr uint32_t kCostInf = 0xFFFFFFFFu;   // a cost of the dynamic program: no pairing
+constexpr uint8_t kViaBoundary = 15, kViaNone = 255;  // the candidate that won a subset: a defect 0 .. 11, the boundary, none
 
 struct Args {
   const uint8_t *rows;
@@ -70,7 +84,7 @@ struct Args {
   int off_lp, off_s, off_par, off_half, off_full, off_wlist, off_misc;
   unsigned long long *dec;    // [0] kept [1] wrong [2] missed
   unsigned long long *pred;   // [n] or NULL
-  unsigned long long *stats;  // [0] most growth rounds [1] rows decoded in LDS
+  unsigned long long *stats;  // [0] most growth rounds [1] rows decoded in LDS [2] clusters matched [3] clusters peeled
   // heralded erasures (NULL / 0 on a handle without heralds)
   int n_det_cols;              // detector columns of a row: the nodes but the boundary, and the heralds
   const int32_t *node_det;     // [n_nodes - 1] the column of node v at v - 1
@@ -82,6 +96,11 @@ struct Args {
   int metric, n_bins;          // 0 rounds 1 full_edges 2 largest_cluster 3 correction_weight; the bin of x is min(x, n_bins - 1)
   unsigned long long *hist;    // [2 * n_bins] kept rows per bin, then the wrong ones among them
   uint32_t *soft;              // [4 * n] the four values of every row (16-byte aligned), or NULL
+  // cluster matching (k_uf<., false, false, true> only; 0 / NULL on other handles)
+  int match_k;                 // K in 1 .. 12: a cluster of 1 .. K defects is matched, a larger one peeled
+  int off_mcost, off_mch, off_mcl, off_mpd;
+  const uint32_t *mdist;       // [n_nodes * n_nodes] the match table: distances (kMatchInf: none) ...
+  const unsigned long long *mmask;  // ... and the observables of the paths
 };
 
 // the layout of one wave's state, shared by the host (sizes, limits) and the kernel
@@ -96,6 +115,12 @@ __host__ inline long long layout(Args *a) {
   a->off_full = (int)at, at += a16(4 * W);
   a->off_wlist = (int)at, at += a16(2 * W);
   a->off_misc = (int)at, at += 16;
+  if (const long long K = a->match_k) {  // the dynamic program: costs, winners, the cluster's defects, its distances [K][K + 1]
+    a->off_mcost = (int)at, at += a16(4ll << K);
+    a->off_mch = (int)at, at += a16(1ll << K);
+    a->off_mcl = (int)at, at += a16(2 * K);
+    a->off_mpd = (int)at, at += a16(4 * K * (K + 1));
+  }
   return at;
 }
 
@@ -121,6 +146,9 @@ struct State {
   //                                                   (half: the 4-bit counters when the growth is weighted)
   uint8_t *s, *par;
   uint16_t *wlist;
+  uint32_t *mcost, *mpd;  // cluster matching only
+  uint8_t *mch;
+  uint16_t *mcl;
 };
 
 // a wave's state at `base`, by the offsets layout() has put into `a`
@@ -137,6 +165,15 @@ __device__ __forceinline__ State state_at(const L &a, uint8_t *base) {
   st.full = reinterpret_cast<uint32_t *>(base + a.off_full);
   st.wlist = reinterpret_cast<uint16_t *>(base + a.off_wlist);
   st.misc = reinterpret_cast<uint32_t *>(base + a.off_misc);
+  return st;
+}
+// the same with the arrays of the dynamic program (a handle of tsim_uf_create_matching)
+__device__ __forceinline__ State match_state_at(const Args &a, uint8_t *base) {
+  State st = state_at(a, base);
+  st.mcost = reinterpret_cast<uint32_t *>(base + a.off_mcost);
+  st.mch = base + a.off_mch;
+  st.mcl = reinterpret_cast<uint16_t *>(base + a.off_mcl);
+  st.mpd = reinterpret_cast<uint32_t *>(base + a.off_mpd);
   return st;
 }
 
@@ -366,9 +403,119 @@ __device__ __forceinline__ void soft_of_growth(const G &a, const State &st, int 
   soft[1] = both & 0xFFFFu;
 }
 
+// The steps of cluster matching, between grow() and forest(), each by the whole wave.
+// the lanes with `flag`, compacted in lane order behind the *at entries there are: this lane's place (if it has the flag)
+__device__ __forceinline__ int compact(bool flag, int lane, int *at) {
+  const uint64_t b = __builtin_amdgcn_ballot_w64(flag);
+  const int pos = *at + __popcll(b & ((1ull << lane) - 1ull));
+  *at += __popcll(b);
+  return pos;
+}
+
+// The clusters growth has left (not a miss): par[r] of a root r = 1 for a MATCHED cluster (1 .. K defects), 2 for a PEELED one
+// (more), 0 for one without a defect; lp[0 .. *n_list - 1] = the defects of the matched clusters, ascending.  counts[0] and
+// counts[1]: the matched and the peeled clusters (wave-uniform).
+__device__ __forceinline__ void mark_clusters(const Args &a, const State &st, int lane, int *n_list, uint32_t *counts) {
+  const int N = a.n_nodes;
+  for (int v = lane; v < N; v += 64) st.lp[v] = 0;
+  wsync();
+  for (int v = lane; v < N; v += 64)
+    if (st.s[v]) atomicAdd(&st.lp[st.label[v]], 1u);  // (s[0] = 0: the boundary is no defect)
+  wsync();
+  uint32_t both = 0;  // matched << 16 | peeled, at most 65535 clusters in all
+  for (int v = lane; v < N; v += 64) {
+    const uint32_t m = st.lp[v];  // (0 off the roots)
+    const uint8_t mark = m == 0 ? 0 : m <= (uint32_t)a.match_k ? 1 : 2;
+    st.par[v] = mark;
+    both += mark == 1 ? 0x10000u : mark == 2 ? 1u : 0u;
+  }
+  wsync();  // (the counts are read: lp[] is free for the list)
+  int at = 0;
+  for (int v0 = 0; v0 < N; v0 += 64) {
+    const int v = v0 + lane;
+    const bool flag = v < N && st.s[v] && st.par[st.label[v]] == 1;
+    const int pos = compact(flag, lane, &at);
+    if (flag) st.lp[pos] = (uint32_t)v;  // (pos <= v: at most one entry per node)
+  }
+  wsync();
+  *n_list = at;
+  both = wave_sum(both);
+  counts[0] = both >> 16;
+  counts[1] = both & 0xFFFFu;
+}
+
+// One matched cluster, of root r, by the whole wave: the mask of the dynamic program of the docstring over its defects, which
+// are the entries of label r in lp[from .. n_list).  The result is in lane 0 (0 in the other lanes).
+__device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st, int lane, int from, int n_list, int r) {
+  const int K = a.match_k;
+  const size_t N = (size_t)a.n_nodes;
+  int m = 0;
+  for (int i0 = from; i0 < n_list; i0 += 64) {
+    const int i = i0 + lane;
+    const int v = i < n_list ? (int)st.lp[i] : 0;
+    const bool flag = i < n_list && st.label[v] == r;
+    const int pos = compact(flag, lane, &m);
+    if (flag && pos < K) st.mcl[pos] = (uint16_t)v;  // (a matched cluster has at most K defects: pos < K)
+  }
+  wsync();
+  m = min(m, K);
+  const int W = m + 1;  // a row of mpd: the distances of defect i to the defects j > i, at [m] to the boundary
+  for (int t = lane; t < m * W; t += 64) {
+    const int i = t / W, j = t % W;
+    if (j <= i) continue;
+    st.mpd[t] = a.mdist[(size_t)st.mcl[i] * N + (j < m ? (size_t)st.mcl[j] : 0)];
+  }
+  if (lane == 0) st.mcost[0] = 0;
+  wsync();
+  const int n_sets = 1 << m;
+  for (int layer = 1; layer <= m; ++layer) {  // f[S] reads subsets of one and of two defects less
+    for (int S = lane; S < n_sets; S += 64) {
+      if (__popc((unsigned)S) != layer) continue;
+      const int i = __builtin_ctz(S), R = S & (S - 1);
+      uint32_t best = kCostInf;
+      uint8_t via = kViaNone;
+      const uint32_t fR = st.mcost[R], b = st.mpd[i * W + m];
+      if (fR != kCostInf && b != kMatchInf) best = fR + b, via = kViaBoundary;
+      for (int rest = R; rest; rest &= rest - 1) {  // ascending j; strict < keeps the first of least cost
+        const int j = __builtin_ctz(rest);
+        const uint32_t f = st.mcost[R ^ (1 << j)], d = st.mpd[i * W + j];
+        if (f != kCostInf && d != kMatchInf && f + d < best) best = f + d, via = (uint8_t)j;
+      }
+      st.mcost[S] = best;
+      st.mch[S] = via;
+    }
+    wsync();
+  }
+  uint64_t mask = 0;
+  if (lane == 0)
+    for (int S = n_sets - 1; S;) {  // the winners, from the full set down: S loses one or two defects per step
+      const int i = __builtin_ctz(S), R = S & (S - 1), via = st.mch[S];
+      if (via == kViaNone) break;  // (no pairing: a cluster is connected and holds an even number of defects or node 0)
+      const size_t row = (size_t)st.mcl[i] * N;
+      if (via == kViaBoundary) mask ^= a.mmask[row], S = R;
+      else mask ^= a.mmask[row + st.mcl[via]], S = R ^ (1 << via);  // (via is a defect of R: below m)
+    }
+  wsync();  // (the next cluster overwrites the arrays)
+  return mask;
+}
+
+// every matched cluster, in the order of its smallest defect: the XOR of their masks, in lane 0
+__device__ __forceinline__ uint64_t match_clusters(const Args &a, const State &st, int lane, int n_list) {
+  uint64_t mask = 0;
+  for (int i = 0; i < n_list; ++i) {
+    const int r = __builtin_amdgcn_readfirstlane((int)st.label[st.lp[i]]);
+    if (__builtin_amdgcn_readfirstlane((int)st.par[r]) != 1) continue;  // (matched before, by an earlier defect of its)
+    mask ^= match_cluster(a, st, lane, i, n_list, r);
+    if (lane == 0) st.par[r] = 3;
+    wsync();
+  }
+  return mask;
+}
+
 // one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform, and so
-// are, with Soft, soft[0 .. 2]: full edges, largest cluster, correction weight
-template <bool Weighted, bool Heralds, bool Soft>
+// are, with Soft, soft[0 .. 2]: full edges, largest cluster, correction weight; with Match, soft[0 .. 1]: the clusters matched
+// and peeled
+template <bool Weighted, bool Heralds, bool Soft, bool Match = false>
 __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds,
                                                 uint32_t *soft) {
   load_defects<Heralds>(a, st, row, lane);
@@ -376,7 +523,18 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   if constexpr (Heralds) pregrow_heralds(a, st, row, lane);
   *missed = grow<Weighted>(a, st, lane, rounds);
   if constexpr (Soft) soft_of_growth(a, st, lane, soft), soft[2] = 0;
+  if constexpr (Match) soft[0] = soft[1] = 0;
   if (*missed) return 0;
+  if constexpr (Match) {
+    int n_list;
+    mark_clusters(a, st, lane, &n_list, soft);
+    uint64_t flips = match_clusters(a, st, lane, n_list);
+    if (soft[1]) {  // a flip counts when its edge, and so its child node, lies in a peeled cluster
+      forest(a, st, lane);
+      flips ^= peel(a, st, lane, [&](int e, int u, int) { return st.par[st.label[u]] == 2 ? a.edge_obs[e] : 0ull; });
+    }
+    return fold_flips(&st.misc[2], flips);
+  }
   forest(a, st, lane);
   uint32_t flipped = 0;  // by this lane
   const uint64_t flips = peel(a, st, lane, [&](int e, int, int) {
@@ -387,18 +545,19 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   return fold_flips(&st.misc[2], flips);
 }
 
-template <bool Weighted, bool Heralds, bool Soft = false>
+template <bool Weighted, bool Heralds, bool Soft = false, bool Match = false>
 __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed; with Soft: the kept rows of bin 0
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
-  const State st = state_at(a, base);
+  const State st = Match ? match_state_at(a, base) : state_at(a, base);
   if (threadIdx.x < 4) stat[threadIdx.x] = 0;
   __syncthreads();
   uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
   int most_rounds = 0;
   uint32_t bin0_acc = 0, bin0_wrong_acc = 0;  // (Soft) wave-uniform: the kept rows of bin 0, the wrong ones among them
+  uint32_t matched_acc = 0, peeled_acc = 0;   // (Match) wave-uniform: the clusters matched and peeled
   const int nd = a.n_nodes - 1;
   const long long tiles = (a.n + 63) >> 6;
   for (long long t = (long long)blockIdx.x * a.waves + wave; t < tiles; t += (long long)gridDim.x * a.waves) {
@@ -419,7 +578,8 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       bool m;
       int rounds;
       uint32_t soft[3];
-      const uint64_t p = decode_shot<Weighted, Heralds, Soft>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, soft);
+      const uint64_t p = decode_shot<Weighted, Heralds, Soft, Match>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, soft);
+      if constexpr (Match) matched_acc += soft[0], peeled_acc += soft[1];
       if (lane == src) pred = p, missed = m;
       if constexpr (Soft)
         if (lane == src) mine[0] = (uint32_t)rounds, mine[1] = soft[0], mine[2] = soft[1], mine[3] = soft[2];
@@ -455,6 +615,10 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     if (miss_acc) atomicAdd(&stat[2], miss_acc);
     if (most_rounds) atomicMax(&a.stats[0], (unsigned long long)most_rounds);
     if (decoded_acc) atomicAdd(&a.stats[1], (unsigned long long)decoded_acc);
+    if constexpr (Match) {
+      if (matched_acc) atomicAdd(&a.stats[2], (unsigned long long)matched_acc);
+      if (peeled_acc) atomicAdd(&a.stats[3], (unsigned long long)peeled_acc);
+    }
     if constexpr (Soft) {
       if (bin0_acc) atomicAdd(&stat[3], bin0_acc);
       if (bin0_wrong_acc) atomicAdd(&a.hist[a.n_bins], (unsigned long long)bin0_wrong_acc);  // (rare: wrong without a defect, or in bin 0)

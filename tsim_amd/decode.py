@@ -94,6 +94,41 @@ wrongly (``soft_kept.sum() == kept``, ``soft_errors.sum() == decoded_errors``); 
 running sum, the error count against the shots accepted.  A soft output of the windowed decoder (below) is out of scope:
 its windows have no common final state.
 
+Cluster matching (:meth:`UnionFindDecoder.with_cluster_matching`; ``tsim_uf_create_matching``).  The forest of
+step 2 ignores ``edge_p``: inside a cluster that holds several corrections peeling takes one by index, not by likelihood.
+A cluster-matching decoder grows as above and then corrects every small cluster by the minimum-weight matching of its defects.
+
+Match weights (:meth:`DecodingGraph.match_weights`, in float64): ``q = clip(edge_p, 1e-12, 0.5)``, ``L = log((1 - q) / q)``,
+``w = clip(rint(scale * L / L.max()), 1, scale)`` (1 everywhere when ``L.max() == 0``); ``scale`` is an int in 1 .. 65535, 1000 by
+default.
+
+Match table (:meth:`UnionFindDecoder.match_table`) for weights ``w``, an integer in 1 .. 65535 per edge: ``dist`` uint32 ``[N, N]``
+and ``mask`` uint64 ``[N, N]``, ``N = n_nodes``.  Row ``a >= 1`` describes the paths from source ``a`` that never pass THROUGH node
+0: the boundary may end a path, no path continues from it (an edge ``(0, v)`` relaxes node 0 from ``v``, never ``v`` from node
+0).  ``dist[a][v]`` is the least sum of ``w`` over such paths, ``INF = 0x7FFFFFFF`` when there is none, ``dist[a][a] = 0``.  For
+``v != a`` of finite distance the PARENT EDGE is the smallest-index edge ``e = (x, v)`` with ``dist[a][x] + w[e] == dist[a][v]``
+and ``x != 0`` (for ``v == 0`` it is an edge ``(0, x)``); ``mask[a][v] = mask[a][x] ^ edge_obs[e]`` and ``mask[a][a] = 0``.  The
+distances are a least fixpoint and the parent is a minimum over a fixed set, so neither depends on an order of traversal;
+``w >= 1`` puts a parent strictly nearer, so the masks are well defined.  ``mask`` is 0 where ``dist`` is ``INF``.  Row 0 is
+``dist[0][0] = 0``, ``INF`` elsewhere, masks 0.  At most ``MAX_MATCH_NODES = 2048`` nodes (16 MB + 32 MB; d = 11 with 11 rounds
+has 1321): beyond, ``NotImplementedError``.
+
+Decoding a row.  Growth is step 1, exactly: ``missed`` and ``growth_rounds`` are the plain decoder's, and a miss predicts 0.
+Otherwise the defects of a cluster (of the full edges when growth ends) are its nodes ``v >= 1`` with ``defect[v] = 1``.  With
+``K = max_defects`` a cluster of ``1 <= m <= K`` defects is MATCHED, one of ``m > K`` defects is PEELED.  Forest and peeling run as
+in steps 2 and 3; a flipped edge contributes ``edge_obs`` only when its child node lies in a peeled cluster.  A matched cluster
+contributes the mask of this dynamic program over its defects ``a_0 < ... < a_{m-1}`` (:meth:`UnionFindDecoder._match_cluster`):
+``f[0] = (cost 0, mask 0)``; for ``S = 1 .. 2^m - 1`` ascending, with ``i`` the lowest set bit of ``S`` and ``R`` = ``S`` without it, the
+candidates are, in this order, the boundary, ``f[R] + (dist[a_i][0], mask[a_i][0])``, then for every set bit ``j`` of ``R``
+ascending ``f[R without j] + (dist[a_i][a_j], mask[a_i][a_j])`` (the source is the smaller node); costs add in 64 bits, masks
+XOR; a candidate with an ``INF`` term or built on an infinite ``f`` is infinite; ``f[S]`` is the first candidate of least cost
+(strict ``<`` replaces).  The cluster's mask is that of ``f[2^m - 1]``, whose cost is finite (asserted in the numpy statement: a
+cluster is connected and holds an even number of defects or node 0).  The prediction is the XOR of the matched clusters' masks
+and the peeled clusters' flips; nothing in it depends on a parallel order.  ``uf.with_cluster_matching(K, weights)`` is the
+decoder of the same graph, caps and observables with ``match_defects = K`` (1 .. 12, default 10) and ``match_weights``
+(default ``graph.match_weights()``).  It takes no graph with heralds (the table is static, a herald is not), no soft output,
+and has no ``flipped_edges``; :class:`WindowedUnionFindDecoder` has no matching.
+
 Sliding-window decoding of long runs (:class:`WindowedUnionFindDecoder`; ``tsim_ufw_*``, ``csrc/tsim_ufw.hip.h``)
 ---------------------------------------------------------------------------------------------------------------------
 A shot's state of the rule above must fit a block's 64 KiB of LDS (about 7000 nodes) and a :class:`DecodingGraph` has at most
@@ -183,6 +218,9 @@ MAX_GRAPH = 65535  # nodes, and edges: uint16 indices on the device
 MAX_CAP = 14       # of an edge: the device counts grown[e] in 4 bits and may pass the cap by one
 SOFT_OUTPUTS = ("rounds", "full_edges", "largest_cluster", "correction_weight")  # the columns of soft_outputs(), the device's metric 0 .. 3
 MAX_SOFT_BINS = 1024
+MAX_MATCH_NODES = 2048   # of a graph with a match table: uint32 + uint64 per pair of nodes
+MAX_MATCH_DEFECTS = 12   # K of cluster matching at most: 2^K subsets of a cluster's defects in LDS
+MATCH_INF = 0x7FFFFFFF   # a distance of the match table: no path
 
 
 def _graph_limit(limit) -> int:
@@ -489,6 +527,19 @@ class DecodingGraph:
             return np.full(self.n_edges, top, np.uint8)
         return np.clip(np.rint(top * L / L.max()), 1, top).astype(np.uint8)
 
+    def match_weights(self, scale: int = 1000) -> np.ndarray:
+        """``uint16[n_edges]``: the weights of cluster matching from ``edge_p`` (module docstring), 1 .. ``scale``; ``scale`` is
+        an int in 1 .. 65535."""
+        if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, np.integer)) or not 1 <= scale <= 65535:
+            raise ValueError(f"scale = {scale!r}: an int in 1 .. 65535")
+        if not self.n_edges:
+            return np.zeros(0, np.uint16)
+        q = np.clip(self.edge_p.astype(np.float64), 1e-12, 0.5)
+        L = np.log((1.0 - q) / q)
+        if L.max() == 0:
+            return np.ones(self.n_edges, np.uint16)
+        return np.clip(np.rint(int(scale) * L / L.max()), 1, int(scale)).astype(np.uint16)
+
     @staticmethod
     def _herald_bits(form) -> dict:
         """``{error bit: herald detector column}`` by the criterion of the module docstring."""
@@ -594,6 +645,15 @@ def uf_shot_bytes(n_nodes: int, n_edges: int, weighted: bool) -> int:
     w32 = max(1, (n_edges + 31) // 32)
     grown = max(1, (n_edges + 7) // 8) if weighted else w32
     return a16(2 * n_nodes) + a16(4 * n_nodes) + 2 * a16(n_nodes) + a16(4 * grown) + a16(4 * w32) + a16(2 * w32) + 16
+
+
+def uf_match_shot_bytes(n_nodes: int, n_edges: int, weighted: bool, max_defects: int) -> int:
+    """The LDS bytes of one shot's state on a cluster-matching handle: :func:`uf_shot_bytes` and, for the dynamic program over
+    the ``2^K`` subsets of a cluster's ``K = max_defects`` defects, a uint32 cost and a byte (the candidate that won) per subset,
+    the cluster's defects (uint16) and their distances, uint32 ``[K, K + 1]`` (the boundary's in the last column)."""
+    a16 = lambda x: (x + 15) // 16 * 16  # noqa: E731
+    K = int(max_defects)
+    return uf_shot_bytes(n_nodes, n_edges, weighted) + a16(4 << K) + a16(1 << K) + a16(2 * K) + a16(4 * K * (K + 1))
 
 
 def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray:
@@ -720,7 +780,8 @@ class UnionFindDecoder(_RowDecoder):
     ``num_observables`` observables (default: as many as the masks of the graph use, at least one; at most 64).
     ``decode`` / ``missed`` have the signatures of :class:`LookupDecoder`; they decode each distinct syndrome once.
     ``edge_caps``: an integer per edge in 1 .. 14 for weighted growth (kept as uint8 in ``self.edge_caps``), ``None`` for the
-    unweighted decoder (a cap of 2 everywhere)."""
+    unweighted decoder (a cap of 2 everywhere).  ``match_defects`` / ``match_weights`` are ``None`` unless the decoder comes from
+    :meth:`with_cluster_matching`."""
 
     def __init__(self, graph: DecodingGraph, num_observables: int | None = None, edge_caps=None):
         used = int(np.bitwise_or.reduce(graph.edge_obs)) if graph.n_edges else 0
@@ -741,6 +802,7 @@ class UnionFindDecoder(_RowDecoder):
             edge_caps = caps.astype(np.uint8)
         self.graph, self._n_obs, self.edge_caps = graph, n_obs, edge_caps
         self.soft_output, self.soft_bins = None, None   # the metric count() bins, and into how many bins (with_soft_output)
+        self.match_defects, self.match_weights = None, None   # K and the weights of cluster matching (with_cluster_matching)
         self._cache: dict = {}   # packed row of detectors -> (prediction, missed, flipped edges, rounds, full edges, largest cluster)
 
     @classmethod
@@ -758,13 +820,152 @@ class UnionFindDecoder(_RowDecoder):
             raise ValueError(f"metric = {metric!r}: one of {', '.join(SOFT_OUTPUTS)}")
         if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= MAX_SOFT_BINS:
             raise ValueError(f"bins = {bins!r}: an int in 2 .. {MAX_SOFT_BINS}")
+        if self.match_defects is not None:
+            raise ValueError("a cluster-matching decoder has no soft output")
         out = object.__new__(UnionFindDecoder)
         out.__dict__.update(self.__dict__)  # (the cache too: what a syndrome decodes to does not depend on the metric)
         out.soft_output, out.soft_bins = metric, int(bins)
         return out
 
+    def with_cluster_matching(self, max_defects: int = 10, weights=None) -> "UnionFindDecoder":
+        """The decoder of the same graph, caps and observables that corrects every cluster of at most ``max_defects`` defects
+        (an int in 1 .. 12) by the minimum-weight matching of its defects ("Cluster matching" in the module docstring) under
+        ``weights``: integers ``[n_edges]`` in 1 .. 65535, default ``graph.match_weights()``.  Its predictions differ, so its
+        cache is a new one."""
+        K = max_defects
+        if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_MATCH_DEFECTS:
+            raise ValueError(f"max_defects = {K!r}: an int in 1 .. {MAX_MATCH_DEFECTS}")
+        if self.soft_output is not None:
+            raise ValueError("a decoder with a soft output takes no cluster matching")
+        g = self.graph
+        if g.n_heralds:
+            raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
+        if g.n_nodes > MAX_MATCH_NODES:
+            raise NotImplementedError(f"{g.n_nodes} nodes (a match table has at most {MAX_MATCH_NODES}: 12 bytes per pair of nodes)")
+        w = g.match_weights() if weights is None else np.asarray(weights)
+        if w.shape != (g.n_edges,) or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError(f"weights must be integers of shape ({g.n_edges},), got {w.dtype} {w.shape}")
+        if len(w) and (w.min() < 1 or w.max() > 65535):
+            bad = int(np.flatnonzero((w < 1) | (w > 65535))[0])
+            raise ValueError(f"edge {bad} has match weight {int(w[bad])} (1 .. 65535)")
+        out = object.__new__(UnionFindDecoder)
+        out.__dict__.update(self.__dict__)
+        out.match_defects, out.match_weights = int(K), w.astype(np.uint16)
+        out._cache, out._table = {}, None
+        return out
+
     def info(self) -> dict:
         return self.graph.info()
+
+    def _matching(self, what: str):
+        if self.match_defects is None:
+            raise ValueError(f"{what} needs a cluster-matching decoder: with_cluster_matching(max_defects, weights)")
+
+    def match_table(self):
+        """``(dist uint32[N, N], mask uint64[N, N])``: the match table of ``match_weights`` ("Match table" in the module
+        docstring), built once.  Distances relax over the arcs into every node to their least fixpoint (no arc leaves node 0);
+        the parent is the first arc, in edge order, that attains the distance; masks follow the parents."""
+        self._matching("match_table()")
+        if self._table is not None:
+            return self._table
+        g = self.graph
+        N, E = g.n_nodes, g.n_edges
+        eu, ev, w = g.edge_u.astype(np.int64), g.edge_v.astype(np.int64), self.match_weights.astype(np.int64)
+        # the arcs x -> v, sorted by (v, edge): v from u unless u is the boundary, u from v always (v >= 1)
+        fwd = np.flatnonzero(eu != 0)
+        tgt = np.concatenate([ev[fwd], eu])
+        src = np.concatenate([eu[fwd], ev])
+        edge = np.concatenate([fwd, np.arange(E)])
+        order = np.lexsort((edge, tgt))
+        tgt, src, edge = tgt[order], src[order], edge[order]
+        has = np.flatnonzero(np.bincount(tgt, minlength=N) > 0)      # the nodes an arc enters
+        start = np.searchsorted(tgt, has)                            # where their arcs begin
+        big = np.int64(1) << 40
+        dist_all, mask_all = np.full((N, N), MATCH_INF, np.uint32), np.zeros((N, N), np.uint64)
+        block = max(1, (1 << 22) // max(1, len(tgt)))   # source rows at a time: [block, arcs] candidates
+        for lo in range(0, N, block):
+            own = np.arange(lo, min(N, lo + block))      # the sources of this block, row k is source own[k]
+            B, at = len(own), np.arange(len(own))
+            dist = np.full((B, N), big, np.int64)
+            dist[at, own] = 0
+            while len(tgt):
+                cand = dist[:, src] + w[edge][None, :]
+                new = dist.copy()
+                new[:, has] = np.minimum(dist[:, has], np.minimum.reduceat(cand, start, axis=1))
+                if np.array_equal(new, dist):
+                    break
+                dist = new
+            finite = dist < big
+            parent = np.full((B, N), -1, np.int64)   # the arc
+            if len(tgt):
+                cand = dist[:, src] + w[edge][None, :]
+                hit = (cand == dist[:, tgt]) & finite[:, src] & finite[:, tgt]
+                first = np.minimum.reduceat(np.where(hit, np.arange(len(tgt))[None, :], len(tgt)), start, axis=1)
+                parent[:, has] = np.where(first < len(tgt), first, -1)
+            parent[at, own] = -1
+            known = np.zeros((B, N), np.bool_)
+            known[at, own] = True
+            assert ((parent >= 0) == (finite & ~known)).all()
+            mask = np.zeros((B, N), np.uint64)
+            rows, cols = np.nonzero(parent >= 0)
+            while len(rows):
+                arc = parent[rows, cols]
+                ready = known[rows, src[arc]]
+                assert ready.any(), "the parent edges are no tree"
+                r, c, k = rows[ready], cols[ready], arc[ready]
+                mask[r, c] = mask[r, src[k]] ^ g.edge_obs[edge[k]]
+                known[r, c] = True
+                rows, cols = rows[~ready], cols[~ready]
+            dist_all[own] = np.where(finite, dist, MATCH_INF).astype(np.uint32)
+            mask_all[own] = mask
+        self._table = (dist_all, mask_all)
+        return self._table
+
+    def _match_cluster(self, defects):
+        """``(cost, mask, pairs)`` of the dynamic program of the module docstring over the defect nodes ``defects`` (ascending,
+        at most 12): ``pairs`` lists ``(a_i, a_j)`` and, for a defect matched to the boundary, ``(a_i, 0)``.  The cost is ``None``
+        when no pairing is finite."""
+        self._matching("_match_cluster()")
+        dist, mask = self.match_table()
+        a = [int(x) for x in defects]
+        m = len(a)
+        if m > MAX_MATCH_DEFECTS or any(x >= y for x, y in zip(a, a[1:])) or (m and (a[0] < 1 or a[-1] >= self.graph.n_nodes)):
+            raise ValueError(f"defects: at most {MAX_MATCH_DEFECTS} ascending nodes in 1 .. {self.graph.n_nodes - 1}")
+        f = [(0, 0, None)] + [None] * ((1 << m) - 1)   # (cost, mask, (what it is built on, the pair)); None: infinite
+        for S in range(1, 1 << m):
+            i = (S & -S).bit_length() - 1
+            R = S & (S - 1)
+            cands = [(R, 0)] + [(R ^ (1 << j), a[j]) for j in range(i + 1, m) if (R >> j) & 1]
+            best = None
+            for base, other in cands:
+                d = int(dist[a[i], other])
+                if f[base] is None or d == MATCH_INF:
+                    continue
+                if best is None or f[base][0] + d < best[0]:
+                    best = (f[base][0] + d, f[base][1] ^ int(mask[a[i], other]), (base, (a[i], other)))
+            f[S] = best
+        S, pairs = (1 << m) - 1, []
+        if f[S] is None:
+            return None, 0, []
+        while S:
+            base, pair = f[S][2]
+            pairs.append(pair)
+            S = base
+        return f[-1][0], f[-1][1], pairs
+
+    def match_counts(self, dets):
+        """``(clusters_matched, clusters_peeled)`` over the rows of ``dets`` that are decoded (a defect, no miss): what the
+        device counts in ``info()["clusters_matched"]`` and ``["clusters_peeled"]``."""
+        self._matching("match_counts()")
+        entries = [e for e in self._decoded(dets) if e is not None]
+        return sum(e[6] for e in entries), sum(e[7] for e in entries)
+
+    def flipped_edges(self, dets) -> list:
+        """Per row the edges of its correction (the base class's); a cluster-matching decoder has none: a matched cluster is
+        corrected by paths of the match table."""
+        if self.match_defects is not None:
+            raise ValueError("a cluster-matching decoder has no flipped edges: a matched cluster is corrected by paths of the match table")
+        return super().flipped_edges(dets)
 
     # -- the numpy statement ---------------------------------------------------------------------------------------------
     def _decode_one(self, defects: np.ndarray, erased_edges=()):
@@ -794,7 +995,8 @@ class UnionFindDecoder(_RowDecoder):
                 break
             new = np.minimum(cap, grown + active[eu] + active[ev]).astype(np.int8)
             if np.array_equal(new, grown):
-                return 0, True, np.zeros(0, np.int64), rounds, int(f.sum()), int(np.bincount(label).max())
+                return (0, True, np.zeros(0, np.int64), rounds, int(f.sum()), int(np.bincount(label).max())) + \
+                    ((0, 0) if self.match_defects is not None else ())
             grown, rounds = new, rounds + 1
         soft = (int((grown == cap).sum()), int(np.bincount(label).max()))  # (label: the clusters of the full edges)
         # the forest: levels from the roots, the parent edge the smallest-index edge to the level above
@@ -816,7 +1018,7 @@ class UnionFindDecoder(_RowDecoder):
             depth += 1
         # peeling, from the deepest level up
         s = defect.copy()
-        prediction, flipped = 0, []
+        prediction, flipped, children = 0, [], []
         for lv in range(depth, 0, -1):
             for v in np.flatnonzero((level == lv) & s):
                 e = int(parent[v])
@@ -824,7 +1026,24 @@ class UnionFindDecoder(_RowDecoder):
                 s[ev[e]] ^= True
                 prediction ^= int(g.edge_obs[e])
                 flipped.append(e)
+                children.append(int(v))
         assert not s[1:].any(), "the correction does not reproduce the syndrome"
+        if self.match_defects is not None:
+            # cluster matching: small clusters by the dynamic program, of the others the flips whose child node lies in them
+            prediction = matched = peeled = 0
+            for r in np.unique(label[defect]):
+                ds = np.flatnonzero(defect & (label == r))
+                if len(ds) <= self.match_defects:
+                    cost, mask, _ = self._match_cluster(ds)
+                    assert cost is not None, "a matched cluster has no finite pairing"
+                    prediction ^= mask
+                    matched += 1
+                else:
+                    for e, v in zip(flipped, children):
+                        if label[v] == r:
+                            prediction ^= int(g.edge_obs[e])
+                    peeled += 1
+            return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft + (matched, peeled)
         return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft
 
     def _decode_bits(self, bits: np.ndarray):
@@ -836,6 +1055,8 @@ class UnionFindDecoder(_RowDecoder):
     def soft_outputs(self, dets) -> np.ndarray:
         """int64 ``[n, 4]``: per row ``rounds``, ``full_edges``, ``largest_cluster`` and ``correction_weight`` ("Soft outputs" in
         the module docstring); a row without defects is all zero."""
+        if self.match_defects is not None:
+            raise ValueError("a cluster-matching decoder has no soft outputs")
         out = np.zeros((len(np.asarray(dets)), 4), dtype=np.int64)
         for r, e in enumerate(self._decoded(dets)):
             if e is not None:
@@ -853,6 +1074,9 @@ class UnionFindDecoder(_RowDecoder):
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _handle(self, hp, n_cols: int):
+        if self.match_defects is not None:
+            h = hp.uf_create_matching(self.graph, n_cols, self.match_weights, self.match_defects, self.edge_caps)
+            return h, hp.uf_decode_device, hp.uf_destroy
         return hp.uf_create(self.graph, n_cols, self.edge_caps), hp.uf_decode_device, hp.uf_destroy
 
     def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
