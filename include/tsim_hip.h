@@ -698,6 +698,20 @@ int tsim_uf_create_matching(int32_t device, const tsim_uf_desc *desc, const uint
 /* The match table of a handle of tsim_uf_create_matching, to the host: dist (uint32[n_nodes * n_nodes], 0x7FFFFFFF: no path)
  * and mask (uint64[n_nodes * n_nodes]), row a = source a.  TSIM_EINVAL for another handle or a NULL.  Synchronous. */
 int tsim_uf_match_table(tsim_uf *h, uint32_t *dist, uint64_t *mask);
+/* Cluster matching with the complementary gap of one observable ("Complementary gap" in the module docstring of
+ * tsim_amd/decode.py): everything tsim_uf_create_matching does, then the class table dist2 (uint32[n_nodes * n_nodes * 2]:
+ * per pair of nodes the least weight of a walk whose bit `observable` of edge_obs XORs to 0, and to 1; 8 bytes per pair, 32 MB
+ * at 2048 nodes) is built on the device and W0, the lightest logical without a defect, is taken from it.  observable is
+ * 0 .. 63 (TSIM_EINVAL), checked with every other argument before any device call.  A shot's state holds both dynamic
+ * programs (13 bytes per subset, 12 bytes per pair of a cluster's defects): TSIM_ENOTSUP when it does not fit a block's
+ * 64 KiB of LDS.  tsim_uf_decode_device on the handle decodes as on a handle of tsim_uf_create_matching, tsim_uf_info [13] ..
+ * [15] mean the same, tsim_uf_decode_soft_device is TSIM_EINVAL; tsim_uf_decode_gap_device is the call it adds. */
+int tsim_uf_create_matching_gap(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const uint16_t *match_w,
+                                int32_t max_defects, int32_t observable, tsim_uf **out);
+/* The class table of a handle of tsim_uf_create_matching_gap, to the host: dist2[(a * n_nodes + v) * 2 + b] (0x7FFFFFFF: no
+ * walk), and *w0 = W0, -1 when no source reaches the boundary in both classes.  TSIM_EINVAL for another handle or a NULL.
+ * Synchronous. */
+int tsim_uf_gap_table(tsim_uf *h, uint32_t *dist2, int64_t *w0);
 void tsim_uf_destroy(tsim_uf *h);
 /* out[0] nodes, [1] edges, [2] LDS bytes per shot, [3] shots (waves) per block, [4] kernel launches so far, [5] the most
  * growth rounds a row took, [6] bytes of device memory, [7] rows decoded in LDS (kept rows with a defect), [8] n_cols,
@@ -728,6 +742,17 @@ int tsim_uf_decode_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t 
 int tsim_uf_decode_soft_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
                                const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
                                int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream);
+/* tsim_uf_decode_device by a handle of tsim_uf_create_matching_gap, with the complementary gap of every row.  Everything up to
+ * d_pred means the same and accumulates the same; the predictions are those of tsim_uf_decode_device.  A kept row with a
+ * defect that is no miss has gap = min(gap_cap, the least gap of its clusters): |g0 - g1| of a matched cluster whose two
+ * classes are finite, gap_cap when one is, 0 for a peeled cluster; a miss has gap 0.  The DEFICIT of a row is gap_cap - gap,
+ * 0 for a row that is not kept and for a kept row without a defect; its bin is min(deficit / gap_step, n_bins - 1).  d_hist
+ * (uint64[2 * n_bins], 8-byte aligned, required, never zeroed here) ACCUMULATES as the soft call's; d_gap: NULL, or
+ * uint32[n] for the deficits.  gap_cap and gap_step are 1 .. 2^31 - 2, n_bins 2 .. 1024: a bad one, a NULL d_hist or another
+ * kind of handle is TSIM_EINVAL before any device call; n == 0 returns 0 without a launch. */
+int tsim_uf_decode_gap_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                              const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                              int64_t gap_cap, int64_t gap_step, int32_t n_bins, uint64_t *d_hist, uint32_t *d_gap, void *stream);
 
 /* ---- sliding-window union-find decoding of long runs (count(decoder=WindowedUnionFindDecoder)) -----------------------
  * `global` is a decoding graph as above without heralds (with heralds: tsim_ufw_create_heralds below), bounded by int32 only; edge_cap as tsim_uf_create_weighted (NULL:

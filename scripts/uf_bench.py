@@ -5,6 +5,7 @@
     python scripts/uf_bench.py --resolution 4        # weighted against unweighted growth: d = 5, 9, 15
     python scripts/uf_bench.py --soft largest_cluster  # the price of a soft output: d = 5, 9
     python scripts/uf_bench.py --match 10 --resolution 4  # the price of cluster matching: d = 5, 9
+    python scripts/uf_bench.py --gap --resolution 4  # the price of the complementary gap, and what it rejects: d = 5, 9
 
 Per distance the ``method="faults"`` sampler counts ``--shots`` shots per call in batches of 10^6, once without a decoder and
 once with ``decoder=UnionFindDecoder.from_circuit(circuit)``, alternating, each warmed up first; the time is a host clock
@@ -28,6 +29,12 @@ curve.  The leg stops when the two calls disagree on a counter or the histograms
 (weighted with ``--resolution R``) and with its ``with_cluster_matching(K)``, alternating over the same seeded rows: both rates,
 their ratio, both decoded error counts, and what ``tsim_uf_info`` says after ``--info-rows`` rows (LDS per shot, shots per block,
 clusters matched and peeled).  The leg stops when the two calls disagree on kept rows, raw flips or misses.
+
+``--gap`` is a leg of its own (``--circuits`` then defaults to d5,d9): the same ``count()`` call with the
+cluster-matching decoder (``--match K``, default 10; weighted with ``--resolution R``) and with its ``with_gap_output(0, --bins)``,
+alternating over the same seeded rows: both rates and their ratio, the histograms, and the rejection table - the errors left among
+the shots kept at 99, 95, 90 and 80 % by the gap, against ``largest_cluster`` of the decoder without matching over the same rows.
+The leg stops when the two calls disagree on a counter or the histograms do not add up to them.
 """
 
 from __future__ import annotations
@@ -195,6 +202,59 @@ def match_leg(args) -> None:
             device_bytes=info["device_bytes"])), flush=True)
 
 
+def gap_leg(args) -> None:
+    K = 10 if args.match is None else args.match
+    for name in (args.circuits or "d5,d9").split(","):
+        d = int(name[1:])
+        c = memory(d, args.p)
+        plain = (UnionFindDecoder.from_circuit(c) if args.resolution is None
+                 else UnionFindDecoder.from_circuit(c, weights="probability", resolution=args.resolution))
+        um = plain.with_cluster_matching(K)
+        decoders = {"matching": um, "gap": um.with_gap_output(0, args.bins)}
+        def sampler():  # a fresh one per call: every call counts the same seeded rows
+            return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+        times, last = {m: [] for m in decoders}, {}
+        for m, uf in decoders.items():
+            sampler().count(args.shots, batch_size=10**6, decoder=uf)  # warm-up at the timed size
+        for _ in range(args.reps):
+            for m, uf in decoders.items():
+                s = sampler()
+                t0 = time.perf_counter()
+                last[m] = s.count(args.shots, batch_size=10**6, decoder=uf)
+                times[m].append(time.perf_counter() - t0)
+        a, b = last["matching"], last["gap"]
+        if (a.kept, a.kept_with_observable_flip, a.decoded_errors, a.decoder_misses) != (b.kept, b.kept_with_observable_flip, b.decoded_errors,
+                                                                                         b.decoder_misses):
+            sys.exit("uf_bench: the gap decoder did not count what the matching one counted")
+        if int(b.soft_kept.sum()) != b.kept or int(b.soft_errors.sum()) != b.decoded_errors:
+            sys.exit("uf_bench: the histograms do not add up to the counters")
+        # the rejection table: the errors left among the shots kept when each signal discards the least sure ones
+        other = sampler().count(args.shots, batch_size=10**6, decoder=plain.with_soft_output("largest_cluster", args.bins))
+        table = {}
+        for signal, counts in (("gap", b), ("largest_cluster", other)):
+            accepted, errors = counts.rejection_curve()
+            for keep in (0.99, 0.95, 0.90, 0.80):
+                t = int((accepted >= keep * counts.kept).argmax())  # the first bin that keeps at least that much
+                table[f"{signal}@{keep:.2f}"] = dict(bin=t, kept=int(accepted[t]), errors=int(errors[t]), rate=float(errors[t] / accepted[t]))
+        hp = s._hip()
+        ug = decoders["gap"]
+        h, _, destroy = ug._handle(hp, ug.num_detectors + ug.num_observables)
+        try:
+            info = hp.uf_info(h)
+        finally:
+            destroy(h)
+        rate = {m: args.shots / statistics.median(t) for m, t in times.items()}
+        print(json.dumps(dict(
+            case=name, leg="gap", max_defects=K, bins=args.bins, gap_cap=ug.gap_cap, gap_step=ug.gap_step, resolution=args.resolution, p=args.p,
+            shots=args.shots, reps=args.reps, graph=plain.info(), median_s={m: statistics.median(t) for m, t in times.items()},
+            min_s={m: min(t) for m, t in times.items()}, max_s={m: max(t) for m, t in times.items()}, shots_per_s=rate,
+            gap_over_matching=rate["gap"] / rate["matching"], kept=b.kept, raw_flips=b.kept_with_observable_flip,
+            decoded_errors=dict(matching=a.decoded_errors, gap=b.decoded_errors, plain=other.decoded_errors), misses=b.decoder_misses,
+            lds_bytes_per_shot=info["lds_bytes_per_shot"], shots_per_block=info["shots_per_block"], device_bytes=info["device_bytes"],
+            rejection=table, soft_kept=b.soft_kept.tolist(), soft_errors=b.soft_errors.tolist())), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shots", type=int, default=10**7)
@@ -209,10 +269,14 @@ def main() -> None:
     ap.add_argument("--bins", type=int, default=64, help="the bins of --soft")
     ap.add_argument("--match", type=int, default=None, metavar="K",
                     help="the leg that runs a decoder with cluster matching of at most K defects against the same decoder without")
+    ap.add_argument("--gap", action="store_true",
+                    help="the leg that runs the cluster-matching decoder (--match K, default 10) with the complementary gap against the same without")
     args = ap.parse_args()
     _lib.load()
     if _lib.device_count() < 1:
         sys.exit("uf_bench: no HIP device - nothing is measured without one")
+    if args.gap:
+        return gap_leg(args)
     if args.match is not None:
         return match_leg(args)
     if args.soft is not None:

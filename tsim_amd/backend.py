@@ -492,6 +492,43 @@ class HipProgram:
                                                      int(min(max(max_defects, -1), 0x7FFFFFFF)), C.byref(h)), "tsim_uf_create_matching")
         return h.value
 
+    def uf_create_matching_gap(self, graph, n_cols: int, match_weights, max_defects: int, observable: int, caps=None) -> int:
+        """:meth:`uf_create_matching` with the class table of ``observable`` (0 .. 63) for the complementary gap
+        (``tsim_uf_create_matching_gap``; "Complementary gap" in the module docstring of :mod:`tsim_amd.decode`).  The handle
+        decodes by :meth:`uf_decode_device` as a cluster-matching one, and by :meth:`uf_decode_gap_device`."""
+        desc, d_caps, her, _keep = self._uf_graph_args(graph, n_cols, caps)
+        if her is not None:
+            raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
+        w = np.ascontiguousarray(match_weights)
+        if w.shape != (graph.n_edges,) or not np.issubdtype(w.dtype, np.integer) or (w.size and (w.min() < 0 or w.max() > 65535)):
+            raise ValueError(f"match_weights: {graph.n_edges} integers in 1 .. 65535 expected")
+        w = np.concatenate([w.astype(np.uint16), np.zeros(1, np.uint16)])  # (never an empty buffer)
+        clip = lambda x: int(min(max(x, -1), 0x7FFFFFFF))  # noqa: E731
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_uf_create_matching_gap(self.device, C.byref(desc), d_caps, C.c_void_p(w.ctypes.data), clip(max_defects),
+                                                         clip(observable), C.byref(h)), "tsim_uf_create_matching_gap")
+        return h.value
+
+    def uf_gap_table(self, handle: int):
+        """``(dist2 uint32[n_nodes, n_nodes, 2], W0 or None)``: the class table the handle of :meth:`uf_create_matching_gap` built
+        on the device, and the lightest logical without a defect (``tsim_uf_gap_table``)."""
+        n_nodes = self.uf_info(handle)["n_nodes"]
+        dist2, w0 = np.zeros((n_nodes, n_nodes, 2), np.uint32), C.c_int64(0)
+        _lib.check(self._lib.tsim_uf_gap_table(C.c_void_p(handle), _lib.ptr(dist2), C.byref(w0)), "tsim_uf_gap_table")
+        return dist2, None if w0.value < 0 else int(w0.value)
+
+    def uf_decode_gap_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, gap_cap: int,
+                             gap_step: int, n_bins: int, d_hist: int, *, d_gap: int = 0, d_pred: int = 0, d_xor: int = 0, d_test: int = 0,
+                             stream: int = 0) -> None:
+        """:meth:`uf_decode_device` by a handle of :meth:`uf_create_matching_gap`, with the complementary gap
+        (``tsim_uf_decode_gap_device``): the deficit ``gap_cap - gap`` of every row is binned in steps of ``gap_step`` into
+        ``n_bins`` bins, the kept rows and the wrong ones among them ACCUMULATE into ``uint64[2 * n_bins]`` at ``d_hist``;
+        ``d_gap``: ``uint32[n]`` for the deficits."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
+        clip = lambda x: int(min(max(x, -1), 1 << 62))  # noqa: E731
+        self._uf_decode("tsim_uf_decode_gap_device", handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test, stream,
+                        clip(gap_cap), clip(gap_step), int(min(max(n_bins, -1), 0x7FFFFFFF)), ptr(d_hist), ptr(d_gap))
+
     def uf_match_table(self, handle: int):
         """``(dist uint32[n_nodes, n_nodes], mask uint64[n_nodes, n_nodes])``: the match table the handle of
         :meth:`uf_create_matching` built on the device (``tsim_uf_match_table``)."""

@@ -57,7 +57,8 @@ class ShotCounts:
     pattern found no room (``sum(pattern_counts) + pattern_overflow == kept``; the patterns present are exact).
     ``decoded_errors`` / ``decoder_misses`` (``None`` without a decoder): kept shots whose observables differ from the
     decoder's prediction, and kept shots whose syndrome the decoder does not know (it predicts no flip for them).
-    ``soft_output`` (``None`` unless the decoder is a ``UnionFindDecoder.with_soft_output(metric, bins)``): the metric's name;
+    ``soft_output`` (``None`` unless the decoder is a ``UnionFindDecoder.with_soft_output(metric, bins)`` or a cluster-matching
+    one ``with_gap_output(...)``, whose metric is ``"gap"`` and whose value is the deficit ``(gap_cap - gap) // gap_step``): the metric's name;
     then ``soft_kept[b]`` (int64 ``[bins]``) are the kept shots whose metric falls into bin ``b = min(value, bins - 1)`` and
     ``soft_errors[b]`` those of them that count in ``decoded_errors`` (``soft_kept.sum() == kept``,
     ``soft_errors.sum() == decoded_errors``); :meth:`rejection_curve` sums them up.  ``corrected`` (``count(decoder=...,
@@ -531,7 +532,7 @@ class _DeviceTally:
                 self.d_decoded = self._upload(np.zeros(3, dtype=np.uint64))
                 if self.soft:
                     self.d_soft_hist = self._upload(np.zeros(2 * self.soft[1], dtype=np.uint64))
-                    self._dec = (self._dec[0], lambda *a, **k: hp.uf_decode_soft_device(*a, *self.soft, self.d_soft_hist.ptr, **k), self._dec[2])
+                    self._dec = (self._dec[0], decoder._soft_call(hp, self.d_soft_hist.ptr), self._dec[2])
             self.d_counts = self._upload(np.zeros(counters_length(self.n_cols, len(self.hc)), dtype=np.uint64))
             self.d_xor = self._upload(self._row(xor_bits)) if xor_bits is not None and np.any(xor_bits) else None
             self.d_test = self._upload(self._row(test_bits)) if test_bits is not None else None

@@ -13,6 +13,8 @@ struct tsim_uf {
   int max_cap = 0;  // 0: unweighted
   int n_heralds = 0;
   ufk::TableArgs table{};  // cluster matching: the match table (a.match_k != 0)
+  ufk::GapTableArgs gtable{};  // the complementary gap: the class table (a.gap != 0) ...
+  int64_t w0 = -1;             // ... and the lightest logical without a defect, -1: none
   tsimh::Uploads up;  // the tables a points to
 };
 
@@ -24,13 +26,13 @@ extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc,
   return tsim_uf_create_heralds(device, desc, edge_cap, nullptr, out);
 }
 
-// every create call; match_w != NULL: tsim_uf_create_matching, with max_defects
+// every create call; match_w != NULL: tsim_uf_create_matching, with max_defects; gap_obs >= 0: tsim_uf_create_matching_gap
 static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her, const uint16_t *match_w,
-                     int32_t max_defects, tsim_uf **out);
+                     int32_t max_defects, int32_t gap_obs, tsim_uf **out);
 
 extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
                                       tsim_uf **out) {
-  return uf_create(device, desc, edge_cap, her, nullptr, 0, out);
+  return uf_create(device, desc, edge_cap, her, nullptr, 0, -1, out);
 }
 
 extern "C" int tsim_uf_create_matching(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const uint16_t *match_w,
@@ -40,11 +42,22 @@ extern "C" int tsim_uf_create_matching(int32_t device, const tsim_uf_desc *desc,
   if (!match_w) return tsim_fail(TSIM_EINVAL, "match_w is NULL");
   if (max_defects < 1 || max_defects > ufk::kMaxMatchDefects)
     return tsim_fail(TSIM_EINVAL, "max_defects = %d (1 .. %d)", max_defects, ufk::kMaxMatchDefects);
-  return uf_create(device, desc, edge_cap, nullptr, match_w, max_defects, out);
+  return uf_create(device, desc, edge_cap, nullptr, match_w, max_defects, -1, out);
+}
+
+extern "C" int tsim_uf_create_matching_gap(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const uint16_t *match_w,
+                                           int32_t max_defects, int32_t observable, tsim_uf **out) {
+  if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!match_w) return tsim_fail(TSIM_EINVAL, "match_w is NULL");
+  if (max_defects < 1 || max_defects > ufk::kMaxMatchDefects)
+    return tsim_fail(TSIM_EINVAL, "max_defects = %d (1 .. %d)", max_defects, ufk::kMaxMatchDefects);
+  if (observable < 0 || observable > 63) return tsim_fail(TSIM_EINVAL, "observable = %d (0 .. 63)", observable);
+  return uf_create(device, desc, edge_cap, nullptr, match_w, max_defects, observable, out);
 }
 
 static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her, const uint16_t *match_w,
-                     int32_t max_defects, tsim_uf **out) {
+                     int32_t max_defects, int32_t gap_obs, tsim_uf **out) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
   *out = nullptr;
   if (!desc) return tsim_fail(TSIM_EINVAL, "desc is NULL");
@@ -83,10 +96,12 @@ static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *ed
   a.w32 = std::max(1, (E + 31) / 32);
   a.w_cnt = edge_cap ? std::max(1, (E + 7) / 8) : 0;
   a.match_k = match_w ? max_defects : 0;
+  a.gap = match_w && gap_obs >= 0;
   const long long shot = ufk::layout(&a);
   if (16 + shot > ufk::kLdsBlock)
     return tsim_fail(TSIM_ENOTSUP, "one shot's state takes %lld bytes of LDS (%d nodes, %d edges%s), a block has %d", shot, N, E,
-                     match_w ? ", the dynamic program of max_defects" : "", ufk::kLdsBlock - 16);
+                     a.gap ? ", the dynamic programs of max_defects: the winners and the classes" : match_w ? ", the dynamic program of max_defects" : "",
+                     ufk::kLdsBlock - 16);
   a.shot_bytes = (int)shot;
   int per_cu = 1;
   ufh::choose_waves(shot, &a.waves, &per_cu);
@@ -139,6 +154,18 @@ static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *ed
       up.err = hipGetLastError();
     }
     a.mdist = t.dist, a.mmask = t.mask;
+    if (a.gap) {  // the class table, after it
+      ufk::GapTableArgs &g = h->gtable;
+      g.n_nodes = N, g.observable = gap_obs, g.edge_uv = a.edge_uv, g.edge_obs = a.edge_obs, g.w = t.w, g.adj_ptr = a.adj_ptr, g.adj_edge = a.adj_edge;
+      g.dist2 = static_cast<uint32_t *>(up.room(pairs * 2 * sizeof(uint32_t)));
+      g.w0 = static_cast<uint32_t *>(up.room((size_t)N * sizeof(uint32_t)));
+      up.bytes += (int64_t)(pairs * 8 + (size_t)N * 4);
+      if (up.err == hipSuccess) {
+        hipLaunchKernelGGL(ufk::k_gap_table, dim3(N), dim3(ufk::kTableThreads), ufk::gap_table_lds(N), nullptr, g);
+        up.err = hipGetLastError();
+      }
+      a.gdist = g.dist2;
+    }
   }
   if (her) {
     a.node_det = up.put(her_tab);
@@ -149,6 +176,12 @@ static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *ed
     a.hmask = a.dmask + mask_bytes;
   }
   if (up.err == hipSuccess) up.err = hipDeviceSynchronize();
+  if (up.err == hipSuccess && a.gap) {  // W0: the least of the sources' sums
+    std::vector<uint32_t> sums((size_t)N);
+    up.err = hipMemcpy(sums.data(), h->gtable.w0, sums.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    const uint32_t least = *std::min_element(sums.begin(), sums.end());
+    h->w0 = up.err == hipSuccess && least != ufk::kMatchInf ? (int64_t)least : -1;
+  }
   if (up.err != hipSuccess) {
     const hipError_t e = up.err;
     tsim_uf_destroy(h);
@@ -195,11 +228,17 @@ extern "C" int tsim_uf_info(tsim_uf *h, int64_t out[16]) {
 }
 
 namespace {
-struct SoftOut {  // what tsim_uf_decode_soft_device adds to tsim_uf_decode_device
+struct SoftOut {  // what tsim_uf_decode_soft_device adds to tsim_uf_decode_device; gap_cap != 0: what tsim_uf_decode_gap_device adds
   int metric, n_bins;
   uint64_t *d_hist;
-  uint32_t *d_soft;
+  uint32_t *d_soft;  // four values per row, or the gap call's deficit per row
+  uint32_t gap_cap = 0, gap_step = 0;
 };
+
+void uf_launch_gap(const ufk::Args &a, unsigned blocks, size_t lds, hipStream_t stream) {
+  if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, false, false, true, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+  else hipLaunchKernelGGL((ufk::k_uf<false, false, false, true, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+}
 
 template <bool Soft>
 void uf_launch(const ufk::Args &a, unsigned blocks, size_t lds, hipStream_t stream) {
@@ -217,13 +256,18 @@ void uf_launch(const ufk::Args &a, unsigned blocks, size_t lds, hipStream_t stre
 }
 }  // namespace
 
-// both decode entry points; soft == NULL: tsim_uf_decode_device
+// the decode entry points; soft == NULL: tsim_uf_decode_device
 static int uf_decode(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor, const uint8_t *d_test,
                      int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred, const SoftOut *soft, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "decoder is NULL");
   ufk::Args a = h->a;
   if (const int rc = ufh::check_rows(a, d_rows, n, row_bytes, obs_lo, obs_hi, d_counters, d_pred)) return rc;
-  if (soft) {
+  const bool gap = soft && soft->gap_cap;
+  if (gap) {
+    a.gap_cap = soft->gap_cap, a.gap_step = soft->gap_step;
+    a.n_bins = soft->n_bins;
+    a.hist = reinterpret_cast<unsigned long long *>(soft->d_hist);
+  } else if (soft) {
     if (a.match_k) return tsim_fail(TSIM_EINVAL, "a cluster-matching handle has no soft outputs");
     if (soft->metric < 0 || soft->metric > 3) return tsim_fail(TSIM_EINVAL, "metric = %d (0 rounds, 1 full_edges, 2 largest_cluster, 3 correction_weight)", soft->metric);
     if (soft->n_bins < 2 || soft->n_bins > 1024) return tsim_fail(TSIM_EINVAL, "n_bins = %d (2 .. 1024)", soft->n_bins);
@@ -237,7 +281,10 @@ static int uf_decode(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_b
   HIP_TRY(hipSetDevice(h->device));
   ufh::fill_rows(a, d_rows, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters);
   return ufh::launch_rows(a, d_rows, n, d_pred, h->grid, &h->launches, [&](ufk::Args &a, int64_t r0, unsigned blocks, size_t lds) {
-    if (soft) {
+    if (gap) {
+      a.soft = soft->d_soft ? soft->d_soft + r0 : nullptr;
+      uf_launch_gap(a, blocks, lds, (hipStream_t)stream);
+    } else if (soft) {
       a.soft = soft->d_soft ? soft->d_soft + 4 * r0 : nullptr;
       uf_launch<true>(a, blocks, lds, (hipStream_t)stream);
     } else {
@@ -257,6 +304,31 @@ extern "C" int tsim_uf_decode_soft_device(tsim_uf *h, const uint8_t *d_rows, int
                                           int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream) {
   const SoftOut soft{metric, n_bins, d_hist, d_soft};
   return uf_decode(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, d_pred, &soft, stream);
+}
+
+extern "C" int tsim_uf_decode_gap_device(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                         const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                         int64_t gap_cap, int64_t gap_step, int32_t n_bins, uint64_t *d_hist, uint32_t *d_gap, void *stream) {
+  if (gap_cap < 1 || gap_cap > 0x7FFFFFFEll) return tsim_fail(TSIM_EINVAL, "gap_cap = %lld (1 .. 2^31 - 2)", (long long)gap_cap);
+  if (gap_step < 1 || gap_step > 0x7FFFFFFEll) return tsim_fail(TSIM_EINVAL, "gap_step = %lld (1 .. 2^31 - 2)", (long long)gap_step);
+  if (n_bins < 2 || n_bins > 1024) return tsim_fail(TSIM_EINVAL, "n_bins = %d (2 .. 1024)", n_bins);
+  if (!d_hist || reinterpret_cast<uintptr_t>(d_hist) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_hist is NULL or not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_gap) % 4 != 0) return tsim_fail(TSIM_EINVAL, "d_gap is not 4-byte aligned");
+  if (!h) return tsim_fail(TSIM_EINVAL, "decoder is NULL");
+  if (!h->a.gap) return tsim_fail(TSIM_EINVAL, "the handle has no class table (tsim_uf_create_matching_gap makes one)");
+  SoftOut soft{0, n_bins, d_hist, d_gap};
+  soft.gap_cap = (uint32_t)gap_cap, soft.gap_step = (uint32_t)gap_step;
+  return uf_decode(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, d_pred, &soft, stream);
+}
+
+extern "C" int tsim_uf_gap_table(tsim_uf *h, uint32_t *dist2, int64_t *w0) {
+  if (!h || !dist2 || !w0) return tsim_fail(TSIM_EINVAL, "NULL argument");
+  if (!h->a.gap) return tsim_fail(TSIM_EINVAL, "the handle has no class table (tsim_uf_create_matching_gap makes one)");
+  const size_t pairs = (size_t)h->a.n_nodes * (size_t)h->a.n_nodes;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemcpy(dist2, h->gtable.dist2, pairs * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *w0 = h->w0;
+  return TSIM_OK;
 }
 
 extern "C" int tsim_uf_match_table(tsim_uf *h, uint32_t *dist, uint64_t *mask) {

@@ -47,6 +47,14 @@
 // subsets, keeping per subset the cost (uint32: at most 12 finite terms below 2^27 each, so the 64-bit sum of the rule fits) and
 // the candidate that won, and one lane walks the winners back from the full set, XORing the table's masks.  forest() and peel()
 // run only when a peeled cluster exists, and a flip counts only when its child node lies in one.
+// The complementary gap (k_uf<Weighted, false, false, true, true>, tsim_uf_create_matching_gap; "Complementary gap" in the docstring):
+// the winner program above runs as it is, and beside it, in the same layers, the class program g[S] = (least cost of a pairing
+// of S whose paths' class bits XOR to 0, to 1), a uint2 per subset in LDS, from the class distances of the cluster's pairs
+// (dist2 of tsim_uf_match.hip.h, a uint2 per pair, read from global memory into LDS with the distances).  A finite class
+// distance is below 2^28 and a pairing has at most 12 terms, so a finite cost is below 3 * 2^30 and kCostInf = 2^32 - 1 is never
+// reached by a sum.  The cluster's gap, the zero of a peeled cluster and of a miss fold into one wave-uniform number per row,
+// whose deficit cap - gap is binned as the soft kernel bins its metric.  The arrays exist only in the layout of such a handle
+// (Args::gap): a handle of tsim_uf_create_matching keeps its bytes per shot and its waves per block.
 // Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
 #pragma once
 #include "tsim_bitrows.hip.h"
@@ -101,6 +109,11 @@ struct Args {
   int off_mcost, off_mch, off_mcl, off_mpd;
   const uint32_t *mdist;       // [n_nodes * n_nodes] the match table: distances (kMatchInf: none) ...
   const unsigned long long *mmask;  // ... and the observables of the paths
+  // the complementary gap (k_uf<., false, false, true, true> only; 0 / NULL on other handles)
+  int gap;                     // 1 on a handle of tsim_uf_create_matching_gap: layout() adds the class program's arrays
+  int off_gcost, off_gpd;
+  uint32_t gap_cap, gap_step;  // G >= 1 and the width of a bin of the deficit G - gap
+  const uint32_t *gdist;       // [n_nodes * n_nodes * 2] the class table: the two distances of a pair side by side (8-byte aligned)
 };
 
 // the layout of one wave's state, shared by the host (sizes, limits) and the kernel
@@ -120,6 +133,10 @@ __host__ inline long long layout(Args *a) {
     a->off_mch = (int)at, at += a16(1ll << K);
     a->off_mcl = (int)at, at += a16(2 * K);
     a->off_mpd = (int)at, at += a16(4 * K * (K + 1));
+    if (a->gap) {  // the class program: two costs per subset, two distances per pair
+      a->off_gcost = (int)at, at += a16(8ll << K);
+      a->off_gpd = (int)at, at += a16(8 * K * (K + 1));
+    }
   }
   return at;
 }
@@ -149,6 +166,7 @@ struct State {
   uint32_t *mcost, *mpd;  // cluster matching only
   uint8_t *mch;
   uint16_t *mcl;
+  uint2 *gcost, *gpd;  // the complementary gap only: .x class 0, .y class 1
 };
 
 // a wave's state at `base`, by the offsets layout() has put into `a`
@@ -174,6 +192,13 @@ __device__ __forceinline__ State match_state_at(const Args &a, uint8_t *base) {
   st.mch = base + a.off_mch;
   st.mcl = reinterpret_cast<uint16_t *>(base + a.off_mcl);
   st.mpd = reinterpret_cast<uint32_t *>(base + a.off_mpd);
+  return st;
+}
+// the same with the arrays of the class program (a handle of tsim_uf_create_matching_gap)
+__device__ __forceinline__ State gap_state_at(const Args &a, uint8_t *base) {
+  State st = match_state_at(a, base);
+  st.gcost = reinterpret_cast<uint2 *>(base + a.off_gcost);
+  st.gpd = reinterpret_cast<uint2 *>(base + a.off_gpd);
   return st;
 }
 
@@ -445,8 +470,10 @@ __device__ __forceinline__ void mark_clusters(const Args &a, const State &st, in
 }
 
 // One matched cluster, of root r, by the whole wave: the mask of the dynamic program of the docstring over its defects, which
-// are the entries of label r in lp[from .. n_list).  The result is in lane 0 (0 in the other lanes).
-__device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st, int lane, int from, int n_list, int r) {
+// are the entries of label r in lp[from .. n_list).  The result is in lane 0 (0 in the other lanes).  Gap: *gap = min(*gap, the
+// cluster's gap) in every lane, the gap being |g0 - g1| of the class program at the full set, a.gap_cap when one class is infinite.
+template <bool Gap = false>
+__device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st, int lane, int from, int n_list, int r, uint32_t *gap = nullptr) {
   const int K = a.match_k;
   const size_t N = (size_t)a.n_nodes;
   int m = 0;
@@ -466,6 +493,14 @@ __device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st
     st.mpd[t] = a.mdist[(size_t)st.mcl[i] * N + (j < m ? (size_t)st.mcl[j] : 0)];
   }
   if (lane == 0) st.mcost[0] = 0;
+  if constexpr (Gap) {
+    for (int t = lane; t < m * W; t += 64) {
+      const int i = t / W, j = t % W;
+      if (j <= i) continue;
+      st.gpd[t] = reinterpret_cast<const uint2 *>(a.gdist)[(size_t)st.mcl[i] * N + (j < m ? (size_t)st.mcl[j] : 0)];
+    }
+    if (lane == 0) st.gcost[0] = make_uint2(0u, kCostInf);
+  }
   wsync();
   const int n_sets = 1 << m;
   for (int layer = 1; layer <= m; ++layer) {  // f[S] reads subsets of one and of two defects less
@@ -483,8 +518,28 @@ __device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st
       }
       st.mcost[S] = best;
       st.mch[S] = via;
+      if constexpr (Gap) {  // a pure minimum of costs: g[S][b] over the class cb of the pair's path and g[.][b ^ cb] of the rest
+        uint32_t g0 = kCostInf, g1 = kCostInf;
+        const auto offer = [&](const uint2 f, const uint2 d) {
+          if (f.x != kCostInf && d.x != kMatchInf) g0 = min(g0, f.x + d.x);
+          if (f.y != kCostInf && d.y != kMatchInf) g0 = min(g0, f.y + d.y);
+          if (f.x != kCostInf && d.y != kMatchInf) g1 = min(g1, f.x + d.y);
+          if (f.y != kCostInf && d.x != kMatchInf) g1 = min(g1, f.y + d.x);
+        };
+        offer(st.gcost[R], st.gpd[i * W + m]);
+        for (int rest = R; rest; rest &= rest - 1) {
+          const int j = __builtin_ctz(rest);
+          offer(st.gcost[R ^ (1 << j)], st.gpd[i * W + j]);
+        }
+        st.gcost[S] = make_uint2(g0, g1);
+      }
     }
     wsync();
+  }
+  if constexpr (Gap) {  // (one address for the wave: the number is wave-uniform)
+    const uint2 g = st.gcost[n_sets - 1];
+    const uint32_t mine = g.x != kCostInf && g.y != kCostInf ? (g.x > g.y ? g.x - g.y : g.y - g.x) : a.gap_cap;
+    *gap = min(*gap, mine);
   }
   uint64_t mask = 0;
   if (lane == 0)
@@ -499,13 +554,14 @@ __device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st
   return mask;
 }
 
-// every matched cluster, in the order of its smallest defect: the XOR of their masks, in lane 0
-__device__ __forceinline__ uint64_t match_clusters(const Args &a, const State &st, int lane, int n_list) {
+// every matched cluster, in the order of its smallest defect: the XOR of their masks, in lane 0; Gap: *gap as match_cluster
+template <bool Gap = false>
+__device__ __forceinline__ uint64_t match_clusters(const Args &a, const State &st, int lane, int n_list, uint32_t *gap = nullptr) {
   uint64_t mask = 0;
   for (int i = 0; i < n_list; ++i) {
     const int r = __builtin_amdgcn_readfirstlane((int)st.label[st.lp[i]]);
     if (__builtin_amdgcn_readfirstlane((int)st.par[r]) != 1) continue;  // (matched before, by an earlier defect of its)
-    mask ^= match_cluster(a, st, lane, i, n_list, r);
+    mask ^= match_cluster<Gap>(a, st, lane, i, n_list, r, gap);
     if (lane == 0) st.par[r] = 3;
     wsync();
   }
@@ -514,8 +570,8 @@ __device__ __forceinline__ uint64_t match_clusters(const Args &a, const State &s
 
 // one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform, and so
 // are, with Soft, soft[0 .. 2]: full edges, largest cluster, correction weight; with Match, soft[0 .. 1]: the clusters matched
-// and peeled
-template <bool Weighted, bool Heralds, bool Soft, bool Match = false>
+// and peeled; with Gap, soft[2]: the row's gap, min(a.gap_cap, the least gap of its clusters), 0 with a peeled cluster and for a miss
+template <bool Weighted, bool Heralds, bool Soft, bool Match = false, bool Gap = false>
 __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds,
                                                 uint32_t *soft) {
   load_defects<Heralds>(a, st, row, lane);
@@ -524,11 +580,14 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   *missed = grow<Weighted>(a, st, lane, rounds);
   if constexpr (Soft) soft_of_growth(a, st, lane, soft), soft[2] = 0;
   if constexpr (Match) soft[0] = soft[1] = 0;
+  if constexpr (Gap) soft[2] = 0;
   if (*missed) return 0;
   if constexpr (Match) {
     int n_list;
     mark_clusters(a, st, lane, &n_list, soft);
-    uint64_t flips = match_clusters(a, st, lane, n_list);
+    uint32_t gap = a.gap_cap;
+    uint64_t flips = match_clusters<Gap>(a, st, lane, n_list, &gap);
+    if constexpr (Gap) soft[2] = soft[1] ? 0u : gap;
     if (soft[1]) {  // a flip counts when its edge, and so its child node, lies in a peeled cluster
       forest(a, st, lane);
       flips ^= peel(a, st, lane, [&](int e, int u, int) { return st.par[st.label[u]] == 2 ? a.edge_obs[e] : 0ull; });
@@ -545,13 +604,13 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   return fold_flips(&st.misc[2], flips);
 }
 
-template <bool Weighted, bool Heralds, bool Soft = false, bool Match = false>
+template <bool Weighted, bool Heralds, bool Soft = false, bool Match = false, bool Gap = false>
 __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed; with Soft: the kept rows of bin 0
+  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed; with Soft or Gap: the kept rows of bin 0
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
-  const State st = Match ? match_state_at(a, base) : state_at(a, base);
+  const State st = Gap ? gap_state_at(a, base) : Match ? match_state_at(a, base) : state_at(a, base);
   if (threadIdx.x < 4) stat[threadIdx.x] = 0;
   __syncthreads();
   uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
@@ -571,6 +630,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     uint64_t pred = 0;
     bool missed = false;
     uint32_t mine[4] = {0, 0, 0, 0};  // (Soft) this lane's row: rounds, full edges, largest cluster, correction weight
+    uint32_t deficit = 0;             // (Gap) this lane's row: gap_cap - its gap; 0 for a row that is not decoded
     uint64_t work = __builtin_amdgcn_ballot_w64(kept && defects != 0);
     while (work) {
       const int src = __builtin_ctzll(work);
@@ -578,11 +638,13 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       bool m;
       int rounds;
       uint32_t soft[3];
-      const uint64_t p = decode_shot<Weighted, Heralds, Soft, Match>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, soft);
+      const uint64_t p = decode_shot<Weighted, Heralds, Soft, Match, Gap>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, soft);
       if constexpr (Match) matched_acc += soft[0], peeled_acc += soft[1];
       if (lane == src) pred = p, missed = m;
       if constexpr (Soft)
         if (lane == src) mine[0] = (uint32_t)rounds, mine[1] = soft[0], mine[2] = soft[1], mine[3] = soft[2];
+      if constexpr (Gap)
+        if (lane == src) deficit = a.gap_cap - soft[2];
       most_rounds = max(most_rounds, rounds);
       ++decoded_acc;
     }
@@ -590,8 +652,10 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
     miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && missed));
     if (a.pred && valid) a.pred[r] = pred;  // (0 for a row that is not kept, and for a miss)
-    if constexpr (Soft) {
-      const uint32_t x = a.metric == 0 ? mine[0] : a.metric == 1 ? mine[1] : a.metric == 2 ? mine[2] : mine[3];
+    if constexpr (Soft || Gap) {
+      uint32_t x;
+      if constexpr (Gap) x = deficit / a.gap_step;
+      else x = a.metric == 0 ? mine[0] : a.metric == 1 ? mine[1] : a.metric == 2 ? mine[2] : mine[3];
       const uint32_t bin = min(x, (uint32_t)a.n_bins - 1u);
       const bool wrong = kept && pred != obs;
       bin0_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && bin == 0));
@@ -606,7 +670,11 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
         }
         todo &= ~same;
       }
-      if (a.soft && valid) reinterpret_cast<uint4 *>(a.soft)[r] = make_uint4(mine[0], mine[1], mine[2], mine[3]);  // (zeros for a row that is not kept)
+      if constexpr (Gap) {
+        if (a.soft && valid) a.soft[r] = deficit;  // (uint32[n] on this call; 0 for a row that is not kept)
+      } else {
+        if (a.soft && valid) reinterpret_cast<uint4 *>(a.soft)[r] = make_uint4(mine[0], mine[1], mine[2], mine[3]);  // (zeros for a row that is not kept)
+      }
     }
   }
   if (lane == 0) {
@@ -619,14 +687,14 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       if (matched_acc) atomicAdd(&a.stats[2], (unsigned long long)matched_acc);
       if (peeled_acc) atomicAdd(&a.stats[3], (unsigned long long)peeled_acc);
     }
-    if constexpr (Soft) {
+    if constexpr (Soft || Gap) {
       if (bin0_acc) atomicAdd(&stat[3], bin0_acc);
       if (bin0_wrong_acc) atomicAdd(&a.hist[a.n_bins], (unsigned long long)bin0_wrong_acc);  // (rare: wrong without a defect, or in bin 0)
     }
   }
   __syncthreads();
   if (threadIdx.x < 3 && stat[threadIdx.x]) atomicAdd(&a.dec[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
-  if constexpr (Soft)
+  if constexpr (Soft || Gap)
     if (threadIdx.x == 3 && stat[3]) atomicAdd(&a.hist[0], (unsigned long long)stat[3]);
 }
 

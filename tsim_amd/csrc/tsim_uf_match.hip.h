@@ -92,4 +92,63 @@ __global__ void __launch_bounds__(kTableThreads) k_match_table(TableArgs a) {
   }
 }
 
+// The class table of a handle of tsim_uf_create_matching_gap ("Complementary gap" in the docstring): dist2[a][v][b], the least
+// sum of the match weights over walks from a to v whose edges' bit `observable` of edge_obs XOR to b, over the arcs of the
+// table above.  One block per source a, the two distances of every node in LDS (8 bytes a node): every state (v, b), v >= 1, of
+// finite distance offers dist2[v][b] + w[e] to the state (x, b ^ c(e)) of the other end of each of its edges by atomicMin, until
+// a sweep lowers nothing.  Node 0 never offers.  No parents and no masks: a least fixpoint of minima does not depend on the
+// order of the threads.  A finite entry is a shortest path over at most 2 n_nodes states, so it is below 4095 * 65535 < 2^28
+// and no sum passes kMatchInf.  w0[a] = dist2[a][0][0] + dist2[a][0][1] where a >= 1 and both are finite, else kMatchInf: the
+// host takes the minimum.  Indices come from the checked tables; stores go to 64-bit addresses.
+struct GapTableArgs {
+  int n_nodes, observable;
+  const uint32_t *edge_uv;
+  const unsigned long long *edge_obs;
+  const uint16_t *w;
+  const uint32_t *adj_ptr;
+  const uint16_t *adj_edge;
+  uint32_t *dist2;  // [n_nodes * n_nodes * 2]
+  uint32_t *w0;     // [n_nodes]
+};
+
+__host__ __device__ inline size_t gap_table_lds(int n_nodes) { return 8 * (size_t)n_nodes; }
+
+__global__ void __launch_bounds__(kTableThreads) k_gap_table(GapTableArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+  const int N = a.n_nodes, src = blockIdx.x, tid = threadIdx.x;
+  uint32_t *d2 = reinterpret_cast<uint32_t *>(lds_raw);  // the state (v, b) at 2 v + b
+  for (int v = tid; v < N; v += kTableThreads) d2[2 * v] = v == src ? 0u : kMatchInf, d2[2 * v + 1] = kMatchInf;
+  __syncthreads();
+  for (;;) {
+    bool moved = false;
+    for (int v = tid; v < N; v += kTableThreads) {
+      const uint32_t d0 = d2[2 * v], d1 = d2[2 * v + 1];
+      if (v == 0 || (d0 == kMatchInf && d1 == kMatchInf)) continue;
+      for (uint32_t k = a.adj_ptr[v]; k < a.adj_ptr[v + 1]; ++k) {
+        const int e = a.adj_edge[k];
+        const uint32_t uv = a.edge_uv[e];
+        const int x = (int)(uv & 0xFFFFu) == v ? (int)(uv >> 16) : (int)(uv & 0xFFFFu);
+        const uint32_t c = (uint32_t)(a.edge_obs[e] >> a.observable) & 1u, w = a.w[e];
+        if (d0 != kMatchInf) {
+          const uint32_t cand = d0 + w;
+          uint32_t *to = &d2[2 * x + (int)c];
+          if (cand < *to && cand < atomicMin(to, cand)) moved = true;
+        }
+        if (d1 != kMatchInf) {
+          const uint32_t cand = d1 + w;
+          uint32_t *to = &d2[2 * x + (int)(c ^ 1u)];
+          if (cand < *to && cand < atomicMin(to, cand)) moved = true;
+        }
+      }
+    }
+    if (!__syncthreads_or(moved)) break;
+  }
+  for (int v = tid; v < N; v += kTableThreads) {
+    const size_t at = 2 * ((size_t)src * (size_t)N + (size_t)v);
+    a.dist2[at] = d2[2 * v];
+    a.dist2[at + 1] = d2[2 * v + 1];
+  }
+  if (tid == 0) a.w0[src] = src >= 1 && d2[0] != kMatchInf && d2[1] != kMatchInf ? d2[0] + d2[1] : kMatchInf;
+}
+
 }  // namespace ufk

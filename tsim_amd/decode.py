@@ -129,6 +129,39 @@ decoder of the same graph, caps and observables with ``match_defects = K`` (1 ..
 (default ``graph.match_weights()``).  It takes no graph with heralds (the table is static, a herald is not), no soft output,
 and has no ``flipped_edges``; :class:`WindowedUnionFindDecoder` has no matching.
 
+Complementary gap (:meth:`UnionFindDecoder.with_gap_output`; ``tsim_uf_create_matching_gap``, ``tsim_uf_decode_gap_device``,
+DESIGN.md 3.27).  The soft outputs above are growth statistics.  The signal of a matching decoder is how much heavier the best
+correction of the OTHER logical class is than the best correction overall.  The decoder is given a cluster-matching decoder
+(graph without heralds, weights ``w``, ``K = match_defects``) and an observable index ``k``; ``c(e)`` is bit ``k`` of
+``edge_obs[e]``.  Predictions, misses, growth rounds and ``match_counts`` stay the cluster-matching decoder's, bit for bit.
+
+Class table (:meth:`UnionFindDecoder.gap_table`) ``dist2`` uint32 ``[N, N, 2]``: ``dist2[a][v][b]`` is the least sum of ``w`` over
+walks from ``a`` to ``v`` whose ``c(e)`` XOR to ``b`` (an edge may repeat).  The walks never continue from node 0: the arcs are
+exactly the match table's (an edge ``(0, v)`` relaxes node 0 from ``v``, never ``v`` from node 0).  It is the least fixpoint of
+``dist2[a][a][0] = 0``, ``dist2[a][v][b ^ c(e)] <= dist2[a][x][b] + w[e]`` over the arcs ``x -> v``, and ``INF = 0x7FFFFFFF`` where no
+walk exists; row 0 is ``dist2[0][0][0] = 0``, ``INF`` elsewhere.  ``min(dist2[a][v][0], dist2[a][v][1]) == dist[a][v]`` of the match
+table (asserted).  A finite entry is a shortest path over at most ``2 N`` states, so it is below ``(2 N - 1) * 65535 < 2^28``.
+``W0``, the lightest logical without a defect, is the minimum over ``a >= 1`` of ``dist2[a][0][0] + dist2[a][0][1]`` where both
+are finite, ``None`` when no ``a`` has both.
+
+The class program of a matched cluster with the defects ``a_0 < ... < a_{m-1}`` (:meth:`UnionFindDecoder._gap_cluster`):
+``g[0] = (0, INF)``; for ``S`` ascending, ``i`` its lowest set bit and ``R`` = ``S`` without it, ``g[S][b]`` is the minimum over ``cb``
+in {0, 1} of ``g[R][b ^ cb] + dist2[a_i][0][cb]`` and, over the set bits ``j`` of ``R``, of
+``g[R without j][b ^ cb] + dist2[a_i][a_j][cb]``; infinite terms are skipped.  It is a pure minimum of costs and needs no tie
+rule.  ``min(g[2^m - 1])`` is the cost of ``_match_cluster`` and, where the two classes differ, the cheaper class is bit ``k`` of
+its mask (both asserted in the numpy statement).
+
+The gap of a cluster with a defect, given a cap ``G >= 1``: ``|g0 - g1|`` of a matched cluster whose two classes are finite, ``G``
+when one is, 0 for a peeled cluster (more than ``K`` defects).  A kept row with a defect and no miss has
+``gap = min(G, the least gap of its clusters)``; a miss has gap 0.  The DEFICIT is ``D = G - gap``
+(:meth:`UnionFindDecoder.gap_outputs`), the soft value ``x = D // step`` and the bin ``min(x, B - 1)``: a larger value means less
+sure, as with the metrics above, so :meth:`ShotCounts.rejection_curve` works unchanged.  ``D = 0`` for a row that is not kept and
+for a kept row without a defect, which counts in bin 0 (``soft_kept.sum() == kept``).
+``um.with_gap_output(observable=0, bins=64, step=None, cap=None)`` is the decoder of the same graph, caps, weights and ``K`` with
+``soft_output = "gap"``, ``soft_bins``, ``gap_observable``, ``gap_cap`` (default ``W0``; ``ValueError`` when that is ``None``) and
+``gap_step`` (default ``cap // bins + 1``).  Not done: a gap under heralds, a gap of the windowed decoder, several observables at
+once, and complements that cross clusters (the gap of a row is the least of its clusters' own).
+
 Sliding-window decoding of long runs (:class:`WindowedUnionFindDecoder`; ``tsim_ufw_*``, ``csrc/tsim_ufw.hip.h``)
 ---------------------------------------------------------------------------------------------------------------------
 A shot's state of the rule above must fit a block's 64 KiB of LDS (about 7000 nodes) and a :class:`DecodingGraph` has at most
@@ -221,6 +254,8 @@ MAX_SOFT_BINS = 1024
 MAX_MATCH_NODES = 2048   # of a graph with a match table: uint32 + uint64 per pair of nodes
 MAX_MATCH_DEFECTS = 12   # K of cluster matching at most: 2^K subsets of a cluster's defects in LDS
 MATCH_INF = 0x7FFFFFFF   # a distance of the match table: no path
+MAX_GAP_CAP = 0x7FFFFFFE  # the cap G of a complementary gap at most
+_GAP_INF = 1 << 62        # the gap of a cluster with one finite class, before the cap
 
 
 def _graph_limit(limit) -> int:
@@ -647,13 +682,16 @@ def uf_shot_bytes(n_nodes: int, n_edges: int, weighted: bool) -> int:
     return a16(2 * n_nodes) + a16(4 * n_nodes) + 2 * a16(n_nodes) + a16(4 * grown) + a16(4 * w32) + a16(2 * w32) + 16
 
 
-def uf_match_shot_bytes(n_nodes: int, n_edges: int, weighted: bool, max_defects: int) -> int:
+def uf_match_shot_bytes(n_nodes: int, n_edges: int, weighted: bool, max_defects: int, gap: bool = False) -> int:
     """The LDS bytes of one shot's state on a cluster-matching handle: :func:`uf_shot_bytes` and, for the dynamic program over
     the ``2^K`` subsets of a cluster's ``K = max_defects`` defects, a uint32 cost and a byte (the candidate that won) per subset,
-    the cluster's defects (uint16) and their distances, uint32 ``[K, K + 1]`` (the boundary's in the last column)."""
+    the cluster's defects (uint16) and their distances, uint32 ``[K, K + 1]`` (the boundary's in the last column).  ``gap``: a
+    handle of ``tsim_uf_create_matching_gap``, whose class program adds two uint32 costs per subset and two class distances
+    per entry of ``[K, K + 1]``."""
     a16 = lambda x: (x + 15) // 16 * 16  # noqa: E731
     K = int(max_defects)
-    return uf_shot_bytes(n_nodes, n_edges, weighted) + a16(4 << K) + a16(1 << K) + a16(2 * K) + a16(4 * K * (K + 1))
+    classes = a16(8 << K) + a16(8 * K * (K + 1)) if gap else 0
+    return uf_shot_bytes(n_nodes, n_edges, weighted) + a16(4 << K) + a16(1 << K) + a16(2 * K) + a16(4 * K * (K + 1)) + classes
 
 
 def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray:
@@ -803,6 +841,7 @@ class UnionFindDecoder(_RowDecoder):
         self.graph, self._n_obs, self.edge_caps = graph, n_obs, edge_caps
         self.soft_output, self.soft_bins = None, None   # the metric count() bins, and into how many bins (with_soft_output)
         self.match_defects, self.match_weights = None, None   # K and the weights of cluster matching (with_cluster_matching)
+        self.gap_observable = self.gap_cap = self.gap_step = None   # the complementary gap (with_gap_output)
         self._cache: dict = {}   # packed row of detectors -> (prediction, missed, flipped edges, rounds, full edges, largest cluster)
 
     @classmethod
@@ -852,6 +891,34 @@ class UnionFindDecoder(_RowDecoder):
         out.__dict__.update(self.__dict__)
         out.match_defects, out.match_weights = int(K), w.astype(np.uint16)
         out._cache, out._table = {}, None
+        return out
+
+    def with_gap_output(self, observable: int = 0, bins: int = 64, step: int | None = None, cap: int | None = None) -> "UnionFindDecoder":
+        """The cluster-matching decoder of the same graph, caps, weights and ``max_defects`` with the complementary gap of
+        ``observable`` as its soft output ("Complementary gap" in the module docstring): ``soft_output = "gap"``,
+        ``soft_bins = bins`` (2 .. 1024), ``gap_observable``, ``gap_cap`` (``cap``, an int in 1 .. 2^31 - 2; default ``W0`` of
+        :meth:`gap_table`) and ``gap_step`` (``step >= 1``; default ``cap // bins + 1``).  Its predictions are this decoder's;
+        ``count(decoder=...)`` fills ``ShotCounts.soft_kept`` / ``soft_errors`` with the deficits ``cap - gap``."""
+        is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))  # noqa: E731
+        self._matching("with_gap_output()")
+        if not is_int(observable) or not 0 <= observable < self._n_obs:
+            raise ValueError(f"observable = {observable!r}: an int in 0 .. {self._n_obs - 1}")
+        if not is_int(bins) or not 2 <= bins <= MAX_SOFT_BINS:
+            raise ValueError(f"bins = {bins!r}: an int in 2 .. {MAX_SOFT_BINS}")
+        if cap is not None and (not is_int(cap) or not 1 <= cap <= MAX_GAP_CAP):
+            raise ValueError(f"cap = {cap!r}: an int in 1 .. {MAX_GAP_CAP}")
+        if step is not None and (not is_int(step) or not 1 <= step <= MAX_GAP_CAP):
+            raise ValueError(f"step = {step!r}: an int in 1 .. {MAX_GAP_CAP}")
+        out = object.__new__(UnionFindDecoder)
+        out.__dict__.update(self.__dict__)
+        out.soft_output, out.soft_bins, out.gap_observable = "gap", int(bins), int(observable)
+        out._cache, out._gap_table = {}, None   # (an entry ends with the row's gap, which depends on the observable)
+        if cap is None:
+            cap = out.gap_table()[1]
+            if cap is None:
+                raise ValueError(f"observable {observable} has no W0 (no node reaches the boundary in both classes): give cap=")
+        out.gap_cap = int(cap)
+        out.gap_step = out.gap_cap // out.soft_bins + 1 if step is None else int(step)
         return out
 
     def info(self) -> dict:
@@ -953,6 +1020,96 @@ class UnionFindDecoder(_RowDecoder):
             S = base
         return f[-1][0], f[-1][1], pairs
 
+    def _gap(self, what: str):
+        if self.gap_observable is None:
+            raise ValueError(f"{what} needs a decoder with the complementary gap: with_gap_output(observable, bins, step, cap)")
+
+    def gap_table(self):
+        """``(dist2 uint32[N, N, 2], W0)``: the class table of ``gap_observable`` under ``match_weights`` and the lightest logical
+        without a defect, ``None`` when there is none ("Complementary gap" in the module docstring), built once.  The states
+        ``(v, b)`` relax over the arcs of the match table, doubled by the class of their edge, to their least fixpoint."""
+        self._gap("gap_table()")
+        if self._gap_table is not None:
+            return self._gap_table
+        g = self.graph
+        N, E = g.n_nodes, g.n_edges
+        eu, ev, w = g.edge_u.astype(np.int64), g.edge_v.astype(np.int64), self.match_weights.astype(np.int64)
+        c = ((g.edge_obs >> np.uint64(self.gap_observable)) & np.uint64(1)).astype(np.int64)
+        # the arcs x -> v of the match table, then the arcs (x, b) -> (v, b ^ c(e)) between the states 2 * node + class
+        fwd = np.flatnonzero(eu != 0)
+        tgt, src, edge = np.concatenate([ev[fwd], eu]), np.concatenate([eu[fwd], ev]), np.concatenate([fwd, np.arange(E)])
+        tgt2 = np.concatenate([2 * tgt + c[edge], 2 * tgt + (1 - c[edge])])
+        src2 = np.concatenate([2 * src, 2 * src + 1])
+        w2 = np.concatenate([w[edge], w[edge]])
+        order = np.argsort(tgt2, kind="stable")
+        tgt2, src2, w2 = tgt2[order], src2[order], w2[order]
+        has = np.flatnonzero(np.bincount(tgt2, minlength=2 * N) > 0)
+        start = np.searchsorted(tgt2, has)
+        big = np.int64(1) << 40
+        dist2 = np.full((N, 2 * N), MATCH_INF, np.uint32)
+        block = max(1, (1 << 22) // max(1, len(tgt2)))
+        for lo in range(0, N, block):
+            own = np.arange(lo, min(N, lo + block))
+            d = np.full((len(own), 2 * N), big, np.int64)
+            d[np.arange(len(own)), 2 * own] = 0
+            while len(tgt2):
+                new = d.copy()
+                new[:, has] = np.minimum(d[:, has], np.minimum.reduceat(d[:, src2] + w2[None, :], start, axis=1))
+                if np.array_equal(new, d):
+                    break
+                d = new
+            dist2[own] = np.where(d < big, d, MATCH_INF).astype(np.uint32)
+        dist2 = dist2.reshape(N, N, 2)
+        assert np.array_equal(dist2.min(axis=2), self.match_table()[0]), "the cheaper class is not the match table's distance"
+        both = (dist2[1:, 0, 0] != MATCH_INF) & (dist2[1:, 0, 1] != MATCH_INF)
+        sums = dist2[1:, 0, 0].astype(np.int64) + dist2[1:, 0, 1].astype(np.int64)
+        self._gap_table = (dist2, int(sums[both].min()) if both.any() else None)
+        return self._gap_table
+
+    def _gap_cluster(self, defects):
+        """``(g0, g1)`` of the class program of the module docstring over the defect nodes ``defects`` (ascending, at most 12):
+        the least cost of a pairing whose paths' classes XOR to 0, and to 1; ``None`` for an infinite one."""
+        self._gap("_gap_cluster()")
+        dist2 = self.gap_table()[0]
+        a = [int(x) for x in defects]
+        m = len(a)
+        if m > MAX_MATCH_DEFECTS or any(x >= y for x, y in zip(a, a[1:])) or (m and (a[0] < 1 or a[-1] >= self.graph.n_nodes)):
+            raise ValueError(f"defects: at most {MAX_MATCH_DEFECTS} ascending nodes in 1 .. {self.graph.n_nodes - 1}")
+        g = [[0, None]] + [None] * ((1 << m) - 1)
+        for S in range(1, 1 << m):
+            i = (S & -S).bit_length() - 1
+            R = S & (S - 1)
+            best = [None, None]
+            for base, other in [(R, 0)] + [(R ^ (1 << j), a[j]) for j in range(i + 1, m) if (R >> j) & 1]:
+                for cb in (0, 1):
+                    d = int(dist2[a[i], other, cb])
+                    if d == MATCH_INF:
+                        continue
+                    for b in (0, 1):
+                        f = g[base][b ^ cb]
+                        if f is not None and (best[b] is None or f + d < best[b]):
+                            best[b] = f + d
+            g[S] = best
+        return tuple(g[-1])
+
+    def _cluster_gap(self, defects, cost, mask) -> int:
+        """The gap of a matched cluster before the cap (``_GAP_INF`` when one class is infinite), its two invariants asserted
+        against ``(cost, mask)`` of :meth:`_match_cluster`."""
+        g0, g1 = self._gap_cluster(defects)
+        finite = [x for x in (g0, g1) if x is not None]
+        assert finite and min(finite) == cost, "the cheaper class does not cost what the matching costs"
+        if g0 is None or g1 is None:
+            assert (g1 is not None) == bool((mask >> self.gap_observable) & 1), "the only finite class is not the matching's"
+            return _GAP_INF
+        assert g0 == g1 or (g1 < g0) == bool((mask >> self.gap_observable) & 1), "the cheaper class is not the matching's"
+        return abs(g0 - g1)
+
+    def gap_outputs(self, dets) -> np.ndarray:
+        """int64 ``[n]``: the deficit ``D = gap_cap - gap`` of every row ("Complementary gap" in the module docstring): 0 for a
+        row without a defect, ``gap_cap`` for a miss and for a row with a peeled cluster."""
+        self._gap("gap_outputs()")
+        return np.array([0 if e is None else self.gap_cap - min(self.gap_cap, e[8]) for e in self._decoded(dets)], dtype=np.int64)
+
     def match_counts(self, dets):
         """``(clusters_matched, clusters_peeled)`` over the rows of ``dets`` that are decoded (a defect, no miss): what the
         device counts in ``info()["clusters_matched"]`` and ``["clusters_peeled"]``."""
@@ -996,7 +1153,7 @@ class UnionFindDecoder(_RowDecoder):
             new = np.minimum(cap, grown + active[eu] + active[ev]).astype(np.int8)
             if np.array_equal(new, grown):
                 return (0, True, np.zeros(0, np.int64), rounds, int(f.sum()), int(np.bincount(label).max())) + \
-                    ((0, 0) if self.match_defects is not None else ())
+                    ((0, 0) if self.match_defects is not None else ()) + ((0,) if self.gap_observable is not None else ())
             grown, rounds = new, rounds + 1
         soft = (int((grown == cap).sum()), int(np.bincount(label).max()))  # (label: the clusters of the full edges)
         # the forest: levels from the roots, the parent edge the smallest-index edge to the level above
@@ -1030,7 +1187,9 @@ class UnionFindDecoder(_RowDecoder):
         assert not s[1:].any(), "the correction does not reproduce the syndrome"
         if self.match_defects is not None:
             # cluster matching: small clusters by the dynamic program, of the others the flips whose child node lies in them
+            # (the complementary gap: the least gap of the row's clusters before the cap, 0 with a peeled cluster)
             prediction = matched = peeled = 0
+            gap = _GAP_INF
             for r in np.unique(label[defect]):
                 ds = np.flatnonzero(defect & (label == r))
                 if len(ds) <= self.match_defects:
@@ -1038,12 +1197,16 @@ class UnionFindDecoder(_RowDecoder):
                     assert cost is not None, "a matched cluster has no finite pairing"
                     prediction ^= mask
                     matched += 1
+                    if self.gap_observable is not None:
+                        gap = min(gap, self._cluster_gap(ds, cost, mask))
                 else:
                     for e, v in zip(flipped, children):
                         if label[v] == r:
                             prediction ^= int(g.edge_obs[e])
                     peeled += 1
-            return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft + (matched, peeled)
+                    gap = 0
+            return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft + (matched, peeled) + \
+                ((gap,) if self.gap_observable is not None else ())
         return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft
 
     def _decode_bits(self, bits: np.ndarray):
@@ -1068,35 +1231,48 @@ class UnionFindDecoder(_RowDecoder):
         them that are ``wrong`` (bool ``[n]``) - what the device adds to ``d_hist``."""
         if self.soft_output is None:
             raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
-        bins = np.minimum(self.soft_outputs(dets)[:, SOFT_OUTPUTS.index(self.soft_output)], self.soft_bins - 1)
+        if self.gap_observable is not None:
+            values = self.gap_outputs(dets) // self.gap_step
+        else:
+            values = self.soft_outputs(dets)[:, SOFT_OUTPUTS.index(self.soft_output)]
+        bins = np.minimum(values, self.soft_bins - 1)
         return (np.bincount(bins, minlength=self.soft_bins).astype(np.int64),
                 np.bincount(bins[np.asarray(wrong, dtype=np.bool_)], minlength=self.soft_bins).astype(np.int64))
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _handle(self, hp, n_cols: int):
+        if self.gap_observable is not None:
+            h = hp.uf_create_matching_gap(self.graph, n_cols, self.match_weights, self.match_defects, self.gap_observable, self.edge_caps)
+            return h, hp.uf_decode_device, hp.uf_destroy
         if self.match_defects is not None:
             h = hp.uf_create_matching(self.graph, n_cols, self.match_weights, self.match_defects, self.edge_caps)
             return h, hp.uf_decode_device, hp.uf_destroy
         return hp.uf_create(self.graph, n_cols, self.edge_caps), hp.uf_decode_device, hp.uf_destroy
+
+    def _soft_call(self, hp, d_hist: int, d_values: int = 0):
+        """What decodes rows by this decoder's handle in the place of the plain call when the soft output is wanted: the two
+        histograms accumulate at ``d_hist``, the values of every row go to ``d_values`` (0: not wanted)."""
+        if self.gap_observable is not None:
+            return lambda *a, **k: hp.uf_decode_gap_device(*a, self.gap_cap, self.gap_step, self.soft_bins, d_hist, d_gap=d_values, **k)
+        return lambda *a, **k: hp.uf_decode_soft_device(*a, self.soft_output, self.soft_bins, d_hist, d_soft=d_values, **k)
 
     def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
                       stream: int = 0, soft: bool = False):
         """``(predictions uint64[n], (kept, wrong, missed))`` of ``n`` bit-packed rows already in HBM by one ``tsim_uf`` handle on
         ``hp``'s device, created and destroyed here: every argument and result as the base class states them.  ``soft`` (the
         decoder of :meth:`with_soft_output`; ``tsim_uf_decode_soft_device``): two more results, the soft outputs of every row as
-        uint32 ``[n, 4]`` (zeros for a row that is not kept) and ``(kept int64[soft_bins], errors int64[soft_bins])``."""
+        uint32 ``[n, 4]`` (zeros for a row that is not kept) and ``(kept int64[soft_bins], errors int64[soft_bins])``.  Of the
+        decoder of :meth:`with_gap_output` (``tsim_uf_decode_gap_device``) the values are the deficits, uint32 ``[n]``."""
         if not soft:
             return self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream)
         if self.soft_output is None:
             raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
-        values = np.zeros((int(n), 4), np.uint32)
+        values = np.zeros(int(n) if self.gap_observable is not None else (int(n), 4), np.uint32)
         hist = np.zeros(2 * self.soft_bins, np.uint64)
         d_values, d_hist = hp.malloc(values.nbytes + 16), hp.malloc(hist.nbytes + 16)
         try:
             hp.h2d(d_hist, hist)
-            pred, cnt = self._decode_device(
-                hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream,
-                lambda *a, **k: hp.uf_decode_soft_device(*a, self.soft_output, self.soft_bins, d_hist.ptr, d_soft=d_values.ptr, **k))
+            pred, cnt = self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream, self._soft_call(hp, d_hist.ptr, d_values.ptr))
             if n:
                 hp.d2h(values, d_values)
             hp.d2h(hist, d_hist)
