@@ -30,27 +30,40 @@ enum { LWF_NRUNS = 0, LWF_FLIP0, LWF_FLIP1, LWF_RUNS /* image offset: n_runs x (
 #define TSIMK_LWF_MAX_NOUT 8
 
 // u < t as integers: see bernoulli_threshold
-__device__ __forceinline__ uint32_t threefry_bits32_lo(uint32_t k0, uint32_t k1, uint32_t k0hi, uint32_t lo) {
+// PINNED: the statement is volatile, so it keeps its place among the memory instructions round it - reads requested in front of
+// a draw stay in front of it, their waits behind it.  Left alone the scheduler puts every draw of k_sample_lw_fast first and
+// the threshold reads, each waited for at once, behind them.
+template <bool PINNED>
+__device__ __forceinline__ uint32_t threefry_bits32_lo_at(uint32_t k0, uint32_t k1, uint32_t k0hi, uint32_t lo) {
   // threefry_bits32 for a counter (hi, lo) whose high word is wave-uniform: k0hi = k0 + hi formed on the scalar unit
   const uint32_t k2 = k0 ^ k1 ^ 0x1BD11BDAu;
   uint32_t x0, x1, t;
 #define TF_RN(r) "v_alignbit_b32 %[x1], %[x1], %[x1], " #r "\n v_xor_b32 %[x1], %[x1], %[x0]\n"
 #define TF_RA(r) "v_add_u32 %[x0], %[x0], %[x1]\n" TF_RN(r)
 #define TF_INJ(kb, i, ka) "s_add_i32 %[t], %[" #kb "], " #i "\n v_add_u32 %[x1], %[t], %[x1]\n v_add3_u32 %[x0], %[x0], %[x1], %[" #ka "]\n"
-  asm("v_add_u32 %[x1], %[k1], %[lo]\n v_add_u32 %[x0], %[k0hi], %[x1]\n"
-      TF_RN(19) TF_RA(17) TF_RA(6) TF_RA(26)
-      TF_INJ(k2, 1, k1) TF_RN(15) TF_RA(3) TF_RA(16) TF_RA(8)
-      TF_INJ(k0, 2, k2) TF_RN(19) TF_RA(17) TF_RA(6) TF_RA(26)
-      TF_INJ(k1, 3, k0) TF_RN(15) TF_RA(3) TF_RA(16) TF_RA(8)
-      TF_INJ(k2, 4, k1) TF_RN(19) TF_RA(17) TF_RA(6) TF_RA(26)
-      "s_add_i32 %[t], %[k0], 5\n v_add_u32 %[x0], %[k2], %[x0]\n v_add_u32 %[x1], %[t], %[x1]\n v_xor_b32 %[x0], %[x0], %[x1]\n"
-      : [x0] "=&v"(x0), [x1] "=&v"(x1), [t] "=&s"(t)
-      : [lo] "v"(lo), [k0] "s"(k0), [k1] "s"(k1), [k2] "s"(k2), [k0hi] "s"(k0hi)
-      : "scc");
+#define TF_BLOCK                                                                                                           \
+  "v_add_u32 %[x1], %[k1], %[lo]\n v_add_u32 %[x0], %[k0hi], %[x1]\n"                                                     \
+  TF_RN(19) TF_RA(17) TF_RA(6) TF_RA(26)                                                                                   \
+  TF_INJ(k2, 1, k1) TF_RN(15) TF_RA(3) TF_RA(16) TF_RA(8)                                                                  \
+  TF_INJ(k0, 2, k2) TF_RN(19) TF_RA(17) TF_RA(6) TF_RA(26)                                                                 \
+  TF_INJ(k1, 3, k0) TF_RN(15) TF_RA(3) TF_RA(16) TF_RA(8)                                                                  \
+  TF_INJ(k2, 4, k1) TF_RN(19) TF_RA(17) TF_RA(6) TF_RA(26)                                                                 \
+  "s_add_i32 %[t], %[k0], 5\n v_add_u32 %[x0], %[k2], %[x0]\n v_add_u32 %[x1], %[t], %[x1]\n v_xor_b32 %[x0], %[x0], %[x1]\n"
+#define TF_OPERANDS                                                                                \
+  [x0] "=&v"(x0), [x1] "=&v"(x1), [t] "=&s"(t)                                                     \
+      : [lo] "v"(lo), [k0] "s"(k0), [k1] "s"(k1), [k2] "s"(k2), [k0hi] "s"(k0hi)                   \
+      : "scc"
+  if constexpr (PINNED) asm volatile(TF_BLOCK : TF_OPERANDS);
+  else asm(TF_BLOCK : TF_OPERANDS);
+#undef TF_OPERANDS
+#undef TF_BLOCK
 #undef TF_INJ
 #undef TF_RA
 #undef TF_RN
   return x0;
+}
+__device__ __forceinline__ uint32_t threefry_bits32_lo(uint32_t k0, uint32_t k1, uint32_t k0hi, uint32_t lo) {
+  return threefry_bits32_lo_at<false>(k0, k1, k0hi, lo);
 }
 
 template <int WF32, int NOUT>
@@ -205,10 +218,18 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
     const uint32_t thr = tab_byte + (pat << (NOUT + 2));  // byte offset of the pattern's row
     const uint32_t slo = so_lo + row;  // the host launches this kernel only when shot_offset + B stays below the next 2^32
     cptr kp = (cptr)((cbytes)S + __builtin_offsetof(LwStep, keys)) + 2u * keybase;
+    // Every output's key is requested before the first draw, and the draws keep their places (PINNED): a level group's
+    // threshold reads are under way while its draws run and are waited for behind them.
+    uint32_t key0[NOUT], key1[NOUT];
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) {
+      key0[o] = kp[2 * o];
+      key1[o] = kp[2 * o + 1];
+    }
     auto draw = [&](int o) -> uint32_t {
-      const uint32_t k0 = kp[2 * o], k1 = kp[2 * o + 1];
+      const uint32_t k0 = key0[o], k1 = key1[o];
       if (TSIMK_LWM_SKIP & 1) return (slo * 0x9E3779B9u + k0 + k1) >> 9;  // diagnostic: no Threefry
-      return threefry_bits32_lo(k0, k1, k0 + so_hi, slo) >> 9;
+      return threefry_bits32_lo_at<true>(k0, k1, k0 + so_hi, slo) >> 9;
     };
     uint32_t node = 1u;
     int i = 0;
