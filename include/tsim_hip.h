@@ -712,6 +712,25 @@ int tsim_uf_create_matching_gap(int32_t device, const tsim_uf_desc *desc, const 
  * walk), and *w0 = W0, -1 when no source reaches the boundary in both classes.  TSIM_EINVAL for another handle or a NULL.
  * Synchronous. */
 int tsim_uf_gap_table(tsim_uf *h, uint32_t *dist2, int64_t *w0);
+/* Cluster matching for a graph with heralds ("Cluster matching under heralds" in the module docstring of tsim_amd/decode.py):
+ * growth as tsim_uf_create_heralds, the match table (and, with observable >= 0, the class table and W0) as
+ * tsim_uf_create_matching(_gap) over the nodes and edges of the herald graph.  A cluster of 1 .. max_defects defects whose hub
+ * graph - its defects and the other non-boundary ends of its erased edges - has at most max_hubs hubs is corrected by the
+ * minimum-weight matching of its defects in that graph, where an erased edge e of the cluster weighs min(match_w[e], erased_w);
+ * every other cluster is peeled.  her is required (a graph without heralds: tsim_uf_create_matching), max_defects is 1 .. 12,
+ * erased_w 1 .. 65535, max_hubs max_defects .. 32, observable 0 .. 63 or -1 for a handle without the gap: all checked with the
+ * graph, the caps, the heralds and the weights before any device call (TSIM_EINVAL).  TSIM_ENOTSUP for more than 2048 nodes and
+ * when a shot's state - that of tsim_uf_create_matching(_gap) and the hub graph's, 12 bytes per pair of hubs, 20 with the gap -
+ * does not fit a block's 64 KiB of LDS.  tsim_uf_decode_device takes the handle, tsim_uf_decode_gap_device one with an
+ * observable, tsim_uf_decode_soft_device is TSIM_EINVAL; tsim_uf_info [13] .. [15] mean what they mean on a matching handle (a
+ * cluster peeled for its hubs counts as peeled), tsim_uf_match_table and tsim_uf_gap_table give its tables. */
+int tsim_uf_create_matching_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
+                                    const uint16_t *match_w, int32_t max_defects, int32_t erased_w, int32_t max_hubs,
+                                    int32_t observable, tsim_uf **out);
+/* Of a handle of tsim_uf_create_matching_heralds (TSIM_EINVAL for another): out[0] erased_w, [1] max_hubs, [2] the matched
+ * clusters that had an erased edge, [3] the clusters of at most max_defects defects that were peeled for having more than
+ * max_hubs hubs, both over the rows decoded in LDS that are no miss.  Synchronises the device. */
+int tsim_uf_erasure_info(tsim_uf *h, int64_t out[4]);
 void tsim_uf_destroy(tsim_uf *h);
 /* out[0] nodes, [1] edges, [2] LDS bytes per shot, [3] shots (waves) per block, [4] kernel launches so far, [5] the most
  * growth rounds a row took, [6] bytes of device memory, [7] rows decoded in LDS (kept rows with a defect), [8] n_cols,

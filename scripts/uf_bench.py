@@ -6,6 +6,7 @@
     python scripts/uf_bench.py --soft largest_cluster  # the price of a soft output: d = 5, 9
     python scripts/uf_bench.py --match 10 --resolution 4  # the price of cluster matching: d = 5, 9
     python scripts/uf_bench.py --gap --resolution 4  # the price of the complementary gap, and what it rejects: d = 5, 9
+    python scripts/uf_bench.py --erasure-matching [--gap]  # cluster matching (and the gap) under heralded erasures: d = 5, 9
 
 Per distance the ``method="faults"`` sampler counts ``--shots`` shots per call in batches of 10^6, once without a decoder and
 once with ``decoder=UnionFindDecoder.from_circuit(circuit)``, alternating, each warmed up first; the time is a host clock
@@ -35,6 +36,14 @@ cluster-matching decoder (``--match K``, default 10; weighted with ``--resolutio
 alternating over the same seeded rows: both rates and their ratio, the histograms, and the rejection table - the errors left among
 the shots kept at 99, 95, 90 and 80 % by the gap, against ``largest_cluster`` of the decoder without matching over the same rows.
 The leg stops when the two calls disagree on a counter or the histograms do not add up to them.
+
+``--erasure-matching`` is a leg of its own (``--circuits`` then defaults to d5,d9): the memory circuit with
+``after_clifford_heralded_erasure=--pe`` beside the depolarizing and measurement noise of ``--p``, decoded by the herald decoder
+(weighted, ``--resolution R``, default 4) and by its ``with_erasure_matching(--match K, erased_weight=--erased-weight,
+max_hubs=--max-hubs)``, with ``--gap`` also by that decoder's ``with_gap_output(0, --bins)``, alternating over the same seeded rows:
+the rates and their ratios, the decoded errors, what ``tsim_uf_info`` and ``tsim_uf_erasure_info`` say after ``--info-rows`` rows and,
+with ``--gap``, the rejection table against ``largest_cluster`` of the herald decoder.  The leg stops when the calls disagree on kept
+rows, raw flips or misses, or the gap decoder on the decoded errors of the matching one.
 """
 
 from __future__ import annotations
@@ -255,6 +264,79 @@ def gap_leg(args) -> None:
             rejection=table, soft_kept=b.soft_kept.tolist(), soft_errors=b.soft_errors.tolist())), flush=True)
 
 
+def erasure_leg(args) -> None:
+    import numpy as np
+
+    K = 10 if args.match is None else args.match
+    R = 4 if args.resolution is None else args.resolution
+    for name in (args.circuits or "d5,d9").split(","):
+        d = int(name[1:])
+        c = CliffordCircuit(circuits.rotated_surface_code_memory(d, d, after_clifford_depolarization=args.p, before_measure_flip_probability=args.p,
+                                                                 after_clifford_heralded_erasure=args.pe))
+        plain = UnionFindDecoder.from_circuit(c, weights="probability", resolution=R, heralds=True)
+        ue = plain.with_erasure_matching(K, erased_weight=args.erased_weight, max_hubs=args.max_hubs)
+        decoders = {"heralds": plain, "erasure_matching": ue}
+        if args.gap:
+            decoders["gap"] = ue.with_gap_output(0, args.bins)
+        def sampler():  # a fresh one per call: every call counts the same seeded rows
+            return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+        times, last = {m: [] for m in decoders}, {}
+        for m, uf in decoders.items():
+            sampler().count(args.shots, batch_size=10**6, decoder=uf)  # warm-up at the timed size
+        for _ in range(args.reps):
+            for m, uf in decoders.items():
+                s = sampler()
+                t0 = time.perf_counter()
+                last[m] = s.count(args.shots, batch_size=10**6, decoder=uf)
+                times[m].append(time.perf_counter() - t0)
+        a = last["heralds"]
+        for m in decoders:
+            if (a.kept, a.kept_with_observable_flip, a.decoder_misses) != (last[m].kept, last[m].kept_with_observable_flip, last[m].decoder_misses):
+                sys.exit(f"uf_bench: {m} did not see the rows, or the misses, of the herald decoder")
+        table = None
+        if args.gap:
+            b = last["gap"]
+            if b.decoded_errors != last["erasure_matching"].decoded_errors or int(b.soft_kept.sum()) != b.kept or int(b.soft_errors.sum()) != b.decoded_errors:
+                sys.exit("uf_bench: the gap decoder did not count what the matching one counted")
+            other = sampler().count(args.shots, batch_size=10**6, decoder=plain.with_soft_output("largest_cluster", args.bins))
+            table = {}
+            for signal, counts in (("gap", b), ("largest_cluster", other)):
+                accepted, errors = counts.rejection_curve()
+                for keep in (0.99, 0.95, 0.90, 0.80):
+                    t = int((accepted >= keep * counts.kept).argmax())  # the first bin that keeps at least that much
+                    table[f"{signal}@{keep:.2f}"] = dict(bin=t, kept=int(accepted[t]), errors=int(errors[t]), rate=float(errors[t] / accepted[t]))
+        hp = s._hip()
+        rows = c.compile_detector_sampler(seed=3, noise="device", method="faults").sample(args.info_rows, append_observables=True)
+        packed = np.ascontiguousarray(np.packbits(rows, axis=1, bitorder="little"))
+        nd, n_cols = ue.num_detectors, ue.num_detectors + ue.num_observables
+        info = {}
+        for m, uf in decoders.items():
+            h, decode, destroy = uf._handle(hp, n_cols)
+            d_rows, d_cnt = hp.malloc(packed.nbytes + 16), hp.malloc(64)
+            try:
+                hp.h2d(d_rows, packed)
+                hp.h2d(d_cnt, np.zeros(3, np.uint64))
+                decode(h, d_rows.ptr, len(packed), packed.shape[1], (nd, n_cols), d_cnt.ptr)
+                info[m] = dict(hp.uf_info(h), **(hp.uf_erasure_info(h) if m != "heralds" else {}))
+            finally:
+                destroy(h)
+                d_rows.free()
+                d_cnt.free()
+        rate = {m: args.shots / statistics.median(t) for m, t in times.items()}
+        keys = ("lds_bytes_per_shot", "shots_per_block", "grid_blocks", "max_rounds", "rows_decoded", "clusters_matched", "clusters_peeled",
+                "clusters_erased", "clusters_hub_overflow", "device_bytes")
+        print(json.dumps(dict(
+            case=name, leg="erasure_matching", max_defects=K, erased_weight=args.erased_weight, max_hubs=args.max_hubs, resolution=R, p=args.p,
+            pe=args.pe, shots=args.shots, reps=args.reps, graph=plain.info(), median_s={m: statistics.median(t) for m, t in times.items()},
+            min_s={m: min(t) for m, t in times.items()}, max_s={m: max(t) for m, t in times.items()}, shots_per_s=rate,
+            over_heralds={m: rate[m] / rate["heralds"] for m in decoders if m != "heralds"}, kept=a.kept, raw_flips=a.kept_with_observable_flip,
+            decoded_errors={m: last[m].decoded_errors for m in decoders}, misses=a.decoder_misses, info_rows=args.info_rows,
+            info={m: {k: v[k] for k in keys if k in v} for m, v in info.items()}, rejection=table,
+            **(dict(gap_cap=decoders["gap"].gap_cap, gap_step=decoders["gap"].gap_step, soft_kept=last["gap"].soft_kept.tolist(),
+                    soft_errors=last["gap"].soft_errors.tolist()) if args.gap else {}))), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shots", type=int, default=10**7)
@@ -271,10 +353,17 @@ def main() -> None:
                     help="the leg that runs a decoder with cluster matching of at most K defects against the same decoder without")
     ap.add_argument("--gap", action="store_true",
                     help="the leg that runs the cluster-matching decoder (--match K, default 10) with the complementary gap against the same without")
+    ap.add_argument("--erasure-matching", action="store_true",
+                    help="the leg that runs cluster matching under heralded erasures (with --gap: and its gap) against the herald decoder")
+    ap.add_argument("--pe", type=float, default=1e-2, help="the heralded erasure probability of --erasure-matching")
+    ap.add_argument("--erased-weight", type=int, default=1)
+    ap.add_argument("--max-hubs", type=int, default=24)
     args = ap.parse_args()
     _lib.load()
     if _lib.device_count() < 1:
         sys.exit("uf_bench: no HIP device - nothing is measured without one")
+    if args.erasure_matching:
+        return erasure_leg(args)
     if args.gap:
         return gap_leg(args)
     if args.match is not None:

@@ -177,6 +177,8 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_uf_create_matching_gap": (C.c_int, [_I32, C.POINTER(UfDesc), _P, _P, _I32, _I32, C.POINTER(_P)]),
     "tsim_uf_gap_table": (C.c_int, [_P, _P, C.POINTER(_I64)]),
     "tsim_uf_decode_gap_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _I64, _I64, _I32, _P, _P, _P]),
+    "tsim_uf_create_matching_heralds": (C.c_int, [_I32, C.POINTER(UfDesc), _P, C.POINTER(UfHeralds), _P, _I32, _I32, _I32, _I32, C.POINTER(_P)]),
+    "tsim_uf_erasure_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_uf_destroy": (None, [_P]),
     "tsim_uf_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_uf_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _P]),

@@ -509,6 +509,36 @@ class HipProgram:
                                                          clip(observable), C.byref(h)), "tsim_uf_create_matching_gap")
         return h.value
 
+    def uf_create_matching_heralds(self, graph, n_cols: int, match_weights, max_defects: int, erased_weight: int, max_hubs: int,
+                                   observable: int = -1, caps=None) -> int:
+        """A cluster-matching union-find decoder over a ``graph`` with heralds (``tsim_uf_create_matching_heralds``; "Cluster
+        matching under heralds" in the module docstring of :mod:`tsim_amd.decode`): ``match_weights`` and ``max_defects`` as
+        :meth:`uf_create_matching`, ``erased_weight`` in 1 .. 65535, ``max_hubs`` in ``max_defects`` .. 32, ``observable`` -1 or,
+        for the complementary gap, 0 .. 63.  The handle decodes by :meth:`uf_decode_device` and, with an observable, by
+        :meth:`uf_decode_gap_device`; :meth:`uf_erasure_info` reads its counters."""
+        desc, d_caps, her, _keep = self._uf_graph_args(graph, n_cols, caps)
+        if her is None:
+            raise ValueError("the graph has no heralds: uf_create_matching() is the matching handle of such a graph")
+        w = np.ascontiguousarray(match_weights)
+        if w.shape != (graph.n_edges,) or not np.issubdtype(w.dtype, np.integer) or (w.size and (w.min() < 0 or w.max() > 65535)):
+            raise ValueError(f"match_weights: {graph.n_edges} integers in 1 .. 65535 expected")
+        w = np.concatenate([w.astype(np.uint16), np.zeros(1, np.uint16)])  # (never an empty buffer)
+        clip = lambda x: int(min(max(x, -2), 0x7FFFFFFF))  # noqa: E731
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_uf_create_matching_heralds(self.device, C.byref(desc), d_caps, C.byref(her), C.c_void_p(w.ctypes.data),
+                                                             clip(max_defects), clip(erased_weight), clip(max_hubs), clip(observable),
+                                                             C.byref(h)), "tsim_uf_create_matching_heralds")
+        return h.value
+
+    UF_ERASURE_INFO = ("erased_weight", "max_hubs", "clusters_erased", "clusters_hub_overflow")
+
+    def uf_erasure_info(self, handle: int) -> dict:
+        """Of a handle of :meth:`uf_create_matching_heralds` (``tsim_uf_erasure_info``): its ``erased_weight`` and ``max_hubs``, the
+        matched clusters that had an erased edge and the clusters peeled for having more than ``max_hubs`` hubs."""
+        out = (C.c_int64 * 4)()
+        _lib.check(self._lib.tsim_uf_erasure_info(C.c_void_p(handle), out), "tsim_uf_erasure_info")
+        return {k: int(v) for k, v in zip(self.UF_ERASURE_INFO, out)}
+
     def uf_gap_table(self, handle: int):
         """``(dist2 uint32[n_nodes, n_nodes, 2], W0 or None)``: the class table the handle of :meth:`uf_create_matching_gap` built
         on the device, and the lightest logical without a defect (``tsim_uf_gap_table``)."""

@@ -18,8 +18,9 @@ exact count (the row table, ``tsim_rowtab_*``, ``csrc/tsim_rowtab.hip.h``) - wha
 without the rows crossing PCIe.  ``decoder`` (:class:`tsim_amd.decode.LookupDecoder`, a table of syndromes, or
 :class:`tsim_amd.decode.UnionFindDecoder`, cluster growth on the circuit's decoding graph, ``tsim_uf_*``, or
 :class:`tsim_amd.decode.WindowedUnionFindDecoder`, the same window after window for long runs, ``tsim_ufw_*``, with heralded
-erasures too when the decoder has ``heralds=True``) is applied to every kept shot where it lies, and the wrong predictions are
-counted.  ``corrected=True`` goes one step further: the predictions are XORed into the observable columns of the rows in HBM
+erasures too when the decoder has ``heralds=True``; ``uf.with_cluster_matching()`` and, on a graph with heralds,
+``uf.with_erasure_matching()`` are union-find decoders that match small clusters) is applied to every kept shot where it lies,
+and the wrong predictions are counted.  ``corrected=True`` goes one step further: the predictions are XORed into the observable columns of the rows in HBM
 (``tsim_pred_rows_device``, ``csrc/tsim_predrows.hip.h``) before anything is counted, so the column counts, the histogram, the
 pair counts and the patterns are those of the corrected rows - per-observable logical error rates and the joint law of the
 residual flips.

@@ -26,9 +26,10 @@ extern "C" int tsim_uf_create_weighted(int32_t device, const tsim_uf_desc *desc,
   return tsim_uf_create_heralds(device, desc, edge_cap, nullptr, out);
 }
 
-// every create call; match_w != NULL: tsim_uf_create_matching, with max_defects; gap_obs >= 0: tsim_uf_create_matching_gap
+// every create call; match_w != NULL: tsim_uf_create_matching, with max_defects; gap_obs >= 0: tsim_uf_create_matching_gap;
+// max_hubs != 0: tsim_uf_create_matching_heralds, with erased_w
 static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her, const uint16_t *match_w,
-                     int32_t max_defects, int32_t gap_obs, tsim_uf **out);
+                     int32_t max_defects, int32_t gap_obs, tsim_uf **out, int32_t erased_w = 0, int32_t max_hubs = 0);
 
 extern "C" int tsim_uf_create_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
                                       tsim_uf **out) {
@@ -56,8 +57,24 @@ extern "C" int tsim_uf_create_matching_gap(int32_t device, const tsim_uf_desc *d
   return uf_create(device, desc, edge_cap, nullptr, match_w, max_defects, observable, out);
 }
 
+extern "C" int tsim_uf_create_matching_heralds(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her,
+                                               const uint16_t *match_w, int32_t max_defects, int32_t erased_w, int32_t max_hubs,
+                                               int32_t observable, tsim_uf **out) {
+  if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!her) return tsim_fail(TSIM_EINVAL, "her is NULL (a graph without heralds: tsim_uf_create_matching)");
+  if (!match_w) return tsim_fail(TSIM_EINVAL, "match_w is NULL");
+  if (max_defects < 1 || max_defects > ufk::kMaxMatchDefects)
+    return tsim_fail(TSIM_EINVAL, "max_defects = %d (1 .. %d)", max_defects, ufk::kMaxMatchDefects);
+  if (erased_w < 1 || erased_w > 65535) return tsim_fail(TSIM_EINVAL, "erased_w = %d (1 .. 65535)", erased_w);
+  if (max_hubs < max_defects || max_hubs > ufk::kMaxMatchHubs)
+    return tsim_fail(TSIM_EINVAL, "max_hubs = %d (max_defects = %d .. %d)", max_hubs, max_defects, ufk::kMaxMatchHubs);
+  if (observable < -1 || observable > 63) return tsim_fail(TSIM_EINVAL, "observable = %d (0 .. 63, or -1: no gap)", observable);
+  return uf_create(device, desc, edge_cap, her, match_w, max_defects, observable, out, erased_w, max_hubs);
+}
+
 static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *edge_cap, const tsim_uf_heralds *her, const uint16_t *match_w,
-                     int32_t max_defects, int32_t gap_obs, tsim_uf **out) {
+                     int32_t max_defects, int32_t gap_obs, tsim_uf **out, int32_t erased_w, int32_t max_hubs) {
   if (!out) return tsim_fail(TSIM_EINVAL, "out is NULL");
   *out = nullptr;
   if (!desc) return tsim_fail(TSIM_EINVAL, "desc is NULL");
@@ -97,10 +114,16 @@ static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *ed
   a.w_cnt = edge_cap ? std::max(1, (E + 7) / 8) : 0;
   a.match_k = match_w ? max_defects : 0;
   a.gap = match_w && gap_obs >= 0;
+  a.max_hubs = max_hubs;
+  a.erased_w = (uint32_t)erased_w;
+  a.gap_obs = std::max(0, gap_obs);
   const long long shot = ufk::layout(&a);
   if (16 + shot > ufk::kLdsBlock)
     return tsim_fail(TSIM_ENOTSUP, "one shot's state takes %lld bytes of LDS (%d nodes, %d edges%s), a block has %d", shot, N, E,
-                     a.gap ? ", the dynamic programs of max_defects: the winners and the classes" : match_w ? ", the dynamic program of max_defects" : "",
+                     max_hubs ? ", the dynamic programs of max_defects and the hub graph of max_hubs"
+                     : a.gap  ? ", the dynamic programs of max_defects: the winners and the classes"
+                     : match_w ? ", the dynamic program of max_defects"
+                              : "",
                      ufk::kLdsBlock - 16);
   a.shot_bytes = (int)shot;
   int per_cu = 1;
@@ -138,14 +161,15 @@ static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *ed
   a.adj_ptr = up.put(ptr);
   a.adj_edge = up.put(adj);
   if (edge_cap) a.cap = up.put(cap);
-  const uint64_t zero[4] = {0, 0, 0, 0};
-  a.stats = reinterpret_cast<unsigned long long *>(up.put(zero, match_w ? 4 : 2));
+  const uint64_t zero[6] = {0, 0, 0, 0, 0, 0};
+  a.stats = reinterpret_cast<unsigned long long *>(up.put(zero, max_hubs ? 6 : match_w ? 4 : 2));
   if (match_w) {  // the match table, built here once
     const std::vector<uint16_t> w(match_w, match_w + E);
     const size_t pairs = (size_t)N * (size_t)N;
     ufk::TableArgs &t = h->table;
     t.n_nodes = N, t.edge_uv = a.edge_uv, t.edge_obs = a.edge_obs, t.adj_ptr = a.adj_ptr, t.adj_edge = a.adj_edge;
     t.w = up.put(w);
+    if (max_hubs) a.match_w = t.w;
     t.dist = static_cast<uint32_t *>(up.room(pairs * sizeof(uint32_t)));
     t.mask = static_cast<unsigned long long *>(up.room(pairs * sizeof(uint64_t)));
     up.bytes += (int64_t)(pairs * 12);
@@ -227,6 +251,20 @@ extern "C" int tsim_uf_info(tsim_uf *h, int64_t out[16]) {
   return TSIM_OK;
 }
 
+extern "C" int tsim_uf_erasure_info(tsim_uf *h, int64_t out[4]) {
+  if (!h || !out) return tsim_fail(TSIM_EINVAL, "NULL argument");
+  if (!h->a.max_hubs) return tsim_fail(TSIM_EINVAL, "the handle matches no clusters under heralds (tsim_uf_create_matching_heralds makes one)");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint64_t st[2];
+  HIP_TRY(hipMemcpy(st, h->a.stats + 4, 16, hipMemcpyDeviceToHost));
+  out[0] = h->a.erased_w;
+  out[1] = h->a.max_hubs;
+  out[2] = (int64_t)st[0];
+  out[3] = (int64_t)st[1];
+  return TSIM_OK;
+}
+
 namespace {
 struct SoftOut {  // what tsim_uf_decode_soft_device adds to tsim_uf_decode_device; gap_cap != 0: what tsim_uf_decode_gap_device adds
   int metric, n_bins;
@@ -236,12 +274,23 @@ struct SoftOut {  // what tsim_uf_decode_soft_device adds to tsim_uf_decode_devi
 };
 
 void uf_launch_gap(const ufk::Args &a, unsigned blocks, size_t lds, hipStream_t stream) {
+  if (a.max_hubs) {  // (a handle of tsim_uf_create_matching_heralds with an observable)
+    if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, true, false, true, true, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+    else hipLaunchKernelGGL((ufk::k_uf<false, true, false, true, true, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+    return;
+  }
   if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, false, false, true, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
   else hipLaunchKernelGGL((ufk::k_uf<false, false, false, true, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
 }
 
 template <bool Soft>
 void uf_launch(const ufk::Args &a, unsigned blocks, size_t lds, hipStream_t stream) {
+  if constexpr (!Soft)
+    if (a.max_hubs) {  // (a handle of tsim_uf_create_matching_heralds: its own kernel; the classes run in the gap call only)
+      if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, true, false, true, false, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+      else hipLaunchKernelGGL((ufk::k_uf<false, true, false, true, false, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+      return;
+    }
   if constexpr (!Soft)
     if (a.match_k) {  // (a handle of tsim_uf_create_matching: no heralds, no soft outputs)
       if (a.cap) hipLaunchKernelGGL((ufk::k_uf<true, false, false, true>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);

@@ -55,6 +55,18 @@
 // reached by a sum.  The cluster's gap, the zero of a peeled cluster and of a miss fold into one wave-uniform number per row,
 // whose deficit cap - gap is binned as the soft kernel bins its metric.  The arrays exist only in the layout of such a handle
 // (Args::gap): a handle of tsim_uf_create_matching keeps its bytes per shot and its waves per block.
+// Cluster matching under heralds (k_uf<Weighted, true, false, true, Gap, true>, tsim_uf_create_matching_heralds; "Cluster matching
+// under heralds" in the docstring): pregrow_heralds also sets the edge's bit in `ebits`, the row's erased edges.  After
+// mark_clusters bit 1 of s[v] tags every non-boundary end of an erased edge.  A cluster of 1 .. K defects in turn, by the whole
+// wave: its hubs are its defects, then its tagged nodes that are no defect, both compacted by ballot in ascending node order;
+// more than H hubs make it a peeled cluster (par[r] = 2).  The hubs' n * n + n static distances and masks (uint2 class pairs with
+// Gap) are read from the tables into LDS, every erased edge of the cluster lowers the entry of its pair of hubs (the pairs of a
+// graph are distinct, so one lane writes an entry), the distances relax in the ordered k loop of the docstring, lanes over
+// (i, j) - row and column k stand still in step k - and the classes relax in place until a sweep lowers nothing: a least
+// fixpoint, whichever lane writes first.  The boundary folds into the defects' rows, the results go where match_cluster reads
+// its distances, and the layered programs run as they are; lane 0 walks the winners back over the masks in LDS.  An erased edge
+// is an edge of the graph, so a finite hub distance is at most the static one of its pair, below 2^27 (2^28 for a class): the
+// bounds of the programs stand.  Every step is a fixpoint, a minimum over a fixed set or the ordered k loop.
 // Every index into LDS comes from tables tsim_uf_create has checked; every address is formed in 64 bits.
 #pragma once
 #include "tsim_bitrows.hip.h"
@@ -70,6 +82,7 @@ constexpr int kLdsCU = 160 * 1024;
 constexpr int kMaxCap = 14;              // of an edge: its 4-bit counter may pass the cap by one
 constexpr int kMaxMatchNodes = 2048;     // of a graph with a match table (uint32 + uint64 per pair of nodes)
 constexpr int kMaxMatchDefects = 12;     // K at most: 2^K subsets of a cluster's defects in LDS
+constexpr int kMaxMatchHubs = 32;        // H at most: [H][H] hub distances in LDS
 constexpr uint32_t kMatchInf = 0x7FFFFFFFu;  // a distance of the match table: no path
 constexpr uint32_t kCostInf = 0xFFFFFFFFu;   // a cost of the dynamic program: no pairing
 constexpr uint8_t kViaBoundary = 15, kViaNone = 255;  // the candidate that won a subset: a defect 0 .. 11, the boundary, none
@@ -93,6 +106,7 @@ struct Args {
   unsigned long long *dec;    // [0] kept [1] wrong [2] missed
   unsigned long long *pred;   // [n] or NULL
   unsigned long long *stats;  // [0] most growth rounds [1] rows decoded in LDS [2] clusters matched [3] clusters peeled
+  //                             [4] matched clusters with an erased edge [5] clusters peeled for their hubs (the last two pairs: such handles only)
   // heralded erasures (NULL / 0 on a handle without heralds)
   int n_det_cols;              // detector columns of a row: the nodes but the boundary, and the heralds
   const int32_t *node_det;     // [n_nodes - 1] the column of node v at v - 1
@@ -114,6 +128,12 @@ struct Args {
   int off_gcost, off_gpd;
   uint32_t gap_cap, gap_step;  // G >= 1 and the width of a bin of the deficit G - gap
   const uint32_t *gdist;       // [n_nodes * n_nodes * 2] the class table: the two distances of a pair side by side (8-byte aligned)
+  // cluster matching under heralds (k_uf<., true, false, true, ., true> only; 0 / NULL on other handles)
+  int max_hubs;                // H in K .. 32: a cluster of 1 .. K defects and at most H hubs is matched; 0 on other handles
+  int gap_obs;                 // the observable of the class table: the class of an erased edge is this bit of its mask
+  uint32_t erased_w;           // w_h: an erased edge e of the cluster weighs min(match_w[e], w_h)
+  int off_ebits, off_hub, off_hd, off_hm, off_hb, off_hmb, off_bm, off_hd2, off_hb2;
+  const uint16_t *match_w;     // [n_edges] the match weights
 };
 
 // the layout of one wave's state, shared by the host (sizes, limits) and the kernel
@@ -136,6 +156,19 @@ __host__ inline long long layout(Args *a) {
     if (a->gap) {  // the class program: two costs per subset, two distances per pair
       a->off_gcost = (int)at, at += a16(8ll << K);
       a->off_gpd = (int)at, at += a16(8 * K * (K + 1));
+    }
+    if (const long long H = a->max_hubs) {  // the hub graph: the erased edges, the hubs, distances and masks [H][H] and [H], folded masks [K]
+      a->off_ebits = (int)at, at += a16(4 * W);
+      a->off_hub = (int)at, at += a16(2 * H);
+      a->off_hd = (int)at, at += a16(4 * H * H);
+      a->off_hm = (int)at, at += a16(8 * H * H);
+      a->off_hb = (int)at, at += a16(4 * H);
+      a->off_hmb = (int)at, at += a16(8 * H);
+      a->off_bm = (int)at, at += a16(8 * K);
+      if (a->gap) {
+        a->off_hd2 = (int)at, at += a16(8 * H * H);
+        a->off_hb2 = (int)at, at += a16(8 * H);
+      }
     }
   }
   return at;
@@ -167,6 +200,10 @@ struct State {
   uint8_t *mch;
   uint16_t *mcl;
   uint2 *gcost, *gpd;  // the complementary gap only: .x class 0, .y class 1
+  uint32_t *ebits, *hd, *hb;  // cluster matching under heralds only: the erased edges (a bitmap), hub distances [n][n], to the boundary [n]
+  uint16_t *hub;
+  unsigned long long *hm, *hmb, *bm;  // the masks of hd, of hb, and of the defects' folded boundary distances
+  uint2 *hd2, *hb2;                   // with the gap: the class distances of hd and hb
 };
 
 // a wave's state at `base`, by the offsets layout() has put into `a`
@@ -199,6 +236,21 @@ __device__ __forceinline__ State gap_state_at(const Args &a, uint8_t *base) {
   State st = match_state_at(a, base);
   st.gcost = reinterpret_cast<uint2 *>(base + a.off_gcost);
   st.gpd = reinterpret_cast<uint2 *>(base + a.off_gpd);
+  return st;
+}
+
+// the same with the arrays of the hub graph (a handle of tsim_uf_create_matching_heralds)
+__device__ __forceinline__ State hub_state_at(const Args &a, uint8_t *base) {
+  State st = a.gap ? gap_state_at(a, base) : match_state_at(a, base);
+  st.ebits = reinterpret_cast<uint32_t *>(base + a.off_ebits);
+  st.hub = reinterpret_cast<uint16_t *>(base + a.off_hub);
+  st.hd = reinterpret_cast<uint32_t *>(base + a.off_hd);
+  st.hm = reinterpret_cast<unsigned long long *>(base + a.off_hm);
+  st.hb = reinterpret_cast<uint32_t *>(base + a.off_hb);
+  st.hmb = reinterpret_cast<unsigned long long *>(base + a.off_hmb);
+  st.bm = reinterpret_cast<unsigned long long *>(base + a.off_bm);
+  st.hd2 = reinterpret_cast<uint2 *>(base + a.off_hd2);
+  st.hb2 = reinterpret_cast<uint2 *>(base + a.off_hb2);
   return st;
 }
 
@@ -251,7 +303,8 @@ __device__ __forceinline__ void clear_edges(const G &a, const State &st, int lan
   wsync();
 }
 
-// the edges of the heralds that are set start full
+// the edges of the heralds that are set start full; Erasure: and are the row's erased edges, a bit each in ebits (zeroed)
+template <bool Erasure = false>
 __device__ __forceinline__ void pregrow_heralds(const Args &a, const State &st, const uint8_t *row, int lane) {
   const int det_bytes = (a.n_det_cols + 7) >> 3;
   for (int b = 8 * lane; b < det_bytes; b += 8 * 64) {
@@ -262,6 +315,7 @@ __device__ __forceinline__ void pregrow_heralds(const Args &a, const State &st, 
       const int h = a.col_herald[8 * b + __builtin_ctzll(w)];
       for (int k = a.herald_ptr[h]; k < a.herald_ptr[h + 1]; ++k) {
         const int e = a.herald_edges[k], fw = e >> 5;
+        if constexpr (Erasure) atomicOr(&st.ebits[fw], 1u << (e & 31));
         if (atomicOr(&st.full[fw], 1u << (e & 31)) == 0) st.wlist[atomicAdd(&st.misc[0], 1u)] = (uint16_t)fw;  // (each word once)
       }
     }
@@ -469,6 +523,47 @@ __device__ __forceinline__ void mark_clusters(const Args &a, const State &st, in
   counts[1] = both & 0xFFFFu;
 }
 
+// The layered programs of a cluster of m defects over mpd (and, with Gap, gpd), rows of m + 1 entries: the distances of defect i
+// to the defects j > i, at [m] to the boundary; mcost[0] (and gcost[0]) are set.  Per subset the winner's cost and candidate in
+// mcost / mch, with Gap the two classes' costs in gcost.
+template <bool Gap>
+__device__ __forceinline__ void pair_programs(const State &st, int lane, int m) {
+  const int n_sets = 1 << m, W = m + 1;
+  for (int layer = 1; layer <= m; ++layer) {  // f[S] reads subsets of one and of two defects less
+    for (int S = lane; S < n_sets; S += 64) {
+      if (__popc((unsigned)S) != layer) continue;
+      const int i = __builtin_ctz(S), R = S & (S - 1);
+      uint32_t best = kCostInf;
+      uint8_t via = kViaNone;
+      const uint32_t fR = st.mcost[R], b = st.mpd[i * W + m];
+      if (fR != kCostInf && b != kMatchInf) best = fR + b, via = kViaBoundary;
+      for (int rest = R; rest; rest &= rest - 1) {  // ascending j; strict < keeps the first of least cost
+        const int j = __builtin_ctz(rest);
+        const uint32_t f = st.mcost[R ^ (1 << j)], d = st.mpd[i * W + j];
+        if (f != kCostInf && d != kMatchInf && f + d < best) best = f + d, via = (uint8_t)j;
+      }
+      st.mcost[S] = best;
+      st.mch[S] = via;
+      if constexpr (Gap) {  // a pure minimum of costs: g[S][b] over the class cb of the pair's path and g[.][b ^ cb] of the rest
+        uint32_t g0 = kCostInf, g1 = kCostInf;
+        const auto offer = [&](const uint2 f, const uint2 d) {
+          if (f.x != kCostInf && d.x != kMatchInf) g0 = min(g0, f.x + d.x);
+          if (f.y != kCostInf && d.y != kMatchInf) g0 = min(g0, f.y + d.y);
+          if (f.x != kCostInf && d.y != kMatchInf) g1 = min(g1, f.x + d.y);
+          if (f.y != kCostInf && d.x != kMatchInf) g1 = min(g1, f.y + d.x);
+        };
+        offer(st.gcost[R], st.gpd[i * W + m]);
+        for (int rest = R; rest; rest &= rest - 1) {
+          const int j = __builtin_ctz(rest);
+          offer(st.gcost[R ^ (1 << j)], st.gpd[i * W + j]);
+        }
+        st.gcost[S] = make_uint2(g0, g1);
+      }
+    }
+    wsync();
+  }
+}
+
 // One matched cluster, of root r, by the whole wave: the mask of the dynamic program of the docstring over its defects, which
 // are the entries of label r in lp[from .. n_list).  The result is in lane 0 (0 in the other lanes).  Gap: *gap = min(*gap, the
 // cluster's gap) in every lane, the gap being |g0 - g1| of the class program at the full set, a.gap_cap when one class is infinite.
@@ -503,39 +598,7 @@ __device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st
   }
   wsync();
   const int n_sets = 1 << m;
-  for (int layer = 1; layer <= m; ++layer) {  // f[S] reads subsets of one and of two defects less
-    for (int S = lane; S < n_sets; S += 64) {
-      if (__popc((unsigned)S) != layer) continue;
-      const int i = __builtin_ctz(S), R = S & (S - 1);
-      uint32_t best = kCostInf;
-      uint8_t via = kViaNone;
-      const uint32_t fR = st.mcost[R], b = st.mpd[i * W + m];
-      if (fR != kCostInf && b != kMatchInf) best = fR + b, via = kViaBoundary;
-      for (int rest = R; rest; rest &= rest - 1) {  // ascending j; strict < keeps the first of least cost
-        const int j = __builtin_ctz(rest);
-        const uint32_t f = st.mcost[R ^ (1 << j)], d = st.mpd[i * W + j];
-        if (f != kCostInf && d != kMatchInf && f + d < best) best = f + d, via = (uint8_t)j;
-      }
-      st.mcost[S] = best;
-      st.mch[S] = via;
-      if constexpr (Gap) {  // a pure minimum of costs: g[S][b] over the class cb of the pair's path and g[.][b ^ cb] of the rest
-        uint32_t g0 = kCostInf, g1 = kCostInf;
-        const auto offer = [&](const uint2 f, const uint2 d) {
-          if (f.x != kCostInf && d.x != kMatchInf) g0 = min(g0, f.x + d.x);
-          if (f.y != kCostInf && d.y != kMatchInf) g0 = min(g0, f.y + d.y);
-          if (f.x != kCostInf && d.y != kMatchInf) g1 = min(g1, f.x + d.y);
-          if (f.y != kCostInf && d.x != kMatchInf) g1 = min(g1, f.y + d.x);
-        };
-        offer(st.gcost[R], st.gpd[i * W + m]);
-        for (int rest = R; rest; rest &= rest - 1) {
-          const int j = __builtin_ctz(rest);
-          offer(st.gcost[R ^ (1 << j)], st.gpd[i * W + j]);
-        }
-        st.gcost[S] = make_uint2(g0, g1);
-      }
-    }
-    wsync();
-  }
+  pair_programs<Gap>(st, lane, m);
   if constexpr (Gap) {  // (one address for the wave: the number is wave-uniform)
     const uint2 g = st.gcost[n_sets - 1];
     const uint32_t mine = g.x != kCostInf && g.y != kCostInf ? (g.x > g.y ? g.x - g.y : g.y - g.x) : a.gap_cap;
@@ -568,26 +631,240 @@ __device__ __forceinline__ uint64_t match_clusters(const Args &a, const State &s
   return mask;
 }
 
+// The steps of cluster matching under heralds, in the place of match_clusters.
+// bit 1 of s[v] for every non-boundary end v of an erased edge of the row (bit 0 stays the defect); untag_erased takes it back
+// before peel() reads s[]
+__device__ __forceinline__ void tag_erased(const Args &a, const State &st, int lane) {
+  for (int w = lane; w < a.w32; w += 64)
+    for (uint32_t bits = st.ebits[w]; bits; bits &= bits - 1) {
+      const uint32_t uv = a.edge_uv[32 * w + __builtin_ctz(bits)];
+      const int u = (int)(uv & 0xFFFFu), v = (int)(uv >> 16);
+      if (u) atomicOr(&st.s32[u >> 2], 2u << (8 * (u & 3)));
+      atomicOr(&st.s32[v >> 2], 2u << (8 * (v & 3)));
+    }
+  wsync();
+}
+__device__ __forceinline__ void untag_erased(const Args &a, const State &st, int lane) {
+  for (int v = lane; v < a.n_nodes; v += 64) st.s[v] &= 1;
+  wsync();
+}
+
+// a + b of two distances, kMatchInf when one is (finite ones are below 2^28)
+__device__ __forceinline__ uint32_t add_inf(uint32_t x, uint32_t y) { return x == kMatchInf || y == kMatchInf ? kMatchInf : x + y; }
+// the two classes of a walk made of one of classes x and one of classes y
+__device__ __forceinline__ uint2 join_classes(uint2 x, uint2 y) {
+  return make_uint2(min(add_inf(x.x, y.x), add_inf(x.y, y.y)), min(add_inf(x.x, y.y), add_inf(x.y, y.x)));
+}
+
+// One cluster of root r with 1 .. K defects (the entries of label r in lp[from .. n_list)), by the whole wave, over its hub graph:
+// the mask of the winner program in lane 0 (0 in the other lanes), *gap as match_cluster.  *erased: the cluster has an erased
+// edge; *overflow: it has more than H hubs, nothing is matched and the result is 0 (both wave-uniform).
+template <bool Gap>
+__device__ __forceinline__ uint64_t hub_cluster(const Args &a, const State &st, int lane, int from, int n_list, int r, uint32_t *gap, bool *erased,
+                                                bool *overflow) {
+  const int K = a.match_k, H = a.max_hubs, N = a.n_nodes;
+  int m = 0;
+  for (int i0 = from; i0 < n_list; i0 += 64) {
+    const int i = i0 + lane;
+    const int v = i < n_list ? (int)st.lp[i] : 0;
+    const bool flag = i < n_list && st.label[v] == r;
+    const int pos = compact(flag, lane, &m);
+    if (flag && pos < K) st.hub[pos] = (uint16_t)v;  // (at most K defects: pos < K <= H)
+  }
+  m = min(m, K);
+  int n = m;
+  for (int v0 = 0; v0 < N; v0 += 64) {  // the other ends of its erased edges: tagged, no defect (s[0] is never tagged)
+    const int v = v0 + lane;
+    const bool flag = v < N && st.s[v] == 2 && st.label[v] == r;
+    const int pos = compact(flag, lane, &n);
+    if (flag && pos < H) st.hub[pos] = (uint16_t)v;
+  }
+  wsync();
+  *overflow = n > H;
+  if (*overflow) {
+    *erased = true;
+    return 0;
+  }
+  // the static distances of the hubs, and to the boundary
+  for (int t = lane; t < n * n; t += 64) {
+    const size_t x = st.hub[t / n], y = st.hub[t % n], at = min(x, y) * (size_t)N + max(x, y);
+    st.hd[t] = a.mdist[at];
+    st.hm[t] = a.mmask[at];
+    if constexpr (Gap) st.hd2[t] = reinterpret_cast<const uint2 *>(a.gdist)[at];
+  }
+  for (int x = lane; x < n; x += 64) {
+    const size_t at = (size_t)st.hub[x] * (size_t)N;
+    st.hb[x] = a.mdist[at];
+    st.hmb[x] = a.mmask[at];
+    if constexpr (Gap) st.hb2[x] = reinterpret_cast<const uint2 *>(a.gdist)[at];
+  }
+  wsync();
+  // its erased edges: a pair of nodes has one edge, so an entry has one writer
+  bool any = false;
+  for (int w = lane; w < a.w32; w += 64)
+    for (uint32_t bits = st.ebits[w]; bits; bits &= bits - 1) {
+      const int e = 32 * w + __builtin_ctz(bits);
+      const uint32_t uv = a.edge_uv[e];
+      const int u = (int)(uv & 0xFFFFu), v = (int)(uv >> 16);
+      if (st.label[v] != r) continue;
+      any = true;
+      int i = -1, j = -1;
+      for (int x = 0; x < n; ++x) {
+        if (st.hub[x] == u) i = x;
+        if (st.hub[x] == v) j = x;
+      }
+      if (j < 0 || (u && i < 0)) continue;  // (never: both ends are tagged nodes of the cluster)
+      const uint32_t x = min((uint32_t)a.match_w[e], a.erased_w);
+      const unsigned long long obs = a.edge_obs[e];
+      const bool odd = (obs >> a.gap_obs) & 1ull;
+      if (u) {
+        if (x < st.hd[i * n + j]) st.hd[i * n + j] = st.hd[j * n + i] = x, st.hm[i * n + j] = st.hm[j * n + i] = obs;
+        if constexpr (Gap) {
+          uint2 d = st.hd2[i * n + j];
+          if (odd) d.y = min(d.y, x);
+          else d.x = min(d.x, x);
+          st.hd2[i * n + j] = st.hd2[j * n + i] = d;
+        }
+      } else {
+        if (x < st.hb[j]) st.hb[j] = x, st.hmb[j] = obs;
+        if constexpr (Gap) {
+          uint2 d = st.hb2[j];
+          if (odd) d.y = min(d.y, x);
+          else d.x = min(d.x, x);
+          st.hb2[j] = d;
+        }
+      }
+    }
+  wsync();
+  *erased = __builtin_amdgcn_ballot_w64(any) != 0;
+  if (*erased) {  // (without an erased edge the static distances obey the triangle inequality: nothing would move)
+    for (int k = 0; k < n; ++k) {  // the ordered relaxation: row and column k stand still in step k
+      for (int t = lane; t < n * n; t += 64) {
+        const int i = t / n, j = t % n;
+        if (i == j || i == k || j == k) continue;
+        const uint32_t via = add_inf(st.hd[i * n + k], st.hd[k * n + j]);
+        if (via < st.hd[t]) st.hd[t] = via, st.hm[t] = st.hm[i * n + k] ^ st.hm[k * n + j];
+      }
+      wsync();
+    }
+    if constexpr (Gap)
+      for (;;) {  // the classes: in place to the least fixpoint (an entry only ever falls, to the weight of a walk)
+        bool moved = false;
+        for (int t = lane; t < n * n; t += 64) {
+          const int i = t / n, j = t % n;
+          const uint2 was = st.hd2[t];
+          uint2 d = was;
+          for (int k = 0; k < n; ++k) {
+            const uint2 via = join_classes(st.hd2[i * n + k], st.hd2[k * n + j]);
+            d.x = min(d.x, via.x), d.y = min(d.y, via.y);
+          }
+          if (d.x != was.x || d.y != was.y) st.hd2[t] = d, moved = true;
+        }
+        wsync();
+        if (!__builtin_amdgcn_ballot_w64(moved)) break;
+      }
+  }
+  // the boundary folds into the defects' rows; the results go where the layered programs read them
+  const int W = m + 1;
+  for (int t = lane; t < m * W; t += 64) {
+    const int i = t / W, j = t % W;
+    if (j <= i) continue;
+    if (j < m) {
+      st.mpd[t] = st.hd[i * n + j];
+      if constexpr (Gap) st.gpd[t] = st.hd2[i * n + j];
+      continue;
+    }
+    uint32_t best = st.hb[i];
+    unsigned long long mask = st.hmb[i];
+    for (int x = 0; x < n; ++x) {  // ascending x; strict < keeps the first of least cost
+      if (x == i) continue;
+      const uint32_t via = add_inf(st.hd[i * n + x], st.hb[x]);
+      if (via < best) best = via, mask = st.hm[i * n + x] ^ st.hmb[x];
+    }
+    st.mpd[t] = best;
+    st.bm[i] = mask;
+    if constexpr (Gap) {
+      uint2 d = make_uint2(kMatchInf, kMatchInf);
+      for (int x = 0; x < n; ++x) {
+        const uint2 via = join_classes(st.hd2[i * n + x], st.hb2[x]);
+        d.x = min(d.x, via.x), d.y = min(d.y, via.y);
+      }
+      st.gpd[t] = d;
+    }
+  }
+  if (lane == 0) {
+    st.mcost[0] = 0;
+    if constexpr (Gap) st.gcost[0] = make_uint2(0u, kCostInf);
+  }
+  wsync();
+  const int n_sets = 1 << m;
+  pair_programs<Gap>(st, lane, m);
+  if constexpr (Gap) {
+    const uint2 g = st.gcost[n_sets - 1];
+    const uint32_t mine = g.x != kCostInf && g.y != kCostInf ? (g.x > g.y ? g.x - g.y : g.y - g.x) : a.gap_cap;
+    *gap = min(*gap, mine);
+  }
+  uint64_t mask = 0;
+  if (lane == 0)
+    for (int S = n_sets - 1; S;) {  // the winners, from the full set down, over the masks in LDS
+      const int i = __builtin_ctz(S), R = S & (S - 1), via = st.mch[S];
+      if (via == kViaNone) break;
+      if (via == kViaBoundary) mask ^= st.bm[i], S = R;
+      else mask ^= st.hm[i * n + via], S = R ^ (1 << via);  // (via is a defect of R: below m <= n)
+    }
+  wsync();  // (the next cluster overwrites the arrays)
+  return mask;
+}
+
+// every cluster of 1 .. K defects, in the order of its smallest defect: the XOR of the matched ones' masks, in lane 0; *gap as
+// match_cluster.  A cluster of more than H hubs becomes a peeled one: counts[0] / counts[1], the matched and the peeled clusters
+// of mark_clusters, move by one; counts[2]: the matched clusters with an erased edge, counts[3]: those peeled for their hubs.
+template <bool Gap>
+__device__ __forceinline__ uint64_t hub_clusters(const Args &a, const State &st, int lane, int n_list, uint32_t *gap, uint32_t *counts) {
+  uint64_t mask = 0;
+  counts[2] = counts[3] = 0;
+  tag_erased(a, st, lane);
+  for (int i = 0; i < n_list; ++i) {
+    const int r = __builtin_amdgcn_readfirstlane((int)st.label[st.lp[i]]);
+    if (__builtin_amdgcn_readfirstlane((int)st.par[r]) != 1) continue;  // (seen before, by an earlier defect of its)
+    bool erased, overflow;
+    mask ^= hub_cluster<Gap>(a, st, lane, i, n_list, r, gap, &erased, &overflow);
+    if (overflow) --counts[0], ++counts[1], ++counts[3];
+    else if (erased) ++counts[2];
+    if (lane == 0) st.par[r] = overflow ? 2 : 3;
+    wsync();
+  }
+  untag_erased(a, st, lane);
+  return mask;
+}
+
 // one kept row with a defect, by the whole wave: the prediction (0 for a miss); *missed and *rounds are wave-uniform, and so
 // are, with Soft, soft[0 .. 2]: full edges, largest cluster, correction weight; with Match, soft[0 .. 1]: the clusters matched
-// and peeled; with Gap, soft[2]: the row's gap, min(a.gap_cap, the least gap of its clusters), 0 with a peeled cluster and for a miss
-template <bool Weighted, bool Heralds, bool Soft, bool Match = false, bool Gap = false>
+// and peeled; with Gap, soft[2]: the row's gap, min(a.gap_cap, the least gap of its clusters), 0 with a peeled cluster and for a miss;
+// with Erasure (soft has five entries), soft[2 .. 3]: the matched clusters with an erased edge and the clusters peeled for their
+// hubs, soft[4]: the row's gap
+template <bool Weighted, bool Heralds, bool Soft, bool Match = false, bool Gap = false, bool Erasure = false>
 __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, const uint8_t *row, int lane, bool *missed, int *rounds,
                                                 uint32_t *soft) {
   load_defects<Heralds>(a, st, row, lane);
+  if constexpr (Erasure)
+    for (int i = lane; i < a.w32; i += 64) st.ebits[i] = 0;
   clear_edges<Weighted>(a, st, lane);
-  if constexpr (Heralds) pregrow_heralds(a, st, row, lane);
+  if constexpr (Heralds) pregrow_heralds<Erasure>(a, st, row, lane);
   *missed = grow<Weighted>(a, st, lane, rounds);
   if constexpr (Soft) soft_of_growth(a, st, lane, soft), soft[2] = 0;
   if constexpr (Match) soft[0] = soft[1] = 0;
   if constexpr (Gap) soft[2] = 0;
+  if constexpr (Erasure) soft[2] = soft[3] = soft[4] = 0;
   if (*missed) return 0;
   if constexpr (Match) {
     int n_list;
     mark_clusters(a, st, lane, &n_list, soft);
     uint32_t gap = a.gap_cap;
-    uint64_t flips = match_clusters<Gap>(a, st, lane, n_list, &gap);
-    if constexpr (Gap) soft[2] = soft[1] ? 0u : gap;
+    uint64_t flips;
+    if constexpr (Erasure) flips = hub_clusters<Gap>(a, st, lane, n_list, &gap, soft);
+    else flips = match_clusters<Gap>(a, st, lane, n_list, &gap);
+    if constexpr (Gap) soft[Erasure ? 4 : 2] = soft[1] ? 0u : gap;
     if (soft[1]) {  // a flip counts when its edge, and so its child node, lies in a peeled cluster
       forest(a, st, lane);
       flips ^= peel(a, st, lane, [&](int e, int u, int) { return st.par[st.label[u]] == 2 ? a.edge_obs[e] : 0ull; });
@@ -604,19 +881,20 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   return fold_flips(&st.misc[2], flips);
 }
 
-template <bool Weighted, bool Heralds, bool Soft = false, bool Match = false, bool Gap = false>
+template <bool Weighted, bool Heralds, bool Soft = false, bool Match = false, bool Gap = false, bool Erasure = false>
 __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed; with Soft or Gap: the kept rows of bin 0
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
-  const State st = Gap ? gap_state_at(a, base) : Match ? match_state_at(a, base) : state_at(a, base);
+  const State st = Erasure ? hub_state_at(a, base) : Gap ? gap_state_at(a, base) : Match ? match_state_at(a, base) : state_at(a, base);
   if (threadIdx.x < 4) stat[threadIdx.x] = 0;
   __syncthreads();
   uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
   int most_rounds = 0;
   uint32_t bin0_acc = 0, bin0_wrong_acc = 0;  // (Soft) wave-uniform: the kept rows of bin 0, the wrong ones among them
   uint32_t matched_acc = 0, peeled_acc = 0;   // (Match) wave-uniform: the clusters matched and peeled
+  uint32_t erased_acc = 0, hubs_acc = 0;      // (Erasure) wave-uniform: the matched clusters with an erased edge, those peeled for their hubs
   const int nd = a.n_nodes - 1;
   const long long tiles = (a.n + 63) >> 6;
   for (long long t = (long long)blockIdx.x * a.waves + wave; t < tiles; t += (long long)gridDim.x * a.waves) {
@@ -637,14 +915,15 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       work &= work - 1;
       bool m;
       int rounds;
-      uint32_t soft[3];
-      const uint64_t p = decode_shot<Weighted, Heralds, Soft, Match, Gap>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, soft);
+      uint32_t soft[Erasure ? 5 : 3];
+      const uint64_t p = decode_shot<Weighted, Heralds, Soft, Match, Gap, Erasure>(a, st, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, soft);
       if constexpr (Match) matched_acc += soft[0], peeled_acc += soft[1];
+      if constexpr (Erasure) erased_acc += soft[2], hubs_acc += soft[3];
       if (lane == src) pred = p, missed = m;
       if constexpr (Soft)
         if (lane == src) mine[0] = (uint32_t)rounds, mine[1] = soft[0], mine[2] = soft[1], mine[3] = soft[2];
       if constexpr (Gap)
-        if (lane == src) deficit = a.gap_cap - soft[2];
+        if (lane == src) deficit = a.gap_cap - soft[Erasure ? 4 : 2];
       most_rounds = max(most_rounds, rounds);
       ++decoded_acc;
     }
@@ -686,6 +965,10 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
     if constexpr (Match) {
       if (matched_acc) atomicAdd(&a.stats[2], (unsigned long long)matched_acc);
       if (peeled_acc) atomicAdd(&a.stats[3], (unsigned long long)peeled_acc);
+    }
+    if constexpr (Erasure) {
+      if (erased_acc) atomicAdd(&a.stats[4], (unsigned long long)erased_acc);
+      if (hubs_acc) atomicAdd(&a.stats[5], (unsigned long long)hubs_acc);
     }
     if constexpr (Soft || Gap) {
       if (bin0_acc) atomicAdd(&stat[3], bin0_acc);

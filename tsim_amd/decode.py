@@ -126,8 +126,9 @@ XOR; a candidate with an ``INF`` term or built on an infinite ``f`` is infinite;
 cluster is connected and holds an even number of defects or node 0).  The prediction is the XOR of the matched clusters' masks
 and the peeled clusters' flips; nothing in it depends on a parallel order.  ``uf.with_cluster_matching(K, weights)`` is the
 decoder of the same graph, caps and observables with ``match_defects = K`` (1 .. 12, default 10) and ``match_weights``
-(default ``graph.match_weights()``).  It takes no graph with heralds (the table is static, a herald is not), no soft output,
-and has no ``flipped_edges``; :class:`WindowedUnionFindDecoder` has no matching.
+(default ``graph.match_weights()``).  It takes no graph with heralds (the table is static, a herald is not: the section "Cluster
+matching under heralds" below is the decoder of such a graph), no soft output, and has no ``flipped_edges``;
+:class:`WindowedUnionFindDecoder` has no matching.
 
 Complementary gap (:meth:`UnionFindDecoder.with_gap_output`; ``tsim_uf_create_matching_gap``, ``tsim_uf_decode_gap_device``,
 DESIGN.md 3.27).  The soft outputs above are growth statistics.  The signal of a matching decoder is how much heavier the best
@@ -159,8 +160,54 @@ sure, as with the metrics above, so :meth:`ShotCounts.rejection_curve` works unc
 for a kept row without a defect, which counts in bin 0 (``soft_kept.sum() == kept``).
 ``um.with_gap_output(observable=0, bins=64, step=None, cap=None)`` is the decoder of the same graph, caps, weights and ``K`` with
 ``soft_output = "gap"``, ``soft_bins``, ``gap_observable``, ``gap_cap`` (default ``W0``; ``ValueError`` when that is ``None``) and
-``gap_step`` (default ``cap // bins + 1``).  Not done: a gap under heralds, a gap of the windowed decoder, several observables at
-once, and complements that cross clusters (the gap of a row is the least of its clusters' own).
+``gap_step`` (default ``cap // bins + 1``).  Not done: a gap of the windowed decoder, several observables at once, and complements
+that cross clusters (the gap of a row is the least of its clusters' own); a gap under heralds is the next section.
+
+Cluster matching under heralds (:meth:`UnionFindDecoder.with_erasure_matching`; ``tsim_uf_create_matching_heralds``).
+A static match table ignores what a herald says: the erased edges of a row are nearly free, and matching that does not see them
+is worse than peeling.  ``uf.with_erasure_matching(max_defects=10, weights=None, erased_weight=1, max_hubs=24)`` is the decoder of a
+graph WITH heralds that matches each cluster in a small HUB GRAPH, which joins the static tables and the row's erased edges.
+``K = max_defects`` is 1 .. 12, ``weights`` as in ``with_cluster_matching``, ``w_h = erased_weight`` an int in 1 .. 65535 and
+``H = max_hubs`` an int in ``K`` .. 32; a graph without heralds is a ``ValueError`` (``with_cluster_matching`` is its decoder), more
+than 2048 nodes ``NotImplementedError``, a decoder that has a soft output ``ValueError``.  ``ue.with_gap_output(...)`` works on it.
+
+The static tables ``dist`` / ``mask`` and, with a gap, ``dist2`` and ``W0`` are exactly those above, over the nodes and edges of the
+herald graph under the static weights ``w``.  Growth is the herald rule, unchanged: ``missed`` and ``growth_rounds`` are the plain
+herald decoder's, a miss predicts 0 and has gap 0.  An ERASED EDGE of a row is an edge listed under a herald that is set, each taken
+once.  For a cluster of root ``r`` with the defects ``a_0 < ... < a_{m-1}``, ``E_C`` is the set of erased edges ``e`` with
+``label[edge_v[e]] == r``, and its HUBS ``h_0 .. h_{n-1}`` are its defects, ascending, followed by the other non-boundary ends of
+``E_C``, ascending.  The cluster is MATCHED iff ``1 <= m <= K`` and ``n <= H``; otherwise it is PEELED exactly as above (forest and
+peeling run, its flips count).  Without an erased edge ``n = m <= K <= H``.
+
+Hub distances (:meth:`UnionFindDecoder.hub_graph`).  ``D[i][i] = 0``, ``M[i][i] = 0``; for ``i != j``
+``D[i][j] = dist[min(h_i, h_j)][max(h_i, h_j)]`` with its ``mask``.  Then every ``e = (u, v)`` of ``E_C`` with ``u >= 1``, in ascending
+``e``, with ``x = min(w[e], w_h)`` and ``i``, ``j`` the hubs of its ends: if ``x < D[i][j]``, ``D[i][j] = D[j][i] = x`` and both masks
+become ``edge_obs[e]`` (a pair of nodes has one edge, so the order decides nothing).  Then the relaxation: for ``k = 0 .. n - 1``
+ascending, for all ``i != j`` both different from ``k``, if both terms are finite and ``D[i][k] + D[k][j] < D[i][j]``, that sum
+replaces ``D[i][j]`` and ``M[i][j] = M[i][k] ^ M[k][j]``.  Row and column ``k`` do not change in step ``k`` (``D[k][k] = 0``), so the
+pairs of one step may run in parallel, in place.  The boundary: ``B[x] = dist[h_x][0]``, ``MB[x] = mask[h_x][0]``; every
+``e = (0, v)`` of ``E_C``, ascending, with ``x`` the hub of ``v``: if ``min(w[e], w_h) < B[x]`` it replaces ``B[x]`` and
+``MB[x] = edge_obs[e]``.  For a defect ``i < m``, ``b[i]`` starts at ``(B[i], MB[i])``; then, for ``x`` ascending, ``x != i``, a finite
+``D[i][x] + B[x]`` that is strictly smaller replaces it, with the mask ``M[i][x] ^ MB[x]``.  The dynamic program of cluster
+matching then runs unchanged over ``D[i][j]``, ``i < j < m``, and ``b[i]``.  An erased edge is an edge of the graph, so hubs that
+the hub graph joins are joined by the static table too and a finite ``D`` or ``b`` is at most its static entry, below
+``2047 * 65535 < 2^27``: a cost has at most 12 such terms and stays below ``2^31``.  ``D[i][j]`` is the distance of ``h_i`` and ``h_j``
+in the whole graph, never through node 0, under ``w`` lowered to ``min(w, w_h)`` on ``E_C``, and ``b[i]`` that of ``a_i`` and node 0.
+
+Classes (a decoder with a gap).  The hub class distances ``D2[i][j][b]`` and ``B2[x][b]`` are the least weights of walks in the hub
+graph whose arcs are the static ``dist2`` entries of the pairs of hubs (``dist2[h_x][0]`` towards the boundary) and the edges of
+``E_C`` at ``min(w[e], w_h)`` in the class of bit ``k`` of ``edge_obs[e]``; ``b2[i][b]`` is the minimum over ``x`` and ``c`` of
+``D2[i][x][c] + B2[x][b ^ c]``.  They are pure minima and a least fixpoint: no order matters and no tie rule is needed.  The class
+program of the complementary gap then runs over ``D2`` and ``b2``.  The gap of a cluster is ``|g0 - g1|``, the cap when one class
+is infinite, 0 for a peeled cluster, one peeled for its hubs included; the row's gap, the deficit and the bins are those above,
+``cap`` defaults to the static ``W0``.  On every matched cluster ``min(g)`` is the winner's cost and, where the classes differ, the
+cheaper class is bit ``k`` of the winner's mask (both asserted in the numpy statement).
+
+Reduction.  On a cluster without an erased edge every number equals the two sections above bit for bit: the static distances obey
+the triangle inequality, so no relaxation fires, and ``b[i]`` keeps its own entry (asserted in the numpy statement).
+:meth:`UnionFindDecoder.erasure_counts` counts the matched clusters that had an erased edge and the clusters of at most ``K``
+defects that were peeled for ``n > H``; ``match_counts`` counts the latter as peeled.  Out of scope: the windowed decoder, erased
+edges of other clusters (a cluster sees its own), several observables per gap.
 
 Sliding-window decoding of long runs (:class:`WindowedUnionFindDecoder`; ``tsim_ufw_*``, ``csrc/tsim_ufw.hip.h``)
 ---------------------------------------------------------------------------------------------------------------------
@@ -253,6 +300,7 @@ SOFT_OUTPUTS = ("rounds", "full_edges", "largest_cluster", "correction_weight") 
 MAX_SOFT_BINS = 1024
 MAX_MATCH_NODES = 2048   # of a graph with a match table: uint32 + uint64 per pair of nodes
 MAX_MATCH_DEFECTS = 12   # K of cluster matching at most: 2^K subsets of a cluster's defects in LDS
+MAX_MATCH_HUBS = 32      # H of cluster matching under heralds at most: [H, H] hub distances in LDS
 MATCH_INF = 0x7FFFFFFF   # a distance of the match table: no path
 MAX_GAP_CAP = 0x7FFFFFFE  # the cap G of a complementary gap at most
 _GAP_INF = 1 << 62        # the gap of a cluster with one finite class, before the cap
@@ -694,6 +742,19 @@ def uf_match_shot_bytes(n_nodes: int, n_edges: int, weighted: bool, max_defects:
     return uf_shot_bytes(n_nodes, n_edges, weighted) + a16(4 << K) + a16(1 << K) + a16(2 * K) + a16(4 * K * (K + 1)) + classes
 
 
+def uf_erasure_shot_bytes(n_nodes: int, n_edges: int, weighted: bool, max_defects: int, max_hubs: int, gap: bool = False) -> int:
+    """The LDS bytes of one shot's state on a handle of ``tsim_uf_create_matching_heralds``: :func:`uf_match_shot_bytes` and, for
+    the hub graph of a cluster of ``H = max_hubs`` hubs, the bitmap of the row's erased edges, the hubs (uint16), their distances
+    uint32 ``[H, H]`` and masks uint64 ``[H, H]``, the boundary's ``[H]`` of each, and the folded boundary masks uint64
+    ``[K]``; ``gap``: the class distances, two uint32 per entry of ``[H, H]`` and of ``[H]``."""
+    a16 = lambda x: (x + 15) // 16 * 16  # noqa: E731
+    K, H = int(max_defects), int(max_hubs)
+    w32 = max(1, (n_edges + 31) // 32)
+    classes = a16(8 * H * H) + a16(8 * H) if gap else 0
+    return (uf_match_shot_bytes(n_nodes, n_edges, weighted, K, gap) + a16(4 * w32) + a16(2 * H) + a16(4 * H * H) + a16(8 * H * H) +
+            a16(4 * H) + a16(8 * H) + a16(8 * K) + classes)
+
+
 def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray:
     """Min-label propagation over the edges ``(fu, fv)``, from labels that are upper bounds (each a node of its own cluster),
     to its fixpoint."""
@@ -819,7 +880,7 @@ class UnionFindDecoder(_RowDecoder):
     ``decode`` / ``missed`` have the signatures of :class:`LookupDecoder`; they decode each distinct syndrome once.
     ``edge_caps``: an integer per edge in 1 .. 14 for weighted growth (kept as uint8 in ``self.edge_caps``), ``None`` for the
     unweighted decoder (a cap of 2 everywhere).  ``match_defects`` / ``match_weights`` are ``None`` unless the decoder comes from
-    :meth:`with_cluster_matching`."""
+    :meth:`with_cluster_matching` or :meth:`with_erasure_matching`, ``erased_weight`` / ``max_hubs`` unless from the latter."""
 
     def __init__(self, graph: DecodingGraph, num_observables: int | None = None, edge_caps=None):
         used = int(np.bitwise_or.reduce(graph.edge_obs)) if graph.n_edges else 0
@@ -842,6 +903,7 @@ class UnionFindDecoder(_RowDecoder):
         self.soft_output, self.soft_bins = None, None   # the metric count() bins, and into how many bins (with_soft_output)
         self.match_defects, self.match_weights = None, None   # K and the weights of cluster matching (with_cluster_matching)
         self.gap_observable = self.gap_cap = self.gap_step = None   # the complementary gap (with_gap_output)
+        self.erased_weight = self.max_hubs = None   # w_h and H of cluster matching under heralds (with_erasure_matching)
         self._cache: dict = {}   # packed row of detectors -> (prediction, missed, flipped edges, rounds, full edges, largest cluster)
 
     @classmethod
@@ -881,24 +943,58 @@ class UnionFindDecoder(_RowDecoder):
             raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
         if g.n_nodes > MAX_MATCH_NODES:
             raise NotImplementedError(f"{g.n_nodes} nodes (a match table has at most {MAX_MATCH_NODES}: 12 bytes per pair of nodes)")
+        out = object.__new__(UnionFindDecoder)
+        out.__dict__.update(self.__dict__)
+        out.match_defects, out.match_weights = int(K), self._match_weights(weights)
+        out._cache, out._table = {}, None
+        return out
+
+    def with_erasure_matching(self, max_defects: int = 10, weights=None, erased_weight: int = 1, max_hubs: int = 24) -> "UnionFindDecoder":
+        """Cluster matching for a graph WITH heralds ("Cluster matching under heralds" in the module docstring): every cluster of
+        at most ``max_defects`` defects (1 .. 12) and at most ``max_hubs`` hubs (``max_defects`` .. 32) is corrected by the
+        minimum-weight matching of its defects in its hub graph, where an erased edge of the cluster weighs
+        ``min(weights[e], erased_weight)`` (``erased_weight``: an int in 1 .. 65535); ``weights`` as in
+        :meth:`with_cluster_matching`.  :meth:`with_gap_output` works on the result."""
+        is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))  # noqa: E731
+        K, H = max_defects, max_hubs
+        if not is_int(K) or not 1 <= K <= MAX_MATCH_DEFECTS:
+            raise ValueError(f"max_defects = {K!r}: an int in 1 .. {MAX_MATCH_DEFECTS}")
+        if not is_int(erased_weight) or not 1 <= erased_weight <= 65535:
+            raise ValueError(f"erased_weight = {erased_weight!r}: an int in 1 .. 65535")
+        if not is_int(H) or not K <= H <= MAX_MATCH_HUBS:
+            raise ValueError(f"max_hubs = {H!r}: an int in max_defects = {K} .. {MAX_MATCH_HUBS}")
+        if self.soft_output is not None:
+            raise ValueError("a decoder with a soft output takes no cluster matching")
+        g = self.graph
+        if not g.n_heralds:
+            raise ValueError("the graph has no heralds: with_cluster_matching() is the matching decoder of such a graph")
+        if g.n_nodes > MAX_MATCH_NODES:
+            raise NotImplementedError(f"{g.n_nodes} nodes (a match table has at most {MAX_MATCH_NODES}: 12 bytes per pair of nodes)")
+        out = object.__new__(UnionFindDecoder)
+        out.__dict__.update(self.__dict__)
+        out.match_defects, out.match_weights = int(K), self._match_weights(weights)
+        out.erased_weight, out.max_hubs = int(erased_weight), int(H)
+        out._cache, out._table = {}, None
+        return out
+
+    def _match_weights(self, weights) -> np.ndarray:
+        """``weights`` of a matching decoder as uint16 ``[n_edges]``, checked; ``None``: ``graph.match_weights()``."""
+        g = self.graph
         w = g.match_weights() if weights is None else np.asarray(weights)
         if w.shape != (g.n_edges,) or not np.issubdtype(w.dtype, np.integer):
             raise ValueError(f"weights must be integers of shape ({g.n_edges},), got {w.dtype} {w.shape}")
         if len(w) and (w.min() < 1 or w.max() > 65535):
             bad = int(np.flatnonzero((w < 1) | (w > 65535))[0])
             raise ValueError(f"edge {bad} has match weight {int(w[bad])} (1 .. 65535)")
-        out = object.__new__(UnionFindDecoder)
-        out.__dict__.update(self.__dict__)
-        out.match_defects, out.match_weights = int(K), w.astype(np.uint16)
-        out._cache, out._table = {}, None
-        return out
+        return w.astype(np.uint16)
 
     def with_gap_output(self, observable: int = 0, bins: int = 64, step: int | None = None, cap: int | None = None) -> "UnionFindDecoder":
-        """The cluster-matching decoder of the same graph, caps, weights and ``max_defects`` with the complementary gap of
-        ``observable`` as its soft output ("Complementary gap" in the module docstring): ``soft_output = "gap"``,
-        ``soft_bins = bins`` (2 .. 1024), ``gap_observable``, ``gap_cap`` (``cap``, an int in 1 .. 2^31 - 2; default ``W0`` of
-        :meth:`gap_table`) and ``gap_step`` (``step >= 1``; default ``cap // bins + 1``).  Its predictions are this decoder's;
-        ``count(decoder=...)`` fills ``ShotCounts.soft_kept`` / ``soft_errors`` with the deficits ``cap - gap``."""
+        """The cluster-matching decoder of the same graph, caps, weights and ``max_defects`` (one of :meth:`with_cluster_matching`
+        or of :meth:`with_erasure_matching`) with the complementary gap of ``observable`` as its soft output ("Complementary gap"
+        in the module docstring): ``soft_output = "gap"``, ``soft_bins = bins`` (2 .. 1024), ``gap_observable``, ``gap_cap`` (``cap``,
+        an int in 1 .. 2^31 - 2; default ``W0`` of :meth:`gap_table`) and ``gap_step`` (``step >= 1``; default ``cap // bins + 1``).
+        Its predictions are this decoder's; ``count(decoder=...)`` fills ``ShotCounts.soft_kept`` / ``soft_errors`` with the
+        deficits ``cap - gap``."""
         is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))  # noqa: E731
         self._matching("with_gap_output()")
         if not is_int(observable) or not 0 <= observable < self._n_obs:
@@ -988,28 +1084,23 @@ class UnionFindDecoder(_RowDecoder):
         self._table = (dist_all, mask_all)
         return self._table
 
-    def _match_cluster(self, defects):
-        """``(cost, mask, pairs)`` of the dynamic program of the module docstring over the defect nodes ``defects`` (ascending,
-        at most 12): ``pairs`` lists ``(a_i, a_j)`` and, for a defect matched to the boundary, ``(a_i, 0)``.  The cost is ``None``
-        when no pairing is finite."""
-        self._matching("_match_cluster()")
-        dist, mask = self.match_table()
-        a = [int(x) for x in defects]
-        m = len(a)
-        if m > MAX_MATCH_DEFECTS or any(x >= y for x, y in zip(a, a[1:])) or (m and (a[0] < 1 or a[-1] >= self.graph.n_nodes)):
-            raise ValueError(f"defects: at most {MAX_MATCH_DEFECTS} ascending nodes in 1 .. {self.graph.n_nodes - 1}")
+    @staticmethod
+    def _pair_program(m: int, term):
+        """The dynamic program of the module docstring over the defects ``0 .. m - 1``: ``term(i, j)`` is ``(distance, mask)`` of
+        defect ``i`` and defect ``j > i``, of defect ``i`` and the boundary for ``j = None`` (``MATCH_INF``: none).  ``(cost, mask,
+        pairs)``, the pairs as ``(i, j)``; the cost is ``None`` when no pairing is finite."""
         f = [(0, 0, None)] + [None] * ((1 << m) - 1)   # (cost, mask, (what it is built on, the pair)); None: infinite
         for S in range(1, 1 << m):
             i = (S & -S).bit_length() - 1
             R = S & (S - 1)
-            cands = [(R, 0)] + [(R ^ (1 << j), a[j]) for j in range(i + 1, m) if (R >> j) & 1]
+            cands = [(R, None)] + [(R ^ (1 << j), j) for j in range(i + 1, m) if (R >> j) & 1]
             best = None
-            for base, other in cands:
-                d = int(dist[a[i], other])
+            for base, j in cands:
+                d, mk = term(i, j)
                 if f[base] is None or d == MATCH_INF:
                     continue
                 if best is None or f[base][0] + d < best[0]:
-                    best = (f[base][0] + d, f[base][1] ^ int(mask[a[i], other]), (base, (a[i], other)))
+                    best = (f[base][0] + d, f[base][1] ^ mk, (base, (i, j)))
             f[S] = best
         S, pairs = (1 << m) - 1, []
         if f[S] is None:
@@ -1019,6 +1110,24 @@ class UnionFindDecoder(_RowDecoder):
             pairs.append(pair)
             S = base
         return f[-1][0], f[-1][1], pairs
+
+    def _check_defects(self, defects) -> list:
+        a = [int(x) for x in defects]
+        m = len(a)
+        if m > MAX_MATCH_DEFECTS or any(x >= y for x, y in zip(a, a[1:])) or (m and (a[0] < 1 or a[-1] >= self.graph.n_nodes)):
+            raise ValueError(f"defects: at most {MAX_MATCH_DEFECTS} ascending nodes in 1 .. {self.graph.n_nodes - 1}")
+        return a
+
+    def _match_cluster(self, defects):
+        """``(cost, mask, pairs)`` of the dynamic program of the module docstring over the defect nodes ``defects`` (ascending,
+        at most 12): ``pairs`` lists ``(a_i, a_j)`` and, for a defect matched to the boundary, ``(a_i, 0)``.  The cost is ``None``
+        when no pairing is finite."""
+        self._matching("_match_cluster()")
+        dist, mask = self.match_table()
+        a = self._check_defects(defects)
+        other = lambda j: 0 if j is None else a[j]  # noqa: E731
+        cost, mk, pairs = self._pair_program(len(a), lambda i, j: (int(dist[a[i], other(j)]), int(mask[a[i], other(j)])))
+        return cost, mk, [(a[i], other(j)) for i, j in pairs]
 
     def _gap(self, what: str):
         if self.gap_observable is None:
@@ -1066,23 +1175,19 @@ class UnionFindDecoder(_RowDecoder):
         self._gap_table = (dist2, int(sums[both].min()) if both.any() else None)
         return self._gap_table
 
-    def _gap_cluster(self, defects):
-        """``(g0, g1)`` of the class program of the module docstring over the defect nodes ``defects`` (ascending, at most 12):
-        the least cost of a pairing whose paths' classes XOR to 0, and to 1; ``None`` for an infinite one."""
-        self._gap("_gap_cluster()")
-        dist2 = self.gap_table()[0]
-        a = [int(x) for x in defects]
-        m = len(a)
-        if m > MAX_MATCH_DEFECTS or any(x >= y for x, y in zip(a, a[1:])) or (m and (a[0] < 1 or a[-1] >= self.graph.n_nodes)):
-            raise ValueError(f"defects: at most {MAX_MATCH_DEFECTS} ascending nodes in 1 .. {self.graph.n_nodes - 1}")
+    @staticmethod
+    def _class_program(m: int, term2):
+        """The class program of the module docstring over the defects ``0 .. m - 1``: ``term2(i, j)`` is the pair of class
+        distances of defect ``i`` and defect ``j > i``, the boundary for ``j = None``.  ``(g0, g1)``, ``None`` for an infinite one."""
         g = [[0, None]] + [None] * ((1 << m) - 1)
         for S in range(1, 1 << m):
             i = (S & -S).bit_length() - 1
             R = S & (S - 1)
             best = [None, None]
-            for base, other in [(R, 0)] + [(R ^ (1 << j), a[j]) for j in range(i + 1, m) if (R >> j) & 1]:
+            for base, j in [(R, None)] + [(R ^ (1 << j), j) for j in range(i + 1, m) if (R >> j) & 1]:
+                d2 = term2(i, j)
                 for cb in (0, 1):
-                    d = int(dist2[a[i], other, cb])
+                    d = int(d2[cb])
                     if d == MATCH_INF:
                         continue
                     for b in (0, 1):
@@ -1092,10 +1197,23 @@ class UnionFindDecoder(_RowDecoder):
             g[S] = best
         return tuple(g[-1])
 
+    def _gap_cluster(self, defects):
+        """``(g0, g1)`` of the class program of the module docstring over the defect nodes ``defects`` (ascending, at most 12):
+        the least cost of a pairing whose paths' classes XOR to 0, and to 1; ``None`` for an infinite one."""
+        self._gap("_gap_cluster()")
+        dist2 = self.gap_table()[0]
+        a = self._check_defects(defects)
+        return self._class_program(len(a), lambda i, j: dist2[a[i], 0 if j is None else a[j]])
+
     def _cluster_gap(self, defects, cost, mask) -> int:
         """The gap of a matched cluster before the cap (``_GAP_INF`` when one class is infinite), its two invariants asserted
         against ``(cost, mask)`` of :meth:`_match_cluster`."""
-        g0, g1 = self._gap_cluster(defects)
+        return self._gap_of_classes(self._gap_cluster(defects), cost, mask)
+
+    def _gap_of_classes(self, classes, cost, mask) -> int:
+        """:meth:`_cluster_gap` from ``classes``, the ``(g0, g1)`` of a cluster's class program, and ``(cost, mask)`` of its
+        winner program."""
+        g0, g1 = classes
         finite = [x for x in (g0, g1) if x is not None]
         assert finite and min(finite) == cost, "the cheaper class does not cost what the matching costs"
         if g0 is None or g1 is None:
@@ -1103,6 +1221,108 @@ class UnionFindDecoder(_RowDecoder):
             return _GAP_INF
         assert g0 == g1 or (g1 < g0) == bool((mask >> self.gap_observable) & 1), "the cheaper class is not the matching's"
         return abs(g0 - g1)
+
+    def hub_graph(self, defects, erased_edges) -> dict:
+        """The hub graph of one cluster ("Cluster matching under heralds" in the module docstring): ``defects``, its defect nodes
+        ascending, and ``erased_edges``, its erased edges ``E_C``.  ``hubs`` (int64 ``[n]``), ``D`` / ``M`` (int64 / uint64 ``[n, n]``,
+        ``MATCH_INF``: none), ``B`` / ``MB`` (``[n]``) and, per defect, ``b`` / ``mb`` (``[m]``); of a decoder with a gap also ``D2``
+        (``[n, n, 2]``), ``B2`` (``[n, 2]``) and ``b2`` (``[m, 2]``)."""
+        self._erasure("hub_graph()")
+        g, w_h = self.graph, self.erased_weight
+        eu, ev, w = g.edge_u, g.edge_v, self.match_weights
+        dist, mask = self.match_table()
+        ds = self._check_defects(defects)
+        ec = sorted(int(e) for e in erased_edges)
+        ends = {int(x) for e in ec for x in (eu[e], ev[e]) if x >= 1} - set(ds)
+        hubs = np.array(ds + sorted(ends), np.int64)
+        m, n = len(ds), len(hubs)
+        at = {int(h): i for i, h in enumerate(hubs)}
+        lo, hi = np.minimum.outer(hubs, hubs), np.maximum.outer(hubs, hubs)
+        D, M = dist[lo, hi].astype(np.int64), mask[lo, hi].copy()
+        B, MB = dist[hubs, 0].astype(np.int64), mask[hubs, 0].copy()
+        static = (D.copy(), M.copy(), B.copy(), MB.copy())
+        for e in ec:
+            x = min(int(w[e]), w_h)
+            if eu[e] >= 1:
+                i, j = at[int(eu[e])], at[int(ev[e])]
+                if x < D[i, j]:
+                    D[i, j] = D[j, i] = x
+                    M[i, j] = M[j, i] = g.edge_obs[e]
+            elif x < B[at[int(ev[e])]]:
+                B[at[int(ev[e])]], MB[at[int(ev[e])]] = x, g.edge_obs[e]
+        for k in range(n):  # (row and column k stand still in step k: the pairs of one step are independent)
+            via = D[:, k, None] + D[None, k, :]
+            better = (D[:, k, None] != MATCH_INF) & (D[None, k, :] != MATCH_INF) & (via < D)
+            better[k, :] = better[:, k] = False
+            better[np.arange(n), np.arange(n)] = False
+            D, M = np.where(better, via, D), np.where(better, M[:, k, None] ^ M[None, k, :], M)
+        b, mb = B[:m].copy(), MB[:m].copy()
+        for i in range(m):
+            for x in range(n):
+                if x != i and D[i, x] != MATCH_INF and B[x] != MATCH_INF and D[i, x] + B[x] < b[i]:
+                    b[i], mb[i] = D[i, x] + B[x], M[i, x] ^ MB[x]
+        if not ec:  # the reduction: static distances obey the triangle inequality, so nothing has moved
+            assert all(np.array_equal(x, y) for x, y in zip(static, (D, M, B, MB))) and np.array_equal(b, B[:m]) and np.array_equal(mb, MB[:m])
+        out = dict(hubs=hubs, D=D, M=M, B=B, MB=MB, b=b, mb=mb)
+        if self.gap_observable is None:
+            return out
+        # the classes: least walks in the hub graph, the states (hub, class) closed under min-plus to their least fixpoint
+        dist2 = self.gap_table()[0]
+        c = ((g.edge_obs >> np.uint64(self.gap_observable)) & np.uint64(1)).astype(np.int64)
+        big = np.int64(1) << 40
+        D2 = dist2[lo, hi].astype(np.int64)
+        B2 = dist2[hubs, 0].astype(np.int64)
+        D2[D2 == MATCH_INF], B2[B2 == MATCH_INF] = big, big
+        for e in ec:
+            x = min(int(w[e]), w_h)
+            if eu[e] >= 1:
+                i, j = at[int(eu[e])], at[int(ev[e])]
+                D2[i, j, c[e]] = D2[j, i, c[e]] = min(D2[i, j, c[e]], x)
+            else:
+                B2[at[int(ev[e])], c[e]] = min(B2[at[int(ev[e])], c[e]], x)
+        A = np.empty((2 * n, 2 * n), np.int64)   # state 2 * hub + class; an arc of class c joins (i, a) and (j, a ^ c)
+        for a in (0, 1):
+            for cc in (0, 1):
+                A[a::2, a ^ cc::2] = D2[:, :, cc]
+        while True:
+            new = np.minimum(A, (A[:, :, None] + A[None, :, :]).min(axis=1))
+            if np.array_equal(new, A):
+                break
+            A = new
+        D2 = np.stack([A[0::2, 0::2], A[0::2, 1::2]], axis=2)
+        b2 = np.stack([(D2[:m, :, :] + B2[None, :, ::(1 if bb == 0 else -1)]).min(axis=(1, 2)) for bb in (0, 1)], axis=1)
+        for a in (D2, B2, b2):
+            a[a >= big] = MATCH_INF
+        assert np.array_equal(D2.min(axis=2), D) and np.array_equal(b2.min(axis=1), b), "the cheaper class is not the winner's distance"
+        out.update(D2=D2, B2=B2, b2=b2)
+        return out
+
+    def _hub_cluster(self, defects, erased_edges):
+        """A matched cluster under heralds: ``(cost, mask, gap before the cap or None)`` of the two programs over its hub graph.
+        Without an erased edge every number is that of :meth:`_match_cluster` / :meth:`_cluster_gap` (asserted)."""
+        h = self.hub_graph(defects, erased_edges)
+        D, M, b, mb = h["D"], h["M"], h["b"], h["mb"]
+        m = len(b)
+        cost, mask, _ = self._pair_program(m, lambda i, j: (int(b[i]), int(mb[i])) if j is None else (int(D[i, j]), int(M[i, j])))
+        assert cost is not None and cost < 1 << 31, "a matched cluster has no finite pairing"
+        gap = None
+        if self.gap_observable is not None:
+            classes = self._class_program(m, lambda i, j: h["b2"][i] if j is None else h["D2"][i, j])
+            gap = self._gap_of_classes(classes, cost, mask)
+        if not len(erased_edges):
+            assert (cost, mask) == self._match_cluster(defects)[:2] and (gap is None or gap == self._cluster_gap(defects, cost, mask))
+        return cost, mask, gap
+
+    def _erasure(self, what: str):
+        if self.erased_weight is None:
+            raise ValueError(f"{what} needs a decoder of with_erasure_matching(max_defects, weights, erased_weight, max_hubs)")
+
+    def erasure_counts(self, dets):
+        """``(matched clusters that had an erased edge, clusters of at most max_defects defects peeled for more than max_hubs
+        hubs)`` over the decoded rows of ``dets``: what the device counts in ``tsim_uf_erasure_info`` [2] and [3]."""
+        self._erasure("erasure_counts()")
+        entries = [e for e in self._decoded(dets) if e is not None]
+        return sum(e[-2] for e in entries), sum(e[-1] for e in entries)
 
     def gap_outputs(self, dets) -> np.ndarray:
         """int64 ``[n]``: the deficit ``D = gap_cap - gap`` of every row ("Complementary gap" in the module docstring): 0 for a
@@ -1138,7 +1358,7 @@ class UnionFindDecoder(_RowDecoder):
         defect[defects] = True
         cap = np.full(g.n_edges, 2, np.int8) if self.edge_caps is None else self.edge_caps.astype(np.int8)
         grown = np.zeros(g.n_edges, np.int8)
-        erased = np.asarray(erased_edges, dtype=np.int64)
+        erased = np.unique(np.asarray(erased_edges, dtype=np.int64))   # each taken once
         grown[erased] = cap[erased]
         label = np.arange(n)
         rounds = 0
@@ -1153,7 +1373,8 @@ class UnionFindDecoder(_RowDecoder):
             new = np.minimum(cap, grown + active[eu] + active[ev]).astype(np.int8)
             if np.array_equal(new, grown):
                 return (0, True, np.zeros(0, np.int64), rounds, int(f.sum()), int(np.bincount(label).max())) + \
-                    ((0, 0) if self.match_defects is not None else ()) + ((0,) if self.gap_observable is not None else ())
+                    ((0, 0) if self.match_defects is not None else ()) + ((0,) if self.gap_observable is not None else ()) + \
+                    ((0, 0) if self.erased_weight is not None else ())
             grown, rounds = new, rounds + 1
         soft = (int((grown == cap).sum()), int(np.bincount(label).max()))  # (label: the clusters of the full edges)
         # the forest: levels from the roots, the parent edge the smallest-index edge to the level above
@@ -1188,17 +1409,28 @@ class UnionFindDecoder(_RowDecoder):
         if self.match_defects is not None:
             # cluster matching: small clusters by the dynamic program, of the others the flips whose child node lies in them
             # (the complementary gap: the least gap of the row's clusters before the cap, 0 with a peeled cluster)
-            prediction = matched = peeled = 0
+            prediction = matched = peeled = with_erased = overflowed = 0
             gap = _GAP_INF
             for r in np.unique(label[defect]):
                 ds = np.flatnonzero(defect & (label == r))
-                if len(ds) <= self.match_defects:
-                    cost, mask, _ = self._match_cluster(ds)
-                    assert cost is not None, "a matched cluster has no finite pairing"
+                small = len(ds) <= self.match_defects
+                if small and self.erased_weight is not None:  # under heralds: the cluster's erased edges and its hubs
+                    ec = erased[label[ev[erased]] == r]
+                    ends = np.concatenate([eu[ec], ev[ec]])
+                    if len(np.union1d(ds, ends[ends >= 1])) > self.max_hubs:
+                        small, overflowed = False, overflowed + 1
+                if small:
+                    if self.erased_weight is not None:
+                        cost, mask, cluster_gap = self._hub_cluster(ds, ec)
+                        with_erased += len(ec) > 0
+                    else:
+                        cost, mask, _ = self._match_cluster(ds)
+                        assert cost is not None, "a matched cluster has no finite pairing"
+                        cluster_gap = self._cluster_gap(ds, cost, mask) if self.gap_observable is not None else None
                     prediction ^= mask
                     matched += 1
                     if self.gap_observable is not None:
-                        gap = min(gap, self._cluster_gap(ds, cost, mask))
+                        gap = min(gap, cluster_gap)
                 else:
                     for e, v in zip(flipped, children):
                         if label[v] == r:
@@ -1206,7 +1438,7 @@ class UnionFindDecoder(_RowDecoder):
                     peeled += 1
                     gap = 0
             return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft + (matched, peeled) + \
-                ((gap,) if self.gap_observable is not None else ())
+                ((gap,) if self.gap_observable is not None else ()) + ((with_erased, overflowed) if self.erased_weight is not None else ())
         return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft
 
     def _decode_bits(self, bits: np.ndarray):
@@ -1241,6 +1473,10 @@ class UnionFindDecoder(_RowDecoder):
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _handle(self, hp, n_cols: int):
+        if self.erased_weight is not None:
+            h = hp.uf_create_matching_heralds(self.graph, n_cols, self.match_weights, self.match_defects, self.erased_weight, self.max_hubs,
+                                              -1 if self.gap_observable is None else self.gap_observable, self.edge_caps)
+            return h, hp.uf_decode_device, hp.uf_destroy
         if self.gap_observable is not None:
             h = hp.uf_create_matching_gap(self.graph, n_cols, self.match_weights, self.match_defects, self.gap_observable, self.edge_caps)
             return h, hp.uf_decode_device, hp.uf_destroy
