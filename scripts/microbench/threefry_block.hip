@@ -5,19 +5,34 @@
 // the 35-qubit shape, 385 of the 523 VALU instructions a wave issues.  Every variant below computes the SAME bits
 // (checked against the host loop in main) - they differ only in which instructions form the round.
 //
+// Variants a - l (profiles/threefry_schedule.txt): the kernel form (one asm statement per draw, folded injections, keys in SGPRs)
+// with a key schedule in vector registers read from LDS (a, b, d), v_perm_b32 on the byte rotations (c, d, f), the injection's
+// constant on a second add3 (e, f), the scalar sums formed outside the loop (g), and s_nop at several densities (h - l).
+//
+// Timing: the bits of every variant are checked once; then >= 30 ms of untimed work (the clocks rise over the first ~25 ms),
+// then every variant [rounds = 10] times, 5 launches per timing, in an order rotated by one from round to round; min / median /
+// max per variant.  Exit status 1 if a variant's bits differ from the host loop's.
+//
+// Run: scripts/microbench/threefry_block.bin [rounds]
 // Build: hipcc --offload-arch=gfx950 -O3 scripts/microbench/threefry_block.hip -o scripts/microbench/threefry_block.bin
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <algorithm>
 #include <vector>
 
 enum { V_C = 0, V_ALIGNBIT_ASM, V_SHR_SHL_BITOP3, V_SHR_LSHLOR, V_SHR_LSHLADD, V_PERM_BYTES, V_PERM_BYTES_BITOP, V_VGPR_KEYS_C,
-       V_VGPR_KEYS_BITOP3, V_FOLD_INJECT, V_FOLD_ASM, V_FOLD_ASM_X2, V_FOLD_ASM_X3, V_FOLD_ASM_X5, N_VARIANTS };
+       V_VGPR_KEYS_BITOP3, V_FOLD_INJECT, V_FOLD_ASM, V_FOLD_ASM_X2, V_FOLD_ASM_X3, V_FOLD_ASM_X5,
+       V_VREC, V_VREC_THREE, V_FOLD_ASM_PERM, V_VREC_PERM, V_FOLD_IMM, V_FOLD_IMM_PERM, V_FOLD_SUMS, V_FOLD_NOP1, V_FOLD_NOP2, V_FOLD_NOP3, V_FOLD_NOP4, V_FOLD_NOP5, N_VARIANTS };
 static const char *VNAME[N_VARIANTS] = {"c_form(compiler)", "alignbit+xor asm", "lshr+lshl+bitop3", "lshr+lshl_or+xor",
                                         "lshr+lshl_add+xor", "perm(16,24)+alignbit", "perm(16,24)+shifts+bitop3",
                                         "c_form, keys in VGPRs", "shifts+bitop3, keys in VGPRs", "c_form, injections folded into add3",
-                                        "asm block, folded injections (kernel form)", "asm, 2 draws interleaved", "asm, 3+2 draws interleaved", "asm, 5 draws interleaved"};
+                                        "asm block, folded injections (kernel form)", "asm, 2 draws interleaved", "asm, 3+2 draws interleaved", "asm, 5 draws interleaved",
+                                        "a: kernel form, key records in VGPRs (LDS)", "b: a with three-add injections", "c: kernel form, perm(16,24)", "d: a + c",
+                                        "e: kernel form, constants on a second add3", "f: e + c", "g: kernel form, key sums outside the loop",
+                                        "h: kernel form, s_nop behind every round", "i: kernel form, s_nop behind every 2nd round",
+                                        "j: kernel form, s_nop behind every instruction", "k: kernel form, s_nop behind add and xor", "l: kernel form, s_nop 1 behind every round"};
 
 __host__ __device__ inline uint32_t rotl_c(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
@@ -117,8 +132,49 @@ struct Keys { uint32_t k[10]; };
 template <int V>
 __global__ void __launch_bounds__(1024) k_blocks(uint32_t *out, Keys K, uint32_t n_shots, uint32_t perm16, uint32_t perm24) {
   uint32_t acc = 0;
+  // the key records of the vector-register schedule: five of twelve words, filled once per block
+  __shared__ __attribute__((aligned(16))) uint32_t rec[V == V_VREC || V == V_VREC_THREE || V == V_VREC_PERM ? 5 * 12 : 4];
+  if constexpr (V == V_VREC || V == V_VREC_THREE || V == V_VREC_PERM) {
+    if (threadIdx.x < 5) {
+      const uint32_t k0 = K.k[2 * threadIdx.x], k1 = K.k[2 * threadIdx.x + 1], k2 = k0 ^ k1 ^ 0x1BD11BDAu;
+      const uint32_t w[12] = {k1, k0, k2 + 1u, k1, k0 + 2u, k2, k1 + 3u, k0, k2 + 4u, k1, k2, k0 + 5u};  // shot offset 0
+      for (int i = 0; i < 12; ++i) rec[12 * threadIdx.x + i] = w[i];
+    }
+    __syncthreads();
+  }
   for (uint32_t shot = blockIdx.x * blockDim.x + threadIdx.x; shot < n_shots; shot += gridDim.x * blockDim.x) {
-    if constexpr (V == V_FOLD_ASM) {
+    if constexpr (V == V_VREC || V == V_VREC_THREE || V == V_VREC_PERM) {
+      // One vector register per trip holds the record base (the kernel's step changes from trip to trip; here the move keeps
+      // the reads inside the loop).  Same address in every lane: three ds_read_b128 per draw, the next draw's requested in
+      // front of the present one.
+      uint32_t base;
+      asm volatile("v_mov_b32 %0, 0" : "=v"(base));
+      const tf_u32x4 *r4 = reinterpret_cast<const tf_u32x4 *>(rec) + base;
+      tf_u32x4 a = r4[0], b = r4[1], c = r4[2];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {
+        tf_u32x4 na = a, nb = b, nc = c;
+        if (j < 4) { na = r4[3 * j + 3]; nb = r4[3 * j + 4]; nc = r4[3 * j + 5]; }
+        acc ^= threefry_bits32_vrec<V != V_VREC_THREE, V == V_VREC_PERM>(a, b, c, shot, perm16, perm24) >> j;
+        a = na; b = nb; c = nc;
+      }
+    } else if constexpr (V == V_FOLD_ASM_PERM) {
+      uint32_t b;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) { threefry_bits32_x1_perm(K.k[2 * j], K.k[2 * j + 1], shot, perm16, perm24, b); acc ^= b >> j; }
+    } else if constexpr (V == V_FOLD_IMM || V == V_FOLD_IMM_PERM) {
+      uint32_t b;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) { threefry_bits32_x1_imm<V == V_FOLD_IMM_PERM>(K.k[2 * j], K.k[2 * j + 1], shot, perm16, perm24, b); acc ^= b >> j; }
+    } else if constexpr (V >= V_FOLD_NOP1 && V <= V_FOLD_NOP5) {
+      uint32_t b;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) { threefry_bits32_x1_nop<V - V_FOLD_NOP1 + 1>(K.k[2 * j], K.k[2 * j + 1], shot, b); acc ^= b >> j; }
+    } else if constexpr (V == V_FOLD_SUMS) {
+      uint32_t b;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) { threefry_bits32_x1_sums(K.k[2 * j], K.k[2 * j + 1], shot, b); acc ^= b >> j; }
+    } else if constexpr (V == V_FOLD_ASM) {
       uint32_t b;
 #pragma unroll
       for (int j = 0; j < 5; ++j) { threefry_bits32_x1(K.k[2 * j], K.k[2 * j + 1], shot, b); acc ^= b >> j; }
@@ -173,25 +229,53 @@ int main(int argc, char **argv) {
       for (int j = 0; j < 5; ++j) { uint32_t x0 = 0, x1 = shot; host_tf(K.k[2 * j], K.k[2 * j + 1], x0, x1); acc ^= (x0 ^ x1) >> j; }
     want[check_lanes[li]] = acc;
   }
-  const kern_t fns[N_VARIANTS] = {k_blocks<0>, k_blocks<1>, k_blocks<2>, k_blocks<3>, k_blocks<4>, k_blocks<5>, k_blocks<6>, k_blocks<7>, k_blocks<8>, k_blocks<9>, k_blocks<10>, k_blocks<11>, k_blocks<12>, k_blocks<13>};
-  printf("%-44s %9s %14s %16s %6s\n", "variant", "ms", "blocks/s", "us/1e6 shots", "ok");
+  const kern_t fns[N_VARIANTS] = {k_blocks<0>, k_blocks<1>, k_blocks<2>, k_blocks<3>, k_blocks<4>, k_blocks<5>, k_blocks<6>, k_blocks<7>, k_blocks<8>, k_blocks<9>,
+                                  k_blocks<10>, k_blocks<11>, k_blocks<12>, k_blocks<13>, k_blocks<14>, k_blocks<15>, k_blocks<16>, k_blocks<17>,
+                                  k_blocks<18>, k_blocks<19>, k_blocks<20>, k_blocks<21>, k_blocks<22>, k_blocks<23>, k_blocks<24>, k_blocks<25>};
+  const uint32_t p16 = 0x01000302u, p24 = 0x00030201u;
+  // every variant once: the bits against the host loop
   std::vector<uint32_t> got((size_t)blocks * threads);
+  bool ok[N_VARIANTS];
   for (int v = 0; v < N_VARIANTS; ++v) {
-    if (argc > 1 && atoi(argv[1]) != v) continue;
-    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    fns[v]<<<blocks, threads>>>(d, K, n_shots, 0x01000302u, 0x00030201u);
-    hipDeviceSynchronize();
-    hipEventRecord(e0);
-    const int reps = 5;
-    for (int r = 0; r < reps; ++r) fns[v]<<<blocks, threads>>>(d, K, n_shots, 0x01000302u, 0x00030201u);
-    hipEventRecord(e1); hipEventSynchronize(e1);
-    float ms; hipEventElapsedTime(&ms, e0, e1);
+    hipMemset(d, 0, got.size() * 4);
+    fns[v]<<<blocks, threads>>>(d, K, n_shots, p16, p24);
     hipMemcpy(got.data(), d, got.size() * 4, hipMemcpyDeviceToHost);
-    bool ok = true;
-    for (int li = 0; li < 6; ++li) ok = ok && got[check_lanes[li]] == want[check_lanes[li]];
-    const double per = ms / reps;
-    printf("%-44s %9.4f %14.4e %16.2f %6s\n", VNAME[v], per, 5.0 * n_shots / (per * 1e-3), per * 1e3 / (n_shots / 1e6),
-           ok ? "yes" : "NO");
+    ok[v] = true;
+    for (int li = 0; li < 6; ++li) ok[v] = ok[v] && got[check_lanes[li]] == want[check_lanes[li]];
   }
-  return 0;
+  // untimed work until the clocks have risen (they rise over the first ~25 ms of load): >= 30 ms of the kernel form
+  hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+  {
+    float warm = 0.f;
+    while (warm < 30.f) {
+      hipEventRecord(e0);
+      for (int r = 0; r < 20; ++r) fns[V_FOLD_ASM]<<<blocks, threads>>>(d, K, n_shots, p16, p24);
+      hipEventRecord(e1); hipEventSynchronize(e1);
+      float ms; hipEventElapsedTime(&ms, e0, e1);
+      warm += ms;
+    }
+  }
+  // every variant `rounds` times, the order rotated by one from round to round; no pause between timings
+  const int rounds = argc > 1 ? atoi(argv[1]) : 10, reps = 5;
+  std::vector<std::vector<double>> us(N_VARIANTS);
+  for (int r = 0; r < rounds; ++r)
+    for (int i = 0; i < N_VARIANTS; ++i) {
+      const int v = (i + r) % N_VARIANTS;
+      hipEventRecord(e0);
+      for (int q = 0; q < reps; ++q) fns[v]<<<blocks, threads>>>(d, K, n_shots, p16, p24);
+      hipEventRecord(e1); hipEventSynchronize(e1);
+      float ms; hipEventElapsedTime(&ms, e0, e1);
+      us[v].push_back(ms / reps * 1e3 / (n_shots / 1e6));
+    }
+  printf("us per 1e6 shots (5 draws each), %d timings of %d launches per variant, order rotated\n", rounds, reps);
+  printf("%-46s %8s %8s %8s %6s\n", "variant", "min", "median", "max", "ok");
+  bool all_ok = true;
+  for (int v = 0; v < N_VARIANTS; ++v) {
+    std::sort(us[v].begin(), us[v].end());
+    const size_t n = us[v].size();
+    const double med = n % 2 ? us[v][n / 2] : 0.5 * (us[v][n / 2 - 1] + us[v][n / 2]);
+    printf("%-46s %8.3f %8.3f %8.3f %6s\n", VNAME[v], us[v].front(), med, us[v].back(), ok[v] ? "yes" : "NO");
+    all_ok = all_ok && ok[v];
+  }
+  return all_ok ? 0 : 1;
 }

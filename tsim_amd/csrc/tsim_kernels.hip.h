@@ -279,6 +279,10 @@ __host__ __device__ __forceinline__ void threefry2x32(uint32_t k0, uint32_t k1, 
 //   * a key injection `x0 += ka; x1 += kb + i` and the add of the following round are two instructions instead of
 //     three: x1 += (kb + i) with the sum formed on the scalar unit, then x0 = x0 + x1 + ka as one v_add3_u32.
 // The asm is not volatile: the compiler may still interleave the blocks of different draws.
+// What the instruction classes do not tell (profiles/threefry_schedule.txt): the block is one chain of dependent instructions, and
+// such a chain issues faster with an s_nop 0 behind each full-rate instruction of a round - 12 % less time for the block alone.
+// threefry_bits32_lo_at (tsim_lw_fast.hip.h), the block of the fused first passes, has them; this one, the block of the generic
+// pass and of uniform01, is as it was: the two stay independent statements of the same function, which the tests compare.
 __device__ __forceinline__ uint32_t threefry_bits32(uint32_t k0, uint32_t k1, unsigned long long s) {
   const uint32_t k2 = k0 ^ k1 ^ 0x1BD11BDAu;
   const uint32_t j1 = k2 + 1u, j2 = k0 + 2u, j3 = k1 + 3u, j4 = k2 + 4u, j5 = k0 + 5u;

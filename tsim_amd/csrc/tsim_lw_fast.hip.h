@@ -33,13 +33,18 @@ enum { LWF_NRUNS = 0, LWF_FLIP0, LWF_FLIP1, LWF_RUNS /* image offset: n_runs x (
 // PINNED: the statement is volatile, so it keeps its place among the memory instructions round it - reads requested in front of
 // a draw stay in front of it, their waits behind it.  Left alone the scheduler puts every draw of k_sample_lw_fast first and
 // the threshold reads, each waited for at once, behind them.
+// TF_NOP: an s_nop 0 behind every round's add and behind its xor, the two full-rate instructions of the round (none behind the
+// half-rate v_alignbit_b32).  The block is one chain of dependent vector instructions, and a wave issues such a chain faster with
+// them than without: 35 more instructions per draw and 12 % less time for the block alone (scripts/microbench/threefry_block.hip,
+// variant k; profiles/threefry_schedule.txt).  Behind every instruction, or as s_nop 1, they cost time instead.
 template <bool PINNED>
 __device__ __forceinline__ uint32_t threefry_bits32_lo_at(uint32_t k0, uint32_t k1, uint32_t k0hi, uint32_t lo) {
   // threefry_bits32 for a counter (hi, lo) whose high word is wave-uniform: k0hi = k0 + hi formed on the scalar unit
   const uint32_t k2 = k0 ^ k1 ^ 0x1BD11BDAu;
   uint32_t x0, x1, t;
-#define TF_RN(r) "v_alignbit_b32 %[x1], %[x1], %[x1], " #r "\n v_xor_b32 %[x1], %[x1], %[x0]\n"
-#define TF_RA(r) "v_add_u32 %[x0], %[x0], %[x1]\n" TF_RN(r)
+#define TF_NOP "s_nop 0\n"
+#define TF_RN(r) "v_alignbit_b32 %[x1], %[x1], %[x1], " #r "\n v_xor_b32 %[x1], %[x1], %[x0]\n" TF_NOP
+#define TF_RA(r) "v_add_u32 %[x0], %[x0], %[x1]\n" TF_NOP TF_RN(r)
 #define TF_INJ(kb, i, ka) "s_add_i32 %[t], %[" #kb "], " #i "\n v_add_u32 %[x1], %[t], %[x1]\n v_add3_u32 %[x0], %[x0], %[x1], %[" #ka "]\n"
 #define TF_BLOCK                                                                                                           \
   "v_add_u32 %[x1], %[k1], %[lo]\n v_add_u32 %[x0], %[k0hi], %[x1]\n"                                                     \
@@ -60,6 +65,7 @@ __device__ __forceinline__ uint32_t threefry_bits32_lo_at(uint32_t k0, uint32_t 
 #undef TF_INJ
 #undef TF_RA
 #undef TF_RN
+#undef TF_NOP
   return x0;
 }
 __device__ __forceinline__ uint32_t threefry_bits32_lo(uint32_t k0, uint32_t k1, uint32_t k0hi, uint32_t lo) {
