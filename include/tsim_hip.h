@@ -815,6 +815,20 @@ int tsim_ufw_info(tsim_ufw *h, int64_t out[16]);
 int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
                            const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
                            void *stream);
+/* tsim_ufw_decode_device with the windowed decoder's soft outputs ("Soft outputs in windows" in the module docstring of
+ * tsim_amd/decode.py); the contract is that of tsim_uf_decode_soft_device.  Everything up to d_pred means the same and
+ * accumulates the same.  Four values per row, over its DECODED windows (those with a defect after the carries, in order, up to
+ * and including one that misses): [0] rounds, the most of a window; [1] full_edges, the SUM of the windows' local edges that are
+ * full when the window's growth ends (pre-grown and virtual ones included; an edge two windows fill counts twice);
+ * [2] largest_cluster, the MAXIMUM of the windows' largest clusters; [3] correction_weight, the committed flips, 0 for a miss.
+ * All four are 0 for a row that is not kept and for a kept row without a defect on a node column.  metric (0 .. 3), n_bins
+ * (2 .. 1024), d_hist (uint64[2 * n_bins], 8-byte aligned, required, ACCUMULATES, never zeroed here) and d_soft (NULL, or
+ * uint32[4 * n], 16-byte aligned) as there: a bad metric or n_bins, or a NULL d_hist, is TSIM_EINVAL before any device call;
+ * n == 0 returns 0 without a launch; the launches count in out[7] of tsim_ufw_info.  Both kinds of handle take it; a shot's
+ * state in LDS, the shots of a block and the grid are those of tsim_ufw_decode_device. */
+int tsim_ufw_decode_soft_device(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream);
 
 /* ---- stim's shot-data formats on the device (stim.read_shot_data_file / write_shot_data_file, the samplers'
  *      sample_write, CompiledMeasurementsToDetectionEventsConverter.convert_file) ------------------------------------

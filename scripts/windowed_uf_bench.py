@@ -1,6 +1,6 @@
 """Sliding-window union-find decoding next to the whole-graph decoder: surface code memory, one MI355X.
 
-    python scripts/windowed_uf_bench.py                                  # the three legs below, JSON lines
+    python scripts/windowed_uf_bench.py                                  # the four legs below, JSON lines
     python scripts/windowed_uf_bench.py --legs rate --cases d9x27c9
     python scripts/windowed_uf_bench.py --legs quality --shots 1000000
 
@@ -22,6 +22,10 @@ and a stream synchronise, median of ``--reps``), with what ``tsim_uf_info`` / ``
 --p`` and ``after_clifford_heralded_erasure = --pe``; ``count(--erasure-shots, decoder=...)`` as in ``rate``, of the whole-graph
 decoder with heralds (where it is built and fits), of the windowed decoder with heralds, and of the same windows over heralds
 that list no edge (what ignoring the heralds costs in decoded errors), on the same seeded rows.
+
+``soft`` (``profiles/windowed_soft_bench.txt``): ``--soft-case`` (d = 5, 400 rounds, commit = 120 and window = 240
+columns), ``count(--soft-shots, decoder=...)`` as in ``rate`` of the windowed decoder and of the same decoder
+``with_soft_output(--soft-metric, --soft-bins)``, alternating, and the errors ``rejection_curve()`` leaves at ``--soft-kept``.
 """
 
 from __future__ import annotations
@@ -222,9 +226,58 @@ def erasure_leg(args) -> None:
         print(json.dumps(out), flush=True)
 
 
+def soft_leg(args) -> None:
+    """``count(--soft-shots, decoder=...)`` of the windowed decoder of ``--soft-case`` with and without
+    ``with_soft_output(--soft-metric, --soft-bins)``, alternating on the same seeded rows, and what ``rejection_curve()`` leaves
+    at each of ``--soft-kept``: the lowest bin threshold that accepts at least that share of the kept shots."""
+    d, rounds, commit = parse(args.soft_case)
+    c = memory(d, rounds, args.p)
+    t0 = time.perf_counter()
+    form = c.compile_faults()
+    form_s = time.perf_counter() - t0
+    cols = commit * (d * d - 1)
+    t0 = time.perf_counter()
+    plain = WindowedUnionFindDecoder(DecodingGraph.from_form(form, limit=None), cols, 2 * cols, int(form.n_out) - int(form.num_detectors))
+    decoders = {"plain": plain, "soft": plain.with_soft_output(args.soft_metric, args.soft_bins)}
+    out = dict(leg="soft", case=args.soft_case, p=args.p, commit_columns=cols, window_columns=2 * cols, metric=args.soft_metric,
+               bins=args.soft_bins, form_s=form_s, decoders_s=time.perf_counter() - t0, graph=plain.info())
+
+    def sampler():  # a fresh one per call: every call counts the same seeded rows
+        return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+    times, last = {m: [] for m in decoders}, {}
+    for m, dec in decoders.items():
+        sampler().count(args.soft_shots, batch_size=args.batch, decoder=dec)  # warm-up at the timed size
+    for _ in range(args.reps):
+        for m, dec in decoders.items():
+            s = sampler()
+            t0 = time.perf_counter()
+            last[m] = s.count(args.soft_shots, batch_size=args.batch, decoder=dec)
+            times[m].append(time.perf_counter() - t0)
+    out["count"] = {m: dict(spread(t), shots=args.soft_shots, shots_per_s=args.soft_shots / statistics.median(t), kept=last[m].kept,
+                            raw_flips=last[m].kept_with_observable_flip, decoded_errors=last[m].decoded_errors,
+                            misses=last[m].decoder_misses) for m, t in times.items()}
+    if (last["plain"].kept, last["plain"].decoded_errors) != (last["soft"].kept, last["soft"].decoded_errors):
+        sys.exit("windowed_uf_bench: the soft call does not count what the plain call counts")
+    res = last["soft"]
+    accepted, errors = res.rejection_curve()
+    out["soft_kept"], out["soft_errors"] = res.soft_kept.tolist(), res.soft_errors.tolist()
+    out["rejection"] = []
+    for share in (float(x) for x in args.soft_kept.split(",")):
+        t = int(np.searchsorted(accepted, share * res.kept))  # (the last entry is `kept`: always found)
+        out["rejection"].append(dict(kept_share_asked=share, threshold_bin=t, accepted=int(accepted[t]), errors=int(errors[t]),
+                                     accepted_share=int(accepted[t]) / res.kept, error_rate=int(errors[t]) / int(accepted[t])))
+    print(json.dumps(out), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="rate,quality,erasure")
+    ap.add_argument("--legs", default="rate,quality,erasure,soft")
+    ap.add_argument("--soft-case", default="d5x400c5")
+    ap.add_argument("--soft-shots", type=int, default=100000)
+    ap.add_argument("--soft-metric", default="largest_cluster")
+    ap.add_argument("--soft-bins", type=int, default=64)
+    ap.add_argument("--soft-kept", default="0.99,0.95,0.90")
     ap.add_argument("--erasure-cases", default="d5x20c5,d9x27c9")
     ap.add_argument("--erasure-shots", type=int, default=200000)
     ap.add_argument("--pe", type=float, default=1e-2)
@@ -248,6 +301,8 @@ def main() -> None:
         rate_leg(args, HipProgram(synth.kat_h_m()))
     if "erasure" in args.legs.split(","):
         erasure_leg(args)
+    if "soft" in args.legs.split(","):
+        soft_leg(args)
 
 
 if __name__ == "__main__":

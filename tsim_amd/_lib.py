@@ -188,6 +188,7 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_ufw_destroy": (None, [_P]),
     "tsim_ufw_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_ufw_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _P]),
+    "tsim_ufw_decode_soft_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P]),
     "tsim_shotdata_create": (C.c_int, [_I32, C.POINTER(_P)]),
     "tsim_shotdata_destroy": (None, [_P]),
     "tsim_shotdata_encode": (C.c_int, [_P, _I32, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I64, C.POINTER(_I64), _P]),

@@ -628,9 +628,15 @@ class HipProgram:
         """:meth:`uf_decode_device` with the soft outputs (``tsim_uf_decode_soft_device``): ``metric`` (one of
         ``UF_SOFT_METRICS``, or its index) is binned into ``n_bins`` bins, the kept rows and the wrong ones among them ACCUMULATE
         into ``uint64[2 * n_bins]`` at ``d_hist``; ``d_soft``: ``uint32[4 * n]`` (16-byte aligned) for the four values of every row."""
+        self._uf_decode_soft("tsim_uf_decode_soft_device", handle, d_rows, n, row_bytes, observables, d_counters, metric, n_bins, d_hist,
+                             d_soft, d_pred, d_xor, d_test, stream)
+
+    def _uf_decode_soft(self, entry: str, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, metric,
+                        n_bins: int, d_hist: int, d_soft: int, d_pred: int, d_xor: int, d_test: int, stream: int) -> None:
+        """The soft decode entry point ``entry`` of either handle."""
         m = self.UF_SOFT_METRICS.index(metric) if isinstance(metric, str) else int(metric)
         ptr = lambda p: C.c_void_p(int(p)) if p else None  # noqa: E731
-        self._uf_decode("tsim_uf_decode_soft_device", handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test, stream,
+        self._uf_decode(entry, handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test, stream,
                         m, int(n_bins), ptr(d_hist), ptr(d_soft))
 
     def uf_info(self, handle: int) -> dict:
@@ -668,6 +674,14 @@ class HipProgram:
                           d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
         """:meth:`uf_decode_device` by a handle of :meth:`ufw_create` (``tsim_ufw_decode_device``)."""
         self._uf_decode("tsim_ufw_decode_device", handle, d_rows, n, row_bytes, observables, d_counters, d_pred, d_xor, d_test, stream)
+
+    def ufw_decode_soft_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, metric,
+                               n_bins: int, d_hist: int, *, d_soft: int = 0, d_pred: int = 0, d_xor: int = 0, d_test: int = 0,
+                               stream: int = 0) -> None:
+        """:meth:`uf_decode_soft_device` by a handle of :meth:`ufw_create` (``tsim_ufw_decode_soft_device``): the four values of a
+        row are those of "Soft outputs in windows" in the module docstring of :mod:`tsim_amd.decode`."""
+        self._uf_decode_soft("tsim_ufw_decode_soft_device", handle, d_rows, n, row_bytes, observables, d_counters, metric, n_bins, d_hist,
+                             d_soft, d_pred, d_xor, d_test, stream)
 
     def ufw_info(self, handle: int) -> dict:
         out = (C.c_int64 * 16)()

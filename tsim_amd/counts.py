@@ -58,7 +58,8 @@ class ShotCounts:
     pattern found no room (``sum(pattern_counts) + pattern_overflow == kept``; the patterns present are exact).
     ``decoded_errors`` / ``decoder_misses`` (``None`` without a decoder): kept shots whose observables differ from the
     decoder's prediction, and kept shots whose syndrome the decoder does not know (it predicts no flip for them).
-    ``soft_output`` (``None`` unless the decoder is a ``UnionFindDecoder.with_soft_output(metric, bins)`` or a cluster-matching
+    ``soft_output`` (``None`` unless the decoder is a ``UnionFindDecoder.with_soft_output(metric, bins)``, a
+    ``WindowedUnionFindDecoder.with_soft_output(metric, bins)``, whose values combine over its windows, or a cluster-matching
     one ``with_gap_output(...)``, whose metric is ``"gap"`` and whose value is the deficit ``(gap_cap - gap) // gap_step``): the metric's name;
     then ``soft_kept[b]`` (int64 ``[bins]``) are the kept shots whose metric falls into bin ``b = min(value, bins - 1)`` and
     ``soft_errors[b]`` those of them that count in ``decoded_errors`` (``soft_kept.sum() == kept``,
@@ -283,7 +284,7 @@ class _HostTally:
         self.overflow = 0
         self.decoder = decoder
         self.errors = self.misses = 0
-        self.soft = _soft_choice(decoder)   # (metric, bins) of a UnionFindDecoder.with_soft_output, or None
+        self.soft = _soft_choice(decoder)   # (metric, bins) of a union-find decoder with_soft_output (whole or windowed), or None
         self.soft_hist = np.zeros((2, self.soft[1]), dtype=np.int64) if self.soft else None
         self.pc = tuple(pair_columns)
         self.pairs = np.zeros((len(self.pc), len(self.pc)), dtype=np.int64) if self.pc else None
@@ -353,8 +354,9 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
     (:func:`check_pattern_columns`): the distinct patterns of the kept rows (``np.unique``) with their counts, in the order
     of :class:`ShotCounts`; ``pattern_capacity`` (default: no limit) admits that many patterns in the order of first
     appearance and counts the rows of the others in ``pattern_overflow``.  ``decoder``: a
-    :class:`tsim_amd.decode.LookupDecoder` or :class:`tsim_amd.decode.UnionFindDecoder` applied to the kept rows; one with a
-    soft output (``with_soft_output``) also fills ``soft_kept`` / ``soft_errors``, from its ``soft_outputs()``.  ``corrected``
+    :class:`tsim_amd.decode.LookupDecoder`, :class:`tsim_amd.decode.UnionFindDecoder` or
+    :class:`tsim_amd.decode.WindowedUnionFindDecoder` applied to the kept rows; a union-find decoder with a soft output
+    (``with_soft_output``, whole or windowed) also fills ``soft_kept`` / ``soft_errors``, from its ``soft_outputs()``.  ``corrected``
     (needs a decoder): every kept row gets ``obs ^= decoder.decode(dets)`` before anything but the decoder's own counts is
     taken (:class:`ShotCounts`); ``rows`` itself is not changed."""
     rows = np.asarray(rows, dtype=np.bool_)
@@ -374,10 +376,11 @@ def tally_rows(rows, *, num_detectors: int, postselection_mask=None, histogram_c
 
 
 def _soft_choice(decoder):
-    """``(metric, bins)`` of a :class:`tsim_amd.decode.UnionFindDecoder` that carries a soft output, else ``None``."""
-    from .decode import UnionFindDecoder
+    """``(metric, bins)`` of a :class:`tsim_amd.decode.UnionFindDecoder` or :class:`tsim_amd.decode.WindowedUnionFindDecoder`
+    that carries a soft output, else ``None``."""
+    from .decode import UnionFindDecoder, WindowedUnionFindDecoder
 
-    if isinstance(decoder, UnionFindDecoder) and decoder.soft_output is not None:
+    if isinstance(decoder, (UnionFindDecoder, WindowedUnionFindDecoder)) and decoder.soft_output is not None:
         return decoder.soft_output, int(decoder.soft_bins)
     return None
 
@@ -521,7 +524,7 @@ class _DeviceTally:
         self._dec = None         # the decoder's (handle, what decodes rows by it, what destroys it): a row table loaded from the
         #                          host (a LookupDecoder), a tsim_uf (a UnionFindDecoder) or a tsim_ufw (a WindowedUnionFindDecoder)
         self.d_decoded = None    # its three counters
-        self.soft = _soft_choice(decoder)   # (metric, bins): the union-find decoder's soft output, binned on the device
+        self.soft = _soft_choice(decoder)   # (metric, bins): the union-find decoder's soft output (whole or windowed), binned on the device
         self.d_soft_hist = None  # its two histograms, uint64[2 * bins]
         try:
             if self.pc:

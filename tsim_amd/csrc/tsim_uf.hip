@@ -318,13 +318,7 @@ static int uf_decode(tsim_uf *h, const uint8_t *d_rows, int64_t n, int64_t row_b
     a.hist = reinterpret_cast<unsigned long long *>(soft->d_hist);
   } else if (soft) {
     if (a.match_k) return tsim_fail(TSIM_EINVAL, "a cluster-matching handle has no soft outputs");
-    if (soft->metric < 0 || soft->metric > 3) return tsim_fail(TSIM_EINVAL, "metric = %d (0 rounds, 1 full_edges, 2 largest_cluster, 3 correction_weight)", soft->metric);
-    if (soft->n_bins < 2 || soft->n_bins > 1024) return tsim_fail(TSIM_EINVAL, "n_bins = %d (2 .. 1024)", soft->n_bins);
-    if (!soft->d_hist || reinterpret_cast<uintptr_t>(soft->d_hist) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_hist is NULL or not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(soft->d_soft) % 16 != 0) return tsim_fail(TSIM_EINVAL, "d_soft is not 16-byte aligned");
-    a.metric = soft->metric;
-    a.n_bins = soft->n_bins;
-    a.hist = reinterpret_cast<unsigned long long *>(soft->d_hist);
+    if (const int rc = ufh::check_soft(a, soft->metric, soft->n_bins, soft->d_hist, soft->d_soft)) return rc;
   }
   if (n == 0) return TSIM_OK;
   HIP_TRY(hipSetDevice(h->device));

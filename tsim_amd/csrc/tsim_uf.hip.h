@@ -37,7 +37,8 @@
 // forest(), so every end of a full edge adds 1 to lp[label[x]], once, and the largest count is taken.  correction_weight: counted
 // by the lane that flips an edge, in the function handed to peel().  The three per-lane numbers are reduced over the wave in
 // registers.  Of a tile's rows those of bin 0 (every kept row without a defect among them) are counted by ballot into
-// registers and flushed once per wave; the others go to the histogram by global 64-bit adds, one per distinct bin of the tile.
+// registers and flushed once per wave; the others go to the histogram by global 64-bit adds, one per distinct bin of the tile
+// (SoftBins, which k_ufw shares).
 // Cluster matching (k_uf<Weighted, false, false, true>, tsim_uf_create_matching; "Decoding a row" of the cluster-matching section
 // of the docstring): growth is the one above.  Then lp[], dead until forest(), counts the defects of every cluster at its root,
 // par[], dead after growth, marks the roots (1: matched, 1 .. K defects; 2: peeled, more), and a sweep of the nodes compacted by
@@ -482,6 +483,43 @@ __device__ __forceinline__ void soft_of_growth(const G &a, const State &st, int 
   soft[1] = both & 0xFFFFu;
 }
 
+// The binning of a soft value x per row, for k_uf and k_ufw (`A`: their Args, n_bins and hist): the bin of x is min(x, n_bins - 1).
+// Of a tile's rows those of bin 0 (every kept row without a defect among them) are counted by ballot into registers; the others
+// go to the histogram by global 64-bit adds, one per distinct bin of the tile.  Lane 0 flushes the registers once per wave into
+// stat[3], the block's count of bin 0 in LDS (zeroed by the kernel), which one thread adds to hist[0] after the block's barrier.
+struct SoftBins {
+  uint32_t bin0 = 0, bin0_wrong = 0;  // wave-uniform: the kept rows of bin 0, the wrong ones among them
+
+  // a tile: lane = row; kept and wrong (kept, and predicted wrongly) are this lane's row's
+  template <class A>
+  __device__ __forceinline__ void tile(const A &a, uint32_t x, bool kept, bool wrong, int lane) {
+    const uint32_t bin = min(x, (uint32_t)a.n_bins - 1u);
+    bin0 += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && bin == 0));
+    bin0_wrong += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(wrong && bin == 0));
+    uint64_t todo = __builtin_amdgcn_ballot_w64(kept && bin != 0);
+    while (todo) {  // one add per distinct bin of the tile (and one for its wrong rows)
+      const uint32_t b = (uint32_t)__shfl((int)bin, __builtin_ctzll(todo), 64);
+      const uint64_t same = __builtin_amdgcn_ballot_w64(kept && bin == b), bad = __builtin_amdgcn_ballot_w64(wrong && bin == b);
+      if (lane == 0) {
+        atomicAdd(&a.hist[b], (unsigned long long)__popcll(same));
+        if (bad) atomicAdd(&a.hist[(size_t)a.n_bins + b], (unsigned long long)__popcll(bad));
+      }
+      todo &= ~same;
+    }
+  }
+  // after the wave's tiles, by its lane 0
+  template <class A>
+  __device__ __forceinline__ void wave_done(const A &a, uint32_t *stat) const {
+    if (bin0) atomicAdd(&stat[3], bin0);
+    if (bin0_wrong) atomicAdd(&a.hist[a.n_bins], (unsigned long long)bin0_wrong);  // (rare: wrong without a defect, or in bin 0)
+  }
+  // after the block's barrier, by every thread
+  template <class A>
+  __device__ __forceinline__ static void block_done(const A &a, const uint32_t *stat) {
+    if (threadIdx.x == 3 && stat[3]) atomicAdd(&a.hist[0], (unsigned long long)stat[3]);
+  }
+};
+
 // The steps of cluster matching, between grow() and forest(), each by the whole wave.
 // the lanes with `flag`, compacted in lane order behind the *at entries there are: this lane's place (if it has the flag)
 __device__ __forceinline__ int compact(bool flag, int lane, int *at) {
@@ -892,7 +930,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
   __syncthreads();
   uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
   int most_rounds = 0;
-  uint32_t bin0_acc = 0, bin0_wrong_acc = 0;  // (Soft) wave-uniform: the kept rows of bin 0, the wrong ones among them
+  SoftBins bins;                              // (Soft, Gap) the wave's rows of bin 0
   uint32_t matched_acc = 0, peeled_acc = 0;   // (Match) wave-uniform: the clusters matched and peeled
   uint32_t erased_acc = 0, hubs_acc = 0;      // (Erasure) wave-uniform: the matched clusters with an erased edge, those peeled for their hubs
   const int nd = a.n_nodes - 1;
@@ -935,20 +973,7 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       uint32_t x;
       if constexpr (Gap) x = deficit / a.gap_step;
       else x = a.metric == 0 ? mine[0] : a.metric == 1 ? mine[1] : a.metric == 2 ? mine[2] : mine[3];
-      const uint32_t bin = min(x, (uint32_t)a.n_bins - 1u);
-      const bool wrong = kept && pred != obs;
-      bin0_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && bin == 0));
-      bin0_wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(wrong && bin == 0));
-      uint64_t todo = __builtin_amdgcn_ballot_w64(kept && bin != 0);
-      while (todo) {  // one add per distinct bin of the tile (and one for its wrong rows)
-        const uint32_t b = (uint32_t)__shfl((int)bin, __builtin_ctzll(todo), 64);
-        const uint64_t same = __builtin_amdgcn_ballot_w64(kept && bin == b), bad = __builtin_amdgcn_ballot_w64(wrong && bin == b);
-        if (lane == 0) {
-          atomicAdd(&a.hist[b], (unsigned long long)__popcll(same));
-          if (bad) atomicAdd(&a.hist[(size_t)a.n_bins + b], (unsigned long long)__popcll(bad));
-        }
-        todo &= ~same;
-      }
+      bins.tile(a, x, kept, kept && pred != obs, lane);
       if constexpr (Gap) {
         if (a.soft && valid) a.soft[r] = deficit;  // (uint32[n] on this call; 0 for a row that is not kept)
       } else {
@@ -970,15 +995,11 @@ __global__ void __launch_bounds__(64 * kMaxWaves) k_uf(Args a) {
       if (erased_acc) atomicAdd(&a.stats[4], (unsigned long long)erased_acc);
       if (hubs_acc) atomicAdd(&a.stats[5], (unsigned long long)hubs_acc);
     }
-    if constexpr (Soft || Gap) {
-      if (bin0_acc) atomicAdd(&stat[3], bin0_acc);
-      if (bin0_wrong_acc) atomicAdd(&a.hist[a.n_bins], (unsigned long long)bin0_wrong_acc);  // (rare: wrong without a defect, or in bin 0)
-    }
+    if constexpr (Soft || Gap) bins.wave_done(a, stat);
   }
   __syncthreads();
   if (threadIdx.x < 3 && stat[threadIdx.x]) atomicAdd(&a.dec[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
-  if constexpr (Soft || Gap)
-    if (threadIdx.x == 3 && stat[3]) atomicAdd(&a.hist[0], (unsigned long long)stat[3]);
+  if constexpr (Soft || Gap) SoftBins::block_done(a, stat);
 }
 
 }  // namespace ufk

@@ -101,6 +101,19 @@ int check_rows(const Args &a, const uint8_t *d_rows, int64_t n, int64_t row_byte
   return TSIM_OK;
 }
 
+// What a soft decode call adds to the row arguments, set into a's metric, n_bins and hist.  0, or an error code after tsim_fail.
+template <class Args>
+int check_soft(Args &a, int32_t metric, int32_t n_bins, uint64_t *d_hist, const uint32_t *d_soft) {
+  if (metric < 0 || metric > 3) return tsim_fail(TSIM_EINVAL, "metric = %d (0 rounds, 1 full_edges, 2 largest_cluster, 3 correction_weight)", metric);
+  if (n_bins < 2 || n_bins > 1024) return tsim_fail(TSIM_EINVAL, "n_bins = %d (2 .. 1024)", n_bins);
+  if (!d_hist || reinterpret_cast<uintptr_t>(d_hist) % 8 != 0) return tsim_fail(TSIM_EINVAL, "d_hist is NULL or not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_soft) % 16 != 0) return tsim_fail(TSIM_EINVAL, "d_soft is not 16-byte aligned");
+  a.metric = metric;
+  a.n_bins = n_bins;
+  a.hist = reinterpret_cast<unsigned long long *>(d_hist);
+  return TSIM_OK;
+}
+
 // what every launch of a decode call reads the same (check_rows passed)
 template <class Args>
 void fill_rows(Args &a, const uint8_t *d_rows, int64_t row_bytes, const uint8_t *d_xor, const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi,

@@ -308,20 +308,53 @@ extern "C" int tsim_ufw_info(tsim_ufw *h, int64_t out[16]) {
   return TSIM_OK;
 }
 
-extern "C" int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
-                                      const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
-                                      void *stream) {
+namespace {
+struct SoftOut {  // what tsim_ufw_decode_soft_device adds to tsim_ufw_decode_device
+  int metric, n_bins;
+  uint64_t *d_hist;
+  uint32_t *d_soft;  // four values per row, or NULL
+};
+
+template <bool Soft>
+void ufw_launch(const ufwk::Args &a, unsigned blocks, size_t lds, hipStream_t stream) {
+  if (a.node_det) {
+    if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, true, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+    else hipLaunchKernelGGL((ufwk::k_ufw<false, true, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+  } else if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, false, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+  else hipLaunchKernelGGL((ufwk::k_ufw<false, false, Soft>), dim3(blocks), dim3(64 * a.waves), lds, stream, a);
+}
+}  // namespace
+
+// the decode entry points; soft == NULL: tsim_ufw_decode_device
+static int ufw_decode(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor, const uint8_t *d_test,
+                      int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred, const SoftOut *soft, void *stream) {
   if (!h) return tsim_fail(TSIM_EINVAL, "decoder is NULL");
   ufwk::Args a = h->a;
   if (const int rc = ufh::check_rows(a, d_rows, n, row_bytes, obs_lo, obs_hi, d_counters, d_pred)) return rc;
+  if (soft)
+    if (const int rc = ufh::check_soft(a, soft->metric, soft->n_bins, soft->d_hist, soft->d_soft)) return rc;
   if (n == 0) return TSIM_OK;
   HIP_TRY(hipSetDevice(h->device));
   ufh::fill_rows(a, d_rows, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters);
-  return ufh::launch_rows(a, d_rows, n, d_pred, h->grid, &h->launches, [&](ufwk::Args &a, int64_t, unsigned blocks, size_t lds) {
-    if (a.node_det) {
-      if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL((ufwk::k_ufw<false, true>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-    } else if (a.cap) hipLaunchKernelGGL((ufwk::k_ufw<true, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((ufwk::k_ufw<false, false>), dim3(blocks), dim3(64 * a.waves), lds, (hipStream_t)stream, a);
+  return ufh::launch_rows(a, d_rows, n, d_pred, h->grid, &h->launches, [&](ufwk::Args &a, int64_t r0, unsigned blocks, size_t lds) {
+    if (soft) {
+      a.soft = soft->d_soft ? soft->d_soft + 4 * r0 : nullptr;
+      ufw_launch<true>(a, blocks, lds, (hipStream_t)stream);
+    } else {
+      ufw_launch<false>(a, blocks, lds, (hipStream_t)stream);
+    }
   });
+}
+
+extern "C" int tsim_ufw_decode_device(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                      const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                      void *stream) {
+  return ufw_decode(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, d_pred, nullptr, stream);
+}
+
+extern "C" int tsim_ufw_decode_soft_device(tsim_ufw *h, const uint8_t *d_rows, int64_t n, int64_t row_bytes, const uint8_t *d_xor,
+                                           const uint8_t *d_test, int32_t obs_lo, int32_t obs_hi, uint64_t *d_counters, uint64_t *d_pred,
+                                           int32_t metric, int32_t n_bins, uint64_t *d_hist, uint32_t *d_soft, void *stream) {
+  const SoftOut soft{metric, n_bins, d_hist, d_soft};
+  return ufw_decode(h, d_rows, n, row_bytes, d_xor, d_test, obs_lo, obs_hi, d_counters, d_pred, &soft, stream);
 }

@@ -28,6 +28,13 @@
 // local edges win_her_edges[win_her_ptr[j] .. win_her_ptr[j + 1]), appending a word of `full` to wlist when it was zero (the
 // idiom of ufk::pregrow_heralds; half and the counters stay zero: visits test `full` first).  The three tables are in global
 // memory, concatenated over the windows like the others; win_her_ptr is one CSR over the concatenation, absolute.
+// Soft outputs (k_ufw<Weighted, Heralds, true>, tsim_ufw_decode_soft_device; "Soft outputs in windows" in the docstring): four
+// numbers of a decoded row, in registers only - the state in LDS, its bytes and the shots of a block are those of the plain
+// call.  After grow() of every decoded window, miss or not, ufk::soft_of_growth reads the window's full edges and its largest
+// cluster off the state (lp[] is dead until forest()); the first are summed and the second is maximised over the row's windows
+// in wave-uniform registers.  rounds is the most of a window, as before.  The lane that flips a committed edge counts it in the
+// function handed to peel(); the counts are reduced over the wave once per window and summed (0 for a miss).  The row's lane
+// keeps the four numbers; a tile's rows are binned by ufk::SoftBins, as k_uf bins its own.
 // Every index into LDS and into the tables comes from tables tsim_ufw_create has built and checked; every address is formed
 // in 64 bits.
 #pragma once
@@ -80,6 +87,10 @@ struct Args {
   const int32_t *win_herald;  // per window (WinDesc.off_her, n_her) the heralds with a local edge there
   const uint32_t *win_her_ptr;     // [entries of win_herald + 1] where the list of entry j begins in win_her_edges
   const uint16_t *win_her_edges;   // LOCAL edges
+  // soft outputs (k_ufw<., ., true> only), as ufk::Args has them
+  int metric, n_bins;          // 0 rounds 1 full_edges 2 largest_cluster 3 correction_weight; the bin of x is min(x, n_bins - 1)
+  unsigned long long *hist;    // [2 * n_bins] kept rows per bin, then the wrong ones among them
+  uint32_t *soft;              // [4 * n] the four values of every row (16-byte aligned), or NULL
 };
 
 // the bits j of word w of a bitmap whose index 32 w + j lies in [s, e)
@@ -106,15 +117,17 @@ __device__ __forceinline__ void pregrow_window(const Args &a, const WinDesc &d, 
 }
 
 // one kept row with a defect, by the whole wave, window after window: the prediction (0 for a miss); *missed, *rounds (the most
-// of a window) and *windows (those decoded) are wave-uniform
-template <bool Weighted, bool Heralds>
+// of a window) and *windows (those decoded) are wave-uniform, and so are, with Soft, soft[0 .. 2]: the full edges summed and the
+// largest cluster maximised over the decoded windows, a missing one included, and the committed flips (0 for a miss)
+template <bool Weighted, bool Heralds, bool Soft = false>
 __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &st, uint32_t *carry, uint32_t *pred, const uint8_t *row,
-                                               int lane, bool *missed, int *rounds, int *windows) {
+                                               int lane, bool *missed, int *rounds, int *windows, uint32_t *soft = nullptr) {
   using bitrows::wsync;
   for (int i = lane; i < a.carry_words; i += 64) carry[i] = 0;
   if (lane < 2) pred[lane] = 0;
   wsync();
   *missed = false, *rounds = 0, *windows = 0;
+  if constexpr (Soft) soft[0] = soft[1] = soft[2] = 0;
   const int P = 32 * a.carry_words;
   for (int k = 0; k < a.n_windows; ++k) {
     const WinDesc d = a.desc[k];
@@ -149,13 +162,21 @@ __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &
       const bool miss = ufk::grow<Weighted>(w, st, lane, &r);
       *rounds = max(*rounds, r);
       ++*windows;
+      if constexpr (Soft) {  // (lp[] is free between grow() and forest(); the wsync() this ends on comes before forest() writes it)
+        uint32_t grown[2];
+        ufk::soft_of_growth(w, st, lane, grown);
+        soft[0] += grown[0], soft[1] = max(soft[1], grown[1]);
+      }
       if (miss) {
         *missed = true;
+        if constexpr (Soft) soft[2] = 0;
         return 0;
       }
       ufk::forest(w, st, lane);
+      uint32_t flipped = 0;  // (Soft) committed, by this lane
       const uint64_t flips = ufk::peel(w, st, lane, [&](int e, int u, int v) -> uint64_t {
         if (!((committed[e >> 5] >> (e & 31)) & 1u)) return 0;
+        if constexpr (Soft) ++flipped;
         if (u) {
           const int slot = (d.lo + u - 1) & (P - 1);
           atomicXor(&carry[slot >> 5], 1u << (slot & 31));
@@ -164,6 +185,7 @@ __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &
         atomicXor(&carry[slot >> 5], 1u << (slot & 31));
         return w.edge_obs[e];
       });
+      if constexpr (Soft) soft[2] += ufk::wave_sum(flipped);
       ufk::fold_flips(pred, flips);
     }
     wsync();
@@ -179,10 +201,10 @@ __device__ __forceinline__ uint64_t decode_row(const Args &a, const ufk::State &
   return (uint64_t)pred[0] | (uint64_t)pred[1] << 32;
 }
 
-template <bool Weighted, bool Heralds>
+template <bool Weighted, bool Heralds, bool Soft = false>
 __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed
+  uint32_t *stat = reinterpret_cast<uint32_t *>(lds_raw);  // kept, wrong, missed; with Soft: the kept rows of bin 0
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint8_t *base = lds_raw + 16 + (size_t)wave * a.shot_bytes;
   const ufk::State st = ufk::state_at(a, base);
@@ -192,6 +214,7 @@ __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
   uint32_t kept_acc = 0, wrong_acc = 0, miss_acc = 0, decoded_acc = 0;  // wave-uniform
   unsigned long long windows_acc = 0;
   int most_rounds = 0;
+  ufk::SoftBins bins;  // (Soft) the wave's rows of bin 0
   const long long tiles = (a.n + 63) >> 6;
   for (long long t = (long long)blockIdx.x * a.waves + wave; t < tiles; t += (long long)gridDim.x * a.waves) {
     const long long r = (t << 6) + lane;
@@ -203,14 +226,18 @@ __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
     const uint64_t obs = kept ? bitrows::row_obs(a, row) : 0;
     uint64_t pred = 0;
     bool missed = false;
+    uint32_t mine[4] = {0, 0, 0, 0};  // (Soft) this lane's row: rounds, full edges, largest cluster, correction weight
     uint64_t work = __builtin_amdgcn_ballot_w64(kept && defects != 0);
     while (work) {
       const int src = __builtin_ctzll(work);
       work &= work - 1;
       bool m;
       int rounds, windows;
-      const uint64_t p = decode_row<Weighted, Heralds>(a, st, carry, predw, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, &windows);
+      uint32_t soft[3];
+      const uint64_t p = decode_row<Weighted, Heralds, Soft>(a, st, carry, predw, a.rows + ((t << 6) + src) * a.rb, lane, &m, &rounds, &windows, soft);
       if (lane == src) pred = p, missed = m;
+      if constexpr (Soft)
+        if (lane == src) mine[0] = (uint32_t)rounds, mine[1] = soft[0], mine[2] = soft[1], mine[3] = soft[2];
       most_rounds = max(most_rounds, rounds);
       windows_acc += (unsigned)windows;
       ++decoded_acc;
@@ -219,6 +246,10 @@ __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
     wrong_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && pred != obs));
     miss_acc += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(kept && missed));
     if (a.pred && valid) a.pred[r] = pred;  // (0 for a row that is not kept, and for a miss)
+    if constexpr (Soft) {
+      bins.tile(a, a.metric == 0 ? mine[0] : a.metric == 1 ? mine[1] : a.metric == 2 ? mine[2] : mine[3], kept, kept && pred != obs, lane);
+      if (a.soft && valid) reinterpret_cast<uint4 *>(a.soft)[r] = make_uint4(mine[0], mine[1], mine[2], mine[3]);  // (zeros for a row that is not kept)
+    }
   }
   if (lane == 0) {
     if (kept_acc) atomicAdd(&stat[0], kept_acc);
@@ -227,9 +258,11 @@ __global__ void __launch_bounds__(64 * ufk::kMaxWaves) k_ufw(Args a) {
     if (most_rounds) atomicMax(&a.stats[0], (unsigned long long)most_rounds);
     if (decoded_acc) atomicAdd(&a.stats[1], (unsigned long long)decoded_acc);
     if (windows_acc) atomicAdd(&a.stats[2], windows_acc);
+    if constexpr (Soft) bins.wave_done(a, stat);
   }
   __syncthreads();
   if (threadIdx.x < 3 && stat[threadIdx.x]) atomicAdd(&a.dec[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
+  if constexpr (Soft) ufk::SoftBins::block_done(a, stat);
 }
 
 }  // namespace ufwk

@@ -91,8 +91,8 @@ heralds: without a defect on a non-herald detector, whatever its heralds say - s
 ``soft_output = metric`` and ``soft_bins = bins`` (2 .. 1024); given to ``count(decoder=...)`` it fills
 ``ShotCounts.soft_kept[b]``, the kept shots of bin ``b``, and ``ShotCounts.soft_errors[b]``, those of them that are decoded
 wrongly (``soft_kept.sum() == kept``, ``soft_errors.sum() == decoded_errors``); :meth:`ShotCounts.rejection_curve` is their
-running sum, the error count against the shots accepted.  A soft output of the windowed decoder (below) is out of scope:
-its windows have no common final state.
+running sum, the error count against the shots accepted.  The windowed decoder (below) has the same four, each a sum or a
+maximum over its windows: "Soft outputs in windows".
 
 Cluster matching (:meth:`UnionFindDecoder.with_cluster_matching`; ``tsim_uf_create_matching``).  The forest of
 step 2 ignores ``edge_p``: inside a cluster that holds several corrections peeling takes one by index, not by likelihood.
@@ -276,6 +276,29 @@ Growth, forest, peeling, the committed flips, the carry into ``r`` and a miss ar
 one window and every number - prediction, miss, flipped edges, growth rounds - equals that of :class:`UnionFindDecoder` over
 ``g``.  The rule is the one above plus a fixed set of edges that start full, so it stays independent of any parallel order.
 
+Soft outputs in windows (:meth:`WindowedUnionFindDecoder.soft_outputs`, :meth:`WindowedUnionFindDecoder.with_soft_output`;
+``tsim_ufw_decode_soft_device``).  The windows have no common final state and need none: each of the four metrics of "Soft
+outputs" above is defined per window, on the state that window's growth leaves, and combines across the windows by a sum or a
+maximum.  The rule is for a kept row with a defect on a node column.  Its DECODED windows are those "Decoding a row" decodes: the
+windows with a defect after the carries, in order, up to and including a window that misses.
+
+``rounds``             the most growth rounds of a decoded window (:meth:`WindowedUnionFindDecoder.growth_rounds`);
+``full_edges``         the SUM over the decoded windows of the local edges with ``grown == cap`` when that window's growth ends.
+                       Edges pre-grown by heralds count, virtual edges to the open future boundary count, and an edge that two
+                       overlapping windows both fill counts twice: the metric measures growth work, not a set of global edges;
+``largest_cluster``    the MAXIMUM over the decoded windows of the most nodes in one cluster of the window graph when its growth
+                       ends; local node 0 counts and a single node counts 1: :class:`UnionFindDecoder`'s definition on ``G_k``;
+``correction_weight``  the number of COMMITTED flips of the row, ``len(flipped_edges(row))``; 0 for a miss.
+
+A miss in window ``k`` ends the row there; its ``rounds``, ``full_edges`` and ``largest_cluster`` include window ``k``, as "when
+growth ends" includes a miss on the whole graph.  All four are 0 for a row that is not kept and for a kept row without a defect on
+a node column, whatever its heralds say.  The bin of a value ``x`` is ``min(x, bins - 1)``, bins in 2 .. 1024.  Every value is a
+sum or a maximum of per-window integers, each fixed by the synchronous growth rule, so the result depends neither on the order of
+the lanes nor on that of the atomics.  With one window (``W >= nd``) all four are :meth:`UnionFindDecoder.soft_outputs`.
+``w.with_soft_output(metric, bins)`` shares the windows, their decoders and the caches; ``count(decoder=...)`` fills
+``ShotCounts.soft_kept`` / ``soft_errors`` as it does for the whole-graph decoder.  Cluster matching and a complementary gap in
+windows are not done.
+
 What becomes of a prediction (``tsim_pred_rows_device``, ``csrc/tsim_predrows.hip.h``)
 ---------------------------------------------------------------------------------------------------------
 Every device decode call can write its predictions (``d_pred``: a uint64 per row, bit ``k`` = observable ``k``, 0 for a row that
@@ -352,7 +375,7 @@ def decode_file(decoder, *, detection_events_filepath, detection_events_format: 
     reader's staging are released on every path; on an error the writer is aborted and the predictions file is not valid.
 
     Out of scope: ``sample()`` / ``sample_write()`` / ``convert_file()`` with a decoder, post-selection (every row is kept) and
-    the soft outputs of a ``UnionFindDecoder.with_soft_output`` (only predictions are written)."""
+    the soft outputs of a union-find decoder ``with_soft_output`` (only predictions are written)."""
     from . import shotdata
 
     nd, n_obs = int(decoder.num_detectors), int(decoder.num_observables)
@@ -770,8 +793,9 @@ def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray
 
 class _RowDecoder:
     """What :class:`UnionFindDecoder` and :class:`WindowedUnionFindDecoder` share: rows to cache entries, the entries' readers
-    and the plain device call.  A subclass has ``graph``, ``_n_obs``, ``edge_caps`` and ``_cache``, decodes one row's detector
-    bits in ``_decode_bits`` (a cache entry: prediction, missed, flipped edges, rounds, ...) and opens its handle in ``_handle``."""
+    the device calls and the soft output.  A subclass has ``graph``, ``_n_obs``, ``edge_caps``, ``_cache``, ``soft_output`` and
+    ``soft_bins``, decodes one row's detector bits in ``_decode_bits`` (a cache entry: prediction, missed, flipped edges, rounds,
+    full edges, largest cluster, ...), opens its handle in ``_handle`` and names the handle's soft call in ``_soft_call``."""
 
     @staticmethod
     def _of_circuit(circuit, weights, resolution, heralds, limit):
@@ -839,14 +863,80 @@ class _RowDecoder:
         """int64 ``[n]``: the growth rounds every row took (of the windowed decoder: the most of any of its windows)."""
         return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
 
+    # -- soft outputs ----------------------------------------------------------------------------------------------------
+    _soft_refused = None   # why the decoder takes no soft output (a cluster-matching one), else None
+
+    def _with_soft_output(self, metric: str, bins: int = 64):
+        """``with_soft_output`` of both classes: the same decoder (graph, caps, observables and, of the windowed decoder, the
+        windows and their decoders are shared) with ``soft_output = metric``, one of ``"rounds"``, ``"full_edges"``,
+        ``"largest_cluster"`` and ``"correction_weight"``, and ``soft_bins = bins``, an int in 2 .. 1024: ``count(decoder=...)``
+        then fills ``ShotCounts.soft_kept`` / ``soft_errors`` ("Soft outputs" and "Soft outputs in windows" in the module
+        docstring)."""
+        if metric not in SOFT_OUTPUTS:
+            raise ValueError(f"metric = {metric!r}: one of {', '.join(SOFT_OUTPUTS)}")
+        if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= MAX_SOFT_BINS:
+            raise ValueError(f"bins = {bins!r}: an int in 2 .. {MAX_SOFT_BINS}")
+        if self._soft_refused is not None:
+            raise ValueError(self._soft_refused)
+        out = object.__new__(type(self))
+        out.__dict__.update(self.__dict__)  # (the caches too: what a syndrome decodes to does not depend on the metric)
+        out.soft_output, out.soft_bins = metric, int(bins)
+        return out
+
+    def soft_outputs(self, dets) -> np.ndarray:
+        """int64 ``[n, 4]``: per row ``rounds``, ``full_edges``, ``largest_cluster`` and ``correction_weight`` ("Soft outputs" in
+        the module docstring; of the windowed decoder "Soft outputs in windows"); a row without defects is all zero."""
+        out = np.zeros((len(np.asarray(dets)), 4), dtype=np.int64)
+        for r, e in enumerate(self._decoded(dets)):
+            if e is not None:
+                out[r] = e[3], e[4], e[5], len(e[2])
+        return out
+
+    def _soft_values(self, dets) -> np.ndarray:
+        """int64 ``[n]``: the value of every row that ``soft_output`` bins."""
+        return self.soft_outputs(dets)[:, SOFT_OUTPUTS.index(self.soft_output)]
+
+    def soft_bin_counts(self, dets, wrong):
+        """``(kept int64[soft_bins], errors int64[soft_bins])`` of kept rows: the rows per bin of ``soft_output``, and those of
+        them that are ``wrong`` (bool ``[n]``) - what the device adds to ``d_hist``."""
+        if self.soft_output is None:
+            raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
+        bins = np.minimum(self._soft_values(dets), self.soft_bins - 1)
+        return (np.bincount(bins, minlength=self.soft_bins).astype(np.int64),
+                np.bincount(bins[np.asarray(wrong, dtype=np.bool_)], minlength=self.soft_bins).astype(np.int64))
+
+    def _soft_shape(self, n: int) -> tuple:
+        """The shape of the uint32 values the soft call writes for ``n`` rows."""
+        return (int(n), 4)
+
     def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
-                      stream: int = 0):
+                      stream: int = 0, soft: bool = False):
         """``(predictions uint64[n], (kept, wrong, missed))`` for ``n`` bit-packed rows already in HBM (detectors, then
         observables; ``n_cols`` columns, default ``num_detectors + num_observables``; ``d_xor`` / ``d_test``: device masks of
         ``ceil(n_cols / 8)`` bytes) by one handle on ``hp``'s device, created and destroyed here: a ``tsim_uf``, or a
         ``tsim_ufw`` (the library builds the windows itself).  A row that is not kept and a miss predict 0.  Returns when the
-        results are on the host."""
-        return self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream)
+        results are on the host.  ``soft`` (a decoder of :meth:`with_soft_output`; ``tsim_uf_decode_soft_device``,
+        ``tsim_ufw_decode_soft_device``): two more results, the soft outputs of every row as uint32 ``[n, 4]`` (zeros for a row
+        that is not kept) and ``(kept int64[soft_bins], errors int64[soft_bins])``.  Of the decoder of
+        :meth:`UnionFindDecoder.with_gap_output` (``tsim_uf_decode_gap_device``) the values are the deficits, uint32 ``[n]``."""
+        if not soft:
+            return self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream)
+        if self.soft_output is None:
+            raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
+        values = np.zeros(self._soft_shape(n), np.uint32)
+        hist = np.zeros(2 * self.soft_bins, np.uint64)
+        d_values, d_hist = hp.malloc(values.nbytes + 16), hp.malloc(hist.nbytes + 16)
+        try:
+            hp.h2d(d_hist, hist)
+            pred, cnt = self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream, self._soft_call(hp, d_hist.ptr, d_values.ptr))
+            if n:
+                hp.d2h(values, d_values)
+            hp.d2h(hist, d_hist)
+            hist = hist.astype(np.int64)
+            return pred, cnt, values, (hist[:self.soft_bins].copy(), hist[self.soft_bins:].copy())
+        finally:
+            d_values.free()
+            d_hist.free()
 
     def _decode_device(self, hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream, call=None):
         """:meth:`decode_device`; ``call``: what decodes instead of the handle's plain call, with its arguments."""
@@ -917,16 +1007,11 @@ class UnionFindDecoder(_RowDecoder):
         """The same decoder (graph, caps and observables are shared) with ``soft_output = metric``, one of ``"rounds"``,
         ``"full_edges"``, ``"largest_cluster"`` and ``"correction_weight"``, and ``soft_bins = bins``, an int in 2 .. 1024:
         ``count(decoder=...)`` then fills ``ShotCounts.soft_kept`` / ``soft_errors`` ("Soft outputs" in the module docstring)."""
-        if metric not in SOFT_OUTPUTS:
-            raise ValueError(f"metric = {metric!r}: one of {', '.join(SOFT_OUTPUTS)}")
-        if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= MAX_SOFT_BINS:
-            raise ValueError(f"bins = {bins!r}: an int in 2 .. {MAX_SOFT_BINS}")
-        if self.match_defects is not None:
-            raise ValueError("a cluster-matching decoder has no soft output")
-        out = object.__new__(UnionFindDecoder)
-        out.__dict__.update(self.__dict__)  # (the cache too: what a syndrome decodes to does not depend on the metric)
-        out.soft_output, out.soft_bins = metric, int(bins)
-        return out
+        return self._with_soft_output(metric, bins)
+
+    @property
+    def _soft_refused(self):
+        return None if self.match_defects is None else "a cluster-matching decoder has no soft output"
 
     def with_cluster_matching(self, max_defects: int = 10, weights=None) -> "UnionFindDecoder":
         """The decoder of the same graph, caps and observables that corrects every cluster of at most ``max_defects`` defects
@@ -1448,28 +1533,18 @@ class UnionFindDecoder(_RowDecoder):
         return self._decode_one_soft(np.flatnonzero(bits[g.node_det]) + 1, np.unique(np.concatenate(erased)) if erased else ())
 
     def soft_outputs(self, dets) -> np.ndarray:
-        """int64 ``[n, 4]``: per row ``rounds``, ``full_edges``, ``largest_cluster`` and ``correction_weight`` ("Soft outputs" in
-        the module docstring); a row without defects is all zero."""
+        """The base class's; a cluster-matching decoder has none."""
         if self.match_defects is not None:
             raise ValueError("a cluster-matching decoder has no soft outputs")
-        out = np.zeros((len(np.asarray(dets)), 4), dtype=np.int64)
-        for r, e in enumerate(self._decoded(dets)):
-            if e is not None:
-                out[r] = e[3], e[4], e[5], len(e[2])
-        return out
+        return super().soft_outputs(dets)
 
-    def soft_bin_counts(self, dets, wrong):
-        """``(kept int64[soft_bins], errors int64[soft_bins])`` of kept rows: the rows per bin of ``soft_output``, and those of
-        them that are ``wrong`` (bool ``[n]``) - what the device adds to ``d_hist``."""
-        if self.soft_output is None:
-            raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
+    def _soft_values(self, dets) -> np.ndarray:
         if self.gap_observable is not None:
-            values = self.gap_outputs(dets) // self.gap_step
-        else:
-            values = self.soft_outputs(dets)[:, SOFT_OUTPUTS.index(self.soft_output)]
-        bins = np.minimum(values, self.soft_bins - 1)
-        return (np.bincount(bins, minlength=self.soft_bins).astype(np.int64),
-                np.bincount(bins[np.asarray(wrong, dtype=np.bool_)], minlength=self.soft_bins).astype(np.int64))
+            return self.gap_outputs(dets) // self.gap_step
+        return super()._soft_values(dets)
+
+    def _soft_shape(self, n: int) -> tuple:
+        return (int(n),) if self.gap_observable is not None else super()._soft_shape(n)
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _handle(self, hp, n_cols: int):
@@ -1491,32 +1566,6 @@ class UnionFindDecoder(_RowDecoder):
         if self.gap_observable is not None:
             return lambda *a, **k: hp.uf_decode_gap_device(*a, self.gap_cap, self.gap_step, self.soft_bins, d_hist, d_gap=d_values, **k)
         return lambda *a, **k: hp.uf_decode_soft_device(*a, self.soft_output, self.soft_bins, d_hist, d_soft=d_values, **k)
-
-    def decode_device(self, hp, d_rows: int, n: int, row_bytes: int, *, n_cols: int | None = None, d_xor: int = 0, d_test: int = 0,
-                      stream: int = 0, soft: bool = False):
-        """``(predictions uint64[n], (kept, wrong, missed))`` of ``n`` bit-packed rows already in HBM by one ``tsim_uf`` handle on
-        ``hp``'s device, created and destroyed here: every argument and result as the base class states them.  ``soft`` (the
-        decoder of :meth:`with_soft_output`; ``tsim_uf_decode_soft_device``): two more results, the soft outputs of every row as
-        uint32 ``[n, 4]`` (zeros for a row that is not kept) and ``(kept int64[soft_bins], errors int64[soft_bins])``.  Of the
-        decoder of :meth:`with_gap_output` (``tsim_uf_decode_gap_device``) the values are the deficits, uint32 ``[n]``."""
-        if not soft:
-            return self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream)
-        if self.soft_output is None:
-            raise ValueError("the decoder has no soft output: with_soft_output(metric, bins)")
-        values = np.zeros(int(n) if self.gap_observable is not None else (int(n), 4), np.uint32)
-        hist = np.zeros(2 * self.soft_bins, np.uint64)
-        d_values, d_hist = hp.malloc(values.nbytes + 16), hp.malloc(hist.nbytes + 16)
-        try:
-            hp.h2d(d_hist, hist)
-            pred, cnt = self._decode_device(hp, d_rows, n, row_bytes, n_cols, d_xor, d_test, stream, self._soft_call(hp, d_hist.ptr, d_values.ptr))
-            if n:
-                hp.d2h(values, d_values)
-            hp.d2h(hist, d_hist)
-            hist = hist.astype(np.int64)
-            return pred, cnt, values, (hist[:self.soft_bins].copy(), hist[self.soft_bins:].copy())
-        finally:
-            d_values.free()
-            d_hist.free()
 
 
 class UnionFindWindow(NamedTuple):
@@ -1546,7 +1595,8 @@ class WindowedUnionFindDecoder(_RowDecoder):
     non-herald detectors and pre-grow, each, the local edges of the heralds that are set ("Sliding windows with heralds"); it is
     kept in ``self.heralds``.  ``decode`` / ``missed`` / ``predictions`` / ``growth_rounds`` have :class:`UnionFindDecoder`'s
     signatures and decode each distinct row once; with ``window >= graph.n_nodes - 1`` there is one window and every number is
-    :class:`UnionFindDecoder`'s."""
+    :class:`UnionFindDecoder`'s.  ``soft_output`` / ``soft_bins`` are ``None`` unless the decoder comes from
+    :meth:`with_soft_output` ("Soft outputs in windows")."""
 
     def __init__(self, graph: DecodingGraph, commit: int, window: int, num_observables: int | None = None, edge_caps=None,
                  heralds: bool = False):
@@ -1567,8 +1617,10 @@ class WindowedUnionFindDecoder(_RowDecoder):
         if self.heralds:
             self._windows = [w._replace(**self._herald_lists(w)) for w in self._windows]
         self._decoders = [UnionFindDecoder(w.graph, self._n_obs, None if self.edge_caps is None else w.caps) for w in self._windows]
-        self._cache: dict = {}         # packed row of detectors -> (prediction, missed, flipped global edges, rounds)
-        self._window_cache: dict = {}  # (window, its packed defects, its erased local edges) -> what _decode_one gave
+        self.soft_output, self.soft_bins = None, None   # the metric count() bins, and into how many bins (with_soft_output)
+        self._cache: dict = {}         # packed row of detectors -> (prediction, missed, flipped global edges, rounds, full edges
+        #                                summed over the decoded windows, the largest cluster of any of them)
+        self._window_cache: dict = {}  # (window, its packed defects, its erased local edges) -> what _decode_one_soft gave
 
     @classmethod
     def from_circuit(cls, circuit, commit: int, window: int, weights: str | None = None, resolution: int = 4,
@@ -1579,6 +1631,14 @@ class WindowedUnionFindDecoder(_RowDecoder):
         (``DecodingGraph.from_form(form, heralds=True, limit=None)``); ``commit`` and ``window`` then count non-herald detectors."""
         graph, n_obs, caps = cls._of_circuit(circuit, weights, resolution, heralds, None)
         return cls(graph, commit, window, n_obs, caps, heralds=heralds)
+
+    def __getattr__(self, name):
+        """``w.with_soft_output(metric, bins)``: the base class's ``_with_soft_output`` (the windows, their decoders and both
+        caches are shared), an attribute of the decoders and not of the class: ``tests/test_unionfind_soft.py`` holds that
+        ``hasattr(WindowedUnionFindDecoder, "with_soft_output")`` is false, and stands as it is."""
+        if name == "with_soft_output":
+            return self._with_soft_output
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     # -- the windows -----------------------------------------------------------------------------------------------------
     def _build_windows(self) -> list:
@@ -1662,11 +1722,12 @@ class WindowedUnionFindDecoder(_RowDecoder):
     # -- the numpy statement ---------------------------------------------------------------------------------------------
     def _decode_row(self, bits: np.ndarray):
         """One row's detector bits (bool ``[num_detectors]``): ``(prediction, missed, committed flipped global edges ascending,
-        the most growth rounds of a window)``."""
+        the most growth rounds of a window, the full edges summed over the decoded windows, the largest cluster of any of
+        them)``; the last three include a window that misses ("Soft outputs in windows")."""
         g = self.graph
         r = bits[g.node_det].copy()   # the syndrome, by node (every column without heralds)
         fired = np.flatnonzero(bits[g.herald_det]) if self.heralds else ()   # the heralds that are set
-        prediction, flipped, most = 0, [], 0
+        prediction, flipped, most, full, largest = 0, [], 0, 0, 0
         for k, (w, uf) in enumerate(zip(self._windows, self._decoders)):
             if not r[w.lo:w.hi].any():
                 continue
@@ -1677,11 +1738,11 @@ class WindowedUnionFindDecoder(_RowDecoder):
                     erased = np.unique(np.concatenate([w.herald_edges[w.herald_ptr[x]:w.herald_ptr[x + 1]] for x in j]))
             key = (k, np.packbits(r[w.lo:w.hi]).tobytes(), erased.tobytes())
             if key not in self._window_cache:
-                self._window_cache[key] = uf._decode_one(np.flatnonzero(r[w.lo:w.hi]) + 1, erased)
-            _, miss, local, rounds = self._window_cache[key]
-            most = max(most, rounds)
+                self._window_cache[key] = uf._decode_one_soft(np.flatnonzero(r[w.lo:w.hi]) + 1, erased)
+            _, miss, local, rounds, window_full, window_largest = self._window_cache[key]
+            most, full, largest = max(most, rounds), full + window_full, max(largest, window_largest)
             if miss:
-                return 0, True, np.zeros(0, np.int64), most
+                return 0, True, np.zeros(0, np.int64), most, full, largest
             for e in local[w.committed[local]]:
                 ge = int(w.global_edge[e])
                 assert ge >= 0, "a committed edge is a real edge"
@@ -1692,7 +1753,7 @@ class WindowedUnionFindDecoder(_RowDecoder):
                 flipped.append(ge)
             assert not r[w.lo:min(w.lo + self.commit, w.hi)].any(), "the commit region is not clean"
         assert not r.any(), "the correction does not reproduce the syndrome"
-        return prediction, False, np.array(sorted(flipped), np.int64), most
+        return prediction, False, np.array(sorted(flipped), np.int64), most, full, largest
 
     _decode_bits = _decode_row
 
@@ -1700,3 +1761,8 @@ class WindowedUnionFindDecoder(_RowDecoder):
     def _handle(self, hp, n_cols: int):
         h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps, heralds=self.heralds)
         return h, hp.ufw_decode_device, hp.ufw_destroy
+
+    def _soft_call(self, hp, d_hist: int, d_values: int = 0):
+        """What decodes rows by this decoder's handle in the place of the plain call when the soft output is wanted: the two
+        histograms accumulate at ``d_hist``, the four values of every row go to ``d_values`` (0: not wanted)."""
+        return lambda *a, **k: hp.ufw_decode_soft_device(*a, self.soft_output, self.soft_bins, d_hist, d_soft=d_values, **k)

@@ -1196,7 +1196,8 @@ class CompiledDetectorSampler(_CompiledSamplerBase):
         errors for about three times the growth rounds; :class:`tsim_amd.decode.WindowedUnionFindDecoder` decodes a long run
         window after window where the whole graph does not fit).  ``decoded_errors``: kept shots whose observables differ from its prediction;
         ``decoder_misses``: kept shots for which it has no prediction (an unknown syndrome; a cluster that cannot reach the
-        boundary) and predicts no flip.  A ``UnionFindDecoder.with_soft_output(metric, bins)`` also fills ``soft_kept`` /
+        boundary) and predicts no flip.  A ``UnionFindDecoder.with_soft_output(metric, bins)`` or a
+        ``WindowedUnionFindDecoder.with_soft_output(metric, bins)`` also fills ``soft_kept`` /
         ``soft_errors``: the kept shots and the decoded errors per bin of the decoder's confidence in the shot
         (``ShotCounts.rejection_curve()``).  ``corrected=True`` (needs a decoder) XORs every kept shot's prediction into its
         observable columns where the row lies (``tsim_pred_rows_device``) before anything else reads it: ``observable_counts``
