@@ -21,7 +21,7 @@ import collections, json, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FULL = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_mov_b32", "v_not_b32", "v_lshrrev_b32",
-        "v_ashrrev_i32", "v_bitop3_b32", "v_fma_f32", "v_add_f32", "v_sub_f32", "v_add_co_u32", "v_addc_co_u32"}
+        "v_ashrrev_i32", "v_bitop3_b32", "v_fma_f32", "v_add_f32", "v_sub_f32", "v_add_co_u32"}  # v_addc_co_u32: measured 4.4, half
 CYC = {"full": 2.4, "half": 4.3, "salu": 4.4}
 
 
@@ -63,7 +63,8 @@ def main():
         if m and m.group(1) in labels and labels[m.group(1)] < i:
             loops.append((labels[m.group(1)], i))
     lo, hi = max(loops, key=lambda ab: ab[1] - ab[0])
-    # inner loops (the rank loop beyond the second ordinal, the direct-output runs) are counted once: one trip
+    # inner loops (the rank loop beyond the second ordinal, the direct-output runs) are counted once: one trip; so is every case of
+    # the bit-packed store's switch over the row size, of which a launch runs one (scalar branches and stores, and one shift)
     insts = [l.strip() for l in body[lo:hi + 1] if re.match(r"^\s*(v_|s_|global_|buffer_|flat_|ds_)", l)]
     cls = collections.Counter(classify(l) for l in insts)
     ops = collections.Counter(re.sub(r"_(e32|e64)$", "", l.split()[0]) for l in insts)

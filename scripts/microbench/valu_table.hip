@@ -135,6 +135,20 @@ KERNEL_END
 KERNEL_BEGIN(k_cmp_cnd_pair)
   asm volatile("v_cmp_lt_f32 s[20:21], %0, %1\n v_cndmask_b32 %0, %0, %1, s[20:21]" : "+v"(x) : "v"(y) : "s20", "s21");
 KERNEL_END
+// ---- the threshold walk's node = 2 node + (draw < threshold): the compare's mask as the carry-in of an add, against the mask
+// made a vector first.  s_nop 1: the two wait states between a vector write of a mask and its vector read
+KERNEL_BEGIN(k_addc_vcc)
+  asm volatile("v_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(x) : : "vcc");
+KERNEL_END
+KERNEL_BEGIN(k_addc_sgpr)
+  asm volatile("v_addc_co_u32 %0, s[20:21], %0, %0, s[22:23]" : "+v"(x) : : "s20", "s21", "s22", "s23");
+KERNEL_END
+KERNEL_BEGIN(k_cmp_addc_pair)
+  asm volatile("v_cmp_lt_u32 vcc, %0, %1\n s_nop 1\n v_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(x) : "v"(y) : "vcc");
+KERNEL_END
+KERNEL_BEGIN(k_cmp_cnd_lshlor)
+  { uint32_t t; asm volatile("v_cmp_lt_u32 vcc, %0, %2\n s_nop 1\n v_cndmask_b32 %1, 0, 1, vcc\n v_lshl_or_b32 %0, %0, 1, %1" : "+v"(x), "=&v"(t) : "v"(y) : "vcc"); }
+KERNEL_END
 KERNEL_BEGIN(k_readfirstlane)
   { uint32_t s; asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(s) : "v"(x)); (void)s; }
 KERNEL_END
@@ -214,7 +228,8 @@ int main(int argc, char **argv) {
     R(k_bitop3_vvv, 8), R(k_bitop3_vvs, 8), R(k_bitop3_vsv, 8),
     R(k_xad_vvv, 8), R(k_and_or_vvv, 8), R(k_or3_vvv, 8), R(k_mad_u24_vvv, 8), R(k_fma_f32, 8), R(k_med3_u32, 8),
     R(k_cmp_lt_f32, 8), R(k_cmp_gt_u32, 8), R(k_cmp_gt_u32_s, 8), R(k_cndmask_sgpr, 8), R(k_cndmask_vcc, 8),
-    R(k_cndmask_imm, 8), R(k_cmp_cnd_pair, 16), R(k_readfirstlane, 8), R(k_mbcnt_lo, 8),
+    R(k_cndmask_imm, 8), R(k_cmp_cnd_pair, 16), R(k_addc_vcc, 8), R(k_addc_sgpr, 8), R(k_cmp_addc_pair, 16),
+    R(k_cmp_cnd_lshlor, 24), R(k_readfirstlane, 8), R(k_mbcnt_lo, 8),
     R(k_lshl_b64_pair, 8), R(k_lshr_b64_pair, 8), R(k_mad_u64_u32, 8),
     R(r_alignbit, 12), R(r_shr_shl_bitop3, 16), R(r_shr_lshlor_xor, 16), R(r_shr_lshladd_xor, 16),
     R(r_mul_shr_bitop3, 16), R(r16_alignbit, 12), R(r16_perm, 12), R(r16_alignbyte, 12), R(r16_sdwa, 16), R(r_c_form, 12),

@@ -72,6 +72,40 @@ __device__ __forceinline__ uint32_t threefry_bits32_lo(uint32_t k0, uint32_t k1,
   return threefry_bits32_lo_at<false>(k0, k1, k0hi, lo);
 }
 
+// The threshold walk: node = 2 node + (draw < threshold) per level, the next level's threshold chosen by the bits so far.
+// The compare leaves its mask in vcc and v_addc_co_u32 takes it from there as the carry-in of node + node: no bit is made a
+// vector (v_cndmask 0, k), none shifted and or-ed in.  Written out because the compiler, given the same sums, selects the
+// bits into registers first.  A level's selects by the first bit stand in front of the add that spends vcc; s_nop 1 is the two
+// wait states gfx950 wants between a vector instruction's write of a mask and a vector read of it.  t2 = (00, 01, 10, 11).
+#define TSIMK_WALK_BIT(d, t) "v_cmp_lt_u32 vcc, %[" #d "], %[" #t "]\n s_nop 1\n"
+#define TSIMK_WALK_ADD "v_addc_co_u32 %[n], vcc, %[n], %[n], vcc\n"
+__device__ __forceinline__ uint32_t walk1(uint32_t node, uint32_t d0, uint32_t t0) {
+  asm(TSIMK_WALK_BIT(d0, t0) TSIMK_WALK_ADD : [n] "+v"(node) : [d0] "v"(d0), [t0] "v"(t0) : "vcc");
+  return node;
+}
+__device__ __forceinline__ uint32_t walk2(uint32_t node, uint32_t d0, uint32_t d1, uint32_t t0, uint32_t t10, uint32_t t11) {
+  uint32_t a;
+  asm(TSIMK_WALK_BIT(d0, t0) "v_cndmask_b32 %[a], %[t10], %[t11], vcc\n" TSIMK_WALK_ADD
+      TSIMK_WALK_BIT(d1, a) TSIMK_WALK_ADD
+      : [n] "+v"(node), [a] "=&v"(a) : [d0] "v"(d0), [d1] "v"(d1), [t0] "v"(t0), [t10] "v"(t10), [t11] "v"(t11) : "vcc");
+  return node;
+}
+__device__ __forceinline__ uint32_t walk3(uint32_t node, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t t0, uint32_t t10, uint32_t t11,
+                                          uint32_t t200, uint32_t t201, uint32_t t210, uint32_t t211) {
+  uint32_t a, p, q;
+  asm(TSIMK_WALK_BIT(d0, t0) "v_cndmask_b32 %[a], %[t10], %[t11], vcc\n"
+      "v_cndmask_b32 %[p], %[t200], %[t210], vcc\n v_cndmask_b32 %[q], %[t201], %[t211], vcc\n" TSIMK_WALK_ADD
+      TSIMK_WALK_BIT(d1, a) "v_cndmask_b32 %[a], %[p], %[q], vcc\n" TSIMK_WALK_ADD
+      TSIMK_WALK_BIT(d2, a) TSIMK_WALK_ADD
+      : [n] "+v"(node), [a] "=&v"(a), [p] "=&v"(p), [q] "=&v"(q)
+      : [d0] "v"(d0), [d1] "v"(d1), [d2] "v"(d2), [t0] "v"(t0), [t10] "v"(t10), [t11] "v"(t11), [t200] "v"(t200), [t201] "v"(t201),
+        [t210] "v"(t210), [t211] "v"(t211)
+      : "vcc");
+  return node;
+}
+#undef TSIMK_WALK_ADD
+#undef TSIMK_WALK_BIT
+
 template <int WF32, int NOUT>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_SGPRS))) k_sample_lw_fast(LwMultiArgs M) {
   typedef const __attribute__((address_space(4))) uint8_t *cbytes;
@@ -108,6 +142,13 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
   if (vb >= total) return;
   uint32_t step = vb / bps, rb = vb - step * bps;
   const uint32_t Bu = (uint32_t)M.B;
+  // ---- once per thread: what a row's byte offsets hold of the thread.  The row block's part is wave-uniform: formed on the scalar
+  // unit in every trip and handed to the stores as their scalar offset (their descriptors are unbounded; the f load's ends with the
+  // batch, and its whole offset stays in the vector operand: the zeros its idle lanes read are the descriptor's range check at work)
+  const uint32_t tid = threadIdx.x;
+  const uint32_t out_rb = (uint32_t)M.out_rb;
+  const uint32_t tid_pad = tid * 8u, tid_rb = tid * out_rb;
+  const bool lead_wave = __builtin_amdgcn_readfirstlane((int)tid) == 0;  // the wave that holds thread 0
   // the first row's f words; the NEXT row's are requested at the top of every iteration
   uint32_t n[4] = {0u, 0u, 0u, 0u};
   auto load_f = [&](uint32_t st, uint32_t rbk) {
@@ -146,15 +187,17 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
   }
   for (;;) {
     cstep S = steps + step;
-    const uint32_t row = rb * (uint32_t)nthr + threadIdx.x;
-    const bool active = row < Bu;
+    const uint32_t row0 = rb * (uint32_t)nthr;  // the row block's first row (< B): scalar
+    const uint32_t row = row0 + tid;
+    const bool active = tid < Bu - row0;
     uint32_t f[4] = {n[0], n[1], n[2], n[3]};
     uint32_t vb_n = vb + gridDim.x, step_n = step, rb_n = rb + gridDim.x;
     while (rb_n >= bps) { rb_n -= bps; ++step_n; }
     const bool more = vb_n < total;
     if (more) load_f(step_n, rb_n);
-    if (rb == 0u && threadIdx.x <= TSIMK_LW_LISTS)  // reset the slot's other counter set (nobody else touches it now)
-      S->ctl_next[32u * threadIdx.x] = (threadIdx.x == TSIMK_LW_LISTS) ? 0xFFFFFFFFu : 0u;
+    if (rb == 0u) {  // wave-uniform.  Reset the slot's other counter set (nobody else touches it now)
+      if (tid <= TSIMK_LW_LISTS) S->ctl_next[32u * tid] = (tid == TSIMK_LW_LISTS) ? 0xFFFFFFFFu : 0u;
+    }
     // ---- K14: direct outputs f[idx] ^ flip (sampler.py:140-145): bit-field runs, rotate and mask
     uint32_t o0 = 0u, o1 = 0u;
     for (uint32_t r = 0; r < ((TSIMK_LWM_SKIP & 2) ? 0u : n_runs); ++r) {
@@ -177,11 +220,17 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
       m[w] = f[w] & sel[w];
       cnt += (uint32_t)__builtin_popcount(m[w]);
     }
+    // `hard` as a lane predicate and, beside it, as the wave's mask hm: both from the compares' own masks, joined on the scalar unit
     bool hard = cnt > wmax;
-    if (M.has_check && rb == 0u && threadIdx.x == 0u) {  // the normalisation-check row (sampler.py:66-72): always hard
-      hard = true;
-      S->ctl[32 * TSIMK_LW_LISTS] = row;
+    unsigned long long hm = __builtin_amdgcn_ballot_w64(cnt > wmax);
+    if (M.has_check && rb == 0u) {  // wave-uniform: one row block in bps holds the normalisation-check row (sampler.py:66-72), always hard
+      if (tid == 0u) {
+        hard = true;
+        S->ctl[32 * TSIMK_LW_LISTS] = row;
+      }
+      if (lead_wave) hm |= 1ull;
     }
+    hm &= __builtin_amdgcn_ballot_w64(tid < Bu - row0);
     hard = hard && active;
     const bool easy = active && !hard;
     uint32_t pat = lds[L_BASES + cnt];
@@ -222,7 +271,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
     }
     // ---- thresholds of the pattern's prefix tree and the draws (sampler.py:62-79 with the thresholds tabulated)
     const uint32_t thr = tab_byte + (pat << (NOUT + 2));  // byte offset of the pattern's row
-    const uint32_t slo = so_lo + row;  // the host launches this kernel only when shot_offset + B stays below the next 2^32
+    const uint32_t slo = (so_lo + row0) + tid;  // the host launches this kernel only when shot_offset + B stays below the next 2^32
     cptr kp = (cptr)((cbytes)S + __builtin_offsetof(LwStep, keys)) + 2u * keybase;
     // Every output's key is requested before the first draw, and the draws keep their places (PINNED): a level group's
     // threshold reads are under way while its draws run and are waited for behind them.
@@ -246,29 +295,28 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
 #pragma unroll
     for (; i + 3 <= NOUT; i += 3) {
       const uint32_t t0 = __builtin_amdgcn_raw_buffer_load_b32(r_tab, thr + 4u * node, 0, 0);
-      const u32x2 t1 = __builtin_amdgcn_raw_buffer_load_b64(r_tab, thr + 8u * node, 0, 0);
+      // the second level as two words, not a pair: at the root the three reads of levels one and two are one 12-byte read, and a
+      // pair in its upper two registers would be copied to an even register first
+      const uint32_t t10 = __builtin_amdgcn_raw_buffer_load_b32(r_tab, thr + 8u * node, 0, 0);
+      const uint32_t t11 = __builtin_amdgcn_raw_buffer_load_b32(r_tab, thr + 8u * node + 4u, 0, 0);
       const u32x4 t2 = __builtin_amdgcn_raw_buffer_load_b128(r_tab, thr + 16u * node, 0, 0);
       const uint32_t d0 = draw(i), d1 = draw(i + 1), d2 = draw(i + 2);
-      const bool b0 = d0 < t0;
-      const bool b1 = d1 < (b0 ? t1.y : t1.x);
-      const uint32_t lo = b1 ? t2.y : t2.x, hi = b1 ? t2.w : t2.z;
-      const bool b2 = d2 < (b0 ? hi : lo);
-      node = 8u * node + (b0 ? 4u : 0u) + (b1 ? 2u : 0u) + (b2 ? 1u : 0u);
+      node = walk3(node, d0, d1, d2, t0, t10, t11, t2.x, t2.y, t2.z, t2.w);
     }
     if (TSIMK_LWM_SKIP & 32) {
     } else if constexpr (NOUT % 3 == 2) {
       const uint32_t t0 = __builtin_amdgcn_raw_buffer_load_b32(r_tab, thr + 4u * node, 0, 0);
       const u32x2 t1 = __builtin_amdgcn_raw_buffer_load_b64(r_tab, thr + 8u * node, 0, 0);
       const uint32_t d0 = draw(i), d1 = draw(i + 1);
-      const bool b0 = d0 < t0;
-      const bool b1 = d1 < (b0 ? t1.y : t1.x);
-      node = 4u * node + (b0 ? 2u : 0u) + (b1 ? 1u : 0u);
+      node = walk2(node, d0, d1, t0, t1.x, t1.y);
     } else if constexpr (NOUT % 3 == 1) {
       const uint32_t t0 = __builtin_amdgcn_raw_buffer_load_b32(r_tab, thr + 4u * node, 0, 0);
-      node = 2u * node + (draw(i) < t0 ? 1u : 0u);
+      node = walk1(node, draw(i), t0);
     }
     // ---- place the sampled bits (one look-up: leaf -> the two output words), store the row
-    const u32x2 placed = *reinterpret_cast<const u32x2 *>(&lds[L_LUT + 2u * (node & ((1u << NOUT) - 1u))]);
+    // node = 2^NOUT + leaf: the walk's leading one comes off with the table's constant address (L_LUT >= 2 << NOUT), not with a mask
+    static_assert(L_LUT >= (2 << NOUT), "the look-up table's offset must hold the walk's leading one");
+    const u32x2 placed = *reinterpret_cast<const u32x2 *>(&lds[(uint32_t)(L_LUT - (2 << NOUT)) + 2u * node]);
     o0 |= placed.x;
     o1 |= placed.y;
     if (TSIMK_LWM_SKIP & 16) n[0] ^= (o0 ^ o1) & 0x10101010u;  // diagnostic: results stay live without stores
@@ -279,27 +327,49 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(TSIMK_LW_
         const __amdgpu_buffer_rsrc_t r_o = __builtin_amdgcn_make_buffer_rsrc((void *)out, 0, 0xFFFFFFFF, 0x00020000);
         u32x2 v;
         v.x = o0; v.y = o1;
-        __builtin_amdgcn_raw_buffer_store_b64(v, r_o, row * 8u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(v, r_o, tid_pad, row0 * 8u, 0);
       }
       if (oc) {
         const __amdgpu_buffer_rsrc_t r_c = __builtin_amdgcn_make_buffer_rsrc((void *)oc, 0, 0xFFFFFFFF, 0x00020000);
-        // out_rb bytes at row * out_rb (any alignment: the device runs in unaligned-access mode): as few stores as the
-        // size allows - 4-byte pieces, then 2, then 1 (20 outputs: a short and a byte instead of three bytes)
-        const uint32_t off = row * (uint32_t)M.out_rb;
-        const int rb8 = M.out_rb;
-        if (rb8 >= 4) __builtin_amdgcn_raw_buffer_store_b32(o0, r_c, off, 0, 0);
-        if (rb8 == 8) __builtin_amdgcn_raw_buffer_store_b32(o1, r_c, off, 4, 0);
-        else {
-          const uint32_t w = rb8 >= 4 ? o1 : o0;  // the word the remaining 1..3 bytes come from
-          const uint32_t at = rb8 >= 4 ? off + 4u : off;
-          const int rem = rb8 & 3;
-          if (rem >= 2) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)w, r_c, at, 0, 0);
-          if (rem & 1) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(w >> (rem == 3 ? 16 : 0)), r_c, at + (rem == 3 ? 2u : 0u), 0, 0);
+        // out_rb bytes at row * out_rb (any alignment: the device runs in unaligned-access mode): as few stores as the size allows -
+        // 4-byte pieces, then 2, then 1 (20 outputs: a short and a byte instead of three bytes).  The row size is fixed for the
+        // launch: a scalar branch picks the size's straight-line code, every piece at a constant offset and a constant shift.
+        const uint32_t blk = row0 * out_rb;
+        switch (out_rb) {
+          case 1:
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)o0, r_c, tid_rb, blk, 0);
+            break;
+          case 2:
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)o0, r_c, tid_rb, blk, 0);
+            break;
+          case 3:
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)o0, r_c, tid_rb, blk, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(o0 >> 16), r_c, tid_rb + 2u, blk, 0);
+            break;
+          case 4:
+            __builtin_amdgcn_raw_buffer_store_b32(o0, r_c, tid_rb, blk, 0);
+            break;
+          case 5:
+            __builtin_amdgcn_raw_buffer_store_b32(o0, r_c, tid_rb, blk, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)o1, r_c, tid_rb + 4u, blk, 0);
+            break;
+          case 6:
+            __builtin_amdgcn_raw_buffer_store_b32(o0, r_c, tid_rb, blk, 0);
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)o1, r_c, tid_rb + 4u, blk, 0);
+            break;
+          case 7:
+            __builtin_amdgcn_raw_buffer_store_b32(o0, r_c, tid_rb, blk, 0);
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)o1, r_c, tid_rb + 4u, blk, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(o1 >> 16), r_c, tid_rb + 6u, blk, 0);
+            break;
+          default:  // 8
+            __builtin_amdgcn_raw_buffer_store_b32(o0, r_c, tid_rb, blk, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(o1, r_c, tid_rb + 4u, blk, 0);
+            break;
         }
       }
     }
     // ---- wave-aggregated append of the hard rows to this batch's lists
-    const unsigned long long hm = __builtin_amdgcn_ballot_w64(hard);
     if (hm != 0ull) {
       const int lane = (int)(threadIdx.x & 63u);
       const int leader = __builtin_ctzll(hm);
