@@ -802,6 +802,29 @@ int tsim_ufw_create(int32_t device, const tsim_uf_desc *global, const uint8_t *e
  * tables lie in global memory.  her == NULL is tsim_ufw_create. */
 int tsim_ufw_create_heralds(int32_t device, const tsim_uf_desc *global, const uint8_t *edge_cap, int32_t commit,
                             int32_t window, const tsim_uf_heralds *her, tsim_ufw **out);
+/* Cluster matching in windows ("Cluster matching in windows" in the same docstring): everything tsim_ufw_create does, for a
+ * graph without heralds, and in every decoded window that is no miss each cluster of 1 .. max_defects defects is corrected by
+ * the minimum-weight matching of its defects in the window graph, the paths of the chosen pairs walked edge by edge so that
+ * only their COMMITTED edges count; a larger cluster is peeled as before.  match_w (uint16[n_edges], required, 1 .. 65535) are
+ * GLOBAL match weights: the weight of a local edge is the least among the global edges that land on it, computed on the host
+ * beside the caps.  Per DISTINCT window - windows whose local arrays (nodes, edge_uv, edge_obs, weights, adjacency, commit
+ * bitmap) are byte-identical share one - a match table of distances (uint32) and parent edges (uint16), 6 bytes per pair of
+ * nodes and no masks, is built on the device by this call.  max_defects is 1 .. 12.  A NULL match_w, a weight of 0 and a bad
+ * max_defects are TSIM_EINVAL, with everything tsim_ufw_create checks.  TSIM_ENOTSUP for a window of more than 2048 nodes, for
+ * distinct tables of more than 1 GiB together, and when a shot's state - that of tsim_ufw_create, the dynamic program's of
+ * tsim_uf_create_matching and 4 bytes per pair a cluster can choose - does not fit a block's 64 KiB of LDS.  All of it is
+ * checked before any device call.  tsim_ufw_decode_device takes the handle and means what it means on the others;
+ * tsim_ufw_decode_soft_device on it is TSIM_EINVAL. */
+int tsim_ufw_create_matching(int32_t device, const tsim_uf_desc *global, const uint8_t *edge_cap, const uint16_t *match_w,
+                             int32_t max_defects, int32_t commit, int32_t window, tsim_ufw **out);
+/* The match table of window k of a handle of tsim_ufw_create_matching, to the host: dist (uint32[n * n], 0x7FFFFFFF: no path)
+ * and parent (uint16[n * n]: the LOCAL parent edge of v from source a at [a * n + v], 0xFFFF for v == a and where there is no
+ * path), n the nodes of window k.  TSIM_EINVAL for another handle, a NULL or a k outside the windows.  Synchronous. */
+int tsim_ufw_match_table(tsim_ufw *h, int32_t k, uint32_t *dist, uint16_t *parent);
+/* Of a handle of tsim_ufw_create_matching (TSIM_EINVAL for another; tsim_ufw_info has no free slot): out[0] max_defects,
+ * [1] distinct match tables, [2] their bytes, [3] clusters matched and [4] clusters peeled, over the decoded windows of the
+ * rows decoded in LDS that are no miss, [5] the most edges of a path walked, [6] and [7] zero.  Synchronises the device. */
+int tsim_ufw_match_info(tsim_ufw *h, int64_t out[8]);
 void tsim_ufw_destroy(tsim_ufw *h);
 /* out[0] nodes and [1] edges of the global graph, [2] windows, [3] the most nodes and [4] the most edges of a window,
  * [5] LDS bytes per shot, [6] shots (waves) per block, [7] kernel launches so far, [8] the most growth rounds a window

@@ -3,6 +3,7 @@
     python scripts/windowed_uf_bench.py                                  # the four legs below, JSON lines
     python scripts/windowed_uf_bench.py --legs rate --cases d9x27c9
     python scripts/windowed_uf_bench.py --legs quality --shots 1000000
+    python scripts/windowed_uf_bench.py --match 10                       # cluster matching in windows: the ``match`` leg alone
 
 A case ``d<D>x<R>c<C>`` is ``rotated_surface_code_memory(D, R)`` with all three noise options at ``--p``, decoded in windows
 of ``commit = C`` rounds and ``window = 2 C`` rounds (a round is ``D * D - 1`` detector columns), unweighted.
@@ -26,6 +27,13 @@ that list no edge (what ignoring the heralds costs in decoded errors), on the sa
 ``soft`` (``profiles/windowed_soft_bench.txt``): ``--soft-case`` (d = 5, 400 rounds, commit = 120 and window = 240
 columns), ``count(--soft-shots, decoder=...)`` as in ``rate`` of the windowed decoder and of the same decoder
 ``with_soft_output(--soft-metric, --soft-bins)``, alternating, and the errors ``rejection_curve()`` leaves at ``--soft-kept``.
+
+``match`` (``--match K``; ``profiles/windowed_matching_bench.txt``): windowed peeling against
+``with_cluster_matching(K)``.  Error counts: the ``--match-cases`` ``d<D>x<R>p<P>n<ROWS>``, ``weights="probability"``, commit = 2 and
+window = 4 rounds, ``after_clifford_depolarization = before_measure_flip_probability = P``, rows of
+``compile_detector_sampler(seed=3).sample()``; both decoders decode the uploaded rows on the device and by the numpy statement, which
+must agree bit for bit.  Throughput: ``count(--soft-shots, decoder=...)`` of ``--soft-case`` as in ``soft``, the plain windowed
+decoder and the matching one alternating, and the create call alone (it builds the match tables), ``--reps`` times each.
 """
 
 from __future__ import annotations
@@ -270,9 +278,92 @@ def soft_leg(args) -> None:
     print(json.dumps(out), flush=True)
 
 
+def match_leg(args, hp) -> None:
+    """Windowed peeling against windowed cluster matching with ``K = --match``: decoded errors on the ``--match-cases``, device
+    and numpy statement bit for bit, then the shots per second of both on ``--soft-case`` and the time of the create call."""
+    K = args.match
+    for case in args.match_cases.split(","):
+        d, rest = case[1:].split("x")
+        rounds, rest = rest.split("p")
+        p, n = rest.split("n")
+        d, rounds, p, n = int(d), int(rounds), float(p), int(n)
+        c = CliffordCircuit(circuits.rotated_surface_code_memory(d, rounds, after_clifford_depolarization=p, before_measure_flip_probability=p))
+        cols = 2 * (d * d - 1)
+        peel = WindowedUnionFindDecoder.from_circuit(c, cols, 2 * cols, weights="probability")
+        decoders = {"peeling": peel, "matching": peel.with_cluster_matching(K)}
+        bits = np.asarray(c.compile_detector_sampler(seed=3).sample(n, append_observables=True), dtype=np.bool_)
+        nd, n_obs = peel.num_detectors, peel.num_observables
+        obs = (bits[:, nd:nd + n_obs].astype(np.uint64) << np.arange(n_obs, dtype=np.uint64)[None, :]).sum(axis=1, dtype=np.uint64)
+        rows = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little"))
+        rows = np.ascontiguousarray(np.pad(rows, ((0, 0), (0, -rows.shape[1] % 8))))
+        out = dict(leg="match", part="errors", case=case, K=K, rows=n, commit_columns=cols, window_columns=2 * cols, windows=peel.info()["n_windows"],
+                   raw_flips=int((obs != 0).sum()))
+        d_rows = hp.malloc(rows.nbytes + 16)
+        try:
+            hp.h2d(d_rows, rows)
+            for m, dec in decoders.items():
+                t0 = time.perf_counter()
+                want = dec.predictions(bits[:, :nd])
+                host_s = time.perf_counter() - t0
+                pred, (kept, wrong, missed) = dec.decode_device(hp, d_rows.ptr, n, rows.shape[1])
+                if not np.array_equal(pred, want) or wrong != int((want != obs).sum()) or missed != int(dec.missed(bits[:, :nd]).sum()):
+                    sys.exit(f"windowed_uf_bench: {case}: the device and the numpy statement of windowed {m} differ "
+                             f"({int((pred != want).sum())} rows)")
+                out[m] = dict(decoded_errors=wrong, misses=missed, numpy_statement_s=host_s)
+            counts = decoders["matching"].match_counts(bits[:, :nd]).sum(0)
+            out["clusters_matched"], out["clusters_peeled"] = int(counts[0]), int(counts[1])
+            out["rows_with_a_path_committed_in_part"] = int((decoders["matching"].mixed_pairs(bits[:, :nd]) > 0).sum())
+        finally:
+            d_rows.free()
+        print(json.dumps(out), flush=True)
+    # throughput on the long run
+    d, rounds, commit = parse(args.soft_case)
+    c = memory(d, rounds, args.p)
+    form = c.compile_faults()
+    cols = commit * (d * d - 1)
+    plain = WindowedUnionFindDecoder(DecodingGraph.from_form(form, limit=None), cols, 2 * cols, int(form.n_out) - int(form.num_detectors))
+    decoders = {"plain": plain, "matching": plain.with_cluster_matching(K)}
+    out = dict(leg="match", part="throughput", case=args.soft_case, p=args.p, K=K, commit_columns=cols, window_columns=2 * cols, graph=plain.info())
+    n_cols = int(form.n_out)
+    creates = []
+    for _ in range(args.reps + 1):  # (the first call warms up)
+        t0 = time.perf_counter()
+        h = hp.ufw_create_matching(plain.graph, n_cols, decoders["matching"].match_weights, K, plain.commit, plain.window)
+        creates.append(time.perf_counter() - t0)
+        out["handle"], out["match_info"] = hp.ufw_info(h), hp.ufw_match_info(h)
+        hp.ufw_destroy(h)
+    out["create_matching"] = spread(creates[1:])
+    creates = []
+    for _ in range(args.reps + 1):
+        t0 = time.perf_counter()
+        h = hp.ufw_create(plain.graph, n_cols, plain.commit, plain.window)
+        creates.append(time.perf_counter() - t0)
+        hp.ufw_destroy(h)
+    out["create_plain"] = spread(creates[1:])
+
+    def sampler():  # a fresh one per call: every call counts the same seeded rows
+        return c.compile_detector_sampler(seed=1, noise="device", method="faults")
+
+    times, last = {m: [] for m in decoders}, {}
+    for m, dec in decoders.items():
+        sampler().count(args.soft_shots, batch_size=args.batch, decoder=dec)  # warm-up at the timed size
+    for _ in range(args.reps):
+        for m, dec in decoders.items():
+            s = sampler()
+            t0 = time.perf_counter()
+            last[m] = s.count(args.soft_shots, batch_size=args.batch, decoder=dec)
+            times[m].append(time.perf_counter() - t0)
+    out["count"] = {m: dict(spread(t), shots=args.soft_shots, shots_per_s=args.soft_shots / statistics.median(t), kept=last[m].kept,
+                            raw_flips=last[m].kept_with_observable_flip, decoded_errors=last[m].decoded_errors,
+                            misses=last[m].decoder_misses) for m, t in times.items()}
+    print(json.dumps(out), flush=True)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="rate,quality,erasure,soft")
+    ap.add_argument("--legs", default=None, help="rate,quality,erasure,soft (all four unless --match is given), match")
+    ap.add_argument("--match", type=int, default=0, help="K of with_cluster_matching for the match leg")
+    ap.add_argument("--match-cases", default="d3x12p3e-3n40000,d3x12p5e-3n40000,d5x20p3e-3n6000")
     ap.add_argument("--soft-case", default="d5x400c5")
     ap.add_argument("--soft-shots", type=int, default=100000)
     ap.add_argument("--soft-metric", default="largest_cluster")
@@ -292,6 +383,10 @@ def main() -> None:
     ap.add_argument("--quality-shots", type=int, default=10**6)
     ap.add_argument("--commits", default="2,5")
     args = ap.parse_args()
+    if args.legs is None:
+        args.legs = "match" if args.match else "rate,quality,erasure,soft"
+    if "match" in args.legs.split(",") and not 1 <= args.match <= 12:
+        sys.exit("windowed_uf_bench: the match leg needs --match K, 1 .. 12")
     _lib.load()
     if _lib.device_count() < 1:
         sys.exit("windowed_uf_bench: no HIP device - nothing is measured without one")
@@ -303,6 +398,8 @@ def main() -> None:
         erasure_leg(args)
     if "soft" in args.legs.split(","):
         soft_leg(args)
+    if "match" in args.legs.split(","):
+        match_leg(args, HipProgram(synth.kat_h_m()))
 
 
 if __name__ == "__main__":

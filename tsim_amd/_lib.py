@@ -185,6 +185,9 @@ SYMBOLS: dict[str, tuple] = {
     "tsim_uf_decode_soft_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P]),
     "tsim_ufw_create": (C.c_int, [_I32, C.POINTER(UfDesc), _P, _I32, _I32, C.POINTER(_P)]),
     "tsim_ufw_create_heralds": (C.c_int, [_I32, C.POINTER(UfDesc), _P, _I32, _I32, C.POINTER(UfHeralds), C.POINTER(_P)]),
+    "tsim_ufw_create_matching": (C.c_int, [_I32, C.POINTER(UfDesc), _P, _P, _I32, _I32, _I32, C.POINTER(_P)]),
+    "tsim_ufw_match_table": (C.c_int, [_P, _I32, _P, _P]),
+    "tsim_ufw_match_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_ufw_destroy": (None, [_P]),
     "tsim_ufw_info": (C.c_int, [_P, C.POINTER(_I64)]),
     "tsim_ufw_decode_device": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _I32, _I32, _P, _P, _P]),

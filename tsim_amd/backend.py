@@ -670,6 +670,46 @@ class HipProgram:
         _lib.check(rc, name)
         return h.value
 
+    def ufw_create_matching(self, graph, n_cols: int, match_weights, max_defects: int, commit: int, window: int, caps=None) -> int:
+        """A cluster-matching sliding-window decoder over ``graph`` (``tsim_ufw_create_matching``; "Cluster matching in windows" in
+        the module docstring of :mod:`tsim_amd.decode`): ``match_weights``, a GLOBAL integer per edge in 1 .. 65535 (the library
+        makes the windows' local weights of them), ``max_defects`` in 1 .. 12, the rest as :meth:`ufw_create`.  The handle decodes
+        by :meth:`ufw_decode_device` and is given back to :meth:`ufw_destroy`."""
+        desc, d_caps, her, _keep = self._uf_graph_args(graph, n_cols, caps)
+        if her is not None:
+            raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
+        w = np.ascontiguousarray(match_weights)
+        if w.shape != (graph.n_edges,) or not np.issubdtype(w.dtype, np.integer) or (w.size and (w.min() < 0 or w.max() > 65535)):
+            raise ValueError(f"match_weights: {graph.n_edges} integers in 1 .. 65535 expected")
+        w = np.concatenate([w.astype(np.uint16), np.zeros(1, np.uint16)])  # (never an empty buffer)
+        clip = lambda x: int(min(max(x, -1), 0x7FFFFFFF))  # noqa: E731
+        h = C.c_void_p()
+        _lib.check(self._lib.tsim_ufw_create_matching(self.device, C.byref(desc), d_caps, C.c_void_p(w.ctypes.data), clip(max_defects),
+                                                      clip(commit), clip(window), C.byref(h)), "tsim_ufw_create_matching")
+        self.__dict__.setdefault("_ufw_columns", {})[h.value] = (int(commit), int(window))  # (ufw_match_table sizes a window by them)
+        return h.value
+
+    def ufw_match_table(self, handle: int, k: int):
+        """``(dist uint32[n, n], parent uint16[n, n])``: the match table of window ``k`` that the handle of
+        :meth:`ufw_create_matching` built on the device (``tsim_ufw_match_table``); ``n`` is the window's nodes."""
+        info = self.ufw_info(handle)
+        if not 0 <= k < info["n_windows"]:
+            raise ValueError(f"window {k} of {info['n_windows']}")
+        nd, commit, window = info["n_nodes"] - 1, *self._ufw_columns[handle]
+        n = (nd if k == info["n_windows"] - 1 else k * commit + window) - k * commit + 1
+        dist, parent = np.zeros((n, n), np.uint32), np.zeros((n, n), np.uint16)
+        _lib.check(self._lib.tsim_ufw_match_table(C.c_void_p(handle), int(k), _lib.ptr(dist), _lib.ptr(parent)), "tsim_ufw_match_table")
+        return dist, parent
+
+    UFW_MATCH_INFO = ("max_defects", "distinct_tables", "table_bytes", "clusters_matched", "clusters_peeled", "longest_path")
+
+    def ufw_match_info(self, handle: int) -> dict:
+        """Of a handle of :meth:`ufw_create_matching` (``tsim_ufw_match_info``): ``max_defects``, the distinct match tables and
+        their bytes, the clusters matched and peeled so far, and the most edges of a path walked."""
+        out = (C.c_int64 * 8)()
+        _lib.check(self._lib.tsim_ufw_match_info(C.c_void_p(handle), out), "tsim_ufw_match_info")
+        return {k: int(v) for k, v in zip(self.UFW_MATCH_INFO, out)}
+
     def ufw_decode_device(self, handle: int, d_rows: int, n: int, row_bytes: int, observables: tuple, d_counters: int, *, d_pred: int = 0,
                           d_xor: int = 0, d_test: int = 0, stream: int = 0) -> None:
         """:meth:`uf_decode_device` by a handle of :meth:`ufw_create` (``tsim_ufw_decode_device``)."""
@@ -691,6 +731,7 @@ class HipProgram:
         return info
 
     def ufw_destroy(self, handle: int) -> None:
+        self.__dict__.get("_ufw_columns", {}).pop(handle, None)
         self._lib.tsim_ufw_destroy(C.c_void_p(handle))
 
     def sample_batch_device(self, d_f: int, B: int, num_f: int, key, d_out: int, *,

@@ -18,6 +18,15 @@ struct tsim_uf {
   tsimh::Uploads up;  // the tables a points to
 };
 
+hipError_t ufh::launch_match_table(int n_nodes, const uint32_t *edge_uv, const unsigned long long *edge_obs, const uint16_t *w,
+                                   const uint32_t *adj_ptr, const uint16_t *adj_edge, uint32_t *dist, unsigned long long *mask, uint16_t *parent) {
+  ufk::TableArgs t{};
+  t.n_nodes = n_nodes, t.edge_uv = edge_uv, t.edge_obs = edge_obs, t.w = w, t.adj_ptr = adj_ptr, t.adj_edge = adj_edge;
+  t.dist = dist, t.mask = mask, t.parent = parent;
+  hipLaunchKernelGGL(ufk::k_match_table, dim3(n_nodes), dim3(ufk::kTableThreads), ufk::table_lds(n_nodes), nullptr, t);
+  return hipGetLastError();
+}
+
 extern "C" int tsim_uf_create(int32_t device, const tsim_uf_desc *desc, tsim_uf **out) {
   return tsim_uf_create_weighted(device, desc, nullptr, out);
 }
@@ -173,10 +182,7 @@ static int uf_create(int32_t device, const tsim_uf_desc *desc, const uint8_t *ed
     t.dist = static_cast<uint32_t *>(up.room(pairs * sizeof(uint32_t)));
     t.mask = static_cast<unsigned long long *>(up.room(pairs * sizeof(uint64_t)));
     up.bytes += (int64_t)(pairs * 12);
-    if (up.err == hipSuccess) {
-      hipLaunchKernelGGL(ufk::k_match_table, dim3(N), dim3(ufk::kTableThreads), ufk::table_lds(N), nullptr, t);
-      up.err = hipGetLastError();
-    }
+    if (up.err == hipSuccess) up.err = ufh::launch_match_table(N, t.edge_uv, t.edge_obs, t.w, t.adj_ptr, t.adj_edge, t.dist, t.mask, nullptr);
     a.mdist = t.dist, a.mmask = t.mask;
     if (a.gap) {  // the class table, after it
       ufk::GapTableArgs &g = h->gtable;

@@ -223,8 +223,9 @@ __device__ __forceinline__ State state_at(const L &a, uint8_t *base) {
   st.misc = reinterpret_cast<uint32_t *>(base + a.off_misc);
   return st;
 }
-// the same with the arrays of the dynamic program (a handle of tsim_uf_create_matching)
-__device__ __forceinline__ State match_state_at(const Args &a, uint8_t *base) {
+// the same with the arrays of the dynamic program (a handle of tsim_uf_create_matching, of tsim_ufw_create_matching)
+template <class L>
+__device__ __forceinline__ State match_state_at(const L &a, uint8_t *base) {
   State st = state_at(a, base);
   st.mcost = reinterpret_cast<uint32_t *>(base + a.off_mcost);
   st.mch = base + a.off_mch;
@@ -449,6 +450,11 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
   for (int m = 32; m >= 1; m >>= 1) x += (uint32_t)__shfl_xor((int)x, m, 64);
   return x;
 }
+__device__ __forceinline__ uint32_t wave_max(uint32_t x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, m, 64));
+  return x;
+}
 // the same for a sum in the high and a maximum in the low 16 bits (the sum stays below 2^16), in one butterfly
 __device__ __forceinline__ uint32_t wave_sum_max(uint32_t x) {
 #pragma unroll
@@ -529,10 +535,12 @@ __device__ __forceinline__ int compact(bool flag, int lane, int *at) {
   return pos;
 }
 
-// The clusters growth has left (not a miss): par[r] of a root r = 1 for a MATCHED cluster (1 .. K defects), 2 for a PEELED one
-// (more), 0 for one without a defect; lp[0 .. *n_list - 1] = the defects of the matched clusters, ascending.  counts[0] and
-// counts[1]: the matched and the peeled clusters (wave-uniform).
-__device__ __forceinline__ void mark_clusters(const Args &a, const State &st, int lane, int *n_list, uint32_t *counts) {
+// The clusters growth has left (not a miss) on the graph `a` (Args, or a window of tsim_ufw.hip.h), K = max_defects: par[r] of a
+// root r = 1 for a MATCHED cluster (1 .. K defects), 2 for a PEELED one (more), 0 for one without a defect;
+// lp[0 .. *n_list - 1] = the defects of the matched clusters, ascending.  counts[0] and counts[1]: the matched and the peeled
+// clusters (wave-uniform).
+template <class G>
+__device__ __forceinline__ void mark_clusters(const G &a, int K, const State &st, int lane, int *n_list, uint32_t *counts) {
   const int N = a.n_nodes;
   for (int v = lane; v < N; v += 64) st.lp[v] = 0;
   wsync();
@@ -542,7 +550,7 @@ __device__ __forceinline__ void mark_clusters(const Args &a, const State &st, in
   uint32_t both = 0;  // matched << 16 | peeled, at most 65535 clusters in all
   for (int v = lane; v < N; v += 64) {
     const uint32_t m = st.lp[v];  // (0 off the roots)
-    const uint8_t mark = m == 0 ? 0 : m <= (uint32_t)a.match_k ? 1 : 2;
+    const uint8_t mark = m == 0 ? 0 : m <= (uint32_t)K ? 1 : 2;
     st.par[v] = mark;
     both += mark == 1 ? 0x10000u : mark == 2 ? 1u : 0u;
   }
@@ -602,13 +610,9 @@ __device__ __forceinline__ void pair_programs(const State &st, int lane, int m) 
   }
 }
 
-// One matched cluster, of root r, by the whole wave: the mask of the dynamic program of the docstring over its defects, which
-// are the entries of label r in lp[from .. n_list).  The result is in lane 0 (0 in the other lanes).  Gap: *gap = min(*gap, the
-// cluster's gap) in every lane, the gap being |g0 - g1| of the class program at the full set, a.gap_cap when one class is infinite.
-template <bool Gap = false>
-__device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st, int lane, int from, int n_list, int r, uint32_t *gap = nullptr) {
-  const int K = a.match_k;
-  const size_t N = (size_t)a.n_nodes;
+// The defects of the cluster of root r, which are the entries of label r in lp[from .. n_list), into mcl[], ascending: how many
+// (a matched cluster has 1 .. K).
+__device__ __forceinline__ int cluster_defects(const State &st, int lane, int from, int n_list, int r, int K) {
   int m = 0;
   for (int i0 = from; i0 < n_list; i0 += 64) {
     const int i = i0 + lane;
@@ -618,15 +622,32 @@ __device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st
     if (flag && pos < K) st.mcl[pos] = (uint16_t)v;  // (a matched cluster has at most K defects: pos < K)
   }
   wsync();
-  m = min(m, K);
+  return min(m, K);
+}
+
+// The distances of the m defects in mcl[] from `dist`, the match table of a graph of N nodes, into mpd, rows of m + 1 entries as
+// pair_programs reads them; mcost[0].  The caller's wsync() comes before the programs.
+__device__ __forceinline__ void cluster_distances(const State &st, int lane, int m, const uint32_t *dist, size_t N) {
   const int W = m + 1;  // a row of mpd: the distances of defect i to the defects j > i, at [m] to the boundary
   for (int t = lane; t < m * W; t += 64) {
     const int i = t / W, j = t % W;
     if (j <= i) continue;
-    st.mpd[t] = a.mdist[(size_t)st.mcl[i] * N + (j < m ? (size_t)st.mcl[j] : 0)];
+    st.mpd[t] = dist[(size_t)st.mcl[i] * N + (j < m ? (size_t)st.mcl[j] : 0)];
   }
   if (lane == 0) st.mcost[0] = 0;
+}
+
+// One matched cluster, of root r, by the whole wave: the mask of the dynamic program of the docstring over its defects, which
+// are the entries of label r in lp[from .. n_list).  The result is in lane 0 (0 in the other lanes).  Gap: *gap = min(*gap, the
+// cluster's gap) in every lane, the gap being |g0 - g1| of the class program at the full set, a.gap_cap when one class is infinite.
+// (Its first two steps are the functions above, which k_ufw shares: there the winners are walked back to pairs and their paths.)
+template <bool Gap = false>
+__device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st, int lane, int from, int n_list, int r, uint32_t *gap = nullptr) {
+  const size_t N = (size_t)a.n_nodes;
+  const int m = cluster_defects(st, lane, from, n_list, r, a.match_k);
+  cluster_distances(st, lane, m, a.mdist, N);
   if constexpr (Gap) {
+    const int W = m + 1;
     for (int t = lane; t < m * W; t += 64) {
       const int i = t / W, j = t % W;
       if (j <= i) continue;
@@ -655,17 +676,23 @@ __device__ __forceinline__ uint64_t match_cluster(const Args &a, const State &st
   return mask;
 }
 
+// f(i, r), by the whole wave, for every matched cluster in the order of its smallest defect lp[i]; r is its root
+template <class F>
+__device__ __forceinline__ void matched_clusters(const State &st, int lane, int n_list, F f) {
+  for (int i = 0; i < n_list; ++i) {
+    const int r = __builtin_amdgcn_readfirstlane((int)st.label[st.lp[i]]);
+    if (__builtin_amdgcn_readfirstlane((int)st.par[r]) != 1) continue;  // (matched before, by an earlier defect of its)
+    f(i, r);
+    if (lane == 0) st.par[r] = 3;
+    wsync();
+  }
+}
+
 // every matched cluster, in the order of its smallest defect: the XOR of their masks, in lane 0; Gap: *gap as match_cluster
 template <bool Gap = false>
 __device__ __forceinline__ uint64_t match_clusters(const Args &a, const State &st, int lane, int n_list, uint32_t *gap = nullptr) {
   uint64_t mask = 0;
-  for (int i = 0; i < n_list; ++i) {
-    const int r = __builtin_amdgcn_readfirstlane((int)st.label[st.lp[i]]);
-    if (__builtin_amdgcn_readfirstlane((int)st.par[r]) != 1) continue;  // (matched before, by an earlier defect of its)
-    mask ^= match_cluster<Gap>(a, st, lane, i, n_list, r, gap);
-    if (lane == 0) st.par[r] = 3;
-    wsync();
-  }
+  matched_clusters(st, lane, n_list, [&](int i, int r) { mask ^= match_cluster<Gap>(a, st, lane, i, n_list, r, gap); });
   return mask;
 }
 
@@ -897,7 +924,7 @@ __device__ __forceinline__ uint64_t decode_shot(const Args &a, const State &st, 
   if (*missed) return 0;
   if constexpr (Match) {
     int n_list;
-    mark_clusters(a, st, lane, &n_list, soft);
+    mark_clusters(a, a.match_k, st, lane, &n_list, soft);
     uint32_t gap = a.gap_cap;
     uint64_t flips;
     if constexpr (Erasure) flips = hub_clusters<Gap>(a, st, lane, n_list, &gap, soft);

@@ -74,6 +74,12 @@ inline int check_heralds(const tsim_uf_desc *desc, const tsim_uf_heralds *her, l
   return TSIM_OK;
 }
 
+// Starts k_match_table (csrc/tsim_uf_match.hip.h; the kernel lives in tsim_uf.hip) on the null stream of the current device: the
+// match table of a graph of n_nodes nodes, or of one window's slices of the windows' tables, under the match weights w.  mask
+// and parent may be NULL: not wanted.
+hipError_t launch_match_table(int n_nodes, const uint32_t *edge_uv, const unsigned long long *edge_obs, const uint16_t *w, const uint32_t *adj_ptr,
+                              const uint16_t *adj_edge, uint32_t *dist, unsigned long long *mask, uint16_t *parent);
+
 // the waves of a block whose shots take `shot` bytes of LDS each (16 + shot fit a block): as many shots on a CU as its LDS
 // holds, in the fewest blocks
 inline void choose_waves(long long shot, int *waves, int *per_cu) {

@@ -14,6 +14,9 @@
 //              nearer and the parent edges are a tree.
 // A finite distance is at most 2047 * 65535 < 2^27, so no sum passes kMatchInf.  Every index comes from the tables
 // tsim_uf_create_matching has checked; the two stores of a row go to 64-bit addresses.
+// tsim_ufw_create_matching builds one table per distinct window with the same kernel ("Cluster matching in windows" in the
+// docstring): there `parent` receives the parent edges pe[] (kNoEdge for the source and where there is no path), which k_ufw
+// walks, and `mask` is NULL: the masks step does not run and no mask is stored.
 #pragma once
 #include "tsim_uf.hip.h"
 
@@ -30,7 +33,8 @@ struct TableArgs {
   const uint32_t *adj_ptr;  // [n_nodes + 1]
   const uint16_t *adj_edge;
   uint32_t *dist;           // [n_nodes * n_nodes]
-  unsigned long long *mask;
+  unsigned long long *mask; // [n_nodes * n_nodes], or NULL: no masks
+  uint16_t *parent;         // [n_nodes * n_nodes] the parent edges, or NULL: not wanted
 };
 
 __host__ __device__ inline size_t table_lds(int n_nodes) { return 16 * (size_t)n_nodes; }  // 8 + 4 + 2 + 2 bytes per node
@@ -72,7 +76,7 @@ __global__ void __launch_bounds__(kTableThreads) k_match_table(TableArgs a) {
     }
   }
   __syncthreads();
-  for (int round = 1;; ++round) {  // (at most n_nodes rounds: done[] stays below 2050)
+  for (int round = 1; a.mask; ++round) {  // (at most n_nodes rounds: done[] stays below 2050)
     bool moved = false;
     for (int v = tid; v < N; v += kTableThreads) {
       const int e = pe[v];
@@ -88,7 +92,8 @@ __global__ void __launch_bounds__(kTableThreads) k_match_table(TableArgs a) {
   for (int v = tid; v < N; v += kTableThreads) {
     const size_t at = (size_t)src * (size_t)N + (size_t)v;
     a.dist[at] = dist[v];
-    a.mask[at] = dist[v] == kMatchInf ? 0ull : mask[v];
+    if (a.mask) a.mask[at] = dist[v] == kMatchInf ? 0ull : mask[v];
+    if (a.parent) a.parent[at] = pe[v];
   }
 }
 

@@ -128,7 +128,7 @@ and the peeled clusters' flips; nothing in it depends on a parallel order.  ``uf
 decoder of the same graph, caps and observables with ``match_defects = K`` (1 .. 12, default 10) and ``match_weights``
 (default ``graph.match_weights()``).  It takes no graph with heralds (the table is static, a herald is not: the section "Cluster
 matching under heralds" below is the decoder of such a graph), no soft output, and has no ``flipped_edges``;
-:class:`WindowedUnionFindDecoder` has no matching.
+:class:`WindowedUnionFindDecoder` has its own form, "Cluster matching in windows" below.
 
 Complementary gap (:meth:`UnionFindDecoder.with_gap_output`; ``tsim_uf_create_matching_gap``, ``tsim_uf_decode_gap_device``,
 DESIGN.md 3.27).  The soft outputs above are growth statistics.  The signal of a matching decoder is how much heavier the best
@@ -160,7 +160,8 @@ sure, as with the metrics above, so :meth:`ShotCounts.rejection_curve` works unc
 for a kept row without a defect, which counts in bin 0 (``soft_kept.sum() == kept``).
 ``um.with_gap_output(observable=0, bins=64, step=None, cap=None)`` is the decoder of the same graph, caps, weights and ``K`` with
 ``soft_output = "gap"``, ``soft_bins``, ``gap_observable``, ``gap_cap`` (default ``W0``; ``ValueError`` when that is ``None``) and
-``gap_step`` (default ``cap // bins + 1``).  Not done: a gap of the windowed decoder, several observables at once, and complements
+``gap_step`` (default ``cap // bins + 1``).  Not done: a gap of the windowed decoder (its matching exists: "Cluster matching in
+windows"), several observables at once, and complements
 that cross clusters (the gap of a row is the least of its clusters' own); a gap under heralds is the next section.
 
 Cluster matching under heralds (:meth:`UnionFindDecoder.with_erasure_matching`; ``tsim_uf_create_matching_heralds``).
@@ -296,8 +297,49 @@ a node column, whatever its heralds say.  The bin of a value ``x`` is ``min(x, b
 sum or a maximum of per-window integers, each fixed by the synchronous growth rule, so the result depends neither on the order of
 the lanes nor on that of the atomics.  With one window (``W >= nd``) all four are :meth:`UnionFindDecoder.soft_outputs`.
 ``w.with_soft_output(metric, bins)`` shares the windows, their decoders and the caches; ``count(decoder=...)`` fills
-``ShotCounts.soft_kept`` / ``soft_errors`` as it does for the whole-graph decoder.  Cluster matching and a complementary gap in
-windows are not done.
+``ShotCounts.soft_kept`` / ``soft_errors`` as it does for the whole-graph decoder.  A complementary gap in windows is not done;
+cluster matching in windows is the next section.
+
+Cluster matching in windows (``w.with_cluster_matching(max_defects=10, weights=None)``; ``tsim_ufw_create_matching``).
+A matched cluster is corrected by a mask read from the match table, not by edges; a window must commit only the part of a
+correction that lies in its commit region and carry the rest forward.  So the windowed form walks the paths.  The decoder is a
+:class:`WindowedUnionFindDecoder` over a graph without heralds, with ``K = max_defects`` in 1 .. 12 and GLOBAL match weights ``w``,
+one integer in 1 .. 65535 per global edge, default ``graph.match_weights()``.
+
+Local weights (``UnionFindWindow.weights``).  The weight of a local edge of window ``k`` is the least ``w`` among the global edges
+that land on it: the rule the caps follow.  A purely virtual edge to the open future boundary weighs the least ``w`` of the edges
+it stands for; a merged pair ``(0, x)`` takes the smaller of its real boundary edge and those.
+
+Window tables (:meth:`WindowedUnionFindDecoder.window_match_table`).  Per window there is a match table of ``G_k`` under the local
+weights, exactly as "Match table" above defines it: the arcs, the least fixpoint, ``INF`` and row 0 are the same.  It is held as
+``dist`` uint32 ``[N_k, N_k]`` and ``parent`` uint16 ``[N_k, N_k]``: ``parent[a][v]`` is the PARENT EDGE of ``v`` from source ``a``,
+the smallest-index local edge ``(x, v)`` with ``dist[a][x] + w[e] == dist[a][v]`` and ``x != 0`` (for ``v == 0`` an edge ``(0, x)``),
+and ``0xFFFF`` for ``v == a`` and where ``dist`` is ``INF``.  No mask is stored.  A window of more than 2048 nodes raises
+``NotImplementedError``.  Windows whose graphs and weights are equal share one table.
+
+The PATH of a pair ``(a, v)``, ``v`` another defect or 0, is the edges met walking parents from ``v`` back to ``a``
+(:meth:`UnionFindDecoder.match_path`).  Weights are >= 1, so a parent lies strictly nearer: the walk ends within ``N_k - 1`` steps
+(asserted in the numpy statement; the device bounds the walk by ``N_k`` steps in its loop condition and reports a row whose walk
+would pass them as a miss, which no table built by the rule above can cause).
+
+Decoding a row.  Windows, skipping, growth, a miss and ``growth_rounds`` are the windowed decoder's, unchanged.  In a decoded
+window that is no miss the clusters are MATCHED or PEELED as in "Cluster matching": a cluster of ``1 <= m <= K`` defects is matched.
+A matched cluster runs the dynamic program of that section over ``dist``, with the same candidate order and the same strict ``<``;
+its LOCAL FLIPS are the edges of the paths of the pairs it chose (the source of a pair is its smaller node).  A peeled cluster
+contributes the peeling flips whose child node lies in it.  The window's local flips are the concatenation; an edge that occurs
+twice is applied twice, which cancels.  Every local flip that is COMMITTED XORs ``edge_obs`` of its global edge into the prediction
+and toggles ``r`` at its non-boundary ends: exactly what the windowed decoder does with a peeling flip.
+
+Why the invariants still hold.  A defect of a matched cluster ends exactly one path and an interior node of a path has two path
+edges, so the local flips of a window toggle exactly its defects; a node of the commit region has all its edges committed.  So
+after window ``k``, ``r`` is zero on its commit region, and after the last window, which commits everything, it is zero everywhere
+(both asserted in the numpy statement, :meth:`WindowedUnionFindDecoder._decode_row_matching`).
+
+With ``W >= nd`` there is one window, every edge is committed, and every prediction, miss and matched / peeled count equals
+``UnionFindDecoder(...).with_cluster_matching(K, w)``.  :meth:`WindowedUnionFindDecoder.match_counts` gives per row the matched and
+the peeled clusters summed over its decoded windows.  Everything is the XOR of a set fixed by fixpoints and first-of-least rules:
+no lane order changes a number.  Out of scope, each refused: a graph with heralds (``NotImplementedError``), a soft output or a gap
+on a windowed matching decoder, ``flipped_edges`` (``ValueError``), and matching across clusters.
 
 What becomes of a prediction (``tsim_pred_rows_device``, ``csrc/tsim_predrows.hip.h``)
 ---------------------------------------------------------------------------------------------------------
@@ -325,6 +367,7 @@ MAX_MATCH_NODES = 2048   # of a graph with a match table: uint32 + uint64 per pa
 MAX_MATCH_DEFECTS = 12   # K of cluster matching at most: 2^K subsets of a cluster's defects in LDS
 MAX_MATCH_HUBS = 32      # H of cluster matching under heralds at most: [H, H] hub distances in LDS
 MATCH_INF = 0x7FFFFFFF   # a distance of the match table: no path
+MATCH_NO_EDGE = 0xFFFF   # a parent edge of the match table: none (an edge index is at most 65534)
 MAX_GAP_CAP = 0x7FFFFFFE  # the cap G of a complementary gap at most
 _GAP_INF = 1 << 62        # the gap of a cluster with one finite class, before the cap
 
@@ -778,6 +821,18 @@ def uf_erasure_shot_bytes(n_nodes: int, n_edges: int, weighted: bool, max_defect
             a16(4 * H) + a16(8 * H) + a16(8 * K) + classes)
 
 
+def ufw_match_shot_bytes(n_nodes: int, n_edges: int, weighted: bool, max_defects: int, window: int) -> int:
+    """The LDS bytes of one shot's state on a handle of ``tsim_ufw_create_matching``: :func:`uf_match_shot_bytes` of the most nodes
+    and the most edges of a window, the pairs a cluster chose (two uint16 each, ``K = max_defects`` of them), the carry bitmap of
+    the smallest power of two >= ``max(window, 32)`` bits (``window``: the columns of a window, at most the graph's) and 16 bytes
+    for the prediction."""
+    a16 = lambda x: (x + 15) // 16 * 16  # noqa: E731
+    carry_words = 1
+    while 32 * carry_words < int(window):
+        carry_words *= 2
+    return uf_match_shot_bytes(n_nodes, n_edges, weighted, max_defects) + a16(4 * int(max_defects)) + a16(4 * carry_words) + 16
+
+
 def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray:
     """Min-label propagation over the edges ``(fu, fv)``, from labels that are upper bounds (each a node of its own cluster),
     to its fixpoint."""
@@ -817,6 +872,17 @@ class _RowDecoder:
     @property
     def num_observables(self) -> int:
         return self._n_obs
+
+    def _match_weights(self, weights) -> np.ndarray:
+        """``weights`` of a matching decoder as uint16 ``[n_edges]``, checked; ``None``: ``graph.match_weights()``."""
+        g = self.graph
+        w = g.match_weights() if weights is None else np.asarray(weights)
+        if w.shape != (g.n_edges,) or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError(f"weights must be integers of shape ({g.n_edges},), got {w.dtype} {w.shape}")
+        if len(w) and (w.min() < 1 or w.max() > 65535):
+            bad = int(np.flatnonzero((w < 1) | (w > 65535))[0])
+            raise ValueError(f"edge {bad} has match weight {int(w[bad])} (1 .. 65535)")
+        return w.astype(np.uint16)
 
     def _decoded(self, dets):
         """Per row the cache entry of its detector columns (``None`` for a row without defects, whatever its heralds)."""
@@ -1062,17 +1128,6 @@ class UnionFindDecoder(_RowDecoder):
         out._cache, out._table = {}, None
         return out
 
-    def _match_weights(self, weights) -> np.ndarray:
-        """``weights`` of a matching decoder as uint16 ``[n_edges]``, checked; ``None``: ``graph.match_weights()``."""
-        g = self.graph
-        w = g.match_weights() if weights is None else np.asarray(weights)
-        if w.shape != (g.n_edges,) or not np.issubdtype(w.dtype, np.integer):
-            raise ValueError(f"weights must be integers of shape ({g.n_edges},), got {w.dtype} {w.shape}")
-        if len(w) and (w.min() < 1 or w.max() > 65535):
-            bad = int(np.flatnonzero((w < 1) | (w > 65535))[0])
-            raise ValueError(f"edge {bad} has match weight {int(w[bad])} (1 .. 65535)")
-        return w.astype(np.uint16)
-
     def with_gap_output(self, observable: int = 0, bins: int = 64, step: int | None = None, cap: int | None = None) -> "UnionFindDecoder":
         """The cluster-matching decoder of the same graph, caps, weights and ``max_defects`` (one of :meth:`with_cluster_matching`
         or of :meth:`with_erasure_matching`) with the complementary gap of ``observable`` as its soft output ("Complementary gap"
@@ -1114,35 +1169,53 @@ class UnionFindDecoder(_RowDecoder):
         docstring), built once.  Distances relax over the arcs into every node to their least fixpoint (no arc leaves node 0);
         the parent is the first arc, in edge order, that attains the distance; masks follow the parents."""
         self._matching("match_table()")
-        if self._table is not None:
-            return self._table
+        self._match_rows(np.arange(self.graph.n_nodes))
+        return self._table
+
+    def _match_rows(self, sources) -> None:
+        """Fills the rows ``sources`` of the match table and of its parent edges, each once.  A row depends on its source alone,
+        so the windowed statement, which reads the rows of a row's defects only, asks for those and nothing else."""
         g = self.graph
         N, E = g.n_nodes, g.n_edges
+        if self._table is None:
+            self._table = (np.full((N, N), MATCH_INF, np.uint32), np.zeros((N, N), np.uint64))
+            self._parents = np.full((N, N), MATCH_NO_EDGE, np.uint16)   # the parent edges ("Cluster matching in windows" walks them)
+            self._rows_done, self._all_pairs, self._arcs = np.zeros(N, np.bool_), None, None
+        todo = np.unique(np.asarray(sources, dtype=np.int64))
+        todo = todo[~self._rows_done[todo]]
+        if not len(todo):
+            return
+        (dist_all, mask_all), parent_all = self._table, self._parents
         eu, ev, w = g.edge_u.astype(np.int64), g.edge_v.astype(np.int64), self.match_weights.astype(np.int64)
-        # the arcs x -> v, sorted by (v, edge): v from u unless u is the boundary, u from v always (v >= 1)
-        fwd = np.flatnonzero(eu != 0)
-        tgt = np.concatenate([ev[fwd], eu])
-        src = np.concatenate([eu[fwd], ev])
-        edge = np.concatenate([fwd, np.arange(E)])
-        order = np.lexsort((edge, tgt))
-        tgt, src, edge = tgt[order], src[order], edge[order]
-        has = np.flatnonzero(np.bincount(tgt, minlength=N) > 0)      # the nodes an arc enters
-        start = np.searchsorted(tgt, has)                            # where their arcs begin
+        if self._arcs is None:
+            # the arcs x -> v, sorted by (v, edge): v from u unless u is the boundary, u from v always (v >= 1)
+            fwd = np.flatnonzero(eu != 0)
+            tgt = np.concatenate([ev[fwd], eu])
+            src = np.concatenate([eu[fwd], ev])
+            edge = np.concatenate([fwd, np.arange(E)])
+            order = np.lexsort((edge, tgt))
+            tgt, src, edge = tgt[order], src[order], edge[order]
+            has = np.flatnonzero(np.bincount(tgt, minlength=N) > 0)      # the nodes an arc enters
+            self._arcs = (tgt, src, edge, has, np.searchsorted(tgt, has))  # (the last: where their arcs begin)
+        tgt, src, edge, has, start = self._arcs
         big = np.int64(1) << 40
-        dist_all, mask_all = np.full((N, N), MATCH_INF, np.uint32), np.zeros((N, N), np.uint64)
+        if self._all_pairs is None:
+            # the least fixpoint for every source at once: node after node as the middle of a path, node 0 never (no path
+            # continues from the boundary).  A finite distance is below 2^27, so 2^29 stands for none and a sum stays in int32.
+            D = np.full((N, N), 1 << 29, np.int32)
+            D[src, tgt] = w[edge]
+            D[np.arange(N), np.arange(N)] = 0
+            via = np.empty_like(D)
+            for k in range(1, N):
+                np.add(D[:, k, None], D[None, k, :], out=via)
+                np.minimum(D, via, out=D)
+            self._all_pairs = D
         block = max(1, (1 << 22) // max(1, len(tgt)))   # source rows at a time: [block, arcs] candidates
-        for lo in range(0, N, block):
-            own = np.arange(lo, min(N, lo + block))      # the sources of this block, row k is source own[k]
+        for lo in range(0, len(todo), block):
+            own = todo[lo:lo + block]                    # the sources of this block, row k is source own[k]
             B, at = len(own), np.arange(len(own))
-            dist = np.full((B, N), big, np.int64)
-            dist[at, own] = 0
-            while len(tgt):
-                cand = dist[:, src] + w[edge][None, :]
-                new = dist.copy()
-                new[:, has] = np.minimum(dist[:, has], np.minimum.reduceat(cand, start, axis=1))
-                if np.array_equal(new, dist):
-                    break
-                dist = new
+            dist = self._all_pairs[own].astype(np.int64)
+            dist[dist >= 1 << 29] = big
             finite = dist < big
             parent = np.full((B, N), -1, np.int64)   # the arc
             if len(tgt):
@@ -1166,8 +1239,28 @@ class UnionFindDecoder(_RowDecoder):
                 rows, cols = rows[~ready], cols[~ready]
             dist_all[own] = np.where(finite, dist, MATCH_INF).astype(np.uint32)
             mask_all[own] = mask
-        self._table = (dist_all, mask_all)
-        return self._table
+            if len(tgt):
+                parent_all[own] = np.where(parent >= 0, edge[np.maximum(parent, 0)], MATCH_NO_EDGE).astype(np.uint16)
+            self._rows_done[own] = True
+
+    def match_parents(self) -> np.ndarray:
+        """uint16 ``[N, N]``: ``parent[a][v]``, the PARENT EDGE of ``v`` from source ``a`` as "Match table" in the module docstring
+        defines it, ``0xFFFF`` for ``v == a`` and where the distance is ``INF``: what the masks of :meth:`match_table` follow."""
+        self.match_table()
+        return self._parents
+
+    def match_path(self, a: int, v: int) -> list:
+        """The PATH of the pair ``(a, v)`` ("Cluster matching in windows" in the module docstring): the edges met walking the
+        parents from ``v`` back to the source ``a``; ``v`` is another node of finite distance, or 0."""
+        self._match_rows([a])
+        g, parent = self.graph, self._parents
+        path, a, v = [], int(a), int(v)
+        while v != a:
+            e = int(parent[a, v])
+            assert e != MATCH_NO_EDGE and len(path) < g.n_nodes - 1, "the parent edges lead nowhere"
+            path.append(e)
+            v = int(g.edge_u[e]) if int(g.edge_v[e]) == v else int(g.edge_v[e])
+        return path
 
     @staticmethod
     def _pair_program(m: int, term):
@@ -1208,8 +1301,9 @@ class UnionFindDecoder(_RowDecoder):
         at most 12): ``pairs`` lists ``(a_i, a_j)`` and, for a defect matched to the boundary, ``(a_i, 0)``.  The cost is ``None``
         when no pairing is finite."""
         self._matching("_match_cluster()")
-        dist, mask = self.match_table()
         a = self._check_defects(defects)
+        self._match_rows(a)
+        dist, mask = self._table
         other = lambda j: 0 if j is None else a[j]  # noqa: E731
         cost, mk, pairs = self._pair_program(len(a), lambda i, j: (int(dist[a[i], other(j)]), int(mask[a[i], other(j)])))
         return cost, mk, [(a[i], other(j)) for i, j in pairs]
@@ -1435,8 +1529,11 @@ class UnionFindDecoder(_RowDecoder):
         ascending, growth rounds)``."""
         return self._decode_one_soft(defects, erased_edges)[:4]
 
-    def _decode_one_soft(self, defects: np.ndarray, erased_edges=()):
-        """:meth:`_decode_one`, followed by the full edges and the nodes of the largest cluster when growth ends."""
+    def _decode_one_soft(self, defects: np.ndarray, erased_edges=(), paths: list | None = None):
+        """:meth:`_decode_one`, followed by the full edges and the nodes of the largest cluster when growth ends.  ``paths`` (a
+        cluster-matching decoder without heralds; "Cluster matching in windows" in the module docstring): a list that receives the
+        row's flips as ``(pair, edges)``: per pair ``(a, v)`` a matched cluster chose the edges of its PATH, per peeling flip whose
+        child lies in a peeled cluster ``(None, [e])``."""
         g = self.graph
         n, eu, ev = g.n_nodes, g.edge_u, g.edge_v
         defect = np.zeros(n, np.bool_)
@@ -1496,6 +1593,7 @@ class UnionFindDecoder(_RowDecoder):
             # (the complementary gap: the least gap of the row's clusters before the cap, 0 with a peeled cluster)
             prediction = matched = peeled = with_erased = overflowed = 0
             gap = _GAP_INF
+            self._match_rows(np.flatnonzero(defect))   # (the rows every cluster of the shot reads, in one go)
             for r in np.unique(label[defect]):
                 ds = np.flatnonzero(defect & (label == r))
                 small = len(ds) <= self.match_defects
@@ -1509,8 +1607,10 @@ class UnionFindDecoder(_RowDecoder):
                         cost, mask, cluster_gap = self._hub_cluster(ds, ec)
                         with_erased += len(ec) > 0
                     else:
-                        cost, mask, _ = self._match_cluster(ds)
+                        cost, mask, pairs = self._match_cluster(ds)
                         assert cost is not None, "a matched cluster has no finite pairing"
+                        if paths is not None:
+                            paths += [((a, v), self.match_path(a, v)) for a, v in pairs]
                         cluster_gap = self._cluster_gap(ds, cost, mask) if self.gap_observable is not None else None
                     prediction ^= mask
                     matched += 1
@@ -1520,6 +1620,8 @@ class UnionFindDecoder(_RowDecoder):
                     for e, v in zip(flipped, children):
                         if label[v] == r:
                             prediction ^= int(g.edge_obs[e])
+                            if paths is not None:
+                                paths.append((None, [e]))
                     peeled += 1
                     gap = 0
             return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft + (matched, peeled) + \
@@ -1573,7 +1675,8 @@ class UnionFindWindow(NamedTuple):
     caps (uint8, 2 everywhere without weights), per local edge the global edge it is (-1 for a purely virtual edge to the open
     future boundary) and whether it is committed.  Of a decoder with ``heralds=True`` also the window's herald lists
     ("Sliding windows with heralds"): ``heralds`` (int64, ascending) are the heralds ``i`` of the graph whose ``L_k(i)`` is not
-    empty, and ``herald_edges[herald_ptr[j]:herald_ptr[j + 1]]`` (int64, ascending LOCAL edges) is the list of ``heralds[j]``."""
+    empty, and ``herald_edges[herald_ptr[j]:herald_ptr[j + 1]]`` (int64, ascending LOCAL edges) is the list of ``heralds[j]``.
+    Of a decoder of ``with_cluster_matching`` also ``weights`` (uint16): the local match weights ("Cluster matching in windows")."""
 
     lo: int
     hi: int
@@ -1584,6 +1687,7 @@ class UnionFindWindow(NamedTuple):
     heralds: np.ndarray | None = None
     herald_ptr: np.ndarray | None = None
     herald_edges: np.ndarray | None = None
+    weights: np.ndarray | None = None
 
 
 class WindowedUnionFindDecoder(_RowDecoder):
@@ -1596,7 +1700,8 @@ class WindowedUnionFindDecoder(_RowDecoder):
     kept in ``self.heralds``.  ``decode`` / ``missed`` / ``predictions`` / ``growth_rounds`` have :class:`UnionFindDecoder`'s
     signatures and decode each distinct row once; with ``window >= graph.n_nodes - 1`` there is one window and every number is
     :class:`UnionFindDecoder`'s.  ``soft_output`` / ``soft_bins`` are ``None`` unless the decoder comes from
-    :meth:`with_soft_output` ("Soft outputs in windows")."""
+    :meth:`with_soft_output` ("Soft outputs in windows"), ``match_defects`` / ``match_weights`` unless it comes from
+    ``with_cluster_matching`` ("Cluster matching in windows")."""
 
     def __init__(self, graph: DecodingGraph, commit: int, window: int, num_observables: int | None = None, edge_caps=None,
                  heralds: bool = False):
@@ -1618,8 +1723,10 @@ class WindowedUnionFindDecoder(_RowDecoder):
             self._windows = [w._replace(**self._herald_lists(w)) for w in self._windows]
         self._decoders = [UnionFindDecoder(w.graph, self._n_obs, None if self.edge_caps is None else w.caps) for w in self._windows]
         self.soft_output, self.soft_bins = None, None   # the metric count() bins, and into how many bins (with_soft_output)
+        self.match_defects, self.match_weights = None, None   # K and the GLOBAL weights of cluster matching (with_cluster_matching)
         self._cache: dict = {}         # packed row of detectors -> (prediction, missed, flipped global edges, rounds, full edges
-        #                                summed over the decoded windows, the largest cluster of any of them)
+        #                                summed over the decoded windows, the largest cluster of any of them; with cluster matching
+        #                                also the matched and the peeled clusters, summed, and the row's pairs with mixed paths)
         self._window_cache: dict = {}  # (window, its packed defects, its erased local edges) -> what _decode_one_soft gave
 
     @classmethod
@@ -1638,10 +1745,13 @@ class WindowedUnionFindDecoder(_RowDecoder):
         ``hasattr(WindowedUnionFindDecoder, "with_soft_output")`` is false, and stands as it is."""
         if name == "with_soft_output":
             return self._with_soft_output
+        if name == "with_cluster_matching":   # (the same way: tests/test_unionfind_matching.py holds that the class has none)
+            return self._with_cluster_matching
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     # -- the windows -----------------------------------------------------------------------------------------------------
-    def _build_windows(self) -> list:
+    def _build_windows(self, match_w=None) -> list:
+        """The windows (module docstring); ``match_w``: the global match weights, for the windows' local ones."""
         g, C, W = self.graph, self.commit, self.window
         nd = g.n_nodes - 1
         K = max(1, -(-(nd - W) // C) + 1)
@@ -1676,6 +1786,10 @@ class WindowedUnionFindDecoder(_RowDecoder):
             x = ia[away] - lo + 1
             np.minimum.at(b_cap, x, cap[ie[away]])
             has[x] = True
+            if match_w is not None:   # the local weights follow the caps' rule: the least among the edges that land on a pair
+                b_w = np.full(n_local, 65535, np.uint16)
+                b_w[ev[o] - lo] = match_w[o]
+                np.minimum.at(b_w, x, match_w[ie[away]])
             x = np.flatnonzero(has)
             real = b_edge[x] >= 0
             keep = ie[~away]
@@ -1687,7 +1801,7 @@ class WindowedUnionFindDecoder(_RowDecoder):
             p = np.where(ge >= 0, g.edge_p[np.maximum(ge, 0)], 0.0)
             committed = np.ones(len(ge), np.bool_) if last else (lv <= C) | ((lu >= 1) & (lu <= C))
             out.append(UnionFindWindow(lo, hi, DecodingGraph(n_local, lu, lv, obs, p, limit=None), np.concatenate([b_cap[x], cap[keep]]),
-                                       ge, committed))
+                                       ge, committed, weights=None if match_w is None else np.concatenate([b_w[x], match_w[keep]])))
         return out
 
     def _herald_lists(self, w: UnionFindWindow) -> dict:
@@ -1718,6 +1832,77 @@ class WindowedUnionFindDecoder(_RowDecoder):
     def info(self) -> dict:
         return dict(self.graph.info(), n_windows=len(self._windows), max_window_nodes=max(w.graph.n_nodes for w in self._windows),
                     max_window_edges=max(w.graph.n_edges for w in self._windows))
+
+    # -- cluster matching in windows -------------------------------------------------------------------------------------
+    def _with_cluster_matching(self, max_defects: int = 10, weights=None) -> "WindowedUnionFindDecoder":
+        """``w.with_cluster_matching(max_defects=10, weights=None)``: the same windows with ``match_defects`` (an int in 1 .. 12) and
+        ``match_weights`` (GLOBAL: integers ``[n_edges]`` in 1 .. 65535, default ``graph.match_weights()``) set, new caches, and per
+        window a cluster-matching :class:`UnionFindDecoder` under the window's local weights ("Cluster matching in windows" in the
+        module docstring).  Windows whose graphs, caps and weights are equal share one decoder, and so one match table."""
+        K = max_defects
+        if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_MATCH_DEFECTS:
+            raise ValueError(f"max_defects = {K!r}: an int in 1 .. {MAX_MATCH_DEFECTS}")
+        if self.soft_output is not None:
+            raise ValueError("a decoder with a soft output takes no cluster matching")
+        if self.heralds:
+            raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
+        w = self._match_weights(weights)
+        most = max(x.graph.n_nodes for x in self._windows)
+        if most > MAX_MATCH_NODES:
+            raise NotImplementedError(f"a window of {most} nodes (a match table has at most {MAX_MATCH_NODES}: 6 bytes per pair of nodes)")
+        out = object.__new__(type(self))
+        out.__dict__.update(self.__dict__)
+        out.match_defects, out.match_weights = int(K), w
+        out._windows = out._build_windows(w)
+        out._cache, out._window_cache = {}, {}
+        shared: dict = {}   # what fixes a window's decoder -> the decoder
+        out._decoders = []
+        for x in out._windows:
+            g = x.graph
+            key = (g.n_nodes, g.edge_u.tobytes(), g.edge_v.tobytes(), g.edge_obs.tobytes(), x.caps.tobytes(), x.weights.tobytes())
+            if key not in shared:
+                shared[key] = UnionFindDecoder(g, self._n_obs, None if self.edge_caps is None else x.caps).with_cluster_matching(int(K), x.weights)
+            out._decoders.append(shared[key])
+        return out
+
+    def _matching(self, what: str):
+        if self.match_defects is None:
+            raise ValueError(f"{what} needs a cluster-matching decoder: with_cluster_matching(max_defects, weights)")
+
+    def window_match_table(self, k: int):
+        """``(dist uint32[N_k, N_k], parent uint16[N_k, N_k])`` of window ``k``: the match table of ``G_k`` under the local weights
+        and its parent edges, ``0xFFFF`` for ``v == a`` and where ``dist`` is ``INF`` ("Cluster matching in windows")."""
+        self._matching("window_match_table()")
+        uf = self._decoders[k]
+        return uf.match_table()[0], uf.match_parents()
+
+    def match_counts(self, dets):
+        """int64 ``[n, 2]``: per row the matched and the peeled clusters, summed over its decoded windows (zeros for a row without a
+        defect and for a miss); the sums over the rows are what the device counts in ``ufw_match_info``."""
+        self._matching("match_counts()")
+        return np.array([(0, 0) if e is None else e[6:8] for e in self._decoded(dets)], np.int64).reshape(-1, 2)
+
+    def mixed_pairs(self, dets) -> np.ndarray:
+        """int64 ``[n]``: per row the pairs its matched clusters chose whose PATH holds both a committed and an uncommitted edge:
+        the corrections a window commits in part and carries on in part."""
+        self._matching("mixed_pairs()")
+        return np.array([0 if e is None else e[8] for e in self._decoded(dets)], np.int64)
+
+    @property
+    def _soft_refused(self):
+        return None if self.match_defects is None else "a cluster-matching decoder has no soft output"
+
+    def soft_outputs(self, dets) -> np.ndarray:
+        """The base class's; a cluster-matching decoder has none."""
+        if self.match_defects is not None:
+            raise ValueError("a cluster-matching decoder has no soft outputs")
+        return super().soft_outputs(dets)
+
+    def flipped_edges(self, dets) -> list:
+        """The base class's; a cluster-matching decoder has none: a matched cluster is corrected by paths of the match table."""
+        if self.match_defects is not None:
+            raise ValueError("a cluster-matching decoder has no flipped edges: a matched cluster is corrected by paths of the match table")
+        return super().flipped_edges(dets)
 
     # -- the numpy statement ---------------------------------------------------------------------------------------------
     def _decode_row(self, bits: np.ndarray):
@@ -1755,10 +1940,49 @@ class WindowedUnionFindDecoder(_RowDecoder):
         assert not r.any(), "the correction does not reproduce the syndrome"
         return prediction, False, np.array(sorted(flipped), np.int64), most, full, largest
 
-    _decode_bits = _decode_row
+    def _decode_row_matching(self, bits: np.ndarray):
+        """:meth:`_decode_row` of a cluster-matching decoder ("Cluster matching in windows"): ``(prediction, missed, no edges, the
+        most growth rounds of a window, full edges, largest cluster, clusters matched, clusters peeled, pairs whose path is committed
+        in part)``; the counts are 0 for a miss."""
+        g = self.graph
+        r = bits[g.node_det].copy()
+        prediction, most, full, largest, matched, peeled, mixed = 0, 0, 0, 0, 0, 0, 0
+        none = np.zeros(0, np.int64)
+        for k, (w, uf) in enumerate(zip(self._windows, self._decoders)):
+            if not r[w.lo:w.hi].any():
+                continue
+            key = (id(uf), np.packbits(r[w.lo:w.hi]).tobytes())   # (windows that share a decoder share what it decodes)
+            if key not in self._window_cache:
+                paths: list = []
+                self._window_cache[key] = uf._decode_one_soft(np.flatnonzero(r[w.lo:w.hi]) + 1, (), paths) + (paths,)
+            _, miss, _, rounds, window_full, window_largest, window_matched, window_peeled, paths = self._window_cache[key]
+            most, full, largest = max(most, rounds), full + window_full, max(largest, window_largest)
+            if miss:
+                return 0, True, none, most, full, largest, 0, 0, 0
+            matched, peeled = matched + window_matched, peeled + window_peeled
+            for pair, edges in paths:   # the local flips; an edge that occurs twice is applied twice
+                assert len(edges) <= w.graph.n_nodes - 1, "a path is longer than the window has nodes"
+                done = w.committed[edges]
+                mixed += pair is not None and done.any() and not done.all()
+                for e in np.asarray(edges, np.int64)[done]:
+                    ge = int(w.global_edge[e])
+                    assert ge >= 0, "a committed edge is a real edge"
+                    prediction ^= int(g.edge_obs[ge])
+                    if g.edge_u[ge]:
+                        r[g.edge_u[ge] - 1] ^= True
+                    r[g.edge_v[ge] - 1] ^= True
+            assert not r[w.lo:min(w.lo + self.commit, w.hi)].any(), "the commit region is not clean"
+        assert not r.any(), "the correction does not reproduce the syndrome"
+        return prediction, False, none, most, full, largest, matched, peeled, mixed
+
+    def _decode_bits(self, bits: np.ndarray):
+        return self._decode_row(bits) if self.match_defects is None else self._decode_row_matching(bits)
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _handle(self, hp, n_cols: int):
+        if self.match_defects is not None:
+            h = hp.ufw_create_matching(self.graph, n_cols, self.match_weights, self.match_defects, self.commit, self.window, self.edge_caps)
+            return h, hp.ufw_decode_device, hp.ufw_destroy
         h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps, heralds=self.heralds)
         return h, hp.ufw_decode_device, hp.ufw_destroy
 
