@@ -333,7 +333,7 @@ and toggles ``r`` at its non-boundary ends: exactly what the windowed decoder do
 Why the invariants still hold.  A defect of a matched cluster ends exactly one path and an interior node of a path has two path
 edges, so the local flips of a window toggle exactly its defects; a node of the commit region has all its edges committed.  So
 after window ``k``, ``r`` is zero on its commit region, and after the last window, which commits everything, it is zero everywhere
-(both asserted in the numpy statement, :meth:`WindowedUnionFindDecoder._decode_row_matching`).
+(both asserted in the numpy statement, :meth:`WindowedUnionFindDecoder._decode_row`).
 
 With ``W >= nd`` there is one window, every edge is committed, and every prediction, miss and matched / peeled count equals
 ``UnionFindDecoder(...).with_cluster_matching(K, w)``.  :meth:`WindowedUnionFindDecoder.match_counts` gives per row the matched and
@@ -372,11 +372,29 @@ MAX_GAP_CAP = 0x7FFFFFFE  # the cap G of a complementary gap at most
 _GAP_INF = 1 << 62        # the gap of a cluster with one finite class, before the cap
 
 
+def _is_int(x) -> bool:
+    """An int of python or numpy, and no bool."""
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def _check_max_defects(K) -> int:
+    """``max_defects`` of every matching decoder, checked."""
+    if not _is_int(K) or not 1 <= K <= MAX_MATCH_DEFECTS:
+        raise ValueError(f"max_defects = {K!r}: an int in 1 .. {MAX_MATCH_DEFECTS}")
+    return int(K)
+
+
+def _check_match_nodes(n_nodes: int, what: str, pair_bytes: int) -> None:
+    """The most nodes of a match table; ``what`` names the graph that has ``n_nodes``, ``pair_bytes`` what the table holds per pair."""
+    if n_nodes > MAX_MATCH_NODES:
+        raise NotImplementedError(f"{what} (a match table has at most {MAX_MATCH_NODES}: {pair_bytes} bytes per pair of nodes)")
+
+
 def _graph_limit(limit) -> int:
     """The most nodes, and edges, of a :class:`DecodingGraph`: ``limit``, or int32 sizes for ``None``."""
     if limit is None:
         return 0x7FFFFFFF
-    if isinstance(limit, (bool, np.bool_)) or not isinstance(limit, (int, np.integer)) or not 2 <= limit <= 0x7FFFFFFF:
+    if not _is_int(limit) or not 2 <= limit <= 0x7FFFFFFF:
         raise ValueError(f"limit = {limit!r}: an int in 2 .. 2^31 - 1, or None")
     return int(limit)
 
@@ -665,7 +683,7 @@ class DecodingGraph:
     def growth_caps(self, resolution: int = 4) -> np.ndarray:
         """``uint8[n_edges]``: the caps of weighted growth from ``edge_p`` (module docstring), 1 .. ``2 * resolution``;
         ``resolution`` is an int in 1 .. 7."""
-        if isinstance(resolution, (bool, np.bool_)) or not isinstance(resolution, (int, np.integer)) or not 1 <= resolution <= MAX_CAP // 2:
+        if not _is_int(resolution) or not 1 <= resolution <= MAX_CAP // 2:
             raise ValueError(f"resolution = {resolution!r}: an int in 1 .. {MAX_CAP // 2}")
         top = 2 * int(resolution)
         if not self.n_edges:
@@ -679,7 +697,7 @@ class DecodingGraph:
     def match_weights(self, scale: int = 1000) -> np.ndarray:
         """``uint16[n_edges]``: the weights of cluster matching from ``edge_p`` (module docstring), 1 .. ``scale``; ``scale`` is
         an int in 1 .. 65535."""
-        if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, np.integer)) or not 1 <= scale <= 65535:
+        if not _is_int(scale) or not 1 <= scale <= 65535:
             raise ValueError(f"scale = {scale!r}: an int in 1 .. 65535")
         if not self.n_edges:
             return np.zeros(0, np.uint16)
@@ -846,11 +864,95 @@ def _components(label: np.ndarray, fu: np.ndarray, fv: np.ndarray) -> np.ndarray
     return label
 
 
+_NO_EDGES = np.zeros(0, np.int64)
+
+
+class _Decoded(NamedTuple):
+    """What a row, or one window of a row, decodes to: every entry of ``_cache`` and of ``_window_cache`` and what
+    :meth:`UnionFindDecoder._decode_one_soft` returns.  A field the decoder does not produce keeps its default; of a miss only
+    ``missed`` and the three growth numbers are set."""
+
+    prediction: int = 0                 # the observable mask; 0 for a miss
+    missed: bool = False
+    flipped: np.ndarray = _NO_EDGES     # the correction's edges, ascending; of the windowed decoder the committed global ones
+    rounds: int = 0                     # growth rounds; across windows the most
+    full_edges: int = 0                 # when growth ends; across windows the sum
+    largest_cluster: int = 0            # when growth ends; across windows the maximum
+    matched: int = 0                    # cluster matching: the clusters corrected by the dynamic program
+    peeled: int = 0                     # cluster matching: the clusters corrected by peeling
+    gap: int = 0                        # a decoder with the gap: the least gap of the row's clusters before the cap
+    with_erased: int = 0                # erasure matching: the matched clusters that had an erased edge
+    overflowed: int = 0                 # erasure matching: the clusters of at most K defects peeled for their hubs
+    mixed: int = 0                      # matching in windows: the pairs whose path is committed in part
+    paths: list | None = None           # matching for a window: the flips as (pair, edges), in the order they are applied
+
+
+def _grow(graph: "DecodingGraph", cap: np.ndarray, defect: np.ndarray, erased: np.ndarray):
+    """Step 1 of the rule, growth (``ufk::grow``; the edges ``erased`` start full, ``ufk::clear_edges``): ``(grown, label, rounds,
+    missed)`` when growth ends; ``label[v]`` is the root of the cluster of ``v`` under the full edges, its node of smallest index."""
+    n, eu, ev = graph.n_nodes, graph.edge_u, graph.edge_v
+    grown = np.zeros(graph.n_edges, np.int8)
+    grown[erased] = cap[erased]
+    label = np.arange(n)
+    rounds = 0
+    while True:
+        f = grown == cap
+        label = _components(label, eu[f], ev[f])
+        odd = (np.bincount(label[defect], minlength=n) & 1).astype(np.bool_)
+        odd[0] = False
+        active = odd[label]
+        if not active.any():
+            return grown, label, rounds, False
+        new = np.minimum(cap, grown + active[eu] + active[ev]).astype(np.int8)
+        if np.array_equal(new, grown):
+            return grown, label, rounds, True
+        grown, rounds = new, rounds + 1
+
+
+def _forest(graph: "DecodingGraph", fe: np.ndarray, label: np.ndarray):
+    """Step 2, the forest over the full edges ``fe`` (``ufk::forest``): ``(level, parent, depth)``; levels from the roots, the
+    parent edge the smallest-index edge to the level above (-1 for a root), ``depth`` the deepest level."""
+    n, fu, fv = graph.n_nodes, graph.edge_u[fe], graph.edge_v[fe]
+    level = np.where(label == np.arange(n), 0, -1)
+    parent = np.full(n, -1, np.int64)
+    depth = 0
+    while True:
+        down = (level[fu] == depth) & (level[fv] < 0)
+        up = (level[fv] == depth) & (level[fu] < 0)
+        child = np.concatenate([fv[down], fu[up]])
+        if not len(child):
+            return level, parent, depth
+        via = np.concatenate([fe[down], fe[up]])
+        parent[child] = graph.n_edges
+        np.minimum.at(parent, child, via)
+        level[child] = depth + 1
+        depth += 1
+
+
+def _peel(graph: "DecodingGraph", defect: np.ndarray, level: np.ndarray, parent: np.ndarray, depth: int):
+    """Step 3, peeling from the deepest level up (``ufk::peel``): ``(prediction, flipped edges, their child nodes)``, the edges in
+    the order they flip."""
+    eu, ev = graph.edge_u, graph.edge_v
+    s = defect.copy()
+    prediction, flipped, children = 0, [], []
+    for lv in range(depth, 0, -1):
+        for v in np.flatnonzero((level == lv) & s):
+            e = int(parent[v])
+            s[eu[e]] ^= True
+            s[ev[e]] ^= True
+            prediction ^= int(graph.edge_obs[e])
+            flipped.append(e)
+            children.append(int(v))
+    assert not s[1:].any(), "the correction does not reproduce the syndrome"
+    return prediction, flipped, children
+
+
 class _RowDecoder:
     """What :class:`UnionFindDecoder` and :class:`WindowedUnionFindDecoder` share: rows to cache entries, the entries' readers
-    the device calls and the soft output.  A subclass has ``graph``, ``_n_obs``, ``edge_caps``, ``_cache``, ``soft_output`` and
-    ``soft_bins``, decodes one row's detector bits in ``_decode_bits`` (a cache entry: prediction, missed, flipped edges, rounds,
-    full edges, largest cluster, ...), opens its handle in ``_handle`` and names the handle's soft call in ``_soft_call``."""
+    the device calls, the soft output and what a cluster-matching decoder refuses.  A subclass has ``graph``, ``_n_obs``,
+    ``edge_caps``, ``_cache``, ``soft_output``, ``soft_bins`` and ``match_defects``, decodes one row's detector bits in
+    ``_decode_bits`` (a cache entry, :class:`_Decoded`), opens its handle in ``_handle`` and names the handle's soft call in
+    ``_soft_call``."""
 
     @staticmethod
     def _of_circuit(circuit, weights, resolution, heralds, limit):
@@ -908,7 +1010,7 @@ class _RowDecoder:
     def predictions(self, dets) -> np.ndarray:
         """uint64 ``[n]``: the predicted observable mask of every row (bit ``k`` = observable ``k``; 0 for a miss) - what the
         device kernel writes to ``d_pred``."""
-        return np.array([0 if e is None else e[0] for e in self._decoded(dets)], dtype=np.uint64)
+        return np.array([0 if e is None else e.prediction for e in self._decoded(dets)], dtype=np.uint64)
 
     def decode(self, dets) -> np.ndarray:
         """bool ``[n, num_observables]``: the predicted observable flips of detector rows bool ``[n, num_detectors]``."""
@@ -918,19 +1020,34 @@ class _RowDecoder:
     def missed(self, dets) -> np.ndarray:
         """bool ``[n]``: the rows whose growth (in a window, of the windowed decoder) stopped with an active cluster left (no
         flip is predicted for them)."""
-        return np.array([e is not None and e[1] for e in self._decoded(dets)], dtype=np.bool_)
+        return np.array([e is not None and e.missed for e in self._decoded(dets)], dtype=np.bool_)
 
     def flipped_edges(self, dets) -> list:
         """Per row the edges of its correction, as edges of ``graph`` (int64, ascending; empty for a row without defects and
-        for a miss); of the windowed decoder the committed ones."""
-        return [np.zeros(0, np.int64) if e is None else e[2] for e in self._decoded(dets)]
+        for a miss); of the windowed decoder the committed ones.  A cluster-matching decoder has none: a matched cluster is
+        corrected by paths of the match table."""
+        if self.match_defects is not None:
+            raise ValueError("a cluster-matching decoder has no flipped edges: a matched cluster is corrected by paths of the match table")
+        return [np.zeros(0, np.int64) if e is None else e.flipped for e in self._decoded(dets)]
 
     def growth_rounds(self, dets) -> np.ndarray:
         """int64 ``[n]``: the growth rounds every row took (of the windowed decoder: the most of any of its windows)."""
-        return np.array([0 if e is None else e[3] for e in self._decoded(dets)], dtype=np.int64)
+        return np.array([0 if e is None else e.rounds for e in self._decoded(dets)], dtype=np.int64)
+
+    # -- cluster matching: what both classes check, and refuse -----------------------------------------------------------
+    def _matching(self, what: str):
+        if self.match_defects is None:
+            raise ValueError(f"{what} needs a cluster-matching decoder: with_cluster_matching(max_defects, weights)")
+
+    def _no_soft_output(self):
+        if self.soft_output is not None:
+            raise ValueError("a decoder with a soft output takes no cluster matching")
 
     # -- soft outputs ----------------------------------------------------------------------------------------------------
-    _soft_refused = None   # why the decoder takes no soft output (a cluster-matching one), else None
+    @property
+    def _soft_refused(self):
+        """Why the decoder takes no soft output (a cluster-matching one), else ``None``."""
+        return None if self.match_defects is None else "a cluster-matching decoder has no soft output"
 
     def _with_soft_output(self, metric: str, bins: int = 64):
         """``with_soft_output`` of both classes: the same decoder (graph, caps, observables and, of the windowed decoder, the
@@ -940,7 +1057,7 @@ class _RowDecoder:
         docstring)."""
         if metric not in SOFT_OUTPUTS:
             raise ValueError(f"metric = {metric!r}: one of {', '.join(SOFT_OUTPUTS)}")
-        if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= MAX_SOFT_BINS:
+        if not _is_int(bins) or not 2 <= bins <= MAX_SOFT_BINS:
             raise ValueError(f"bins = {bins!r}: an int in 2 .. {MAX_SOFT_BINS}")
         if self._soft_refused is not None:
             raise ValueError(self._soft_refused)
@@ -951,11 +1068,14 @@ class _RowDecoder:
 
     def soft_outputs(self, dets) -> np.ndarray:
         """int64 ``[n, 4]``: per row ``rounds``, ``full_edges``, ``largest_cluster`` and ``correction_weight`` ("Soft outputs" in
-        the module docstring; of the windowed decoder "Soft outputs in windows"); a row without defects is all zero."""
+        the module docstring; of the windowed decoder "Soft outputs in windows"); a row without defects is all zero.  A
+        cluster-matching decoder has none."""
+        if self.match_defects is not None:
+            raise ValueError("a cluster-matching decoder has no soft outputs")
         out = np.zeros((len(np.asarray(dets)), 4), dtype=np.int64)
         for r, e in enumerate(self._decoded(dets)):
             if e is not None:
-                out[r] = e[3], e[4], e[5], len(e[2])
+                out[r] = e.rounds, e.full_edges, e.largest_cluster, len(e.flipped)
         return out
 
     def _soft_values(self, dets) -> np.ndarray:
@@ -1060,7 +1180,7 @@ class UnionFindDecoder(_RowDecoder):
         self.match_defects, self.match_weights = None, None   # K and the weights of cluster matching (with_cluster_matching)
         self.gap_observable = self.gap_cap = self.gap_step = None   # the complementary gap (with_gap_output)
         self.erased_weight = self.max_hubs = None   # w_h and H of cluster matching under heralds (with_erasure_matching)
-        self._cache: dict = {}   # packed row of detectors -> (prediction, missed, flipped edges, rounds, full edges, largest cluster)
+        self._cache: dict = {}   # packed row of detectors -> its _Decoded
 
     @classmethod
     def from_circuit(cls, circuit, weights: str | None = None, resolution: int = 4, heralds: bool = False) -> "UnionFindDecoder":
@@ -1075,30 +1195,28 @@ class UnionFindDecoder(_RowDecoder):
         ``count(decoder=...)`` then fills ``ShotCounts.soft_kept`` / ``soft_errors`` ("Soft outputs" in the module docstring)."""
         return self._with_soft_output(metric, bins)
 
-    @property
-    def _soft_refused(self):
-        return None if self.match_defects is None else "a cluster-matching decoder has no soft output"
+    def _with_matching(self, K: int, weights, **more) -> "UnionFindDecoder":
+        """The tail of both matching constructors: a copy with ``match_defects``, ``match_weights`` and ``more`` set, no table yet
+        and a cache of its own (its predictions differ)."""
+        out = object.__new__(UnionFindDecoder)
+        out.__dict__.update(self.__dict__)
+        out.match_defects, out.match_weights = K, self._match_weights(weights)
+        out.__dict__.update(more)
+        out._cache, out._table = {}, None
+        return out
 
     def with_cluster_matching(self, max_defects: int = 10, weights=None) -> "UnionFindDecoder":
         """The decoder of the same graph, caps and observables that corrects every cluster of at most ``max_defects`` defects
         (an int in 1 .. 12) by the minimum-weight matching of its defects ("Cluster matching" in the module docstring) under
         ``weights``: integers ``[n_edges]`` in 1 .. 65535, default ``graph.match_weights()``.  Its predictions differ, so its
         cache is a new one."""
-        K = max_defects
-        if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_MATCH_DEFECTS:
-            raise ValueError(f"max_defects = {K!r}: an int in 1 .. {MAX_MATCH_DEFECTS}")
-        if self.soft_output is not None:
-            raise ValueError("a decoder with a soft output takes no cluster matching")
+        K = _check_max_defects(max_defects)
+        self._no_soft_output()
         g = self.graph
         if g.n_heralds:
             raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
-        if g.n_nodes > MAX_MATCH_NODES:
-            raise NotImplementedError(f"{g.n_nodes} nodes (a match table has at most {MAX_MATCH_NODES}: 12 bytes per pair of nodes)")
-        out = object.__new__(UnionFindDecoder)
-        out.__dict__.update(self.__dict__)
-        out.match_defects, out.match_weights = int(K), self._match_weights(weights)
-        out._cache, out._table = {}, None
-        return out
+        _check_match_nodes(g.n_nodes, f"{g.n_nodes} nodes", 12)
+        return self._with_matching(K, weights)
 
     def with_erasure_matching(self, max_defects: int = 10, weights=None, erased_weight: int = 1, max_hubs: int = 24) -> "UnionFindDecoder":
         """Cluster matching for a graph WITH heralds ("Cluster matching under heralds" in the module docstring): every cluster of
@@ -1106,27 +1224,17 @@ class UnionFindDecoder(_RowDecoder):
         minimum-weight matching of its defects in its hub graph, where an erased edge of the cluster weighs
         ``min(weights[e], erased_weight)`` (``erased_weight``: an int in 1 .. 65535); ``weights`` as in
         :meth:`with_cluster_matching`.  :meth:`with_gap_output` works on the result."""
-        is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))  # noqa: E731
-        K, H = max_defects, max_hubs
-        if not is_int(K) or not 1 <= K <= MAX_MATCH_DEFECTS:
-            raise ValueError(f"max_defects = {K!r}: an int in 1 .. {MAX_MATCH_DEFECTS}")
-        if not is_int(erased_weight) or not 1 <= erased_weight <= 65535:
+        K, H = _check_max_defects(max_defects), max_hubs
+        if not _is_int(erased_weight) or not 1 <= erased_weight <= 65535:
             raise ValueError(f"erased_weight = {erased_weight!r}: an int in 1 .. 65535")
-        if not is_int(H) or not K <= H <= MAX_MATCH_HUBS:
+        if not _is_int(H) or not K <= H <= MAX_MATCH_HUBS:
             raise ValueError(f"max_hubs = {H!r}: an int in max_defects = {K} .. {MAX_MATCH_HUBS}")
-        if self.soft_output is not None:
-            raise ValueError("a decoder with a soft output takes no cluster matching")
+        self._no_soft_output()
         g = self.graph
         if not g.n_heralds:
             raise ValueError("the graph has no heralds: with_cluster_matching() is the matching decoder of such a graph")
-        if g.n_nodes > MAX_MATCH_NODES:
-            raise NotImplementedError(f"{g.n_nodes} nodes (a match table has at most {MAX_MATCH_NODES}: 12 bytes per pair of nodes)")
-        out = object.__new__(UnionFindDecoder)
-        out.__dict__.update(self.__dict__)
-        out.match_defects, out.match_weights = int(K), self._match_weights(weights)
-        out.erased_weight, out.max_hubs = int(erased_weight), int(H)
-        out._cache, out._table = {}, None
-        return out
+        _check_match_nodes(g.n_nodes, f"{g.n_nodes} nodes", 12)
+        return self._with_matching(K, weights, erased_weight=int(erased_weight), max_hubs=int(H))
 
     def with_gap_output(self, observable: int = 0, bins: int = 64, step: int | None = None, cap: int | None = None) -> "UnionFindDecoder":
         """The cluster-matching decoder of the same graph, caps, weights and ``max_defects`` (one of :meth:`with_cluster_matching`
@@ -1135,20 +1243,19 @@ class UnionFindDecoder(_RowDecoder):
         an int in 1 .. 2^31 - 2; default ``W0`` of :meth:`gap_table`) and ``gap_step`` (``step >= 1``; default ``cap // bins + 1``).
         Its predictions are this decoder's; ``count(decoder=...)`` fills ``ShotCounts.soft_kept`` / ``soft_errors`` with the
         deficits ``cap - gap``."""
-        is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))  # noqa: E731
         self._matching("with_gap_output()")
-        if not is_int(observable) or not 0 <= observable < self._n_obs:
+        if not _is_int(observable) or not 0 <= observable < self._n_obs:
             raise ValueError(f"observable = {observable!r}: an int in 0 .. {self._n_obs - 1}")
-        if not is_int(bins) or not 2 <= bins <= MAX_SOFT_BINS:
+        if not _is_int(bins) or not 2 <= bins <= MAX_SOFT_BINS:
             raise ValueError(f"bins = {bins!r}: an int in 2 .. {MAX_SOFT_BINS}")
-        if cap is not None and (not is_int(cap) or not 1 <= cap <= MAX_GAP_CAP):
+        if cap is not None and (not _is_int(cap) or not 1 <= cap <= MAX_GAP_CAP):
             raise ValueError(f"cap = {cap!r}: an int in 1 .. {MAX_GAP_CAP}")
-        if step is not None and (not is_int(step) or not 1 <= step <= MAX_GAP_CAP):
+        if step is not None and (not _is_int(step) or not 1 <= step <= MAX_GAP_CAP):
             raise ValueError(f"step = {step!r}: an int in 1 .. {MAX_GAP_CAP}")
         out = object.__new__(UnionFindDecoder)
         out.__dict__.update(self.__dict__)
         out.soft_output, out.soft_bins, out.gap_observable = "gap", int(bins), int(observable)
-        out._cache, out._gap_table = {}, None   # (an entry ends with the row's gap, which depends on the observable)
+        out._cache, out._gap_table = {}, None   # (an entry holds the row's gap, which depends on the observable)
         if cap is None:
             cap = out.gap_table()[1]
             if cap is None:
@@ -1159,10 +1266,6 @@ class UnionFindDecoder(_RowDecoder):
 
     def info(self) -> dict:
         return self.graph.info()
-
-    def _matching(self, what: str):
-        if self.match_defects is None:
-            raise ValueError(f"{what} needs a cluster-matching decoder: with_cluster_matching(max_defects, weights)")
 
     def match_table(self):
         """``(dist uint32[N, N], mask uint64[N, N])``: the match table of ``match_weights`` ("Match table" in the module
@@ -1501,144 +1604,100 @@ class UnionFindDecoder(_RowDecoder):
         hubs)`` over the decoded rows of ``dets``: what the device counts in ``tsim_uf_erasure_info`` [2] and [3]."""
         self._erasure("erasure_counts()")
         entries = [e for e in self._decoded(dets) if e is not None]
-        return sum(e[-2] for e in entries), sum(e[-1] for e in entries)
+        return sum(e.with_erased for e in entries), sum(e.overflowed for e in entries)
 
     def gap_outputs(self, dets) -> np.ndarray:
         """int64 ``[n]``: the deficit ``D = gap_cap - gap`` of every row ("Complementary gap" in the module docstring): 0 for a
         row without a defect, ``gap_cap`` for a miss and for a row with a peeled cluster."""
         self._gap("gap_outputs()")
-        return np.array([0 if e is None else self.gap_cap - min(self.gap_cap, e[8]) for e in self._decoded(dets)], dtype=np.int64)
+        return np.array([0 if e is None else self.gap_cap - min(self.gap_cap, e.gap) for e in self._decoded(dets)], dtype=np.int64)
 
     def match_counts(self, dets):
         """``(clusters_matched, clusters_peeled)`` over the rows of ``dets`` that are decoded (a defect, no miss): what the
         device counts in ``info()["clusters_matched"]`` and ``["clusters_peeled"]``."""
         self._matching("match_counts()")
         entries = [e for e in self._decoded(dets) if e is not None]
-        return sum(e[6] for e in entries), sum(e[7] for e in entries)
-
-    def flipped_edges(self, dets) -> list:
-        """Per row the edges of its correction (the base class's); a cluster-matching decoder has none: a matched cluster is
-        corrected by paths of the match table."""
-        if self.match_defects is not None:
-            raise ValueError("a cluster-matching decoder has no flipped edges: a matched cluster is corrected by paths of the match table")
-        return super().flipped_edges(dets)
+        return sum(e.matched for e in entries), sum(e.peeled for e in entries)
 
     # -- the numpy statement ---------------------------------------------------------------------------------------------
     def _decode_one(self, defects: np.ndarray, erased_edges=()):
         """One syndrome (the defect NODES, ascending; ``erased_edges`` start fully grown): ``(prediction, missed, flipped edges
         ascending, growth rounds)``."""
-        return self._decode_one_soft(defects, erased_edges)[:4]
+        d = self._decode_one_soft(defects, erased_edges)
+        return d.prediction, d.missed, d.flipped, d.rounds
 
-    def _decode_one_soft(self, defects: np.ndarray, erased_edges=(), paths: list | None = None):
-        """:meth:`_decode_one`, followed by the full edges and the nodes of the largest cluster when growth ends.  ``paths`` (a
-        cluster-matching decoder without heralds; "Cluster matching in windows" in the module docstring): a list that receives the
-        row's flips as ``(pair, edges)``: per pair ``(a, v)`` a matched cluster chose the edges of its PATH, per peeling flip whose
-        child lies in a peeled cluster ``(None, [e])``."""
+    def _decode_one_soft(self, defects: np.ndarray, erased_edges=(), paths: list | None = None) -> _Decoded:
+        """One syndrome as :meth:`_decode_one` takes it, to its :class:`_Decoded`: the rule's steps in the kernel's order, growth,
+        the forest, peeling and, of a cluster-matching decoder, the correction cluster by cluster.  ``paths`` (a cluster-matching
+        decoder without heralds; "Cluster matching in windows" in the module docstring): a list that receives the row's flips as
+        ``(pair, edges)`` and becomes the entry's ``paths``: per pair ``(a, v)`` a matched cluster chose the edges of its PATH, per
+        peeling flip whose child lies in a peeled cluster ``(None, [e])``."""
         g = self.graph
-        n, eu, ev = g.n_nodes, g.edge_u, g.edge_v
-        defect = np.zeros(n, np.bool_)
+        defect = np.zeros(g.n_nodes, np.bool_)
         defect[defects] = True
         cap = np.full(g.n_edges, 2, np.int8) if self.edge_caps is None else self.edge_caps.astype(np.int8)
-        grown = np.zeros(g.n_edges, np.int8)
         erased = np.unique(np.asarray(erased_edges, dtype=np.int64))   # each taken once
-        grown[erased] = cap[erased]
-        label = np.arange(n)
-        rounds = 0
-        while True:
-            f = grown == cap
-            label = _components(label, eu[f], ev[f])
-            odd = (np.bincount(label[defect], minlength=n) & 1).astype(np.bool_)
-            odd[0] = False
-            active = odd[label]
-            if not active.any():
-                break
-            new = np.minimum(cap, grown + active[eu] + active[ev]).astype(np.int8)
-            if np.array_equal(new, grown):
-                return (0, True, np.zeros(0, np.int64), rounds, int(f.sum()), int(np.bincount(label).max())) + \
-                    ((0, 0) if self.match_defects is not None else ()) + ((0,) if self.gap_observable is not None else ()) + \
-                    ((0, 0) if self.erased_weight is not None else ())
-            grown, rounds = new, rounds + 1
-        soft = (int((grown == cap).sum()), int(np.bincount(label).max()))  # (label: the clusters of the full edges)
-        # the forest: levels from the roots, the parent edge the smallest-index edge to the level above
-        fe = np.flatnonzero(grown == cap)
-        fu, fv = eu[fe], ev[fe]
-        level = np.where(label == np.arange(n), 0, -1)
-        parent = np.full(n, -1, np.int64)
-        depth = 0
-        while True:
-            down = (level[fu] == depth) & (level[fv] < 0)
-            up = (level[fv] == depth) & (level[fu] < 0)
-            child = np.concatenate([fv[down], fu[up]])
-            if not len(child):
-                break
-            via = np.concatenate([fe[down], fe[up]])
-            parent[child] = g.n_edges
-            np.minimum.at(parent, child, via)
-            level[child] = depth + 1
-            depth += 1
-        # peeling, from the deepest level up
-        s = defect.copy()
-        prediction, flipped, children = 0, [], []
-        for lv in range(depth, 0, -1):
-            for v in np.flatnonzero((level == lv) & s):
-                e = int(parent[v])
-                s[eu[e]] ^= True
-                s[ev[e]] ^= True
-                prediction ^= int(g.edge_obs[e])
-                flipped.append(e)
-                children.append(int(v))
-        assert not s[1:].any(), "the correction does not reproduce the syndrome"
+        grown, label, rounds, missed = _grow(g, cap, defect, erased)
+        full = grown == cap
+        growth = dict(rounds=rounds, full_edges=int(full.sum()), largest_cluster=int(np.bincount(label).max()))  # (label: the clusters of the full edges)
+        if missed:
+            return _Decoded(missed=True, **growth)
+        level, parent, depth = _forest(g, np.flatnonzero(full), label)
+        prediction, flipped, children = _peel(g, defect, level, parent, depth)
+        fields = dict(growth, prediction=prediction, flipped=np.array(sorted(flipped), np.int64), paths=paths)
         if self.match_defects is not None:
-            # cluster matching: small clusters by the dynamic program, of the others the flips whose child node lies in them
-            # (the complementary gap: the least gap of the row's clusters before the cap, 0 with a peeled cluster)
-            prediction = matched = peeled = with_erased = overflowed = 0
-            gap = _GAP_INF
-            self._match_rows(np.flatnonzero(defect))   # (the rows every cluster of the shot reads, in one go)
-            for r in np.unique(label[defect]):
-                ds = np.flatnonzero(defect & (label == r))
-                small = len(ds) <= self.match_defects
-                if small and self.erased_weight is not None:  # under heralds: the cluster's erased edges and its hubs
-                    ec = erased[label[ev[erased]] == r]
-                    ends = np.concatenate([eu[ec], ev[ec]])
-                    if len(np.union1d(ds, ends[ends >= 1])) > self.max_hubs:
-                        small, overflowed = False, overflowed + 1
-                if small:
-                    if self.erased_weight is not None:
-                        cost, mask, cluster_gap = self._hub_cluster(ds, ec)
-                        with_erased += len(ec) > 0
-                    else:
-                        cost, mask, pairs = self._match_cluster(ds)
-                        assert cost is not None, "a matched cluster has no finite pairing"
-                        if paths is not None:
-                            paths += [((a, v), self.match_path(a, v)) for a, v in pairs]
-                        cluster_gap = self._cluster_gap(ds, cost, mask) if self.gap_observable is not None else None
-                    prediction ^= mask
-                    matched += 1
-                    if self.gap_observable is not None:
-                        gap = min(gap, cluster_gap)
+            fields.update(self._correct_clusters(defect, label, erased, flipped, children, paths))
+        return _Decoded(**fields)
+
+    def _correct_clusters(self, defect, label, erased, flipped, children, paths) -> dict:
+        """The correction of a cluster-matching decoder, cluster by cluster (``ufk::mark_clusters``, then ``ufk::match_clusters`` or,
+        under heralds, ``ufk::hub_clusters``): small clusters by the dynamic program (:meth:`_match_cluster` / :meth:`_hub_cluster`),
+        of the others the peeling flips ``flipped`` whose child node (``children``) lies in them.  The fields of :class:`_Decoded`
+        this decides (``gap``: the least of the row's clusters before the cap, 0 with a peeled one); ``paths`` receives the flips."""
+        g = self.graph
+        eu, ev = g.edge_u, g.edge_v
+        heralds, with_gap = self.erased_weight is not None, self.gap_observable is not None
+        prediction = matched = peeled = with_erased = overflowed = 0
+        gap = _GAP_INF
+        self._match_rows(np.flatnonzero(defect))   # (the rows every cluster of the shot reads, in one go)
+        for r in np.unique(label[defect]):
+            ds = np.flatnonzero(defect & (label == r))
+            small = len(ds) <= self.match_defects
+            if small and heralds:  # the cluster's erased edges and its hubs
+                ec = erased[label[ev[erased]] == r]
+                ends = np.concatenate([eu[ec], ev[ec]])
+                if len(np.union1d(ds, ends[ends >= 1])) > self.max_hubs:
+                    small, overflowed = False, overflowed + 1
+            if small:
+                if heralds:
+                    cost, mask, cluster_gap = self._hub_cluster(ds, ec)
+                    with_erased += len(ec) > 0
                 else:
-                    for e, v in zip(flipped, children):
-                        if label[v] == r:
-                            prediction ^= int(g.edge_obs[e])
-                            if paths is not None:
-                                paths.append((None, [e]))
-                    peeled += 1
-                    gap = 0
-            return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft + (matched, peeled) + \
-                ((gap,) if self.gap_observable is not None else ()) + ((with_erased, overflowed) if self.erased_weight is not None else ())
-        return (prediction, False, np.array(sorted(flipped), np.int64), rounds) + soft
+                    cost, mask, pairs = self._match_cluster(ds)
+                    assert cost is not None, "a matched cluster has no finite pairing"
+                    if paths is not None:
+                        paths += [((a, v), self.match_path(a, v)) for a, v in pairs]
+                    cluster_gap = self._cluster_gap(ds, cost, mask) if with_gap else None
+                prediction ^= mask
+                matched += 1
+                if with_gap:
+                    gap = min(gap, cluster_gap)
+            else:
+                for e, v in zip(flipped, children):
+                    if label[v] == r:
+                        prediction ^= int(g.edge_obs[e])
+                        if paths is not None:
+                            paths.append((None, [e]))
+                peeled += 1
+                gap = 0
+        return dict(prediction=prediction, matched=matched, peeled=peeled, gap=gap if with_gap else 0, with_erased=with_erased,
+                    overflowed=overflowed)
 
     def _decode_bits(self, bits: np.ndarray):
         """One row's detector bits: the defects of its nodes, the edges of its heralds that are set erased."""
         g = self.graph
         erased = [g.herald_edges[g.herald_ptr[h]:g.herald_ptr[h + 1]] for h in np.flatnonzero(bits[g.herald_det])]
         return self._decode_one_soft(np.flatnonzero(bits[g.node_det]) + 1, np.unique(np.concatenate(erased)) if erased else ())
-
-    def soft_outputs(self, dets) -> np.ndarray:
-        """The base class's; a cluster-matching decoder has none."""
-        if self.match_defects is not None:
-            raise ValueError("a cluster-matching decoder has no soft outputs")
-        return super().soft_outputs(dets)
 
     def _soft_values(self, dets) -> np.ndarray:
         if self.gap_observable is not None:
@@ -1650,17 +1709,17 @@ class UnionFindDecoder(_RowDecoder):
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _handle(self, hp, n_cols: int):
+        """``(handle, what decodes rows by it, what destroys it)``: the create call is the decoder's kind."""
         if self.erased_weight is not None:
             h = hp.uf_create_matching_heralds(self.graph, n_cols, self.match_weights, self.match_defects, self.erased_weight, self.max_hubs,
                                               -1 if self.gap_observable is None else self.gap_observable, self.edge_caps)
-            return h, hp.uf_decode_device, hp.uf_destroy
-        if self.gap_observable is not None:
+        elif self.gap_observable is not None:
             h = hp.uf_create_matching_gap(self.graph, n_cols, self.match_weights, self.match_defects, self.gap_observable, self.edge_caps)
-            return h, hp.uf_decode_device, hp.uf_destroy
-        if self.match_defects is not None:
+        elif self.match_defects is not None:
             h = hp.uf_create_matching(self.graph, n_cols, self.match_weights, self.match_defects, self.edge_caps)
-            return h, hp.uf_decode_device, hp.uf_destroy
-        return hp.uf_create(self.graph, n_cols, self.edge_caps), hp.uf_decode_device, hp.uf_destroy
+        else:
+            h = hp.uf_create(self.graph, n_cols, self.edge_caps)
+        return h, hp.uf_decode_device, hp.uf_destroy
 
     def _soft_call(self, hp, d_hist: int, d_values: int = 0):
         """What decodes rows by this decoder's handle in the place of the plain call when the soft output is wanted: the two
@@ -1712,7 +1771,7 @@ class WindowedUnionFindDecoder(_RowDecoder):
         self.heralds = bool(heralds)
         whole = UnionFindDecoder(graph, num_observables, edge_caps)  # (checks the observables and the caps)
         for name, x in (("commit", commit), ("window", window)):
-            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            if not _is_int(x):
                 raise ValueError(f"{name} = {x!r}: an int (detector columns)")
         if commit < 1 or window <= commit:
             raise ValueError(f"commit = {commit}, window = {window}: 1 <= commit < window expected")
@@ -1724,10 +1783,9 @@ class WindowedUnionFindDecoder(_RowDecoder):
         self._decoders = [UnionFindDecoder(w.graph, self._n_obs, None if self.edge_caps is None else w.caps) for w in self._windows]
         self.soft_output, self.soft_bins = None, None   # the metric count() bins, and into how many bins (with_soft_output)
         self.match_defects, self.match_weights = None, None   # K and the GLOBAL weights of cluster matching (with_cluster_matching)
-        self._cache: dict = {}         # packed row of detectors -> (prediction, missed, flipped global edges, rounds, full edges
-        #                                summed over the decoded windows, the largest cluster of any of them; with cluster matching
-        #                                also the matched and the peeled clusters, summed, and the row's pairs with mixed paths)
-        self._window_cache: dict = {}  # (window, its packed defects, its erased local edges) -> what _decode_one_soft gave
+        self._cache: dict = {}         # packed row of detectors -> its _Decoded, summed or the most over the decoded windows
+        self._window_cache: dict = {}  # (window, its packed defects, its erased local edges) -> the _Decoded of _decode_one_soft;
+        #                                with cluster matching (the window's decoder, its packed defects)
 
     @classmethod
     def from_circuit(cls, circuit, commit: int, window: int, weights: str | None = None, resolution: int = 4,
@@ -1839,20 +1897,16 @@ class WindowedUnionFindDecoder(_RowDecoder):
         ``match_weights`` (GLOBAL: integers ``[n_edges]`` in 1 .. 65535, default ``graph.match_weights()``) set, new caches, and per
         window a cluster-matching :class:`UnionFindDecoder` under the window's local weights ("Cluster matching in windows" in the
         module docstring).  Windows whose graphs, caps and weights are equal share one decoder, and so one match table."""
-        K = max_defects
-        if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_MATCH_DEFECTS:
-            raise ValueError(f"max_defects = {K!r}: an int in 1 .. {MAX_MATCH_DEFECTS}")
-        if self.soft_output is not None:
-            raise ValueError("a decoder with a soft output takes no cluster matching")
+        K = _check_max_defects(max_defects)
+        self._no_soft_output()
         if self.heralds:
             raise NotImplementedError("cluster matching takes a graph without heralds: the match table is static, a herald is not")
         w = self._match_weights(weights)
         most = max(x.graph.n_nodes for x in self._windows)
-        if most > MAX_MATCH_NODES:
-            raise NotImplementedError(f"a window of {most} nodes (a match table has at most {MAX_MATCH_NODES}: 6 bytes per pair of nodes)")
+        _check_match_nodes(most, f"a window of {most} nodes", 6)
         out = object.__new__(type(self))
         out.__dict__.update(self.__dict__)
-        out.match_defects, out.match_weights = int(K), w
+        out.match_defects, out.match_weights = K, w
         out._windows = out._build_windows(w)
         out._cache, out._window_cache = {}, {}
         shared: dict = {}   # what fixes a window's decoder -> the decoder
@@ -1861,13 +1915,9 @@ class WindowedUnionFindDecoder(_RowDecoder):
             g = x.graph
             key = (g.n_nodes, g.edge_u.tobytes(), g.edge_v.tobytes(), g.edge_obs.tobytes(), x.caps.tobytes(), x.weights.tobytes())
             if key not in shared:
-                shared[key] = UnionFindDecoder(g, self._n_obs, None if self.edge_caps is None else x.caps).with_cluster_matching(int(K), x.weights)
+                shared[key] = UnionFindDecoder(g, self._n_obs, None if self.edge_caps is None else x.caps).with_cluster_matching(K, x.weights)
             out._decoders.append(shared[key])
         return out
-
-    def _matching(self, what: str):
-        if self.match_defects is None:
-            raise ValueError(f"{what} needs a cluster-matching decoder: with_cluster_matching(max_defects, weights)")
 
     def window_match_table(self, k: int):
         """``(dist uint32[N_k, N_k], parent uint16[N_k, N_k])`` of window ``k``: the match table of ``G_k`` under the local weights
@@ -1880,110 +1930,74 @@ class WindowedUnionFindDecoder(_RowDecoder):
         """int64 ``[n, 2]``: per row the matched and the peeled clusters, summed over its decoded windows (zeros for a row without a
         defect and for a miss); the sums over the rows are what the device counts in ``ufw_match_info``."""
         self._matching("match_counts()")
-        return np.array([(0, 0) if e is None else e[6:8] for e in self._decoded(dets)], np.int64).reshape(-1, 2)
+        return np.array([(0, 0) if e is None else (e.matched, e.peeled) for e in self._decoded(dets)], np.int64).reshape(-1, 2)
 
     def mixed_pairs(self, dets) -> np.ndarray:
         """int64 ``[n]``: per row the pairs its matched clusters chose whose PATH holds both a committed and an uncommitted edge:
         the corrections a window commits in part and carries on in part."""
         self._matching("mixed_pairs()")
-        return np.array([0 if e is None else e[8] for e in self._decoded(dets)], np.int64)
-
-    @property
-    def _soft_refused(self):
-        return None if self.match_defects is None else "a cluster-matching decoder has no soft output"
-
-    def soft_outputs(self, dets) -> np.ndarray:
-        """The base class's; a cluster-matching decoder has none."""
-        if self.match_defects is not None:
-            raise ValueError("a cluster-matching decoder has no soft outputs")
-        return super().soft_outputs(dets)
-
-    def flipped_edges(self, dets) -> list:
-        """The base class's; a cluster-matching decoder has none: a matched cluster is corrected by paths of the match table."""
-        if self.match_defects is not None:
-            raise ValueError("a cluster-matching decoder has no flipped edges: a matched cluster is corrected by paths of the match table")
-        return super().flipped_edges(dets)
+        return np.array([0 if e is None else e.mixed for e in self._decoded(dets)], np.int64)
 
     # -- the numpy statement ---------------------------------------------------------------------------------------------
-    def _decode_row(self, bits: np.ndarray):
-        """One row's detector bits (bool ``[num_detectors]``): ``(prediction, missed, committed flipped global edges ascending,
-        the most growth rounds of a window, the full edges summed over the decoded windows, the largest cluster of any of
-        them)``; the last three include a window that misses ("Soft outputs in windows")."""
+    def _decode_row(self, bits: np.ndarray) -> _Decoded:
+        """One row's detector bits (bool ``[num_detectors]``) to its :class:`_Decoded`, the one loop over the windows of both the
+        peeling and the cluster-matching decoder (``k_ufw``): ``flipped`` are the committed global edges, ascending (of a matching
+        decoder as often as they were applied), ``rounds`` the most of a window, ``full_edges`` the sum over the decoded windows and
+        ``largest_cluster`` the largest of any of them, the three with a window that misses included ("Soft outputs in windows");
+        ``matched``, ``peeled`` and ``mixed`` are sums over the windows, 0 for a miss."""
         g = self.graph
+        matching = self.match_defects is not None
         r = bits[g.node_det].copy()   # the syndrome, by node (every column without heralds)
         fired = np.flatnonzero(bits[g.herald_det]) if self.heralds else ()   # the heralds that are set
-        prediction, flipped, most, full, largest = 0, [], 0, 0, 0
-        for k, (w, uf) in enumerate(zip(self._windows, self._decoders)):
-            if not r[w.lo:w.hi].any():
-                continue
-            erased = np.zeros(0, np.int64)   # the union of L_k(i) over the heralds that are set
-            if len(fired):
-                j = np.flatnonzero(np.isin(w.heralds, fired))
-                if len(j):
-                    erased = np.unique(np.concatenate([w.herald_edges[w.herald_ptr[x]:w.herald_ptr[x + 1]] for x in j]))
-            key = (k, np.packbits(r[w.lo:w.hi]).tobytes(), erased.tobytes())
-            if key not in self._window_cache:
-                self._window_cache[key] = uf._decode_one_soft(np.flatnonzero(r[w.lo:w.hi]) + 1, erased)
-            _, miss, local, rounds, window_full, window_largest = self._window_cache[key]
-            most, full, largest = max(most, rounds), full + window_full, max(largest, window_largest)
-            if miss:
-                return 0, True, np.zeros(0, np.int64), most, full, largest
-            for e in local[w.committed[local]]:
-                ge = int(w.global_edge[e])
-                assert ge >= 0, "a committed edge is a real edge"
-                prediction ^= int(g.edge_obs[ge])
-                if g.edge_u[ge]:
-                    r[g.edge_u[ge] - 1] ^= True
-                r[g.edge_v[ge] - 1] ^= True
-                flipped.append(ge)
-            assert not r[w.lo:min(w.lo + self.commit, w.hi)].any(), "the commit region is not clean"
-        assert not r.any(), "the correction does not reproduce the syndrome"
-        return prediction, False, np.array(sorted(flipped), np.int64), most, full, largest
+        prediction, flipped = 0, []
+        most = full = largest = matched = peeled = mixed = 0
 
-    def _decode_row_matching(self, bits: np.ndarray):
-        """:meth:`_decode_row` of a cluster-matching decoder ("Cluster matching in windows"): ``(prediction, missed, no edges, the
-        most growth rounds of a window, full edges, largest cluster, clusters matched, clusters peeled, pairs whose path is committed
-        in part)``; the counts are 0 for a miss."""
-        g = self.graph
-        r = bits[g.node_det].copy()
-        prediction, most, full, largest, matched, peeled, mixed = 0, 0, 0, 0, 0, 0, 0
-        none = np.zeros(0, np.int64)
+        def commit(w, e):   # a committed local flip: k_ufw's flip lambda
+            nonlocal prediction
+            ge = int(w.global_edge[e])
+            assert ge >= 0, "a committed edge is a real edge"
+            prediction ^= int(g.edge_obs[ge])
+            if g.edge_u[ge]:
+                r[g.edge_u[ge] - 1] ^= True
+            r[g.edge_v[ge] - 1] ^= True
+            flipped.append(ge)
+
         for k, (w, uf) in enumerate(zip(self._windows, self._decoders)):
             if not r[w.lo:w.hi].any():
                 continue
-            key = (id(uf), np.packbits(r[w.lo:w.hi]).tobytes())   # (windows that share a decoder share what it decodes)
+            j = np.flatnonzero(np.isin(w.heralds, fired)) if len(fired) else ()
+            # the union of L_k(i) over the heralds that are set: the local edges that start full
+            erased = np.unique(np.concatenate([w.herald_edges[w.herald_ptr[x]:w.herald_ptr[x + 1]] for x in j])) if len(j) else _NO_EDGES
+            packed = np.packbits(r[w.lo:w.hi]).tobytes()
+            key = (id(uf), packed) if matching else (k, packed, erased.tobytes())   # (windows that share a decoder share what it decodes)
             if key not in self._window_cache:
-                paths: list = []
-                self._window_cache[key] = uf._decode_one_soft(np.flatnonzero(r[w.lo:w.hi]) + 1, (), paths) + (paths,)
-            _, miss, _, rounds, window_full, window_largest, window_matched, window_peeled, paths = self._window_cache[key]
-            most, full, largest = max(most, rounds), full + window_full, max(largest, window_largest)
-            if miss:
-                return 0, True, none, most, full, largest, 0, 0, 0
-            matched, peeled = matched + window_matched, peeled + window_peeled
-            for pair, edges in paths:   # the local flips; an edge that occurs twice is applied twice
+                self._window_cache[key] = uf._decode_one_soft(np.flatnonzero(r[w.lo:w.hi]) + 1, erased, [] if matching else None)
+            d = self._window_cache[key]
+            most, full, largest = max(most, d.rounds), full + d.full_edges, max(largest, d.largest_cluster)
+            if d.missed:
+                return _Decoded(missed=True, rounds=most, full_edges=full, largest_cluster=largest)
+            matched, peeled = matched + d.matched, peeled + d.peeled
+            # the local flips: the peeled edges, each once, or the edges of the paths, where an edge that occurs twice is applied twice
+            for pair, edges in d.paths if matching else [(None, d.flipped)]:
                 assert len(edges) <= w.graph.n_nodes - 1, "a path is longer than the window has nodes"
+                edges = np.asarray(edges, np.int64)
                 done = w.committed[edges]
                 mixed += pair is not None and done.any() and not done.all()
-                for e in np.asarray(edges, np.int64)[done]:
-                    ge = int(w.global_edge[e])
-                    assert ge >= 0, "a committed edge is a real edge"
-                    prediction ^= int(g.edge_obs[ge])
-                    if g.edge_u[ge]:
-                        r[g.edge_u[ge] - 1] ^= True
-                    r[g.edge_v[ge] - 1] ^= True
+                for e in edges[done]:
+                    commit(w, e)
             assert not r[w.lo:min(w.lo + self.commit, w.hi)].any(), "the commit region is not clean"
         assert not r.any(), "the correction does not reproduce the syndrome"
-        return prediction, False, none, most, full, largest, matched, peeled, mixed
+        return _Decoded(prediction=prediction, flipped=np.array(sorted(flipped), np.int64), rounds=most, full_edges=full,
+                        largest_cluster=largest, matched=matched, peeled=peeled, mixed=mixed)
 
-    def _decode_bits(self, bits: np.ndarray):
-        return self._decode_row(bits) if self.match_defects is None else self._decode_row_matching(bits)
+    _decode_bits = _decode_row
 
     # -- the device side -------------------------------------------------------------------------------------------------
     def _handle(self, hp, n_cols: int):
         if self.match_defects is not None:
             h = hp.ufw_create_matching(self.graph, n_cols, self.match_weights, self.match_defects, self.commit, self.window, self.edge_caps)
-            return h, hp.ufw_decode_device, hp.ufw_destroy
-        h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps, heralds=self.heralds)
+        else:
+            h = hp.ufw_create(self.graph, n_cols, self.commit, self.window, self.edge_caps, heralds=self.heralds)
         return h, hp.ufw_decode_device, hp.ufw_destroy
 
     def _soft_call(self, hp, d_hist: int, d_values: int = 0):
